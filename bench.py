@@ -15,9 +15,16 @@ estimates the pairs whose TARGET it owns (so it builds target-side search struct
 only), the pair records are all-gathered (RCCL) and every rank solves the pose graph.  Every rank
 replays the rand() draws of all pairs, so the stream matches the reference's single global one.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (dominant kernel,
-HIP-event timed on the engine's own stream) and, at N = 1, `cpu_baseline` (the CPU oracle, single
-thread like the reference, on a bounded sample of the same workload).
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times
+--steps steps and prints the headline (`value`, `ms_per_step`) with what the steps themselves report
+(pair-transform CRC, stage seconds of the last step, host CPU).  `--full` adds everything that takes
+work of its own: `roofline` (dominant kernel, HIP-event timed on the engine's own stream; the kernels
+are bracketed with events only then), the isolated per-kernel pass, the pair stage alone, the
+PCIe-inclusive steps, the ground-truth error and, at N = 1, `cpu_baseline` (the CPU oracle, single
+thread like the reference, on a bounded sample of the same workload) with its `parity_check`.
+
+`--dump-outputs DIR` writes what the last timed step returned (the global transforms and the pair
+records, field by field) as DIR/<name>.npy, so that two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -248,7 +255,7 @@ def main():
                     help="diagnostic (one GPU, library engine): hand the clouds over as HOST arrays of pcl::PointXYZRGB records "
                          "(stride 32, rgba at 16) like the reference's callers do, so that the step includes the upload; "
                          "never the reported configuration (inputs are HBM-resident for `value`)")
-    ap.add_argument("--kernel-table", default=None, help="write rank 0's full per-kernel HIP-event table (CSV) here")
+    ap.add_argument("--kernel-table", default=None, help="write rank 0's full per-kernel HIP-event table (CSV) here (implies --full)")
     ap.add_argument("--scenes", choices=["independent", "lattice"], default="independent",
                     help="synthetic scene family: 'independent' (default, the headline workload: every map samples the world on its own) "
                          "or 'lattice' (overlapping maps share the samples of one world-anchored lattice: repeatable keypoints)")
@@ -260,7 +267,16 @@ def main():
                     "as with the reference's --resolution option)")
     ap.add_argument("--no-pair-stage", action="store_true", help="skip the untimed pair-loop-alone pass (pair_stage_pairs_per_s) at N = 1")
     ap.add_argument("--no-pcie", action="store_true", help="skip the extra PCIe-inclusive step (host pcl::PointXYZRGB input) at N = 1")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: kernel events in the timed steps (roofline, per-kernel and per-stage figures), the "
+                         "isolated per-kernel pass, the pair stage alone, the PCIe-inclusive steps, the ground-truth error and the CPU "
+                         "baselines with their parity check (the --no-* options above switch single ones off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (global transforms, pair records) as DIR/<name>.npy")
     args = ap.parse_args()
+    args.full = args.full or bool(args.kernel_table)
+    if args.dump_outputs and args.steps < 1:
+        ap.error("--dump-outputs writes what the last timed step computed: it needs --steps 1 or more")
 
     import torch
     import torch.distributed as dist
@@ -324,7 +340,7 @@ def main():
     torch.cuda.synchronize()
     pairs_idx = [(i, j) for i in range(n_maps - 1) for j in range(i + 1, n_maps)]
     host_pcl = []
-    want_pcie = world == 1 and args.engine == "library" and not args.no_pcie and args.host_input == "none"
+    want_pcie = args.full and world == 1 and args.engine == "library" and not args.no_pcie and args.host_input == "none"
     if args.host_input == "pcl32" or want_pcie:           # pcl::PointXYZRGB as it lies in memory: x y z 1 | rgba pad pad pad
         PCL = np.dtype({"names": ["x", "y", "z", "w", "rgba"], "formats": ["<f4", "<f4", "<f4", "<f4", "<u4"], "offsets": [0, 4, 8, 12, 16],
                         "itemsize": 32})
@@ -334,6 +350,7 @@ def main():
             host_pcl.append(a)
 
     stats = {}
+    last = {}                                              # what the latest step returned to its caller (--dump-outputs)
 
     # Within a rank the maps and pairs are dealt once more over S contexts (one HIP stream, one host
     # thread each): a pair is a chain of dependent launches with a few host round trips, so one
@@ -351,8 +368,10 @@ def main():
         S = max(1, min(S, max(2, int(cpus // max(world, 1)) - (1 if world > 1 else 0))))
     else:
         S = max(1, min(S, max(2, int(cpus / (0.2 * max(n_gpus, 1))))))
-    ctxs = [ctx] + [mm.Context(local_rank) for _ in range(S - 1)]
-    tpool = ThreadPoolExecutor(S) if S > 1 else None
+    library_streams = world > 1 or args.engine in ("library", "shard", "devices")
+    # (the library engines deal the work to S streams inside libmm3d: only the Python-threaded one needs contexts of its own)
+    ctxs = [ctx] + ([] if library_streams else [mm.Context(local_rank) for _ in range(S - 1)])
+    tpool = ThreadPoolExecutor(S) if S > 1 and not library_streams else None
 
     def run_streams(fn):
         if tpool is None:
@@ -383,6 +402,7 @@ def main():
                           icp_iters=[int(x) for x in mine["icp_iterations"]], pairs_here=int(is_mine.sum()),
                           n_estimated=int(sum(1 for t in T if np.any(t))),
                           crc=zlib.crc32(np.ascontiguousarray(mine["transform"]).tobytes()) & 0xffffffff))
+        last.update(transforms=T, pairs=mine)
         return T
 
     def step_pipelined():
@@ -456,6 +476,7 @@ def main():
                           crc=zlib.crc32(np.ascontiguousarray(mine["transform"]).tobytes()) & 0xffffffff))
         for m in maps:
             m.free()
+        last.update(transforms=T, pairs=mine)
         return T
 
     def step_library():
@@ -485,12 +506,10 @@ def main():
                           icp_iters=[int(x) for x in mine["icp_iterations"]],
                           n_estimated=int(sum(1 for t in T if np.any(t))),
                           crc=zlib.crc32(np.ascontiguousarray(mine["transform"]).tobytes()) & 0xffffffff, records=mine))
+        last.update(transforms=T, pairs=mine)
         return T
 
-    if world > 1 or args.engine in ("library", "shard", "devices"):
-        for c in ctxs[1:]:
-            c.close()
-        ctxs = [ctx]
+    if library_streams:
         ctx.setStreams(S)
         step = step_library if (world == 1 and args.engine in ("library", "devices")) else step_sharded
     else:
@@ -504,11 +523,13 @@ def main():
             c.synchronize()
         torch.cuda.synchronize()
 
+    # HIP events around every kernel of the timed steps feed the per-kernel figures of --full only
+    kernel_events = args.full and not args.no_kernel_events
     for _ in range(args.warmup):
         step()
     for c in ctxs:
         c.profile_reset()
-        c.profile(not args.no_kernel_events)
+        c.profile(kernel_events)
     barrier()
     def host_waits():
         # (host waits for a stream, summed over the library's worker contexts: mm3d_debug_waits)
@@ -534,6 +555,8 @@ def main():
                 "cgroup_throttled_ms_per_step": round((cgroup_throttle() - thr0) / 1e3 / max(args.steps, 1), 2)}
     if w0 and w1:
         host_cpu["stream_waits_per_step"] = round((w1[0] - w0[0]) / max(args.steps, 1), 1)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last["transforms"], last["pairs"])
     sacia_certified = None
     if os.environ.get("MM3D_SACIA_STATS"):                 # (a study run: the collection costs a wait per batch of pairs)
         st = mm.sacia_stats()
@@ -541,6 +564,76 @@ def main():
                            "what": "SAC-IA's pick certified from the error sums in double (csrc/registration.hip::k_sacia_select), all steps of this run"}
     for c in ctxs:
         c.profile(False)
+    if world > 1:
+        t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        elapsed = float(t.item())
+
+    def headline():
+        """The contract's fields: the figure, its unit and sense, and the job it was measured on."""
+        n_pairs = stats["n_pairs"]
+        return {
+            "metric": "map-pairs/sec (normals+%s+%s+ICP, end to end incl. per-map features)"
+                      % (args.descriptor, "SAC-IA" if args.method == "SAC_IA" else "matching+RANSAC"),
+            "value": round(n_pairs * args.steps / elapsed, 4), "unit": "map-pairs/s", "n_gpus": n_gpus, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": round(1e3 * elapsed / max(args.steps, 1), 3), "higher_is_better": True,
+            "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "config": {"workload": f"{n_maps} maps x {n_pts} raw pts, {args.descriptor} + {args.method} + ICP refine, {n_pairs} pairs"
+                                   + (f", {args.window:g} m windows" if args.window > 0 else "") + (f", resolution {args.resolution:g}" if args.resolution > 0 else "")
+                                   + (f", '{args.scenes}' scenes, windows {args.overlap_step:g} of a side apart" if args.scenes != "independent" or args.overlap_step != 0.5 else "")
+                                   + (f", {args.sac_iterations} SAC-IA hypotheses" if args.sac_iterations > 0 else "")
+                                   + (" [DIAGNOSTIC: host pcl::PointXYZRGB input, upload inside the step]" if args.host_input != "none" else ""),
+                       "parallelism": (f"ONE process, one mm3d_estimate_maps_transforms call on the device list {dev_list} (mm3d_create_devices): maps by owner, "
+                                       f"bundles pulled with hipMemcpyPeerAsync, pairs by target owner, {S} streams per device, pair records through "
+                                       + ("one in-library ncclAllGather" if ctx.uses_rccl else "host memory (duplicate-device test hook: no RCCL)")
+                                       if dev_list else
+                                       f"one mm3d_estimate_maps_transforms call, {S} streams inside the library"
+                                       if world == 1 and args.engine == "library" else
+                                       f"mm3d_shard_*: maps by owner, pairs by target owner over {world} GPU(s) x {S} streams inside the library"
+                                       if step is step_sharded else
+                                       f"maps and pairs dealt over {S} streams (Python threads)"),
+                       "points_after_filter_mean": int(np.mean(stats["pts_filtered"])), "keypoints_mean": int(np.mean(stats["keypoints"]))},
+        }
+
+    def step_report():
+        """What the timed steps themselves report, at no cost beyond them."""
+        return {
+            "stage_seconds_last_step": {k: round(stats[k], 4) for k in ("t_features", "t_exchange", "t_pairs", "t_gather_graph")},
+            "maps_estimated": stats["n_estimated"],
+            "icp_iterations_histogram": {str(k): int(v) for k, v in zip(*np.unique(stats["icp_iters"], return_counts=True))},
+            "host_cpu": host_cpu,                           # the box's CPU quota bounds how many host threads can wait at once
+            **({"sacia_certified": sacia_certified} if sacia_certified else {}),
+            "pair_transforms_crc32": stats["crc"],          # same job, same bits: independent of --gpus / --streams
+            **({"rccl_gather_us": stats["rccl_gather_us"]} if "rccl_gather_us" in stats else {}),
+        }
+
+    def print_line(out):
+        # Every rank empties its C stdio buffer now (RCCL's banner sits there on each of them, and torchrun merges the ranks'
+        # stdout into one pipe), and rank 0 prints behind a barrier: the JSON line is the LAST line of the job's output.
+        try:
+            C.CDLL(None).fflush(None)
+            sys.stdout.flush()
+        except Exception:
+            pass
+        if world > 1:
+            dist.barrier()
+        if rank == 0:
+            print(json.dumps(out()), flush=True)
+
+    def close():
+        if tpool is not None:
+            tpool.shutdown()
+        for c in ctxs:
+            c.close()
+        if world > 1:
+            dist.destroy_process_group()
+
+    if not args.full:
+        # a plain run: the headline and what the timed steps report; nothing more runs on the GPU
+        print_line(lambda: {**headline(), **step_report()})
+        close()
+        return
+
     # N = 1: the same step with the clouds handed over the way the reference's callers hold them -- host arrays of
     # pcl::PointXYZRGB (stride 32) in pageable memory, uploaded inside the step.  A secondary figure, never `value`.
     pcie = None
@@ -559,10 +652,6 @@ def main():
                 "pair_transforms_crc32": stats["crc"]}
         args.host_input = "none"
         stats.clear(); stats.update(saved)
-    if world > 1:
-        t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed = float(t.item())
     prof = {}
     for c in ctxs:                                         # per-kernel HIP-event times, summed over the rank's streams
         for k, v in c.profile_entries().items():
@@ -744,8 +833,6 @@ def main():
         dist.barrier()
     if rank == 0:
         n_pairs = stats["n_pairs"]
-        ms_per_step = 1e3 * elapsed / max(args.steps, 1)
-        value = n_pairs * args.steps / elapsed
         # dominant kernel of this rank, by device time
         dom = max(prof.items(), key=lambda kv: kv[1]["ms"]) if prof else (None, None)
         roofline = None
@@ -837,26 +924,7 @@ def main():
         npts_f = stats["pts_filtered"]
         icp_pts = sum(npts_f[i] * it for (i, j), it in zip([(i, j) for (i, j) in pairs_idx], stats["icp_iters"]))
         out = {
-            "metric": "map-pairs/sec (normals+%s+%s+ICP, end to end incl. per-map features)"
-                      % (args.descriptor, "SAC-IA" if args.method == "SAC_IA" else "matching+RANSAC"),
-            "value": round(value, 4), "unit": "map-pairs/s", "n_gpus": n_gpus, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
-            "dtype": "f32", "data": "synthetic",
-            "config": {"workload": f"{n_maps} maps x {n_pts} raw pts, {args.descriptor} + {args.method} + ICP refine, {n_pairs} pairs"
-                                   + (f", {args.window:g} m windows" if args.window > 0 else "") + (f", resolution {args.resolution:g}" if args.resolution > 0 else "")
-                                   + (f", '{args.scenes}' scenes, windows {args.overlap_step:g} of a side apart" if args.scenes != "independent" or args.overlap_step != 0.5 else "")
-                                   + (f", {args.sac_iterations} SAC-IA hypotheses" if args.sac_iterations > 0 else "")
-                                   + (" [DIAGNOSTIC: host pcl::PointXYZRGB input, upload inside the step]" if args.host_input != "none" else ""),
-                       "parallelism": (f"ONE process, one mm3d_estimate_maps_transforms call on the device list {dev_list} (mm3d_create_devices): maps by owner, "
-                                       f"bundles pulled with hipMemcpyPeerAsync, pairs by target owner, {S} streams per device, pair records through "
-                                       + ("one in-library ncclAllGather" if ctx.uses_rccl else "host memory (duplicate-device test hook: no RCCL)")
-                                       if dev_list else
-                                       f"one mm3d_estimate_maps_transforms call, {S} streams inside the library"
-                                       if world == 1 and args.engine == "library" else
-                                       f"mm3d_shard_*: maps by owner, pairs by target owner over {world} GPU(s) x {S} streams inside the library"
-                                       if step is step_sharded else
-                                       f"maps and pairs dealt over {S} streams (Python threads)"),
-                       "points_after_filter_mean": int(np.mean(npts_f)), "keypoints_mean": int(np.mean(stats["keypoints"]))},
+            **headline(),
             # pairs / wall time of the per-pair stage alone, on prepared maps (measured after the step loop; null when
             # that pass did not run).  NOT n_pairs / (step - features): in the pipelined step most pairs run beside the features.
             "pair_stage_pairs_per_s": (pair_stage or {}).get("pairs_per_s"),
@@ -883,14 +951,8 @@ def main():
                                                **bound_of(k, v["ms"] / max(v["launches"], 1), v["bytes"] / max(v["launches"], 1)))
                                        for k, v in [kv for n_, kv in enumerate(sorted(iso.items(), key=lambda kv: -kv[1]["ms"]))
                                                     if n_ < 10 or kv[0] in ("desc_knn_mfma", "normals_radius", "icp_corr_reduce", "score_nn_reduce")]},
-            "stage_seconds_last_step": {k: round(stats[k], 4) for k in ("t_features", "t_exchange", "t_pairs", "t_gather_graph")},
             "top_kernels_ms_per_step": {k: round(v["ms"] / max(args.steps, 1), 3) for k, v in top},
-            "maps_estimated": stats["n_estimated"],
-            "icp_iterations_histogram": {str(k): int(v) for k, v in zip(*np.unique(stats["icp_iters"], return_counts=True))},
-            "host_cpu": host_cpu,                           # the box's CPU quota bounds how many host threads can wait at once
-            **({"sacia_certified": sacia_certified} if sacia_certified else {}),
-            "pair_transforms_crc32": stats["crc"],          # same job, same bits: independent of --gpus / --streams
-            **({"rccl_gather_us": stats["rccl_gather_us"]} if "rccl_gather_us" in stats else {}),
+            **step_report(),
             "roofline": roofline,
         }
         # ground truth: the generator knows every map's pose.  Error of the estimated pair transforms (source -> target)
@@ -928,12 +990,20 @@ def main():
         except Exception:
             pass
         print(json.dumps(out), flush=True)
-    if tpool is not None:
-        tpool.shutdown()
-    for c in ctxs:
-        c.close()
-    if world > 1:
-        dist.destroy_process_group()
+    close()
+
+
+def dump_outputs(path, transforms, pairs):
+    """What the last timed step handed its caller, as <path>/<name>.npy (float32 as computed, integer fields as float64):
+    the global transform of every map and every field of the pair records, in the order the step returned them."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {"global_transforms": np.asarray(np.stack(transforms) if len(transforms) else np.zeros((0, 4, 4)), dtype=np.float32),
+              "pair_transform": np.asarray(pairs["transform"], dtype=np.float32),
+              "pair_confidence": np.asarray(pairs["confidence"], dtype=np.float64)}
+    for f in ("source_idx", "target_idx", "icp_iterations", "n_correspondences", "n_inliers", "icp_correspondences"):
+        arrays["pair_" + f] = np.asarray(pairs[f], dtype=np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def cpu_baseline(host, n_maps, n_pairs, gpu_sample, check, descriptor="FPFH", method="SAC_IA", params=None):

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""gpurun_out/<tag>_* (written by scripts/profile_round.sh on the GPU box) -> profiles/<tag>_*.
+"""$RESULTS_DIR/<tag>_* (written by scripts/profile_round.sh on the GPU box; results/ by default) -> profiles/<tag>_*.
 usage: assemble_profiles.py <tag>"""
 import csv
 import json
@@ -9,7 +9,7 @@ import sys
 
 tag = sys.argv[1]
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-src = lambda n: os.path.join(root, "gpurun_out", f"{tag}_{n}")
+src = lambda n: os.path.join(root, os.environ.get("RESULTS_DIR", "results"), f"{tag}_{n}")
 dst = lambda n: os.path.join(root, "profiles", f"{tag}_{n}")
 f = {r["kernel"]: (int(r["dispatches"]), float(r["FETCH_SIZE"])) for r in csv.DictReader(open(src("pmc_FETCH_SIZE.csv")))}
 w = {r["kernel"]: (int(r["dispatches"]), float(r["WRITE_SIZE"])) for r in csv.DictReader(open(src("pmc_WRITE_SIZE.csv")))}

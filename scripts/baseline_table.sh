@@ -1,19 +1,26 @@
 #!/bin/bash
 # BASELINE.md's results table: the five BASELINE.json configurations on one GPU, each with the CPU baselines
-# B1 (one thread) and B2 (all cores) timed in the same run on the same box.  Run through gpurun:
-#   scripts/baseline_table.sh r02        -> gpurun_out/r02_table_cfg{1..5}.json
+# B1 (one thread) and B2 (all cores) timed in the same run on the same box.  Run from the repository root on the GPU box:
+#   scripts/baseline_table.sh r02        -> $RESULTS_DIR/r02_table_cfg{1..5}.json (results/ by default)
 # scripts/fill_baseline_table.py r02 then writes the table into BASELINE.md and copies the lines to profiles/.
+# Each row is one `bench.py --full` run under a time limit of its own; the first row that fails, crashes or runs out of
+# time ends the script (nothing more starts on the GPU after it).
 set -u
 TAG=${1:-round}
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 cd "$R"
-mkdir -p gpurun_out
+OUT=${RESULTS_DIR:-results}
+mkdir -p "$OUT"
 run() {   # run <cfg> <bench args...>       (ONLY="5 1": just those rows)
   local cfg=$1; shift
   if [ -n "${ONLY:-}" ] && [[ " $ONLY " != *" $cfg "* ]]; then return; fi
-  timeout 1500 python3 bench.py "$@" 2> "/tmp/table_cfg$cfg.err" | tail -1 > "gpurun_out/${TAG}_table_cfg$cfg.json"
-  python3 -c "import json; d=json.load(open('gpurun_out/${TAG}_table_cfg$cfg.json')); print('cfg$cfg', d['value'], (d.get('cpu_baseline') or {}).get('value'), (d.get('cpu_baseline_all_cores') or {}).get('value'), (d.get('parity_check') or {}).get('ok'), d.get('icp_iterations_histogram'), d.get('gt_error', {}).get('recovered_within_0.5'))" \
-    || { echo "cfg$cfg failed:"; tail -5 "/tmp/table_cfg$cfg.err"; }
+  local line="$OUT/${TAG}_table_cfg$cfg.json" err="/tmp/table_cfg$cfg.err"
+  timeout -k 10 1500 python3 bench.py --full "$@" > "/tmp/table_cfg$cfg.out" 2> "$err"
+  local rc=$?
+  if [ $rc -ne 0 ]; then echo "cfg$cfg failed (exit $rc), stopping:"; tail -5 "$err"; exit 1; fi
+  tail -1 "/tmp/table_cfg$cfg.out" > "$line"
+  python3 -c "import json, sys; d=json.load(open(sys.argv[1])); print('cfg$cfg', d['value'], (d.get('cpu_baseline') or {}).get('value'), (d.get('cpu_baseline_all_cores') or {}).get('value'), (d.get('parity_check') or {}).get('ok'), d.get('icp_iterations_histogram'), d.get('gt_error', {}).get('recovered_within_0.5'))" "$line" \
+    || { echo "cfg$cfg: no bench line, stopping:"; tail -5 "$err"; exit 1; }
 }
 # (steps of 4 and 14 ms: enough of them that one late host thread does not show -- five steps of row 2 gave 358 ... 435)
 run 1 --maps 2 --points 10000 --steps 30 --warmup 3

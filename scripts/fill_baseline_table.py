@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""gpurun_out/<tag>_table_cfg{1..5}.json (scripts/baseline_table.sh) -> the Results table of BASELINE.md and
+"""$RESULTS_DIR/<tag>_table_cfg{1..5}.json (scripts/baseline_table.sh; results/ by default) -> the Results table of BASELINE.md and
 profiles/<tag>_table_cfgN.json.   usage: fill_baseline_table.py <tag>"""
 import json
 import os
@@ -10,7 +10,7 @@ tag = sys.argv[1]
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 rows = []
 for cfg in (1, 2, 3, 4, 5, "4indoor", "2lattice", "3lattice"):
-    src = os.path.join(root, "gpurun_out", f"{tag}_table_cfg{cfg}.json")
+    src = os.path.join(root, os.environ.get("RESULTS_DIR", "results"), f"{tag}_table_cfg{cfg}.json")
     try:
         d = json.load(open(src))
     except Exception:

@@ -791,8 +791,9 @@ def test_bench_ranks_and_streams_give_the_same_bits():
 
     a = run([sys.executable, "bench.py", "--streams", "1"] + common)
     b = run([sys.executable, "bench.py", "--streams", "4"] + common)
+    # (--full: the multi-rank report path -- the isolated pass on rank 0, the per-kernel figures -- runs too)
     c = run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-             "--master-port", "29533", "bench.py", "--gpus", "2", "--streams", "2"] + common,
+             "--master-port", "29533", "bench.py", "--gpus", "2", "--streams", "2", "--full"] + common,
             env={"MM3D_BENCH_BACKEND": "gloo", "MM3D_BENCH_DEVICE": "0"})
     # the N > 1 driver (mm3d_shard_*) on one rank, and on three ranks (uneven ownership: maps 0..3 -> ranks 0 1 2 2)
     d = run([sys.executable, "bench.py", "--streams", "4", "--engine", "shard"] + common)
@@ -803,6 +804,7 @@ def test_bench_ranks_and_streams_give_the_same_bits():
     assert len(set(crcs)) == 1, crcs
     assert a["maps_estimated"] == b["maps_estimated"] == c["maps_estimated"] == d["maps_estimated"] == e["maps_estimated"]
     assert c["n_gpus"] == 2 and e["n_gpus"] == 3
+    assert "roofline" in c and "roofline" not in a          # the full line from several ranks; the plain line without it
 
 
 def test_round4_shortcuts_do_not_change_a_bit():
@@ -813,8 +815,8 @@ def test_round4_shortcuts_do_not_change_a_bit():
     import json
     import subprocess
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    common = [sys.executable, "bench.py", "--maps", "3", "--points", "120000", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--no-pcie",
-              "--streams", "3"]
+    common = [sys.executable, "bench.py", "--full", "--maps", "3", "--points", "120000", "--steps", "1", "--warmup", "0", "--no-cpu-baseline",
+              "--no-pcie", "--streams", "3"]
 
     def run(env):
         e = dict(os.environ)

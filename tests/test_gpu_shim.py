@@ -1,7 +1,7 @@
 """The reference's C++ API through include/map_merge_3d_shim.hpp on the MI355X: every free function of
 features.h / matching.h / map_merging.h called the way R/src/map_merging.cpp:212-269 and
 map_merge_tool.cpp:37-49 call them, and every result held bit for bit against direct calls of the C ABI
-(which the other -m gpu tests hold against the oracle).  The binary is tests/shim/_build/shim_check,
+(which the other -m gpu tests hold against the oracle).  The binary is oracle/_ref/shim_check,
 built by __graft_entry__.build() where the reference's headers exist (tests/shim/build.sh)."""
 import os
 import struct
@@ -13,7 +13,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EXE = os.path.join(ROOT, "tests", "shim", "_build", "shim_check")
+EXE = os.path.join(ROOT, "oracle", "_ref", "shim_check")
 
 
 class Reader:
