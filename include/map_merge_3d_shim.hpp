@@ -81,10 +81,17 @@ inline mm3d_ctx *ctx()
 {
   // estimateMapsTransforms deals its per-cloud and per-pair loops to 16 HIP streams inside the
   // library (same bits as one stream, about twice the throughput); MM3D_STREAMS overrides
+  // MM3D_MAP_CACHE=<maps> (default 0 = off): the node calls estimateMapsTransforms on a timer with every robot's latest map,
+  // most of them unchanged since the last tick; with the cache on, an unchanged map's features (and, under MATCHING, its
+  // pairs) are reused, bit for bit (mm3d_set_map_cache).  A device list has no cache: that MM3D_EUNSUPPORTED is ignored.
   static mm3d_ctx *c = [] {
     const char *s = std::getenv("MM3D_STREAMS");
     const int n = s ? std::atoi(s) : 16;
-    return make_ctx(n >= 1 && n <= 64 ? n : 16, true);      // (the estimation engine is the one that may span several GPUs)
+    mm3d_ctx *e = make_ctx(n >= 1 && n <= 64 ? n : 16, true);   // (the estimation engine is the one that may span several GPUs)
+    const char *m = std::getenv("MM3D_MAP_CACHE");
+    const int maps = m ? std::atoi(m) : 0;
+    if (maps > 0) (void)mm3d_set_map_cache(e, maps);
+    return e;
   }();
   return c;
 }

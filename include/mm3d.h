@@ -180,6 +180,35 @@ int mm3d_last_run_stage_seconds(const mm3d_ctx *ctx, double *features_s, double 
  * the slowest device had finished its pairs, and the duration of the RCCL gather of the pair records alone */
 int mm3d_last_run_device_seconds(const mm3d_ctx *ctx, double *exchange_s, double *pairs_s, double *gather_s);
 size_t mm3d_last_run_map_sizes(const mm3d_ctx *ctx, size_t *points, size_t *keypoints, size_t capacity);
+/* Feature / pair cache of mm3d_estimate_maps_transforms (off by default).  max_maps > 0 keeps the bundles of up to max_maps
+ * distinct input clouds and the pair records among them; 0 turns it off and frees it.  The results of every call are the
+ * bits of the same call on a context without a cache in the same generator state, and so is the generator state it leaves.
+ *   - A map hits when its n packed records (x, y, z, rgba as mm3d_cloud_create packs them; the padding of wider records does
+ *     not count, floats compare as bits) equal a cached cloud's, byte for byte, and every parameter the per-cloud loop reads
+ *     is the same (resolution, descriptor_radius, outliers_min_neighbours, normal_radius, keypoint_type, keypoint_threshold,
+ *     descriptor_type, max_correspondence_distance, estimation_method).  The slot does not matter: maps may be reordered,
+ *     added, or passed twice.  Deciding costs one device pass over the uploaded records and one wait per map; a hit runs
+ *     nothing else on the device for that map.  Null and empty clouds are never cached.
+ *   - A pair record is reused when both its maps hit (in the same source -> target order) and the parameters the pair loop
+ *     reads are the same (estimation_method, refine_transform, inlier_threshold, max_correspondence_distance,
+ *     max_iterations, matching_k, transform_epsilon) -- and, under SAC_IA, the rand() state it starts from: without
+ *     mm3d_srand to the same seed before each call the generator has moved on, and SAC_IA reuses the features only.
+ *     The draws of a reused pair are replayed, so the generator ends where it would have.  confidence_threshold and
+ *     output_resolution are read by neither key: the pose graph runs on every call.
+ *   - Memory: each cached map keeps its packed input records on the device (16 B per point, 8 MB for 500 000 points) next
+ *     to its filtered points, keypoints, descriptor rows and search structures.
+ *   - Least recently used maps are evicted (at the end of a call; a call's own maps are never evicted while it runs),
+ *     and with them every pair record that names them; at most 4 * max_maps^2 pair records are kept.  A call that fails
+ *     leaves the cache as it was.  The cache survives mm3d_set_streams and goes with mm3d_destroy.
+ * MM3D_EINVAL: ctx NULL or max_maps < 0; MM3D_EUNSUPPORTED: a device-list context (mm3d_create_devices).  Not for
+ * mm3d_shard_* or mm3d_compose_maps. */
+int mm3d_set_map_cache(mm3d_ctx *ctx, int max_maps);
+int mm3d_get_map_cache(const mm3d_ctx *ctx);               /* max_maps, 0 when off or ctx NULL */
+void mm3d_map_cache_clear(mm3d_ctx *ctx);                  /* drops every cached map and pair record */
+/* out[0] map hits, [1] map misses, [2] pairs reused, [3] pairs computed (of calls that succeeded), [4] maps held now, [5] device
+ * bytes held by the cache (raw copies, filtered points, keypoints, descriptor rows and their search structures, as of the
+ * last call); counters since the last reset (reset != 0 resets them after reading).  All zero when the cache is off. */
+int mm3d_map_cache_stats(const mm3d_ctx *ctx, long long out[6], int reset);   /* MM3D_EINVAL for NULL */
 
 /* ---- cloud objects -------------------------------------------------------------------- */
 int mm3d_cloud_create(mm3d_ctx *ctx, const void *points, size_t n, size_t stride, size_t rgba_offset,

@@ -206,6 +206,33 @@ class Context:
         bit-identical for every setting)."""
         self._ck(lib().mm3d_set_streams(self._h, int(n)))
 
+    def lastRunMapSizes(self):
+        """mm3d_last_run_map_sizes: (points after filtering, keypoints after pruning) per cloud of the last estimateMapsTransforms."""
+        f = lib().mm3d_last_run_map_sizes
+        f.restype = C.c_size_t
+        n = f(self._h, None, None, C.c_size_t(0))
+        pts, kps = np.zeros(max(n, 1), dtype=np.uint64), np.zeros(max(n, 1), dtype=np.uint64)
+        f(self._h, pts.ctypes.data_as(C.c_void_p), kps.ctypes.data_as(C.c_void_p), C.c_size_t(n))
+        return pts[:n], kps[:n]
+
+    def setMapCache(self, max_maps: int):
+        """mm3d_set_map_cache: estimateMapsTransforms keeps the features of up to max_maps distinct clouds and the pair
+        records among them, and reuses them while clouds and parameters are unchanged (bit-identical results); 0 = off."""
+        self._ck(lib().mm3d_set_map_cache(self._h, int(max_maps)))
+
+    def getMapCache(self) -> int:
+        return lib().mm3d_get_map_cache(self._h)
+
+    def clearMapCache(self):
+        lib().mm3d_map_cache_clear(self._h)
+
+    def mapCacheStats(self, reset: bool = False) -> dict:
+        """mm3d_map_cache_stats: counters since the last reset, and what the cache holds now."""
+        out = (C.c_longlong * 6)()
+        self._ck(lib().mm3d_map_cache_stats(self._h, out, 1 if reset else 0))
+        keys = ("map_hits", "map_misses", "pairs_reused", "pairs_computed", "maps_held", "device_bytes")
+        return dict(zip(keys, (int(v) for v in out)))
+
     def synchronize(self):
         self._ck(lib().mm3d_synchronize(self._h))
 

@@ -279,6 +279,8 @@ void mm3d_destroy(mm3d_ctx *ctx)
   if (!ctx) return;
   device_set_destroy(ctx->device_set);                  // (the communicators go before the streams they were used on)
   ctx->device_set = nullptr;
+  delete ctx->map_cache;                                // (its buffers go back to the pools of the contexts that made them)
+  ctx->map_cache = nullptr;
   for (mm3d_ctx *p : ctx->peers) mm3d_destroy(p);
   ctx->peers.clear();
   for (mm3d_ctx *h : ctx->helpers) mm3d_destroy(h);
@@ -900,14 +902,18 @@ static void estimate_maps_streams(mm3d_ctx *ctx, const mm3d_cloud_view *clouds, 
   for (size_t i = 0; i + 1 < n; ++i)
     for (size_t j = i + 1; j < n; ++j) all.emplace_back(i, j);
   std::vector<mm3d_map *> maps(n, nullptr);
+  // mm3d_set_map_cache: maps[i] is the cache's (a hit, or a miss handed over once built) where borrowed[i] is set
+  MapCacheBase *const cache = ctx->map_cache;
+  std::vector<char> borrowed(n, 0);
   struct MapsGuard {                                    // the maps go when the call ends, whichever way
     std::vector<mm3d_map *> &m;
+    const std::vector<char> &borrowed;
     ~MapsGuard()
     {
-      for (mm3d_map *x : m)
-        if (x) { delete x->points; delete x->keypoints; delete x->desc; delete x; }
+      for (size_t i = 0; i < m.size(); ++i)
+        if (m[i] && !borrowed[i]) { delete m[i]->points; delete m[i]->keypoints; delete m[i]->desc; delete m[i]; }
     }
-  } maps_guard{maps};
+  } maps_guard{maps, borrowed};
   std::vector<mm3d_pair_result> rec(all.size());
   std::vector<char> ready(n, 0), done(all.size(), 0);
   std::mutex mu;
@@ -1014,6 +1020,23 @@ static void estimate_maps_streams(mm3d_ctx *ctx, const mm3d_cloud_view *clouds, 
         std::unique_ptr<mm3d_cloud> raw(cloud_from_memory(c, clouds[i].points, clouds[i].points ? clouds[i].n : 0,
                                                           clouds[i].stride ? clouds[i].stride : 16,
                                                           clouds[i].stride ? clouds[i].rgba_offset : 12));
+        if (cache && raw->n > 0) {
+          // an unchanged map: its bundle is published at once, nothing else runs on the device for it
+          if (const mm3d_map *hit = cache->lookup(c, i, raw.get())) {
+            raw.reset();
+            {
+              std::lock_guard<std::mutex> lk(mu);
+              maps[i] = const_cast<mm3d_map *>(hit);
+              borrowed[i] = 1;
+              ready[i] = 1;
+              ctx->last_points[i] = hit->points->n;
+              ctx->last_keypoints[i] = hit->keypoints->n;
+              ctx->last_features_s = std::max(ctx->last_features_s, since_start());
+            }
+            cv.notify_all();
+            continue;
+          }
+        }
         // owned here until it is published: a throw from map_prepare_impl must not strand the map's buffers
         struct MapFree {
           void operator()(mm3d_map *x) const { delete x->points; delete x->keypoints; delete x->desc; delete x; }
@@ -1023,33 +1046,43 @@ static void estimate_maps_streams(mm3d_ctx *ctx, const mm3d_cloud_view *clouds, 
         c->private_objects = true;
         std::unique_ptr<mm3d_map, MapFree> held(map_features_impl(c, raw.get(), params, false));
         map_prepare_impl(c, held.get(), params);        // (ends in that wait)
-        raw.reset();
         c->private_objects = false;
+        const bool keep = cache && raw->n > 0;
         {
           std::lock_guard<std::mutex> lk(mu);
           mm3d_map *m = held.release();
           maps[i] = m;
+          if (keep) {
+            cache->insert(i, std::move(raw), m);         // (the cache owns the map and its raw points from here on)
+            borrowed[i] = 1;
+          }
           ready[i] = 1;
           ctx->last_points[i] = m->points->n;
           ctx->last_keypoints[i] = m->keypoints->n;
           ctx->last_features_s = std::max(ctx->last_features_s, since_start());
         }
+        raw.reset();
         cv.notify_all();
       }
-      std::vector<size_t> mine;
+      std::vector<size_t> mine, work_q;
       std::vector<PairWork> work;
       while (claim_pairs(mine)) {
         work.clear();
+        work_q.clear();
         for (size_t p : mine) {
           const mm3d_map *ms = maps[all[p].first], *mt = maps[all[p].second];
           if (ms->keypoints->n > 0 && mt->keypoints->n > 0) {
-            advance_states(p);
+            advance_states(p);                          // (a reused pair's draws are replayed all the same)
             rec[p].source_idx = all[p].first;
             rec[p].target_idx = all[p].second;
+            if (cache && cache->pair_lookup(all[p].first, all[p].second, state_at[p], &rec[p])) continue;
             work.push_back(PairWork{ms, mt, &rec[p], state_at[p]});
+            work_q.push_back(p);
           }
         }
         if (!work.empty()) pairs_estimate_batch(c, work.data(), work.size(), params);
+        if (cache)
+          for (size_t k = 0; k < work.size(); ++k) cache->pair_insert(all[work_q[k]].first, all[work_q[k]].second, work[k].rnd, *work[k].out);
         for (size_t p : mine)
           if (maps[all[p].first]->keypoints->n > 0 && maps[all[p].second]->keypoints->n > 0) done[p] = 1;
       }
@@ -1079,7 +1112,8 @@ static void estimate_maps_streams(mm3d_ctx *ctx, const mm3d_cloud_view *clouds, 
     ctx->rnd = state_at[P];                             // where the sequential loop leaves the generator
   } else {
     // a target turned out to have no keypoints: the states after that pair were positioned wrongly.
-    // Redo the pair loop the reference's way, on the caller's stream.
+    // Redo the pair loop the reference's way, on the caller's stream.  (The map cache is left out of it: the records it took
+    // above are still right for the states they name.)
     ctx->rnd = rnd0;
     std::fill(done.begin(), done.end(), 0);
     for (size_t q = 0; q < P; ++q) {
@@ -1492,13 +1526,25 @@ static void estimate_maps_sequential(mm3d_ctx *ctx, const mm3d_cloud_view *cloud
   ctx->last_keypoints.assign(n, 0);
   std::vector<std::unique_ptr<mm3d_map, std::function<void(mm3d_map *)>>> maps;
   auto del = [](mm3d_map *m) { if (m) { delete m->points; delete m->keypoints; delete m->desc; delete m; } };
+  auto borrow = [](mm3d_map *) {};                     // a bundle of the map cache's (mm3d_set_map_cache)
+  MapCacheBase *const cache = ctx->map_cache;
   for (size_t i = 0; i < n; ++i) {
     // a null / empty map (robot subscribed but no message yet) counts as "no keypoints"
     std::unique_ptr<mm3d_cloud> raw(cloud_from_memory(ctx, clouds[i].points, clouds[i].points ? clouds[i].n : 0,
                                                       clouds[i].stride ? clouds[i].stride : 16,
                                                       clouds[i].stride ? clouds[i].rgba_offset : 12));
-    maps.emplace_back(map_features_impl(ctx, raw.get(), params), del);
-    map_prepare_impl(ctx, maps.back().get(), params);   // search structures and k-NN target operands, once per map
+    const mm3d_map *hit = cache && raw->n > 0 ? cache->lookup(ctx, i, raw.get()) : nullptr;
+    if (hit) {
+      maps.emplace_back(const_cast<mm3d_map *>(hit), borrow);
+    } else {
+      maps.emplace_back(map_features_impl(ctx, raw.get(), params), del);
+      map_prepare_impl(ctx, maps.back().get(), params);   // search structures and k-NN target operands, once per map
+      if (cache && raw->n > 0) {                          // built from the same upload: the cache takes it and the map
+        cache->insert(i, std::move(raw), maps.back().get());
+        mm3d_map *m = maps.back().release();
+        maps.back() = std::unique_ptr<mm3d_map, std::function<void(mm3d_map *)>>(m, borrow);
+      }
+    }
     ctx->last_points[i] = maps.back()->points->n;
     ctx->last_keypoints[i] = maps.back()->keypoints->n;
   }
@@ -1512,7 +1558,17 @@ static void estimate_maps_sequential(mm3d_ctx *ctx, const mm3d_cloud_view *cloud
         r.source_idx = i; r.target_idx = j;
         pairs.push_back(r);
       }
-  for (auto &r : pairs) pair_estimate_impl(ctx, maps[r.source_idx].get(), maps[r.target_idx].get(), params, true, &r);
+  for (auto &r : pairs) {
+    const mm3d_map *ms = maps[r.source_idx].get(), *mt = maps[r.target_idx].get();
+    if (cache && cache->pair_lookup(r.source_idx, r.target_idx, ctx->rnd, &r)) {
+      // reused: the generator still moves on by the draws the pair would have taken
+      pair_rand_replay(ctx->rnd, params->estimation_method, cloud_host(ctx, ms->keypoints), params->inlier_threshold, params->max_iterations);
+      continue;
+    }
+    const GlibcRand r0 = ctx->rnd;
+    pair_estimate_impl(ctx, ms, mt, params, true, &r);
+    if (cache) cache->pair_insert(r.source_idx, r.target_idx, r0, r);
+  }
   if (pairs_out) std::memcpy(pairs_out, pairs.data(), pairs.size() * sizeof(mm3d_pair_result));
   if (n_pairs_out) *n_pairs_out = pairs.size();
   int st = global_transforms(pairs.data(), pairs.size(), params->confidence_threshold, n, out_T, n_out);
@@ -2020,11 +2076,19 @@ int mm3d_estimate_maps_transforms(mm3d_ctx *ctx, const mm3d_cloud_view *clouds, 
       estimate_maps_devices(ctx, clouds, n, params, out_T, n_out, pairs_out, n_pairs_out);
       return;
     }
-    if (!ctx->helpers.empty()) {
+    // mm3d_set_map_cache: what this call adds is committed only when it succeeds (a throw below aborts it)
+    struct CacheCall {
+      MapCacheBase *c;
+      bool ok = false;
+      ~CacheCall() { if (c && !ok) c->abort(); }
+    } cache_call{ctx->map_cache};
+    if (ctx->map_cache) ctx->map_cache->begin(n, params);
+    if (!ctx->helpers.empty())
       estimate_maps_streams(ctx, clouds, n, params, out_T, n_out, pairs_out, n_pairs_out);
-      return;
-    }
-    estimate_maps_sequential(ctx, clouds, n, params, out_T, n_out, pairs_out, n_pairs_out);
+    else
+      estimate_maps_sequential(ctx, clouds, n, params, out_T, n_out, pairs_out, n_pairs_out);
+    if (ctx->map_cache) ctx->map_cache->commit();
+    cache_call.ok = true;
   });
 }
 

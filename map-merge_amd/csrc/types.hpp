@@ -12,10 +12,35 @@
 
 #include "common.hpp"
 
-namespace mm3d { struct DeviceSet; }
+namespace mm3d {
+struct DeviceSet;
+
+// The feature / pair cache of mm3d_estimate_maps_transforms (mm3d_set_map_cache; the concrete class is map_cache.cpp's).  The
+// drivers in capi.cpp only see this interface, so the host code links without it (tests/host_san).  One call at a time -- the
+// context's lock: begin, then lookups and inserts from any worker thread of the call, then commit (the call succeeded) or
+// abort (it did not: the cache is left exactly as it was before the call).
+struct MapCacheBase {
+  virtual ~MapCacheBase() = default;
+  virtual void begin(size_t n_maps, const mm3d_params *p) = 0;
+  // map `slot`'s packed upload `raw` (non-empty, on c's stream): the cached bundle, borrowed for the call, or null.  One launch and
+  // one wait on c (a second compare-only launch and wait when the digest names another candidate than the slot's last entry).
+  virtual const mm3d_map *lookup(Context *c, size_t slot, const mm3d_cloud *raw) = 0;
+  // the bundle built from `raw` after lookup(slot) missed, complete on the device: the cache owns both from here on (the raw
+  // points are kept for the exact compares of later calls)
+  virtual void insert(size_t slot, std::unique_ptr<mm3d_cloud> raw, mm3d_map *m) = 0;
+  // pair (source slot, target slot) of this call from generator state rnd (read under SAC_IA only): true and *out = the
+  // record, with this call's indices, when one is reused
+  virtual bool pair_lookup(size_t s, size_t t, const GlibcRand &rnd, mm3d_pair_result *out) = 0;
+  virtual void pair_insert(size_t s, size_t t, const GlibcRand &rnd, const mm3d_pair_result &r) = 0;
+  virtual void commit() = 0;
+  virtual void abort() noexcept = 0;
+};
+}  // namespace mm3d
 
 // the opaque C handles are these structs
 struct mm3d_ctx : mm3d::Context {
+  // mm3d_set_map_cache: null = off (the drivers take their plain path).  Owned by this context; never set on helpers or peers.
+  mm3d::MapCacheBase *map_cache = nullptr;
   // mm3d_set_streams: helper contexts (one HIP stream + one host thread each while a call is running)
   // that mm3d_estimate_maps_transforms deals maps and pairs to; owned by this context
   std::vector<mm3d_ctx *> helpers;
@@ -321,6 +346,12 @@ int estimate_transform(Context *c, const mm3d_cloud *sp, const mm3d_cloud *skp, 
                        double eps, float T[16], bool execute);
 int global_transforms(const mm3d_pair_result *pairs, size_t n_pairs, double thr, size_t n_clouds, float *out,
                       size_t *n_out);
+
+// map_cache.hip
+struct CloudDigest { unsigned long long h0 = 0, h1 = 0; bool equal = false; };
+// one pass over n packed records at `a` (device, c's stream; ends in a wait): their 128-bit digest (want_digest) and whether
+// they equal the n records at `hint` bit for bit (hint != null; equal is false without one)
+CloudDigest cloud_digest_compare(Context *c, const float4 *a, const float4 *hint, size_t n, bool want_digest);
 
 // devices.cpp (host only): one process, several GPUs
 // The RCCL communicators of a device list (ncclCommInitAll) and what the devices exchange: the maps' bundles, pulled by the
