@@ -127,7 +127,18 @@ int mm3d_debug_float_chain(mm3d_ctx *ctx, const float *incr, const unsigned *hit
 /* test hook: out[i] = the device's restatement of glibc's expf (fn 0), atanf (1), sinf (2), cosf (3) of x[i] or
  * atan2f(y[i], x[i]) (4) -- csrc/libm_exact.hpp, the functions the CPU path's PCL calls through libm */
 int mm3d_debug_libm(mm3d_ctx *ctx, int fn, const float *x, const float *y, int n, float *out);
-/* (fn 5: the raw v_exp_f32, 2^x, of the certified SIFT pass.)
+/* (fn 5: the raw v_exp_f32, 2^x, of the certified SIFT pass.
+ *  fn 6: expf (|x| < 88) as the SIFT kernels call it: the 2^(i/32) table staged in LDS, no range checks (sift.hip).
+ *  fn 7: lm::fdiv_const(x, y, (float)(1.0 / (double)y)), the division by a constant of the SIFT weights, with the
+ *        reciprocal prepared as sift.hip prepares SiftScales::rcp.
+ *  fn 8: acos_abs_greater(x, y) as 1.0f / 0.0f: computePairFeatures' "acos(fabs(x)) > acos(fabs(y))" in double.
+ *  fn 9: atan2_fast(y, x), the polynomial arc tangent of the certified SPFH bins (fpfh.hip).
+ *  fn 10, 11: the raw v_rsq_f32 and v_rcp_f32 of x.)
+ * test hook: per pair i of (p1[4 i], n1[4 i]) and (p2[4 i], n2[4 i]) (x, y, z, w records), out[11 i ..] = the bits of f1, f2, f3
+ * of the SPFH's exact pair features, their branch (0 no switch, 1 switched, 2 f4 == 0: the oracle's mo_pair_features code),
+ * the exact path's three bins, the certified path's (pair_bins_fast) ok flag and its three bins (csrc/fpfh.hip) */
+int mm3d_debug_pair_bins(mm3d_ctx *ctx, const float *p1, const float *n1, const float *p2, const float *n2, int n, int *out);
+/*
  * test hooks of the certified SIFT decision (csrc/sift_cert.hpp; the later octaves of detectKeypoints(SIFT),
  * R/src/features.cpp:45-62): the unsorted scale space of octave `octave` (0-based) on `points` -- val[5 i + s] and
  * bound[5 i + s] >= |the CPU path's float DoG - val| for point i of the octave's cloud -- *n_out = that cloud's size

@@ -12,50 +12,11 @@
 #include <string>
 
 #include "device_util.hpp"
+#include "capi_guard.hpp"
 
 using namespace mm3d;
 
 namespace {
-
-template <class F>
-int guarded(mm3d_ctx *ctx, F &&f)
-{
-  if (!ctx) return MM3D_EINVAL;
-  std::lock_guard<std::mutex> lock(ctx->mu);
-  // error flags waiting for the next sync() belong to the call that recorded them: a call that ends with an
-  // exception must not leave them (their pinned words get reused) to the next one, on this context or its helpers
-  struct Clean {
-    mm3d_ctx *c;
-    ~Clean()
-    {
-      auto one = [](mm3d_ctx *r) {
-        r->deferred.clear();
-        r->private_objects = false;
-        for (mm3d_ctx *h : r->helpers) { h->deferred.clear(); h->private_objects = false; }
-      };
-      one(c);
-      for (mm3d_ctx *p : c->peers) one(p);
-    }
-  } clean{ctx};
-  try {
-    if (hipSetDevice(ctx->device) != hipSuccess) throw Error(MM3D_EDEVICE, "hipSetDevice failed");
-    f();
-    if (!ctx->deferred.empty()) ctx->sync();      // nothing recorded by this call is left unchecked
-    return MM3D_OK;
-  } catch (const Error &e) {
-    ctx->err = e.what();
-    return e.status;
-  } catch (const std::bad_alloc &) {
-    ctx->err = "out of host memory";
-    return MM3D_ENOMEM;
-  } catch (const std::exception &e) {
-    ctx->err = e.what();
-    return MM3D_EDEVICE;
-  } catch (...) {
-    ctx->err = "unknown error";
-    return MM3D_EDEVICE;
-  }
-}
 
 const char *kDescNames[] = {"PFH", "PFHRGB", "FPFH", "RSD", "SHOT", "SC3D"};
 const char *kDescFields[] = {"pfh", "pfhrgb", "fpfh", "r_min", "shot", "shape_context"};
@@ -353,9 +314,11 @@ int mm3d_debug_float_chain(mm3d_ctx *ctx, const float *incr, const unsigned *hit
 }
 int mm3d_debug_libm(mm3d_ctx *ctx, int fn, const float *x, const float *y, int n, float *out)
 {
-  if (n < 0 || fn < 0 || fn > 5 || (n && (!x || !out || (fn == 4 && !y)))) return MM3D_EINVAL;
+  const bool two = fn == 4 || fn == 7 || fn == 8 || fn == 9;
+  if (n < 0 || fn < 0 || fn > 11 || (n && (!x || !out || (two && !y)))) return MM3D_EINVAL;
   return guarded(ctx, [&] { debug_libm(ctx, fn, x, y, n, out); });
 }
+// (mm3d_debug_pair_bins: csrc/fpfh.hip)
 int mm3d_debug_sift_cert_octave(mm3d_ctx *ctx, const mm3d_cloud *points, double min_scale, int octave, float *val, float *bound, size_t capacity,
                                 size_t *n_out)
 {

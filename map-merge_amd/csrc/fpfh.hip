@@ -11,6 +11,7 @@
 //      to sum 100.
 // Algorithmic traffic: SPFH 156 B per support point; weighting 132 B per gathered row.
 #include "sorted_nb.hpp"
+#include "capi_guard.hpp"
 
 namespace mm3d {
 
@@ -70,12 +71,14 @@ __global__ void k_hil_inverse(const float4 *__restrict__ hil_pts, int n, int *__
 // difference vector, so its angles are (-angle2, -angle1): whenever exactly one of the two calls takes the "switch p1 and p2"
 // branch, both continue with the same source point, difference vector and normals.  On a tie neither switches and the
 // results differ (tests/test_oracle_cpu.py::test_pair_features_are_symmetric_under_the_swap_except_on_ties).
+// `branch` (optional, the test hook's): the oracle's mo_pair_features code -- 0 no switch, 1 switched, 2 the f4 == 0 exit.
 __device__ __forceinline__ void pair_features(const float4 &p1, const float4 &n1, const float4 &p2, const float4 &n2,
-                                              float &f1, float &f2, float &f3, bool *symmetric = nullptr)
+                                              float &f1, float &f2, float &f3, bool *symmetric = nullptr, int *branch = nullptr)
 {
   float dx = p2.x - p1.x, dy = p2.y - p1.y, dz = p2.z - p1.z;
   const float f4 = sqrtf(dx * dx + dy * dy + dz * dz);
   if (symmetric) *symmetric = true;
+  if (branch) *branch = 2;
   if (f4 == 0.0f) { f1 = f2 = f3 = 0.0f; return; }
   float ax = n1.x, ay = n1.y, az = n1.z, bx = n2.x, by = n2.y, bz = n2.z;
   const float angle1 = (ax * dx + ay * dy + az * dz) / f4;
@@ -83,6 +86,7 @@ __device__ __forceinline__ void pair_features(const float4 &p1, const float4 &n1
   // acos(fabs(angle1)) > acos(fabs(angle2)) evaluated in double on the CPU: device_util.hpp::acos_abs_greater
   const bool sw = acos_abs_greater(angle1, angle2);
   if (symmetric) *symmetric = sw || acos_abs_greater(angle2, angle1);
+  if (branch) *branch = sw ? 1 : 0;
   if (sw) {
     float t;
     t = ax; ax = bx; bx = t; t = ay; ay = by; by = t; t = az; az = bz; bz = t;
@@ -109,6 +113,16 @@ __device__ __forceinline__ int bin_of(double x)
   return h >= kBins ? kBins - 1 : h;
 }
 
+// the three bins of pair_features' floats as the CPU path computes them (o_fpfh.c::point_spfh): d_pi = float(1 / (2 pi_f)),
+// the rest in double
+__device__ __forceinline__ void pair_bins_exact(float f1, float f2, float f3, int &h1, int &h2, int &h3)
+{
+  const float d_pi = 1.0f / (2.0f * 3.14159274f);
+  h1 = bin_of(kBins * (((double)f1 + 3.14159265358979323846) * (double)d_pi));
+  h2 = bin_of(kBins * (((double)f2 + 1.0) * 0.5));
+  h3 = bin_of(kBins * (((double)f3 + 1.0) * 0.5));
+}
+
 // ---- the three BINS of a pair, certified (round 6) ------------------------------------------------------------------
 // A pair's features only matter through floor(11 (f1 + pi) / (2 pi)), floor(11 (f2 + 1) / 2), floor(11 (f3 + 1) / 2) and
 // the "switch p1 and p2" decision acos|a1| > acos|a2|.  pair_features above reproduces the CPU path's floats -- restated
@@ -127,7 +141,7 @@ __device__ __forceinline__ int bin_of(double x)
 //   y = n2 . (n1 x v^), x = n1 . n2     CPU within 17 kappa u and 3 u;  here within (7 kappa + 11) u and 3 u
 //   f1 = atan2(y, x)         a perturbation delta of (x, y) with delta <= rho / 2, rho = |(x, y)|, turns the angle by at most
 //                            1.6 delta / rho;  glibc's atan2f within 1 ulp (<= 5 u);  the polynomial arc tangent below within
-//                            10 u in all (fit 0.04 u, float evaluation, the two folds; tests/test_gpu_parity.py checks it)
+//                            10 u in all (fit 0.04 u, float evaluation, the two folds; tests/test_libm_exact.py checks it through mm3d_debug_libm fn 9)
 // The constants below are TWICE these sums.  In bin units t = 11 (f + c) / w the float evaluation of t adds <= 22 u.
 __device__ __forceinline__ float atan_poly01(float z)      // atan(z) on [0, 1]: z P(z^2), |error| < 4e-8 before rounding
 {
@@ -288,7 +302,6 @@ k_spfh(const float4 *__restrict__ q_pts, const int2 *__restrict__ items, int n_i
     const int x0 = max(cell_floor(lx - ri, g.minx, g.inv), 0), x1 = min(cell_floor(hx + ri, g.minx, g.inv), g.dx - 1);
     const int y0 = max(cell_floor(ly - ri, g.miny, g.inv), 0), y1 = min(cell_floor(hy + ri, g.miny, g.inv), g.dy - 1);
     const int z0 = max(cell_floor(lz - ri, g.minz, g.inv), 0), z1 = min(cell_floor(hz + ri, g.minz, g.inv), g.dz - 1);
-    const float d_pi = 1.0f / (2.0f * 3.14159274f);
     const float4 *sp = s_pts[wave];
     const float4 *sn = s_nrm[wave];
     unsigned short *pool = s_pool[wave];
@@ -379,9 +392,7 @@ k_spfh(const float4 *__restrict__ q_pts, const int2 *__restrict__ items, int n_i
                 if (act && !ok) {
                   float f1, f2, f3;
                   pair_features(qo, no, p, np, f1, f2, f3, &sym);
-                  h1 = bin_of(kBins * (((double)f1 + 3.14159265358979323846) * (double)d_pi));
-                  h2 = bin_of(kBins * (((double)f2 + 1.0) * 0.5));
-                  h3 = bin_of(kBins * (((double)f3 + 1.0) * 0.5));
+                  pair_bins_exact(f1, f2, f3, h1, h2, h3);
                 }
               }
 #ifdef MM3D_SPFH_VERIFY
@@ -398,9 +409,7 @@ k_spfh(const float4 *__restrict__ q_pts, const int2 *__restrict__ items, int n_i
                     MM3D_SPFH_STAT(5, 1);
                     float f1, f2, f3;
                     pair_features(p, np, qo, no, f1, f2, f3);
-                    h1 = bin_of(kBins * (((double)f1 + 3.14159265358979323846) * (double)d_pi));
-                    h2 = bin_of(kBins * (((double)f2 + 1.0) * 0.5));
-                    h3 = bin_of(kBins * (((double)f3 + 1.0) * 0.5));
+                    pair_bins_exact(f1, f2, f3, h1, h2, h3);
                   }
                   const unsigned onec = 1u << ((c & 1) << 4);
                   atomicAdd(&hist[h1][c >> 1], onec);
@@ -508,6 +517,55 @@ k_fpfh_weight(const float4 *__restrict__ q_pts /* keypoints, Hilbert order, .w =
       left -= fit;
     }
   }
+}
+
+// ---- test hooks (tests/test_libm_exact.py, tests/test_gpu_spfh_pairs.py): the inline functions k_spfh calls, one argument /
+// pair per lane
+__global__ void k_debug_atan2_fast(const float *__restrict__ x, const float *__restrict__ y, int n, float *__restrict__ out)
+{
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = atan2_fast(y[i], x[i]);
+}
+
+// out[11 i ..]: f1, f2, f3 bits of pair_features, its branch code, the exact path's three bins, pair_bins_fast's ok flag and
+// its three bins
+__global__ void k_debug_pair_bins(const float4 *__restrict__ p1, const float4 *__restrict__ n1, const float4 *__restrict__ p2,
+                                  const float4 *__restrict__ n2, int n, int *__restrict__ out)
+{
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float4 a = p1[i], na = n1[i], b = p2[i], nb = n2[i];
+  float f1, f2, f3;
+  int br;
+  pair_features(a, na, b, nb, f1, f2, f3, nullptr, &br);
+  int h1, h2, h3;
+  pair_bins_exact(f1, f2, f3, h1, h2, h3);
+  int g1 = -1, g2 = -1, g3 = -1;
+  const bool ok = pair_bins_fast(a, na, b, nb, g1, g2, g3);
+  int *o = out + (size_t)i * 11;
+  o[0] = __float_as_int(f1); o[1] = __float_as_int(f2); o[2] = __float_as_int(f3); o[3] = br;
+  o[4] = h1; o[5] = h2; o[6] = h3;
+  o[7] = ok ? 1 : 0; o[8] = g1; o[9] = g2; o[10] = g3;
+}
+
+void debug_atan2_fast(Context *c, const float *x_dev, const float *y_dev, int n, float *out_dev)
+{
+  if (n > 0) MM3D_LAUNCH(c, "debug_libm", 0, k_debug_atan2_fast, dim3(div_up(n, 256)), dim3(256), 0, x_dev, y_dev, n, out_dev);
+}
+
+static void debug_pair_bins(Context *c, const float *p1_host, const float *n1_host, const float *p2_host, const float *n2_host, int n, int *out_host)
+{
+  if (n <= 0) return;
+  DevBuf<float4> p1(c, n), n1(c, n), p2(c, n), n2(c, n);
+  DevBuf<int> o(c, (size_t)n * 11);
+  MM3D_HIP(hipMemcpyAsync(p1.get(), p1_host, (size_t)n * 16, hipMemcpyHostToDevice, c->stream));
+  MM3D_HIP(hipMemcpyAsync(n1.get(), n1_host, (size_t)n * 16, hipMemcpyHostToDevice, c->stream));
+  MM3D_HIP(hipMemcpyAsync(p2.get(), p2_host, (size_t)n * 16, hipMemcpyHostToDevice, c->stream));
+  MM3D_HIP(hipMemcpyAsync(n2.get(), n2_host, (size_t)n * 16, hipMemcpyHostToDevice, c->stream));
+  MM3D_LAUNCH(c, "debug_pair_bins", 0, k_debug_pair_bins, dim3(div_up(n, 256)), dim3(256), 0, (const float4 *)p1.get(), (const float4 *)n1.get(),
+              (const float4 *)p2.get(), (const float4 *)n2.get(), n, o.get());
+  MM3D_HIP(hipMemcpyAsync(out_host, o.get(), (size_t)n * 11 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  c->sync();
 }
 
 __global__ void k_compact_rows(const float *__restrict__ in, const int *__restrict__ flags, const int *__restrict__ pos,
@@ -622,6 +680,14 @@ mm3d_desc *compute_fpfh(Context *c, const mm3d_cloud *points, const mm3d_normals
 }
 
 }  // namespace mm3d
+
+// the C entry point of the pair hook (include/mm3d.h) lives with its kernel: the host-only builds of the library
+// (tests/host_san) link capi.cpp without this file
+extern "C" int mm3d_debug_pair_bins(mm3d_ctx *ctx, const float *p1, const float *n1, const float *p2, const float *n2, int n, int *out)
+{
+  if (n < 0 || (n && (!p1 || !n1 || !p2 || !n2 || !out))) return MM3D_EINVAL;
+  return mm3d::guarded(ctx, [&] { mm3d::debug_pair_bins(ctx, p1, n1, p2, n2, n, out); });
+}
 
 #ifdef MM3D_SPFH_STATS
 extern "C" void mm3d_debug_spfh_stats(unsigned long long *out, int reset)

@@ -107,8 +107,9 @@ MM3D_HD float expf_glibc(float x)
 // elementary functions on the IBM RISC System/6000 processor", Theorem: the final fma rounds correctly when the
 // reciprocal is the correctly rounded one and the quotient estimate is within one ulp).  Five operations
 // instead of the hardware's division macro (ten).  Valid away from overflow / underflow of a / b and of the
-// remainders, which is what fdiv_const_ok() checks for the callers' ranges; tests/test_libm_exact.py sweeps it
-// against IEEE division.
+// remainders: on the SIFT weights that is |a| >= 2^-96 b (below it expf of the quotient is 1.0f whatever its last
+// bit).  tests/test_libm_exact.py sweeps both callers' divisions (every intensity numerator, every sigma^2 with
+// quotients at the midpoints between floats) against IEEE division, host and device builds.
 MM3D_HD float fdiv_const(float a, float b, float rcp)
 {
   float q = a * rcp;

@@ -217,6 +217,8 @@ void harris_response(Context *c, const mm3d_cloud *points, const mm3d_normals *n
 // fpfh.hip
 mm3d_desc *compute_fpfh(Context *c, const mm3d_cloud *points, const mm3d_normals *normals,
                         mm3d_cloud *keypoints, double radius);
+// test hook: atan2_fast(y, x) of the certified SPFH bins on device arrays (mm3d_debug_libm fn 9)
+void debug_atan2_fast(Context *c, const float *x_dev, const float *y_dev, int n, float *out_dev);
 
 // pfh.hip
 mm3d_desc *compute_pfh(Context *c, const mm3d_cloud *points, const mm3d_normals *normals,

@@ -108,6 +108,10 @@ int mo_keypoints_harris(const mo_point *in, const mo_normal *normals, int n, dou
 void mo_harris_response(const mo_point *in, const mo_normal *normals, int n, double radius, float *response);
 /* test hook (o_fpfh.c): pcl::computePairFeatures on n pairs, out[5 i ..] = {f1, f2, f3, f4, branch taken} */
 void mo_pair_features(const mo_point *p1, const mo_normal *n1, const mo_point *p2, const mo_normal *n2, int n, float *out);
+/* test hooks (o_fpfh.c): the three SPFH bins point_spfh gives each pair, out[3 i ..]; and the pair features' "switch p1 and
+ * p2" test acos(fabs(a1)) > acos(fabs(a2)) (1 / 0) */
+void mo_spfh_pair_bins(const mo_point *p1, const mo_normal *n1, const mo_point *p2, const mo_normal *n2, int n, int *out);
+int mo_acos_abs_greater(float a1, float a2);
 /* computeLocalDescriptors(FPFH): R/src/features.cpp:99-150 +
  * dispatch_descriptors.h:40.  keypoints are pruned IN PLACE (n_kp updated);
  * desc must hold n_kp*33 floats; returns the number of surviving keypoints. */
@@ -207,7 +211,8 @@ int mo_last_double_sums_correspondences(void);       /* last-iteration count of 
 double mo_transform_score(const mo_point *src, int ns, const mo_point *tgt,
                           int nt, const float T[16], double max_distance);
 
-/* the host libm over arrays: fn 0 expf, 1 atanf, 2 sinf, 3 cosf (of x), 4 atan2f(y, x)  (o_libm.c) */
+/* the host libm over arrays: fn 0 expf, 1 atanf, 2 sinf, 3 cosf (of x), 4 atan2f(y, x); fn 5 acos(fabs(x)) > acos(fabs(y))
+ * in double as 1 / 0, the pair features' switch (o_libm.c) */
 void mo_libm_eval(int fn, const float *x, const float *y, int n, float *out);
 /* small dense helpers exposed for tests */
 void mo_umeyama_f32(const float *src, const float *dst, int n, float T[16]);

@@ -18,6 +18,14 @@
 
 #define NB 11
 
+/* computePairFeatures' "switch p1 and p2" test, acos(fabs(angle1)) > acos(fabs(angle2)), evaluated in double; one helper
+ * for pair_features and mo_pair_features, exposed to the tests as mo_libm_eval fn 5 (the device restates it as
+ * device_util.hpp::acos_abs_greater) */
+static inline int acos_abs_greater(float angle1, float angle2)
+{
+  return acos(fabs(angle1)) > acos(fabs(angle2));
+}
+
 static void pair_features(const mo_point *p1, const mo_normal *n1, const mo_point *p2,
                           const mo_normal *n2, float *f1, float *f2, float *f3, float *f4)
 {
@@ -27,7 +35,7 @@ static void pair_features(const mo_point *p1, const mo_normal *n1, const mo_poin
   float a[3] = {n1->nx, n1->ny, n1->nz}, b[3] = {n2->nx, n2->ny, n2->nz};
   float angle1 = (a[0] * d[0] + a[1] * d[1] + a[2] * d[2]) / *f4;
   float angle2 = (b[0] * d[0] + b[1] * d[1] + b[2] * d[2]) / *f4;
-  if (acos(fabs(angle1)) > acos(fabs(angle2))) {
+  if (acos_abs_greater(angle1, angle2)) {
     /* switch p1 and p2 */
     float t;
     for (int i = 0; i < 3; ++i) { t = a[i]; a[i] = b[i]; b[i] = t; d[i] *= -1.0f; }
@@ -60,7 +68,7 @@ void mo_pair_features(const mo_point *p1, const mo_normal *n1, const mo_point *p
     if (f4 == 0.0f) { o[4] = 2.0f; continue; }
     float angle1 = (n1[i].nx * d[0] + n1[i].ny * d[1] + n1[i].nz * d[2]) / f4;
     float angle2 = (n2[i].nx * d[0] + n2[i].ny * d[1] + n2[i].nz * d[2]) / f4;
-    o[4] = (acos(fabs(angle1)) > acos(fabs(angle2))) ? 1.0f : 0.0f;
+    o[4] = acos_abs_greater(angle1, angle2) ? 1.0f : 0.0f;
   }
 }
 
@@ -72,29 +80,47 @@ static inline int floor_to_int(double x)
   return (int)f;
 }
 
+/* computePointSPFHSignature's three bins of one pair's features */
+static inline void spfh_bins(float f1, float f2, float f3, int h[3])
+{
+  const float d_pi = 1.0f / (2.0f * (float)M_PI);
+  h[0] = floor_to_int(NB * ((f1 + M_PI) * d_pi));
+  h[1] = floor_to_int(NB * ((f2 + 1.0) * 0.5));
+  h[2] = floor_to_int(NB * ((f3 + 1.0) * 0.5));
+  for (int k = 0; k < 3; ++k) {
+    if (h[k] < 0) h[k] = 0;
+    if (h[k] >= NB) h[k] = NB - 1;
+  }
+}
+
 static void point_spfh(const mo_point *cloud, const mo_normal *normals, int p_idx, const int *nbr,
                        int cnt, float *hist /* 33 */)
 {
-  const float d_pi = 1.0f / (2.0f * (float)M_PI);
   float hist_incr = 100.0f / (float)(cnt - 1);
   for (int j = 0; j < cnt; ++j) {
     if (p_idx == nbr[j]) continue;
     float f1, f2, f3, f4;
     pair_features(&cloud[p_idx], &normals[p_idx], &cloud[nbr[j]], &normals[nbr[j]], &f1, &f2, &f3, &f4);
-    int h = floor_to_int(NB * ((f1 + M_PI) * d_pi));
-    if (h < 0) h = 0;
-    if (h >= NB) h = NB - 1;
-    hist[h] += hist_incr;
-    h = floor_to_int(NB * ((f2 + 1.0) * 0.5));
-    if (h < 0) h = 0;
-    if (h >= NB) h = NB - 1;
-    hist[NB + h] += hist_incr;
-    h = floor_to_int(NB * ((f3 + 1.0) * 0.5));
-    if (h < 0) h = 0;
-    if (h >= NB) h = NB - 1;
-    hist[2 * NB + h] += hist_incr;
+    int h[3];
+    spfh_bins(f1, f2, f3, h);
+    hist[h[0]] += hist_incr;
+    hist[NB + h[1]] += hist_incr;
+    hist[2 * NB + h[2]] += hist_incr;
   }
 }
+
+/* Test hook: the three bins point_spfh gives the pair (p1[i], p2[i]), out[3 i ..] (tests/test_gpu_spfh_pairs.py) */
+void mo_spfh_pair_bins(const mo_point *p1, const mo_normal *n1, const mo_point *p2, const mo_normal *n2, int n, int *out)
+{
+  for (int i = 0; i < n; ++i) {
+    float f1, f2, f3, f4;
+    pair_features(&p1[i], &n1[i], &p2[i], &n2[i], &f1, &f2, &f3, &f4);
+    spfh_bins(f1, f2, f3, out + 3 * (size_t)i);
+  }
+}
+
+/* Test hook: acos_abs_greater of o_libm.c's mo_libm_eval fn 5 */
+int mo_acos_abs_greater(float a1, float a2) { return acos_abs_greater(a1, a2); }
 
 int mo_fpfh_raw(const mo_point *surface, const mo_normal *normals, int n,
                 const mo_point *keypoints, int n_kp, double radius, float *desc,

@@ -165,6 +165,16 @@ def pair_features(p1, n1, p2, n2):
     return out
 
 
+def spfh_pair_bins(p1, n1, p2, n2):
+    """The three SPFH bins computePointSPFHSignature gives each pair (test hook): rows {f1 bin, f2 bin, f3 bin}."""
+    p1, p2 = _pts(p1), _pts(p2)
+    n1 = np.ascontiguousarray(n1, dtype=NORMAL)
+    n2 = np.ascontiguousarray(n2, dtype=NORMAL)
+    out = np.empty((len(p1), 3), dtype=np.int32)
+    lib().mo_spfh_pair_bins(_p(p1), _p(n1), _p(p2), _p(n2), len(p1), _p(out))
+    return out
+
+
 def descriptors_pfh(surface, nrm, keypoints, radius):
     """computeLocalDescriptors(PFH): returns (pruned keypoints, desc[n, 125])."""
     surface = _pts(surface)
@@ -420,7 +430,8 @@ def estimate_maps_transforms(clouds, params: Params):
 
 
 def libm_eval(fn, x, y=None):
-    """The host libm's expf (0), atanf (1), sinf (2), cosf (3) of x or atan2f(y, x) (4), element by element."""
+    """The host libm's expf (0), atanf (1), sinf (2), cosf (3) of x or atan2f(y, x) (4), element by element; fn 5: the pair
+    features' switch acos(fabs(x)) > acos(fabs(y)) in double, as 1.0 / 0.0."""
     x = np.ascontiguousarray(x, dtype=np.float32)
     y = np.ascontiguousarray(y if y is not None else x, dtype=np.float32)
     out = np.empty_like(x)

@@ -119,6 +119,28 @@ int main(void)
     if (a != 50 || b != 50 || c != 0) ++failures;
     mo_grid_free(g);
   }
+  /* the pair-feature test hooks: the SPFH bins of a few pairs (a coincident one, a zero normal) and the switch test */
+  {
+    enum { NP = 64 };
+    mo_normal n1[NP], n2[NP];
+    float a[NP], b[NP], sw[NP], feats[5 * NP];
+    int bins[3 * NP], bad = 0;
+    for (int i = 0; i < NP; ++i) {
+      n1[i] = (mo_normal){urand() - 0.5f, urand() - 0.5f, urand() - 0.5f, 0.0f};
+      n2[i] = (mo_normal){urand() - 0.5f, urand() - 0.5f, urand() - 0.5f, 0.0f};
+      a[i] = 2.2f * urand() - 1.1f;
+      b[i] = 2.2f * urand() - 1.1f;
+    }
+    n2[1] = (mo_normal){0.0f, 0.0f, 0.0f, 0.0f};
+    mo_spfh_pair_bins(clouds[0], n1, clouds[0] + 1, n2, NP, bins);
+    mo_spfh_pair_bins(clouds[0], n1, clouds[0], n2, 1, bins);                 /* f4 == 0 */
+    mo_pair_features(clouds[0], n1, clouds[0] + 1, n2, NP, feats);
+    mo_libm_eval(5, a, b, NP, sw);
+    for (int i = 0; i < 3 * NP; ++i) bad += bins[i] < 0 || bins[i] > 10;
+    for (int i = 0; i < NP; ++i) bad += sw[i] != 0.0f && sw[i] != 1.0f;
+    printf("pair hooks: %d out of range\n", bad);
+    failures += bad != 0;
+  }
   for (int m = 0; m < MAPS; ++m) free(clouds[m]);
   printf(failures ? "FAILED: %d checks\n" : "sanitizer driver ok (%d failed checks)\n", failures);
   return failures ? 1 : 0;
