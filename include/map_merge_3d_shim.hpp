@@ -84,13 +84,25 @@ inline mm3d_ctx *ctx()
   // MM3D_MAP_CACHE=<maps> (default 0 = off): the node calls estimateMapsTransforms on a timer with every robot's latest map,
   // most of them unchanged since the last tick; with the cache on, an unchanged map's features (and, under MATCHING, its
   // pairs) are reused, bit for bit (mm3d_set_map_cache).  A device list has no cache: that MM3D_EUNSUPPORTED is ignored.
+  // MM3D_ICP=point_to_plane: the pair stage refines with point-to-plane ICP instead of the reference's point-to-point
+  // (mm3d_set_icp_method); point_to_point or unset keeps the reference's.  Not available on a device list: with MM3D_DEVICES
+  // set as well this throws rather than quietly running point-to-point.
   static mm3d_ctx *c = [] {
+    const char *icp = std::getenv("MM3D_ICP");
+    const std::string icp_method = icp ? icp : "";
+    if (!icp_method.empty() && icp_method != "point_to_point" && icp_method != "point_to_plane")
+      throw std::runtime_error("mm3d: MM3D_ICP must be point_to_point or point_to_plane, not '" + icp_method + "'");
+    const char *devices = std::getenv("MM3D_DEVICES");
+    if (icp_method == "point_to_plane" && devices && *devices)
+      throw std::runtime_error("mm3d: MM3D_ICP=point_to_plane is not available with MM3D_DEVICES (a device list carries no normals)");
     const char *s = std::getenv("MM3D_STREAMS");
     const int n = s ? std::atoi(s) : 16;
     mm3d_ctx *e = make_ctx(n >= 1 && n <= 64 ? n : 16, true);   // (the estimation engine is the one that may span several GPUs)
     const char *m = std::getenv("MM3D_MAP_CACHE");
     const int maps = m ? std::atoi(m) : 0;
     if (maps > 0) (void)mm3d_set_map_cache(e, maps);
+    if (icp_method == "point_to_plane" && mm3d_set_icp_method(e, MM3D_ICP_POINT_TO_PLANE) != MM3D_OK)
+      throw std::runtime_error(std::string("mm3d: ") + mm3d_last_error(e));
     return e;
   }();
   return c;

@@ -45,6 +45,8 @@ typedef enum { MM3D_DESC_PFH = 0, MM3D_DESC_PFHRGB, MM3D_DESC_FPFH, MM3D_DESC_RS
 typedef enum { MM3D_KP_SIFT = 0, MM3D_KP_HARRIS } mm3d_keypoint;
 /* R/include/map_merge_3d/matching.h:103 */
 typedef enum { MM3D_EST_MATCHING = 0, MM3D_EST_SAC_IA } mm3d_estimation_method;
+/* the ICP of the pair stage (mm3d_set_icp_method; not an enum of the reference's: it has point-to-point only) */
+typedef enum { MM3D_ICP_POINT_TO_POINT = 0, MM3D_ICP_POINT_TO_PLANE = 1 } mm3d_icp_method;
 
 /* enums::to_string / enums::from_string (R/include/map_merge_3d/enum.h:30-67) and the
  * PointCloud2 field-name table of R/src/dispatch_descriptors.h:38-48. */
@@ -220,6 +222,33 @@ void mm3d_map_cache_clear(mm3d_ctx *ctx);                  /* drops every cached
  * bytes held by the cache (raw copies, filtered points, keypoints, descriptor rows and their search structures, as of the
  * last call); counters since the last reset (reset != 0 resets them after reading).  All zero when the cache is off. */
 int mm3d_map_cache_stats(const mm3d_ctx *ctx, long long out[6], int reset);   /* MM3D_EINVAL for NULL */
+/* ICP of the pair stage (off the reference's path; MM3D_ICP_POINT_TO_POINT, the reference's, by default).
+ * MM3D_ICP_POINT_TO_PLANE: PCL's IterativeClosestPoint with TransformationEstimationPointToPlaneLLS, the target's normals
+ * being exactly mm3d_compute_normals(target points, normal_radius).  The loop is the point-to-point one in every respect
+ * but the estimate: the source transformed by the current T in float, the exact float nearest neighbour accepted at
+ * d2 <= max_correspondence_distance^2, fewer than 3 correspondences stop (not converged), T <- Tinc * T in float, and the
+ * convergence tests of DefaultConvergenceCriteria (max_iterations -- reported as converged, as in PCL --, the rotation /
+ * translation of Tinc against transform_epsilon, the change of the mean point-to-point d2 below 1e-12).  The estimate: for
+ * each correspondence (s = transformed source point, d = target point, n = its normal) whose normal is finite, the row
+ * [a, b, c, nx, ny, nz] with a = nz sy - ny sz, b = nx sz - nz sx, c = ny sx - nx sy and r = n.d - n.s; AtA and Atr are
+ * summed in double, AtA x = Atr is solved in double, and Tinc = [Rz(x2) Ry(x1) Rx(x0) | x3 x4 x5].  A correspondence whose
+ * normal is not finite counts (and its d2 enters the MSE) but adds no row.  The sign of a normal does not matter (AtA and
+ * Atr do not change under n -> -n).  Unlike PCL, a degenerate system is defined: with fewer than 6 rows, or a pivot of the
+ * (unpivoted LDLt) solve at or below 1e-12 * trace(AtA) / 6 -- a single plane, a line --, the loop stops, not converged,
+ * with T as it was before that iteration (PCL inverts the singular matrix).
+ *   - Applies to the ICP of mm3d_estimate_maps_transforms (every driver, with or without the map cache) and of
+ *     mm3d_pair_estimate; transformScore (the pair's confidence) stays point-to-point.  mm3d_estimate_transform_icp and
+ *     mm3d_estimate_transform mirror reference functions that take no normals: they stay point-to-point whatever the setting.
+ *   - Maps keep their normals (mm3d_map_features made them anyway) and mm3d_map_prepare makes them for maps that lack them
+ *     (mm3d_map_from_parts, maps made while the context was point-to-point); a pair whose target has none makes them on
+ *     first use.  Memory: 16 B per filtered point of every map, cached maps included (mm3d_set_map_cache), and only
+ *     while the setting is point-to-plane.
+ *   - The setting reaches the context's mm3d_set_streams helpers, in either order of the two calls.  Results are
+ *     bit-identical for every stream count, batch and cache setting, as for point-to-point.
+ * MM3D_EINVAL: ctx NULL or an unknown method; MM3D_EUNSUPPORTED: a device-list context (mm3d_create_devices), whose bundles
+ * carry no normals -- nor does mm3d_shard_begin, which returns MM3D_EUNSUPPORTED on a point-to-plane context. */
+int mm3d_set_icp_method(mm3d_ctx *ctx, int method);
+int mm3d_get_icp_method(const mm3d_ctx *ctx);              /* MM3D_ICP_*, MM3D_EINVAL for NULL */
 
 /* ---- cloud objects -------------------------------------------------------------------- */
 int mm3d_cloud_create(mm3d_ctx *ctx, const void *points, size_t n, size_t stride, size_t rgba_offset,
@@ -292,6 +321,14 @@ int mm3d_estimate_transform_icp(mm3d_ctx *ctx, const mm3d_cloud *source, const m
                                 const float initial_guess[16], double max_correspondence_distance,
                                 double outlier_rejection_threshold, int max_iterations,
                                 double transformation_epsilon, float T[16]);
+/* Point-to-plane ICP (mm3d_set_icp_method states the loop and the estimate) from initial_guess, whatever the context's
+ * setting.  target_normals: one per target point, in its order (mm3d_compute_normals of the target, or the caller's).
+ * MM3D_EINVAL when their count differs from the target's.  mm3d_last_icp_iterations / mm3d_last_icp_converged report on it;
+ * a degenerate system returns MM3D_OK, not converged, with T = the transform before the degenerate iteration. */
+int mm3d_estimate_transform_icp_plane(mm3d_ctx *ctx, const mm3d_cloud *source, const mm3d_cloud *target,
+                                      const mm3d_normals *target_normals, const float initial_guess[16],
+                                      double max_correspondence_distance, int max_iterations, double transformation_epsilon,
+                                      float T[16]);
 /* estimateTransform (matching.h:129, matching.cpp:223-257) */
 int mm3d_estimate_transform(mm3d_ctx *ctx, const mm3d_cloud *source_points, const mm3d_cloud *source_keypoints,
                             const mm3d_desc *source_descriptors, const mm3d_cloud *target_points,

@@ -55,6 +55,11 @@ class EstimationMethod(enum.IntEnum):  # matching.h:103
     SAC_IA = 1
 
 
+class IcpMethod(enum.IntEnum):      # mm3d_icp_method (not a reference enum)
+    POINT_TO_POINT = 0
+    POINT_TO_PLANE = 1
+
+
 class MapMergingParams(C.Structure):
     """R/include/map_merge_3d/map_merging.h:28-44, field for field."""
     _fields_ = [("resolution", C.c_double), ("descriptor_radius", C.c_double),
@@ -233,6 +238,13 @@ class Context:
         keys = ("map_hits", "map_misses", "pairs_reused", "pairs_computed", "maps_held", "device_bytes")
         return dict(zip(keys, (int(v) for v in out)))
 
+    def setIcpMethod(self, method):
+        """mm3d_set_icp_method: the pair stage's ICP, IcpMethod.POINT_TO_POINT (the reference's, the default) or POINT_TO_PLANE."""
+        self._ck(lib().mm3d_set_icp_method(self._h, int(method)))
+
+    def getIcpMethod(self) -> "IcpMethod":
+        return IcpMethod(lib().mm3d_get_icp_method(self._h))
+
     def synchronize(self):
         self._ck(lib().mm3d_synchronize(self._h))
 
@@ -358,6 +370,19 @@ class Context:
             C.c_double(max_correspondence_distance), C.c_double(outlier_rejection_threshold), int(max_iterations),
             C.c_double(transformation_epsilon), T.ctypes.data_as(C.c_void_p)))
         self.last_icp_iterations = lib().mm3d_last_icp_iterations(self._h)
+        return _Tout(T)
+
+    def estimateTransformICPPlane(self, source_points, target_points, target_normals, initial_guess, max_correspondence_distance,
+                                  max_iterations=100, transformation_epsilon=0.0):
+        """mm3d_estimate_transform_icp_plane: point-to-plane ICP from initial_guess (target_normals: one per target point)."""
+        g = _T(initial_guess)
+        T = np.zeros(16, dtype=np.float32)
+        self._ck(lib().mm3d_estimate_transform_icp_plane(
+            self._h, source_points._h, target_points._h, target_normals._h, g.ctypes.data_as(C.c_void_p),
+            C.c_double(max_correspondence_distance), int(max_iterations), C.c_double(transformation_epsilon),
+            T.ctypes.data_as(C.c_void_p)))
+        self.last_icp_iterations = lib().mm3d_last_icp_iterations(self._h)
+        self.last_icp_converged = lib().mm3d_last_icp_converged(self._h)
         return _Tout(T)
 
     def estimateTransform(self, source_points, source_keypoints, source_descriptors, target_points,

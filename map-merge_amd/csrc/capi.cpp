@@ -219,6 +219,7 @@ static void set_streams_one(mm3d_ctx *ctx, int n_streams)
     mm3d_ctx *h = nullptr;
     const int st = mm3d_create(ctx->device, &h);
     if (st != MM3D_OK) throw Error(st, "mm3d_set_streams: could not create a helper context");
+    h->icp_method = ctx->icp_method;                    // (mm3d_set_icp_method before mm3d_set_streams)
     ctx->helpers.push_back(h);
   }
 }
@@ -648,6 +649,7 @@ static mm3d_map *map_features_impl(mm3d_ctx *ctx, const mm3d_cloud *raw, const m
   m->points = filt.release();
   m->keypoints = kp.release();
   m->desc = desc.release();
+  if (ctx->icp_method) m->normals = std::move(nrm);    // point-to-plane ICP reads them (mm3d_set_icp_method)
   return m;
 }
 
@@ -674,6 +676,7 @@ int mm3d_map_from_parts(mm3d_ctx *ctx, mm3d_cloud *points, mm3d_cloud *keypoints
 
 static void map_prepare_impl(mm3d_ctx *ctx, mm3d_map *m, const mm3d_params *p)
 {
+  if (ctx->icp_method && !m->normals) m->normals.reset(compute_normals(ctx, m->points, p->normal_radius));
   prepare_pair_search(ctx, m->points, p->max_correspondence_distance, p->max_correspondence_distance);
   if (p->estimation_method == MM3D_EST_SAC_IA) prepare_sacia_target(ctx, m->keypoints, (float)p->max_correspondence_distance);
   desc_knn_prepare_target(ctx, m->desc);
@@ -696,9 +699,32 @@ void mm3d_map_free(mm3d_ctx *ctx, mm3d_map *m)
   delete m;
 }
 
+// The normals point-to-plane ICP reads of a pair's target map: a map that mm3d_map_prepare did not give them (a map made
+// while the context was point-to-point, a cached one of such a call, one from parts) gets them on first use -- under its
+// points' lock, complete on the device before anybody else can see them, since other streams may share the map.
+static const mm3d_normals *map_normals(mm3d_ctx *ctx, const mm3d_map *m, const mm3d_params *p)
+{
+  std::lock_guard<std::recursive_mutex> lk(m->points->cache_mu);
+  if (!m->normals) {
+    std::unique_ptr<mm3d_normals> n(compute_normals(ctx, m->points, p->normal_radius));
+    ctx->sync();
+    const_cast<mm3d_map *>(m)->normals = std::move(n);
+  }
+  return m->normals.get();
+}
+
+struct PairWork { const mm3d_map *s, *t; mm3d_pair_result *out; GlibcRand rnd; };
+static void pairs_estimate_batch(mm3d_ctx *ctx, PairWork *w, size_t n, const mm3d_params *p);
+
 static void pair_estimate_impl(mm3d_ctx *ctx, const mm3d_map *s, const mm3d_map *t, const mm3d_params *p, bool execute,
                                mm3d_pair_result *out)
 {
+  if (execute && ctx->icp_method) {
+    // point-to-plane ICP (mm3d_set_icp_method) lives in the batch path: a batch of one, from (and advancing) the context's generator
+    PairWork w{s, t, out, ctx->rnd};
+    pairs_estimate_batch(ctx, &w, 1, p);
+    return;
+  }
   std::memset(out->transform, 0, sizeof(out->transform));
   out->confidence = 0.0;
   out->icp_iterations = 0;
@@ -744,7 +770,6 @@ static size_t pair_batch_knob()
 
 // Several pairs on one context: the initial estimates one after the other (each from its own generator state),
 // then every pair's ICP + score tail in lockstep, one launch per step for the whole batch (icp_score_batch).
-struct PairWork { const mm3d_map *s, *t; mm3d_pair_result *out; GlibcRand rnd; };
 static void pairs_estimate_batch(mm3d_ctx *ctx, PairWork *w, size_t n, const mm3d_params *p)
 {
   std::vector<PairFront> fronts(n);
@@ -790,8 +815,15 @@ static void pairs_estimate_batch(mm3d_ctx *ctx, PairWork *w, size_t n, const mm3
     std::memcpy(jobs[i].guess_host, fronts[i].T0, sizeof(fronts[i].T0));
   }
   // estimateTransform's ICP and transformScore of its result (R/src/map_merging.cpp:91-107), max_distance = max_correspondence_distance
-  icp_score_batch(ctx, jobs.data(), (int)n, p->refine_transform != 0, p->max_correspondence_distance, p->max_iterations, p->transform_epsilon,
-                  true, p->max_correspondence_distance);
+  if (ctx->icp_method) {                                // point-to-plane (mm3d_set_icp_method): the targets' normals
+    if (p->refine_transform)
+      for (size_t i = 0; i < n; ++i) jobs[i].tgt_normals = map_normals(ctx, w[i].t, p);
+    ctx->icp_method->score_batch(ctx, jobs.data(), (int)n, p->refine_transform != 0, p->max_correspondence_distance, p->max_iterations,
+                                 p->transform_epsilon, true, p->max_correspondence_distance);
+  } else {
+    icp_score_batch(ctx, jobs.data(), (int)n, p->refine_transform != 0, p->max_correspondence_distance, p->max_iterations, p->transform_epsilon,
+                    true, p->max_correspondence_distance);
+  }
   for (size_t i = 0; i < n; ++i) {
     mm3d_pair_result *out = w[i].out;
     std::memcpy(out->transform, jobs[i].out.T, sizeof(out->transform));
@@ -1193,7 +1225,10 @@ int mm3d_shard_begin(mm3d_ctx *ctx, const mm3d_cloud_view *clouds, size_t n, con
 {
   if (!ctx || !params || !out || (n && !clouds) || world < 1 || rank < 0 || rank >= world) return MM3D_EINVAL;
   *out = nullptr;
-  return guarded(ctx, [&] { *out = shard_begin_impl(ctx, clouds, n, params, rank, world); });
+  return guarded(ctx, [&] {
+    if (ctx->icp_method) throw Error(MM3D_EUNSUPPORTED, "mm3d_shard_begin: shard bundles carry no normals for point-to-plane ICP");
+    *out = shard_begin_impl(ctx, clouds, n, params, rank, world);
+  });
 }
 
 int mm3d_shard_bundle_sizes(const mm3d_shard *sh, uint64_t *n_points, uint64_t *n_keypoints)
@@ -2045,7 +2080,7 @@ int mm3d_estimate_maps_transforms(mm3d_ctx *ctx, const mm3d_cloud_view *clouds, 
       bool ok = false;
       ~CacheCall() { if (c && !ok) c->abort(); }
     } cache_call{ctx->map_cache};
-    if (ctx->map_cache) ctx->map_cache->begin(n, params);
+    if (ctx->map_cache) ctx->map_cache->begin(n, params, ctx->icp_method ? ctx->icp_method->method() : MM3D_ICP_POINT_TO_POINT);
     if (!ctx->helpers.empty())
       estimate_maps_streams(ctx, clouds, n, params, out_T, n_out, pairs_out, n_pairs_out);
     else

@@ -1,0 +1,279 @@
+// icp_plane.hip -- point-to-plane ICP, the opt-in alternative to the reference's point-to-point ICP (mm3d_set_icp_method).
+//
+// PCL's IterativeClosestPoint with TransformationEstimationPointToPlaneLLS and DefaultConvergenceCriteria: the loop of nn.hip's
+// ICP (float transform of the source, exact float nearest neighbour accepted at d2 <= max_d2, T <- Tinc * T in float, the
+// convergence tests of k_icp_finalize on the same IcpState) with a different transform estimate.  For each correspondence
+// (s = source point after the current transform, d = target point, n = its normal, finite):
+//   row  = [a, b, c, nx, ny, nz],  a = nz sy - ny sz,  b = nx sz - nz sx,  c = ny sx - nx sy
+//   r    = n.d - n.s
+// and, in double, the 21 sums of the upper triangle of AtA and the 6 of Atr; x = (alpha, beta, gamma, tx, ty, tz) solves
+// AtA x = Atr (an unpivoted LDLt in double), and Tinc = [Rz(gamma) Ry(beta) Rx(alpha) | t] (PCL's constructTransformationMatrix).
+// Both sums are invariant under n -> -n, so the normals' orientation does not matter.
+//
+// Two launches per iteration, like icp_corr_reduce / icp_finalize:
+//   k_icp_plane_wave      nn_search_body.hpp's wave-cooperative search (the same include as k_nn_wave), then the winner's normal
+//                         (one 16-byte load per lane) and the 30 terms (the 27 above, d2, the correspondence, the row) in
+//                         double, reduced one term at a time through wave shuffles -> LDS -> partials[block][kPlaneAcc] in
+//                         k_nn_wave's fixed order (so the result does not depend on the batch or on the split either);
+//   k_icp_plane_finalize  one block per pair: the partials in a fixed order, the 6x6 solve on one lane, Tinc, the convergence tail.
+#include <cmath>
+
+#include "capi_guard.hpp"
+#include "nn_core.hpp"
+
+namespace mm3d {
+
+// A pivot of the LDLt at or below kPlanePivotTau * trace(AtA) / 6 makes the system degenerate (a single plane leaves three
+// directions unconstrained: their pivots are rounding noise, ~1e-16 of the trace).  The loop then stops, not converged, with
+// T as it was before the iteration; so it does with fewer than 6 rows.  (PCL would use ATA.inverse() of a singular matrix.)
+constexpr double kPlanePivotTau = 1e-12;
+
+// the upper triangle of the 6x6 AtA, row by row: term k = row[kUi[k]] * row[kUj[k]]
+__device__ constexpr int kUi[21] = {0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 4, 4, 5};
+__device__ constexpr int kUj[21] = {0, 1, 2, 3, 4, 5, 1, 2, 3, 4, 5, 2, 3, 4, 5, 3, 4, 5, 4, 5, 5};
+
+template <int SPLIT>
+__global__ void __launch_bounds__(256) MM3D_NN_ATTR
+k_icp_plane_wave(const NnPlaneJob *__restrict__ pjobs, float max_d2, float rmax)
+{
+  constexpr int MODE = 0;                                // (nn_search_body.hpp: the keyed search, with the winner's index)
+  const NnJob &job = pjobs[blockIdx.y].nn;
+  if ((int)blockIdx.x >= job.nblocks) return;            // the grid is as wide as the batch's largest job
+  const float4 *__restrict__ src = job.src;
+  const int2 *__restrict__ items = job.items;
+  const int n_items = job.n_items;
+  const GridView g = job.g;
+  const float4 *__restrict__ tgt_ref = job.tgt_ref;
+  const float4 *__restrict__ nrm = pjobs[blockIdx.y].nrm;
+  const IcpState *__restrict__ st = job.st;
+  double *__restrict__ partials = job.partials;
+  const int max_ring = job.max_ring;
+  __shared__ float Ts[16];
+  __shared__ double red[4][kPlaneAcc];
+  __shared__ __attribute__((aligned(16))) float s_cx[4][kTile], s_cy[4][kTile], s_cz[4][kTile];
+  __shared__ __attribute__((aligned(16))) unsigned s_cw[4][kTile];
+  __shared__ int s_off[4][kRows];
+  __shared__ int s_beg[4][kRows];
+  __shared__ unsigned long long s_merge[SPLIT == 4 ? 4 : 1][64];
+  if (st->done) return;
+  if (threadIdx.x < 16) Ts[threadIdx.x] = st->T[threadIdx.x];
+  __syncthreads();
+#include "nn_search_body.hpp"
+  if (SPLIT == 4 && wave != 0) return;     // the four waves hold the same result
+  const bool corr = valid && best <= max_d2;   // false for INFINITY / NaN
+  // the lane's row (zero where it has none, or where the target normal is not finite: such a correspondence still counts,
+  // and its d2 goes into the MSE of the convergence test)
+  double v[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  double r = 0.0, has_row = 0.0;
+  if (corr) {
+    const unsigned w = (unsigned)(bkey & 0xffffffffull);
+    const float4 n = nrm[w];
+    if (isfinite(n.x) && isfinite(n.y) && isfinite(n.z)) {
+      const float4 d = tgt_ref[w];
+      const double sx = p.x, sy = p.y, sz = p.z, nx = n.x, ny = n.y, nz = n.z;
+      v[0] = nz * sy - ny * sz;
+      v[1] = nx * sz - nz * sx;
+      v[2] = ny * sx - nx * sy;
+      v[3] = nx; v[4] = ny; v[5] = nz;
+      r = (nx * (double)d.x + ny * (double)d.y + nz * (double)d.z) - (nx * sx + ny * sy + nz * sz);
+      has_row = 1.0;
+    }
+  }
+  // one term at a time (formed, summed over the wave, stored): 30 doubles held at once would cost 60 VGPRs on top of the search
+  auto term = [&](int k) -> double {
+    if (k < 21) return v[kUi[k]] * v[kUj[k]];
+    if (k < 27) return v[k - 21] * r;
+    if (k == 27) return corr ? (double)best : 0.0;
+    if (k == 28) return corr ? 1.0 : 0.0;
+    return has_row;
+  };
+  // a wave none of whose points found a neighbour in range adds zeros without the reductions (as k_nn_wave does)
+  const bool any_corr = ballot(corr) != 0ull;       // wave-uniform
+  if (SPLIT == 4) {
+#pragma unroll
+    for (int k = 0; k < kPlaneAcc; ++k) {
+      const double s = any_corr ? wave_sum(term(k)) : 0.0;
+      if (lane == 0) partials[(size_t)bid * kPlaneAcc + k] = s;
+    }
+    return;
+  }
+#pragma unroll
+  for (int k = 0; k < kPlaneAcc; ++k) {
+    const double s = any_corr ? wave_sum(term(k)) : 0.0;
+    if (lane == 0) red[wave][k] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x < kPlaneAcc) {
+    const int k = threadIdx.x;
+    partials[(size_t)bid * kPlaneAcc + k] = red[0][k] + red[1][k] + red[2][k] + red[3][k];
+  }
+}
+
+// AtA x = b by an unpivoted LDLt in double; false when a pivot is at or below `floor` (x is then not written)
+__device__ static bool solve6_ldlt(const double A[36], const double b[6], double floor, double x[6])
+{
+  double L[36], D[6];
+  for (int j = 0; j < 6; ++j) {
+    double d = A[j * 6 + j];
+    for (int k = 0; k < j; ++k) d -= L[j * 6 + k] * L[j * 6 + k] * D[k];
+    if (!(d > floor)) return false;                    // (also catches NaN)
+    D[j] = d;
+    for (int i = j + 1; i < 6; ++i) {
+      double s = A[i * 6 + j];
+      for (int k = 0; k < j; ++k) s -= L[i * 6 + k] * L[j * 6 + k] * D[k];
+      L[i * 6 + j] = s / d;
+    }
+  }
+  double y[6];
+  for (int i = 0; i < 6; ++i) {
+    double s = b[i];
+    for (int k = 0; k < i; ++k) s -= L[i * 6 + k] * y[k];
+    y[i] = s;
+  }
+  for (int i = 5; i >= 0; --i) {
+    double s = y[i] / D[i];
+    for (int k = i + 1; k < 6; ++k) s -= L[k * 6 + i] * x[k];
+    x[i] = s;
+  }
+  return true;
+}
+
+__global__ void __launch_bounds__(256) k_icp_plane_finalize(const NnPlaneJob *__restrict__ pjobs)
+{
+  __shared__ double red[4][kPlaneAcc];
+  __shared__ double tot[kPlaneAcc];
+  const NnJob &job = pjobs[blockIdx.x].nn;
+  const double *__restrict__ partials = job.partials;
+  const int split = job.split, n_items = job.n_items;
+  const int nblocks = (n_items + 3) >> 2;              // in units of four items, whichever kernel variant wrote them
+  IcpState *st = job.st;
+  if (st->done) return;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int k = 0; k < kPlaneAcc; ++k) {
+    double acc = 0.0;
+    for (int b = threadIdx.x; b < nblocks; b += blockDim.x) acc += nn_block_partial_n<kPlaneAcc>(partials, b, k, split, n_items);
+    const double s = wave_sum(acc);
+    if (lane == 0) red[wave][k] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x < kPlaneAcc) tot[threadIdx.x] = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+
+  const double cnt = tot[28];
+  st->n_corr = (int)cnt;
+  if (cnt < 3.0) {   // min_number_correspondences_: "Not enough correspondences" -> not converged, stop
+    st->converged = 0;
+    st->done = 1;
+    return;
+  }
+  double A[36], b[6], x[6];
+  for (int k = 0; k < 21; ++k) A[kUi[k] * 6 + kUj[k]] = A[kUj[k] * 6 + kUi[k]] = tot[k];
+  for (int i = 0; i < 6; ++i) b[i] = tot[21 + i];
+  const double trace = A[0] + A[7] + A[14] + A[21] + A[28] + A[35];
+  if (tot[29] < 6.0 || !solve6_ldlt(A, b, kPlanePivotTau * trace / 6.0, x)) {
+    // degenerate (fewer than six rows, or a plane / line that leaves a direction free): stop, not converged, T unchanged
+    st->converged = 0;
+    st->done = 1;
+    return;
+  }
+  // constructTransformationMatrix(alpha, beta, gamma, tx, ty, tz) = [Rz(gamma) Ry(beta) Rx(alpha) | t]:
+  //   | cg cb   -sg ca + cg sb sa    sg sa + cg sb ca |
+  //   | sg cb    cg ca + sg sb sa   -cg sa + sg sb ca |
+  //   | -sb      cb sa               cb ca            |
+  const double sa = sin(x[0]), ca = cos(x[0]), sb = sin(x[1]), cb = cos(x[1]), sg = sin(x[2]), cg = cos(x[2]);
+  const double R[9] = {cg * cb, -sg * ca + cg * sb * sa, sg * sa + cg * sb * ca,
+                       sg * cb, cg * ca + sg * sb * sa, -cg * sa + sg * sb * ca,
+                       -sb, cb * sa, cb * ca};
+  float Ti[16];
+  for (int rr = 0; rr < 3; ++rr)
+    for (int c = 0; c < 3; ++c) Ti[c * 4 + rr] = (float)R[rr * 3 + c];
+  Ti[12] = (float)x[3]; Ti[13] = (float)x[4]; Ti[14] = (float)x[5];
+  Ti[3] = Ti[7] = Ti[11] = 0.0f;
+  Ti[15] = 1.0f;
+  // final = Tinc * final, and the rest of k_icp_finalize's tail
+  float Tn[16];
+  for (int c = 0; c < 4; ++c)
+    for (int rr = 0; rr < 4; ++rr) {
+      float a = 0.0f;
+      for (int k = 0; k < 4; ++k) a += Ti[k * 4 + rr] * st->T[c * 4 + k];
+      Tn[c * 4 + rr] = a;
+    }
+  for (int i = 0; i < 16; ++i) { st->T[i] = Tn[i]; st->Tinc[i] = Ti[i]; }
+  const int iters = ++st->iters;
+  // DefaultConvergenceCriteria::hasConverged
+  if (iters >= st->max_iter) { st->converged = 1; st->done = 1; return; }
+  const double cos_angle = 0.5 * ((double)Ti[0] + (double)Ti[5] + (double)Ti[10] - 1.0);
+  const double translation_sqr = (double)Ti[12] * Ti[12] + (double)Ti[13] * Ti[13] + (double)Ti[14] * Ti[14];
+  if (cos_angle >= st->rot_thresh && translation_sqr <= st->trans_thresh) { st->converged = 1; st->done = 1; return; }
+  const double mse = tot[27] / cnt;
+  if (fabs(mse - st->prev_mse) < 1e-12) { st->converged = 1; st->done = 1; return; }
+  st->prev_mse = mse;
+}
+
+void icp_plane_step(Context *c, const NnPlaneJob *jobs_dev, int count, unsigned grid_x, bool split, float max_d2, float rmax,
+                    double bytes, double finalize_bytes)
+{
+  if (split)
+    MM3D_LAUNCH(c, "icp_plane_corr_reduce", bytes, k_icp_plane_wave<4>, dim3(grid_x, count), dim3(256), 0, jobs_dev, max_d2, rmax);
+  else
+    MM3D_LAUNCH(c, "icp_plane_corr_reduce", bytes, k_icp_plane_wave<1>, dim3(grid_x, count), dim3(256), 0, jobs_dev, max_d2, rmax);
+  MM3D_LAUNCH(c, "icp_plane_finalize", finalize_bytes, k_icp_plane_finalize, dim3(count), dim3(256), 0, jobs_dev);
+}
+
+namespace {
+struct IcpPointToPlane final : IcpMethodBase {
+  int method() const override { return MM3D_ICP_POINT_TO_PLANE; }
+  void score_batch(Context *c, IcpScoreJob *jobs, int n_jobs, bool run_icp, double max_corr_dist, int max_iterations, double eps,
+                   bool want_score, double score_max_distance) const override
+  {
+    icp_plane_score_batch(c, jobs, n_jobs, run_icp, max_corr_dist, max_iterations, eps, want_score, score_max_distance);
+  }
+};
+const IcpPointToPlane g_point_to_plane;
+}  // namespace
+
+}  // namespace mm3d
+
+using namespace mm3d;
+
+extern "C" {
+
+int mm3d_set_icp_method(mm3d_ctx *ctx, int method)
+{
+  if (!ctx || (method != MM3D_ICP_POINT_TO_POINT && method != MM3D_ICP_POINT_TO_PLANE)) return MM3D_EINVAL;
+  std::lock_guard<std::mutex> lock(ctx->mu);        // (no call is running while the method changes)
+  if (ctx->device_set) {
+    ctx->err = "mm3d_set_icp_method: not available on a device-list context";
+    return MM3D_EUNSUPPORTED;
+  }
+  const IcpMethodBase *m = method == MM3D_ICP_POINT_TO_PLANE ? &g_point_to_plane : nullptr;
+  ctx->icp_method = m;
+  for (mm3d_ctx *h : ctx->helpers) h->icp_method = m;
+  return MM3D_OK;
+}
+
+int mm3d_get_icp_method(const mm3d_ctx *ctx)
+{
+  if (!ctx) return MM3D_EINVAL;
+  return ctx->icp_method ? ctx->icp_method->method() : MM3D_ICP_POINT_TO_POINT;
+}
+
+int mm3d_estimate_transform_icp_plane(mm3d_ctx *ctx, const mm3d_cloud *source, const mm3d_cloud *target, const mm3d_normals *target_normals,
+                                      const float initial_guess[16], double max_corr_dist, int max_iterations, double eps, float T[16])
+{
+  if (!source || !target || !target_normals || !initial_guess || !T) return MM3D_EINVAL;
+  if (target_normals->n != target->n) {
+    if (ctx) ctx->err = "mm3d_estimate_transform_icp_plane: the normals do not match the target's points";
+    return MM3D_EINVAL;
+  }
+  return guarded(ctx, [&] {
+    IcpScoreJob J;
+    J.src = source; J.tgt = target; J.tgt_normals = target_normals;
+    std::memcpy(J.guess_host, initial_guess, sizeof(J.guess_host));
+    icp_plane_score_batch(ctx, &J, 1, true, max_corr_dist, max_iterations, eps, false, 0.0);
+    std::memcpy(T, J.out.T, sizeof(J.out.T));
+  });
+}
+
+}  // extern "C"

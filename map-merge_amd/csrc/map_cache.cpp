@@ -39,12 +39,14 @@ std::string feature_key(const mm3d_params *p)
   return k.s;
 }
 
-// what the pair stage reads (pair_estimate_impl / pairs_estimate_batch)
-std::string pair_params_key(const mm3d_params *p)
+// what the pair stage reads (pair_estimate_impl / pairs_estimate_batch), and the ICP method (mm3d_set_icp_method): a
+// point-to-point record is never one of point-to-plane's.  (The map key needs no method: the normals point-to-plane keeps are
+// a function of the points and normal_radius.)
+std::string pair_params_key(const mm3d_params *p, int icp_method)
 {
   KeyBuilder k;
   k.i32(p->estimation_method).i32(p->refine_transform).f64(p->inlier_threshold).f64(p->max_correspondence_distance)
-      .i32(p->max_iterations).u64(p->matching_k).f64(p->transform_epsilon);
+      .i32(p->max_iterations).u64(p->matching_k).f64(p->transform_epsilon).i32(icp_method);
   return k.s;
 }
 
@@ -78,7 +80,11 @@ struct Entry {
   {
     if (map) { delete map->points; delete map->keypoints; delete map->desc; delete map; }
   }
-  size_t bytes() const { return raw->pts.size() * 16 + cloud_bytes(map->points) + cloud_bytes(map->keypoints) + desc_bytes(map->desc); }
+  size_t bytes() const
+  {
+    return raw->pts.size() * 16 + cloud_bytes(map->points) + cloud_bytes(map->keypoints) + desc_bytes(map->desc) +
+           (map->normals ? map->normals->nrm.size() * 16 : 0);    // (normals: point-to-plane ICP only)
+  }
 };
 
 struct PairRecord {
@@ -117,12 +123,12 @@ class MapCache final : public MapCacheBase {
       for (long long &c : counters_) c = 0;
   }
 
-  void begin(size_t n_maps, const mm3d_params *p) override
+  void begin(size_t n_maps, const mm3d_params *p, int icp_method) override
   {
     std::lock_guard<std::mutex> lk(mu_);
     reset_call_locked();
     fkey_ = feature_key(p);
-    pkey_ = pair_params_key(p);
+    pkey_ = pair_params_key(p, icp_method);
     sac_ia_ = p->estimation_method == MM3D_EST_SAC_IA;
     slot_entry_.assign(n_maps, 0);
     slot_digest_.assign(n_maps, {0ull, 0ull});

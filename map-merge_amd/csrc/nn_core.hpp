@@ -1,0 +1,139 @@
+// nn_core.hpp -- what the ICP / score kernels of nn.hip (k_nn_wave) and the point-to-plane ICP kernel of icp_plane.hip
+// (k_icp_plane_wave) share: the search knobs, the ICP state, the job layout and the wave helpers.  The search itself is
+// nn_search_body.hpp (see there).
+#pragma once
+#include <cfloat>
+#include <cstddef>
+#include <type_traits>
+
+#include "device_util.hpp"
+#include "linalg_shared.hpp"
+
+namespace mm3d {
+
+constexpr int kAcc = 17;     // sum p(3) | sum q(3) | sum q p^T (9, row = q) | sum d2 | count
+#ifndef MM3D_NN_TILE
+#define MM3D_NN_TILE 256
+#endif
+#ifndef MM3D_NN_WPE
+#define MM3D_NN_WPE 4
+#endif
+#ifdef MM3D_NN_WPE
+#define MM3D_NN_ATTR __attribute__((amdgpu_waves_per_eu(MM3D_NN_WPE, MM3D_NN_WPE)))
+#else
+#define MM3D_NN_ATTR
+#endif
+constexpr int kTile = MM3D_NN_TILE;   // staged target points per wave and tile (8 KiB of LDS)
+#ifndef MM3D_NN_ROWS_PER_LANE
+#define MM3D_NN_ROWS_PER_LANE 4
+#endif
+// MM3D_NN_PREFETCH=1: the next tile's gathers are issued into registers before this tile is scanned.  Measured and left off:
+// 16 more VGPRs (112: four waves per SIMD instead of five for the ICP variant) for a latency that the other resident waves
+// already cover -- headline 955 against 960 map-pairs/s, 64 x 50 k 10 250 against 10 520 (interleaved A/B, round 4).
+#ifndef MM3D_NN_PREFETCH
+#define MM3D_NN_PREFETCH 0
+#endif
+#ifndef MM3D_NN_TIGHT_BOX
+#define MM3D_NN_TIGHT_BOX 1
+#endif
+#ifndef MM3D_NN_SHELL
+#define MM3D_NN_SHELL 1
+#endif
+#ifndef MM3D_NN_LOWER_BOUND
+#define MM3D_NN_LOWER_BOUND 1
+#endif
+#ifndef MM3D_NN_CORNERS
+#define MM3D_NN_CORNERS 1
+#endif
+constexpr bool kPrefetch = MM3D_NN_PREFETCH != 0;
+constexpr int kRowsPerLane = MM3D_NN_ROWS_PER_LANE;   // row headers a lane reads per chunk
+constexpr int kRows = kWave * kRowsPerLane;           // rows of the box per chunk (power of two: the slot -> row search halves it)
+
+#ifdef MM3D_NN_STATS
+// (static: one per translation unit; mm3d_debug_nn_stats reads nn.hip's)
+static __device__ unsigned long long g_nn_stats[64];   // 0 waves, 1 passes, 2 row chunks, 3 staged points, 4 active lanes at pass, 5 rows, 6 max wave cycles, 7 sum wave cycles, 8.. log2 histogram of wave cycles
+#define MM3D_STAT(i_, v_) do { if (MM3D_NN_STATS == 1 && lane == 0) atomicAdd(&g_nn_stats[i_], (unsigned long long)(v_)); } while (0)
+#define MM3D_TICK(var_) const long long var_ = wall_clock64()
+// (phase ticks are summed in registers and flushed once per wave: an atomic per chunk on one word slowed the kernel threefold)
+#define MM3D_TOCK(i_, from_) do { stat_ticks[(i_) - 32] += wall_clock64() - (from_); } while (0)
+#else
+#define MM3D_STAT(i_, v_)
+#define MM3D_TICK(var_)
+#define MM3D_TOCK(i_, from_)
+#endif
+
+struct IcpState {
+  float T[16];      // cumulative transform applied to the original source points (starts at the guess)
+  float Tinc[16];
+  double prev_mse;
+  double rot_thresh, trans_thresh;
+  int iters, done, converged, n_corr, max_iter;
+  int scored;      // the score of the final transform has been taken (k_score_finalize)
+};
+
+// One (source cloud, target grid) search of a launch: blockIdx.y picks the job, so the searches of several map
+// pairs that are ready at the same time share one launch (many small maps: a launch per pair leaves most of the
+// chip idle, and only four launches run at a time).
+struct NnJob {
+  const float4 *src;          // source points in Hilbert order
+  const int2 *items;          // their work items
+  int n_items, nblocks;       // blocks this job uses of the launch's grid.x
+  int split;                  // 1: one work item per block (partials per item), 0: four items per block
+  GridView g;                 // target grid
+  const float4 *tgt_ref;      // target points in reference order
+  IcpState *st;               // ICP: the pair's state; score: T is read from its head (or from Tc)
+  const float *Tc;            // score: the transform, when it is not the ICP state's
+  double *partials;           // [nblocks][kAcc]
+  double *out;                // score: {sum d2, count}
+  int max_ring;
+};
+
+__device__ __forceinline__ int wave_min_i(int v)
+{
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, kWave));
+  return v;
+}
+__device__ __forceinline__ int wave_max_i(int v)
+{
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, kWave));
+  return v;
+}
+// LDS written by some lanes of a wave and read by others: order the accesses for the compiler;
+// the hardware executes one wave's DS operations in order.
+__device__ __forceinline__ void wave_lds_sync()
+{
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// Partial sums of "block" b as the four-items-per-block kernels write them.  The one-item-per-block kernels leave
+// one partial per item; adding four neighbours here, in the order those kernels' last step does, gives the same
+// bits -- so which variant ran (a choice that depends on what else was ready at the time) never shows in a result.
+template <int NACC>
+__device__ __forceinline__ double nn_block_partial_n(const double *__restrict__ p, int b, int k, int split, int n_items)
+{
+  if (!split) return p[(size_t)b * NACC + k];
+  const int i = b * 4;
+  double v = p[(size_t)i * NACC + k];
+  v += (i + 1 < n_items) ? p[(size_t)(i + 1) * NACC + k] : 0.0;
+  v += (i + 2 < n_items) ? p[(size_t)(i + 2) * NACC + k] : 0.0;
+  v += (i + 3 < n_items) ? p[(size_t)(i + 3) * NACC + k] : 0.0;
+  return v;
+}
+
+// point-to-plane ICP (icp_plane.hip): the search job plus the target's normals, in the target's reference order (tgt_ref's)
+struct NnPlaneJob {
+  NnJob nn;                   // nn.partials: [nblocks][kPlaneAcc]
+  const float4 *nrm;
+};
+// AtA upper triangle (21) | Atr (6) | sum d2 | correspondences | rows with a finite normal
+constexpr int kPlaneAcc = 30;
+// one point-to-plane ICP iteration of a batch (icp_corr_reduce's and icp_finalize's counterparts): the search + reduction
+// launch, then the solve / accumulate / convergence launch, on the same IcpState protocol as icp_score_batch's
+void icp_plane_step(Context *c, const NnPlaneJob *jobs_dev, int count, unsigned grid_x, bool split, float max_d2, float rmax,
+                    double bytes, double finalize_bytes);
+
+}  // namespace mm3d

@@ -14,6 +14,7 @@
 
 namespace mm3d {
 struct DeviceSet;
+struct IcpMethodBase;
 
 // The feature / pair cache of mm3d_estimate_maps_transforms (mm3d_set_map_cache; the concrete class is map_cache.cpp's).  The
 // drivers in capi.cpp only see this interface, so the host code links without it (tests/host_san).  One call at a time -- the
@@ -21,7 +22,7 @@ struct DeviceSet;
 // abort (it did not: the cache is left exactly as it was before the call).
 struct MapCacheBase {
   virtual ~MapCacheBase() = default;
-  virtual void begin(size_t n_maps, const mm3d_params *p) = 0;
+  virtual void begin(size_t n_maps, const mm3d_params *p, int icp_method) = 0;   // icp_method: MM3D_ICP_* of the call (mm3d_set_icp_method)
   // map `slot`'s packed upload `raw` (non-empty, on c's stream): the cached bundle, borrowed for the call, or null.  One launch and
   // one wait on c (a second compare-only launch and wait when the digest names another candidate than the slot's last entry).
   virtual const mm3d_map *lookup(Context *c, size_t slot, const mm3d_cloud *raw) = 0;
@@ -41,6 +42,9 @@ struct MapCacheBase {
 struct mm3d_ctx : mm3d::Context {
   // mm3d_set_map_cache: null = off (the drivers take their plain path).  Owned by this context; never set on helpers or peers.
   mm3d::MapCacheBase *map_cache = nullptr;
+  // mm3d_set_icp_method: null = the reference's point-to-point ICP.  Not owned (a process-wide object of icp_plane.hip's that
+  // holds no state); set on the context and its helpers alike, and copied to helpers that mm3d_set_streams makes later.
+  const mm3d::IcpMethodBase *icp_method = nullptr;
   // mm3d_set_streams: helper contexts (one HIP stream + one host thread each while a call is running)
   // that mm3d_estimate_maps_transforms deals maps and pairs to; owned by this context
   std::vector<mm3d_ctx *> helpers;
@@ -160,6 +164,8 @@ struct mm3d_map {
   mm3d_cloud *points = nullptr;
   mm3d_cloud *keypoints = nullptr;
   mm3d_desc *desc = nullptr;
+  // the points' normals (normal_radius), kept for point-to-plane ICP only (mm3d_set_icp_method): null otherwise
+  std::unique_ptr<mm3d_normals> normals;
 };
 
 namespace mm3d {
@@ -268,9 +274,23 @@ struct IcpScoreJob {
   float guess_host[16] = {0};           // on the host
   PairTail out{};
   bool closed = false;
+  const mm3d_normals *tgt_normals = nullptr;   // point-to-plane ICP: the target's normals, in its order
 };
 void icp_score_batch(Context *c, IcpScoreJob *jobs, int n_jobs, bool run_icp, double max_corr_dist, int max_iterations, double eps,
                      bool want_score, double score_max_distance);
+// the same with point-to-plane ICP (icp_plane.hip's kernels; every job's tgt_normals set).  The score stays point-to-point.
+void icp_plane_score_batch(Context *c, IcpScoreJob *jobs, int n_jobs, bool run_icp, double max_corr_dist, int max_iterations, double eps,
+                           bool want_score, double score_max_distance);
+// The ICP method of a context's pair stage (mm3d_set_icp_method; the one concrete class is icp_plane.hip's).  Like MapCacheBase,
+// the drivers in capi.cpp only see this interface, so the host code links without the new kernels (tests/host_san); a null
+// pointer on the context means the reference's point-to-point ICP (icp_score_batch).
+struct IcpMethodBase {
+  virtual ~IcpMethodBase() = default;
+  virtual int method() const = 0;                        // MM3D_ICP_*
+  // icp_score_batch with this method's ICP
+  virtual void score_batch(Context *c, IcpScoreJob *jobs, int n_jobs, bool run_icp, double max_corr_dist, int max_iterations, double eps,
+                           bool want_score, double score_max_distance) const = 0;
+};
 struct PairCounts { int n_correspondences = 0, n_inliers = 0, icp_correspondences = 0; };
 // ICP (optional) from a guess on the device (guess_dev != null) or on the host, then transformScore
 // (optional) of the result, with one host synchronisation
