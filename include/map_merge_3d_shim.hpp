@@ -87,7 +87,15 @@ inline mm3d_ctx *ctx()
   // MM3D_ICP=point_to_plane: the pair stage refines with point-to-plane ICP instead of the reference's point-to-point
   // (mm3d_set_icp_method); point_to_point or unset keeps the reference's.  Not available on a device list: with MM3D_DEVICES
   // set as well this throws rather than quietly running point-to-point.
+  // MM3D_ALIGN=prerejective: under SAC_IA the pair stage's initial alignment is the prerejective one (mm3d_set_alignment), with
+  // MM3D_ALIGN_SAMPLES=<draws> if given; sac_ia or unset keeps the reference's.  Not available on a device list either.
   static mm3d_ctx *c = [] {
+    const char *al = std::getenv("MM3D_ALIGN");
+    const std::string align = al ? al : "";
+    if (!align.empty() && align != "sac_ia" && align != "prerejective")
+      throw std::runtime_error("mm3d: MM3D_ALIGN must be sac_ia or prerejective, not '" + align + "'");
+    if (align == "prerejective" && std::getenv("MM3D_DEVICES") && *std::getenv("MM3D_DEVICES"))
+      throw std::runtime_error("mm3d: MM3D_ALIGN=prerejective is not available with MM3D_DEVICES (the devices' pair loops run SAC-IA)");
     const char *icp = std::getenv("MM3D_ICP");
     const std::string icp_method = icp ? icp : "";
     if (!icp_method.empty() && icp_method != "point_to_point" && icp_method != "point_to_plane")
@@ -103,6 +111,14 @@ inline mm3d_ctx *ctx()
     if (maps > 0) (void)mm3d_set_map_cache(e, maps);
     if (icp_method == "point_to_plane" && mm3d_set_icp_method(e, MM3D_ICP_POINT_TO_PLANE) != MM3D_OK)
       throw std::runtime_error(std::string("mm3d: ") + mm3d_last_error(e));
+    if (align == "prerejective") {
+      mm3d_alignment_options o;
+      mm3d_alignment_options_default(&o);
+      o.method = MM3D_ALIGN_PREREJECTIVE;
+      if (const char *ns = std::getenv("MM3D_ALIGN_SAMPLES")) o.samples = std::atoi(ns);
+      if (mm3d_set_alignment(e, &o) != MM3D_OK)
+        throw std::runtime_error("mm3d: MM3D_ALIGN=prerejective was refused (MM3D_ALIGN_SAMPLES must be 1 .. 2^30)");
+    }
     return e;
   }();
   return c;

@@ -249,6 +249,65 @@ int mm3d_map_cache_stats(const mm3d_ctx *ctx, long long out[6], int reset);   /*
  * carry no normals -- nor does mm3d_shard_begin, which returns MM3D_EUNSUPPORTED on a point-to-plane context. */
 int mm3d_set_icp_method(mm3d_ctx *ctx, int method);
 int mm3d_get_icp_method(const mm3d_ctx *ctx);              /* MM3D_ICP_*, MM3D_EINVAL for NULL */
+/* Initial alignment of the pair stage where params.estimation_method == SAC_IA (off the reference's path;
+ * MM3D_ALIGN_SAC_IA, the reference's, by default; MATCHING is untouched).  MM3D_ALIGN_PREREJECTIVE runs the algorithm of
+ * pcl::SampleConsensusPrerejective (Buch et al., ICRA 2013) -- the algorithm, not its random stream: no parity is claimed --
+ * on the inputs SAC-IA gets (keypoints, descriptors, inlier distance = max_correspondence_distance), wholly on the device:
+ *   - Table: the k' = min(k, n_target) nearest target descriptors of every source keypoint (findFeatureCorrespondences'
+ *     exact search), nearest first.
+ *   - Draw h, 0 <= h < samples, from six 64-bit words w_j = mix(((seed << 32) | h) + (j + 1) * 0x9E3779B97F4A7C15 mod 2^64),
+ *     mix = splitmix64's finaliser (z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB;
+ *     z ^= z >> 31), seed = the last mm3d_srand value (1 without one; 0 counts as 1, as srand does), and
+ *     bounded(w, n) = ((w >> 32) * n) >> 32.  Three distinct source keypoints: i0 = bounded(w0, ns); i1 = bounded(w1, ns - 1),
+ *     plus one if >= i0; i2 = bounded(w2, ns - 2), plus one if >= min(i0, i1), then plus one if >= max(i0, i1).  Their
+ *     targets: table[i_j][bounded(w_{3+j}, k')].  The stream is a function of (seed, h, ns, k') alone: not of the pair's
+ *     place in the pair loop, the stream count, batching or the cache.  It consumes NOTHING from the context's rand() replay,
+ *     so mm3d_pair_estimate(execute = 0) and mm3d_pairs_skip advance nothing for such a pair.
+ *   - Prerejection: for each of the three edges, the squared lengths ds (source) and dt (target), ((dx dx + dy dy) + dz dz)
+ *     in double on the float coordinates; the draw survives when ds > 0, dt > 0 and min(ds, dt) >= similarity^2 max(ds, dt)
+ *     on all three -- the edge-length ratio min / max >= similarity -- and its three targets are distinct.  Anything not
+ *     finite fails the test.
+ *   - Hypothesis of a survivor: Umeyama's closed form without scale on the three pairs (means, covariance and the 3x3 SVD in
+ *     double), rounded to a float 4x4.
+ *   - Score: every source keypoint transformed in float, its exact float nearest target keypoint (a grid of the target's
+ *     keypoints, built by mm3d_map_prepare); an inlier when d2 <= (float)(inlier distance^2).  Per hypothesis the inlier
+ *     count (integer) and the inliers' d2 sum (double, in a fixed order: bit-identical whatever else runs).
+ *   - Pick: among the hypotheses with count >= 1 and count >= inlier_fraction * ns, the lowest mean inlier d2; ties to the
+ *     lower h.  Then one refit -- Umeyama in double over all the winner's (keypoint, nearest target) inlier pairs --, scored
+ *     the same way and kept when it has more inliers, or as many and a mean d2 not larger.  converged = 1.
+ *     If no hypothesis reaches the fraction: the one with the most inliers (ties to the lower h), no refit, converged = 0.
+ *     No survivor at all, or fewer than three keypoints on either side: the identity (SAC-IA's guess), converged = 0.
+ *     The pair goes on to ICP and its record as after SAC-IA, converged or not.
+ *   - Results are bit-identical for every stream count, batch, driver and cache setting, and after mm3d_srand to the same seed.
+ *   - The map cache's pair key holds the method and its four options, and for a prerejective pair the seed in place of the
+ *     rand() state: such a record is reused without mm3d_srand between the calls. */
+typedef enum { MM3D_ALIGN_SAC_IA = 0, MM3D_ALIGN_PREREJECTIVE = 1 } mm3d_align_method;
+typedef struct mm3d_alignment_options {
+  int method;                 /* MM3D_ALIGN_* */
+  int samples;                /* raw draws, 1 .. 2^30 */
+  int k;                      /* candidate matches per source keypoint, 1 .. 64 (10: SAC-IA's k_correspondences) */
+  double similarity;          /* edge-length ratio a draw must reach, 0 .. 1 */
+  double inlier_fraction;     /* of the source keypoints, 0 .. 1 */
+} mm3d_alignment_options;
+typedef struct mm3d_alignment_stats {
+  long long draws;            /* samples */
+  long long survivors;        /* draws that passed the prerejection */
+  long long hypotheses_scored;/* survivors, plus one for the refit when it ran */
+  long long winner_h;         /* the chosen draw, -1 when there was none */
+  int winner_inliers;         /* inliers of the returned transform */
+  int converged;              /* 1 when a hypothesis reached inlier_fraction */
+} mm3d_alignment_stats;
+/* method MM3D_ALIGN_SAC_IA, samples 2^16 (DESIGN.md section 7c has the measurement), k 10, similarity 0.9, inlier_fraction 0.25 */
+void mm3d_alignment_options_default(mm3d_alignment_options *o);
+/* MM3D_EINVAL: ctx or options NULL, an unknown method, a value outside its range above (the values are checked whatever the
+ * method).  MM3D_EUNSUPPORTED: MM3D_ALIGN_PREREJECTIVE on a device-list context (mm3d_create_devices); mm3d_shard_begin
+ * returns MM3D_EUNSUPPORTED on a prerejective context.  The setting reaches the context's mm3d_set_streams helpers, in
+ * either order of the two calls. */
+int mm3d_set_alignment(mm3d_ctx *ctx, const mm3d_alignment_options *options);
+int mm3d_get_alignment(const mm3d_ctx *ctx, mm3d_alignment_options *options);      /* MM3D_EINVAL for NULL */
+/* The alignment of the last pair that mm3d_pair_estimate or the one-stream mm3d_estimate_maps_transforms ran with
+ * MM3D_ALIGN_PREREJECTIVE on this context (all zero, winner_h -1, before the first).  MM3D_EINVAL for NULL. */
+int mm3d_last_alignment_stats(const mm3d_ctx *ctx, mm3d_alignment_stats *stats);
 
 /* ---- cloud objects -------------------------------------------------------------------- */
 int mm3d_cloud_create(mm3d_ctx *ctx, const void *points, size_t n, size_t stride, size_t rgba_offset,
@@ -329,6 +388,21 @@ int mm3d_estimate_transform_icp_plane(mm3d_ctx *ctx, const mm3d_cloud *source, c
                                       const mm3d_normals *target_normals, const float initial_guess[16],
                                       double max_correspondence_distance, int max_iterations, double transformation_epsilon,
                                       float T[16]);
+/* The prerejective alignment (mm3d_set_alignment states it) of two keypoint sets with their descriptors, whatever the
+ * context's setting and options->method.  stats may be NULL.  Fewer than three keypoints on either side, or no surviving
+ * draw: MM3D_OK, T = identity, converged = 0.  MM3D_EINVAL: a NULL argument, options out of range, inlier_distance not a
+ * positive finite number, descriptor sets that do not match their keypoints. */
+int mm3d_estimate_transform_prerejective(mm3d_ctx *ctx, const mm3d_cloud *source_keypoints, const mm3d_desc *source_descriptors,
+                                         const mm3d_cloud *target_keypoints, const mm3d_desc *target_descriptors,
+                                         double inlier_distance, const mm3d_alignment_options *options, float T[16],
+                                         mm3d_alignment_stats *stats);
+/* test / study hook of the above: the survivors of the prerejection in ascending h, at most cap rows of
+ * (h, source i0 i1 i2, target t0 t1 t2) into rows[cap][7]; counts (may be NULL) receives each scored row's inlier count.
+ * *n_survivors receives their number, which may exceed cap. */
+int mm3d_debug_prerejective_survivors(mm3d_ctx *ctx, const mm3d_cloud *source_keypoints, const mm3d_desc *source_descriptors,
+                                      const mm3d_cloud *target_keypoints, const mm3d_desc *target_descriptors,
+                                      double inlier_distance, const mm3d_alignment_options *options, int *rows, int *counts,
+                                      size_t cap, size_t *n_survivors);
 /* estimateTransform (matching.h:129, matching.cpp:223-257) */
 int mm3d_estimate_transform(mm3d_ctx *ctx, const mm3d_cloud *source_points, const mm3d_cloud *source_keypoints,
                             const mm3d_desc *source_descriptors, const mm3d_cloud *target_points,

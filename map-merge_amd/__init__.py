@@ -60,6 +60,34 @@ class IcpMethod(enum.IntEnum):      # mm3d_icp_method (not a reference enum)
     POINT_TO_PLANE = 1
 
 
+class AlignMethod(enum.IntEnum):    # mm3d_align_method (not a reference enum)
+    SAC_IA = 0
+    PREREJECTIVE = 1
+
+
+class AlignmentOptions(C.Structure):
+    """mm3d_alignment_options (mm3d_set_alignment); the defaults are mm3d_alignment_options_default's."""
+    _fields_ = [("method", C.c_int), ("samples", C.c_int), ("k", C.c_int), ("similarity", C.c_double),
+                ("inlier_fraction", C.c_double)]
+
+    def __init__(self, **kw):
+        super().__init__()
+        lib().mm3d_alignment_options_default(C.byref(self))
+        for k, v in kw.items():
+            if k not in dict(self._fields_):
+                raise TypeError("unknown alignment option " + k)
+            setattr(self, k, int(v) if k in ("method", "samples", "k") else float(v))
+
+
+class AlignmentStats(C.Structure):
+    """mm3d_alignment_stats"""
+    _fields_ = [("draws", C.c_longlong), ("survivors", C.c_longlong), ("hypotheses_scored", C.c_longlong),
+                ("winner_h", C.c_longlong), ("winner_inliers", C.c_int), ("converged", C.c_int)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 class MapMergingParams(C.Structure):
     """R/include/map_merge_3d/map_merging.h:28-44, field for field."""
     _fields_ = [("resolution", C.c_double), ("descriptor_radius", C.c_double),
@@ -245,6 +273,22 @@ class Context:
     def getIcpMethod(self) -> "IcpMethod":
         return IcpMethod(lib().mm3d_get_icp_method(self._h))
 
+    def setAlignment(self, options=None, **kw):
+        """mm3d_set_alignment: the pair stage's initial alignment under SAC_IA.  An AlignmentOptions, or its fields as keywords
+        (method=AlignMethod.PREREJECTIVE, samples=..., k=..., similarity=..., inlier_fraction=...)."""
+        o = options if options is not None else AlignmentOptions(**kw)
+        self._ck(lib().mm3d_set_alignment(self._h, C.byref(o)))
+
+    def getAlignment(self) -> "AlignmentOptions":
+        o = AlignmentOptions()
+        self._ck(lib().mm3d_get_alignment(self._h, C.byref(o)))
+        return o
+
+    def lastAlignmentStats(self) -> dict:
+        st = AlignmentStats()
+        self._ck(lib().mm3d_last_alignment_stats(self._h, C.byref(st)))
+        return st.as_dict()
+
     def synchronize(self):
         self._ck(lib().mm3d_synchronize(self._h))
 
@@ -360,6 +404,32 @@ class Context:
             C.c_double(min_sample_distance), C.c_double(max_correspondence_distance), int(max_iterations),
             T.ctypes.data_as(C.c_void_p)))
         return _Tout(T)
+
+    def estimateTransformPrerejective(self, source_keypoints, source_descriptors, target_keypoints, target_descriptors,
+                                      inlier_distance, options=None, **kw):
+        """mm3d_estimate_transform_prerejective: (T, stats dict), whatever the context's setting."""
+        o = options if options is not None else AlignmentOptions(**kw)
+        T = np.zeros(16, dtype=np.float32)
+        st = AlignmentStats()
+        self._ck(lib().mm3d_estimate_transform_prerejective(
+            self._h, source_keypoints._h, source_descriptors._h, target_keypoints._h, target_descriptors._h,
+            C.c_double(inlier_distance), C.byref(o), T.ctypes.data_as(C.c_void_p), C.byref(st)))
+        return _Tout(T), st.as_dict()
+
+    def prerejectiveSurvivors(self, source_keypoints, source_descriptors, target_keypoints, target_descriptors,
+                              inlier_distance, options=None, cap=1 << 20, **kw):
+        """mm3d_debug_prerejective_survivors: (rows [n][7] = h, i0 i1 i2, t0 t1 t2 in ascending h; their inlier counts;
+        the number of survivors, which may exceed cap)."""
+        o = options if options is not None else AlignmentOptions(**kw)
+        rows = np.zeros((max(cap, 1), 7), dtype=np.int32)
+        counts = np.zeros(max(cap, 1), dtype=np.int32)
+        n = C.c_size_t()
+        self._ck(lib().mm3d_debug_prerejective_survivors(
+            self._h, source_keypoints._h, source_descriptors._h, target_keypoints._h, target_descriptors._h,
+            C.c_double(inlier_distance), C.byref(o), rows.ctypes.data_as(C.c_void_p), counts.ctypes.data_as(C.c_void_p),
+            C.c_size_t(cap), C.byref(n)))
+        m = min(int(n.value), cap)
+        return rows[:m].copy(), counts[:m].copy(), int(n.value)
 
     def estimateTransformICP(self, source_points, target_points, initial_guess, max_correspondence_distance,
                              outlier_rejection_threshold, max_iterations=100, transformation_epsilon=0.0):

@@ -220,6 +220,8 @@ static void set_streams_one(mm3d_ctx *ctx, int n_streams)
     const int st = mm3d_create(ctx->device, &h);
     if (st != MM3D_OK) throw Error(st, "mm3d_set_streams: could not create a helper context");
     h->icp_method = ctx->icp_method;                    // (mm3d_set_icp_method before mm3d_set_streams)
+    h->align_method = ctx->align_method;                // (mm3d_set_alignment likewise)
+    h->align_options = ctx->align_options;
     ctx->helpers.push_back(h);
   }
 }
@@ -678,7 +680,8 @@ static void map_prepare_impl(mm3d_ctx *ctx, mm3d_map *m, const mm3d_params *p)
 {
   if (ctx->icp_method && !m->normals) m->normals.reset(compute_normals(ctx, m->points, p->normal_radius));
   prepare_pair_search(ctx, m->points, p->max_correspondence_distance, p->max_correspondence_distance);
-  if (p->estimation_method == MM3D_EST_SAC_IA) prepare_sacia_target(ctx, m->keypoints, (float)p->max_correspondence_distance);
+  if (p->estimation_method == MM3D_EST_SAC_IA && ctx->align_method) ctx->align_method->prepare(ctx, m->keypoints, p->max_correspondence_distance);
+  else if (p->estimation_method == MM3D_EST_SAC_IA) prepare_sacia_target(ctx, m->keypoints, (float)p->max_correspondence_distance);
   desc_knn_prepare_target(ctx, m->desc);
   (void)cloud_host(ctx, m->keypoints, false);       // (the keypoints' host copy rides on the wait below)
   ctx->sync();                                       // everything complete, the error flags the kernels left looked at
@@ -713,14 +716,23 @@ static const mm3d_normals *map_normals(mm3d_ctx *ctx, const mm3d_map *m, const m
   return m->normals.get();
 }
 
+// The estimation method as the rand() replay sees it: a prerejective alignment (mm3d_set_alignment) draws nothing from rand(),
+// which is MATCHING's case in pair_rand_replay.
+static int replay_method(const mm3d_ctx *ctx, const mm3d_params *p)
+{
+  return ctx->align_method && p->estimation_method == MM3D_EST_SAC_IA ? (int)MM3D_EST_MATCHING : (int)p->estimation_method;
+}
+static bool prerejective(const mm3d_ctx *ctx, const mm3d_params *p) { return ctx->align_method && p->estimation_method == MM3D_EST_SAC_IA; }
+
 struct PairWork { const mm3d_map *s, *t; mm3d_pair_result *out; GlibcRand rnd; };
 static void pairs_estimate_batch(mm3d_ctx *ctx, PairWork *w, size_t n, const mm3d_params *p);
 
 static void pair_estimate_impl(mm3d_ctx *ctx, const mm3d_map *s, const mm3d_map *t, const mm3d_params *p, bool execute,
                                mm3d_pair_result *out)
 {
-  if (execute && ctx->icp_method) {
-    // point-to-plane ICP (mm3d_set_icp_method) lives in the batch path: a batch of one, from (and advancing) the context's generator
+  if (execute && (ctx->icp_method || prerejective(ctx, p))) {
+    // point-to-plane ICP (mm3d_set_icp_method) and the prerejective alignment (mm3d_set_alignment) live in the batch path: a
+    // batch of one, from (and advancing) the context's generator
     PairWork w{s, t, out, ctx->rnd};
     pairs_estimate_batch(ctx, &w, 1, p);
     return;
@@ -729,6 +741,7 @@ static void pair_estimate_impl(mm3d_ctx *ctx, const mm3d_map *s, const mm3d_map 
   out->confidence = 0.0;
   out->icp_iterations = 0;
   out->n_correspondences = out->n_inliers = out->icp_correspondences = 0;
+  if (prerejective(ctx, p)) return;                     // not executed, and nothing to replay (mm3d_set_alignment)
   // estimateTransform and transformScore of its result (R/src/map_merging.cpp:91-107) as one device
   // pipeline: the transform never visits the host in between
   double score = DBL_MAX;
@@ -782,7 +795,11 @@ static void pairs_estimate_batch(mm3d_ctx *ctx, PairWork *w, size_t n, const mm3
     out->icp_iterations = 0;
     out->n_correspondences = out->n_inliers = out->icp_correspondences = 0;
     ctx->rnd = w[i].rnd;
-    if (p->estimation_method == MM3D_EST_SAC_IA) {
+    if (prerejective(ctx, p)) {
+      // the same inputs, max_correspondence_distance as the inlier distance; the generator's seed, none of its draws
+      ctx->align_method->front(ctx, ctx->align_options, w[i].rnd.seed0, w[i].s->keypoints, w[i].s->desc, w[i].t->keypoints, w[i].t->desc,
+                               p->max_correspondence_distance, fronts[i], &ctx->last_align_stats);
+    } else if (p->estimation_method == MM3D_EST_SAC_IA) {
       // argument mapping of matching.cpp:243-246: min_sample_distance := inlier_threshold
       sac_ia_replay(ctx, w[i].s->keypoints, w[i].s->desc, w[i].t->keypoints, w[i].t->desc, p->inlier_threshold, p->max_iterations, true,
                     fronts[i]);
@@ -850,7 +867,7 @@ int mm3d_pairs_skip(mm3d_ctx *ctx, const mm3d_map *const *sources, const mm3d_ma
       const mm3d_map *s = sources[i], *t = targets[i];
       if (!s || !t) throw Error(MM3D_EINVAL, "null map");
       if (s->keypoints->n == 0 || t->keypoints->n == 0) continue;      // not a pair (map_merging.cpp:250)
-      pair_rand_replay(ctx->rnd, params->estimation_method, cloud_host(ctx, s->keypoints), params->inlier_threshold,
+      pair_rand_replay(ctx->rnd, replay_method(ctx, params), cloud_host(ctx, s->keypoints), params->inlier_threshold,
                        params->max_iterations);
     }
   });
@@ -953,7 +970,7 @@ static void estimate_maps_streams(mm3d_ctx *ctx, const mm3d_cloud_view *clouds, 
         else assumed_live[q] = 1;
       }
       GlibcRand r = state_at[q];
-      if (live) pair_rand_replay(r, params->estimation_method, cloud_host(cs[0], maps[a]->keypoints), params->inlier_threshold,
+      if (live) pair_rand_replay(r, replay_method(ctx, params), cloud_host(cs[0], maps[a]->keypoints), params->inlier_threshold,
                                  params->max_iterations);
       state_at[q + 1] = r;
       known_upto = q + 1;
@@ -1227,6 +1244,7 @@ int mm3d_shard_begin(mm3d_ctx *ctx, const mm3d_cloud_view *clouds, size_t n, con
   *out = nullptr;
   return guarded(ctx, [&] {
     if (ctx->icp_method) throw Error(MM3D_EUNSUPPORTED, "mm3d_shard_begin: shard bundles carry no normals for point-to-plane ICP");
+    if (ctx->align_method) throw Error(MM3D_EUNSUPPORTED, "mm3d_shard_begin: the ranks' pair loops run SAC-IA, not the prerejective alignment");
     *out = shard_begin_impl(ctx, clouds, n, params, rank, world);
   });
 }
@@ -1560,7 +1578,7 @@ static void estimate_maps_sequential(mm3d_ctx *ctx, const mm3d_cloud_view *cloud
     const mm3d_map *ms = maps[r.source_idx].get(), *mt = maps[r.target_idx].get();
     if (cache && cache->pair_lookup(r.source_idx, r.target_idx, ctx->rnd, &r)) {
       // reused: the generator still moves on by the draws the pair would have taken
-      pair_rand_replay(ctx->rnd, params->estimation_method, cloud_host(ctx, ms->keypoints), params->inlier_threshold, params->max_iterations);
+      pair_rand_replay(ctx->rnd, replay_method(ctx, params), cloud_host(ctx, ms->keypoints), params->inlier_threshold, params->max_iterations);
       continue;
     }
     const GlibcRand r0 = ctx->rnd;
@@ -2080,7 +2098,7 @@ int mm3d_estimate_maps_transforms(mm3d_ctx *ctx, const mm3d_cloud_view *clouds, 
       bool ok = false;
       ~CacheCall() { if (c && !ok) c->abort(); }
     } cache_call{ctx->map_cache};
-    if (ctx->map_cache) ctx->map_cache->begin(n, params, ctx->icp_method ? ctx->icp_method->method() : MM3D_ICP_POINT_TO_POINT);
+    if (ctx->map_cache) ctx->map_cache->begin(n, params, ctx->icp_method ? ctx->icp_method->method() : MM3D_ICP_POINT_TO_POINT, ctx->align_options);
     if (!ctx->helpers.empty())
       estimate_maps_streams(ctx, clouds, n, params, out_T, n_out, pairs_out, n_pairs_out);
     else

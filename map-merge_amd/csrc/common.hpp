@@ -47,10 +47,12 @@ struct Error : std::runtime_error {
 struct GlibcRand {
   uint32_t ring[31];
   int f = 3, b = 0;
+  unsigned seed0 = 1;         // the last seed (what the counter-based draws of mm3d_set_alignment are keyed by)
   GlibcRand() { seed(1); }
   void seed(unsigned s)
   {
     if (s == 0) s = 1;
+    seed0 = s;
     int32_t r[31];
     r[0] = (int32_t)s;
     for (int i = 1; i < 31; ++i) {

@@ -42,11 +42,13 @@ std::string feature_key(const mm3d_params *p)
 // what the pair stage reads (pair_estimate_impl / pairs_estimate_batch), and the ICP method (mm3d_set_icp_method): a
 // point-to-point record is never one of point-to-plane's.  (The map key needs no method: the normals point-to-plane keeps are
 // a function of the points and normal_radius.)
-std::string pair_params_key(const mm3d_params *p, int icp_method)
+std::string pair_params_key(const mm3d_params *p, int icp_method, const mm3d_alignment_options &align)
 {
   KeyBuilder k;
   k.i32(p->estimation_method).i32(p->refine_transform).f64(p->inlier_threshold).f64(p->max_correspondence_distance)
       .i32(p->max_iterations).u64(p->matching_k).f64(p->transform_epsilon).i32(icp_method);
+  // the alignment (mm3d_set_alignment): a SAC-IA record is never a prerejective one's, nor one of other options
+  k.i32(align.method).i32(align.samples).i32(align.k).f64(align.similarity).f64(align.inlier_fraction);
   return k.s;
 }
 
@@ -123,13 +125,14 @@ class MapCache final : public MapCacheBase {
       for (long long &c : counters_) c = 0;
   }
 
-  void begin(size_t n_maps, const mm3d_params *p, int icp_method) override
+  void begin(size_t n_maps, const mm3d_params *p, int icp_method, const mm3d_alignment_options &align) override
   {
     std::lock_guard<std::mutex> lk(mu_);
     reset_call_locked();
     fkey_ = feature_key(p);
-    pkey_ = pair_params_key(p, icp_method);
+    pkey_ = pair_params_key(p, icp_method, align);
     sac_ia_ = p->estimation_method == MM3D_EST_SAC_IA;
+    prerej_ = sac_ia_ && align.method == MM3D_ALIGN_PREREJECTIVE;
     slot_entry_.assign(n_maps, 0);
     slot_digest_.assign(n_maps, {0ull, 0ull});
     staged_.reserve(n_maps);             // (insert never reallocates: it cannot fail once it owns a map)
@@ -263,7 +266,9 @@ class MapCache final : public MapCacheBase {
     KeyBuilder k;
     k.s = pkey_;
     k.u64(src).u64(tgt);
-    if (sac_ia_) {                       // the whole generator state the pair starts from
+    if (prerej_) {                       // prerejective alignment (mm3d_set_alignment) reads the seed and draws nothing from rand()
+      k.i32((int)rnd.seed0);
+    } else if (sac_ia_) {                // the whole generator state the pair starts from
       for (uint32_t w : rnd.ring) k.i32((int)w);
       k.i32(rnd.f).i32(rnd.b);
     }
@@ -320,6 +325,7 @@ class MapCache final : public MapCacheBase {
   // the running call
   std::string fkey_, pkey_;
   bool sac_ia_ = false;
+  bool prerej_ = false;
   std::vector<uint64_t> slot_entry_;                               // 0: none (not yet looked up, or not cached)
   std::vector<std::pair<unsigned long long, unsigned long long>> slot_digest_;
   std::vector<std::unique_ptr<Entry>> staged_;

@@ -15,6 +15,7 @@
 namespace mm3d {
 struct DeviceSet;
 struct IcpMethodBase;
+struct AlignMethodBase;
 
 // The feature / pair cache of mm3d_estimate_maps_transforms (mm3d_set_map_cache; the concrete class is map_cache.cpp's).  The
 // drivers in capi.cpp only see this interface, so the host code links without it (tests/host_san).  One call at a time -- the
@@ -22,7 +23,8 @@ struct IcpMethodBase;
 // abort (it did not: the cache is left exactly as it was before the call).
 struct MapCacheBase {
   virtual ~MapCacheBase() = default;
-  virtual void begin(size_t n_maps, const mm3d_params *p, int icp_method) = 0;   // icp_method: MM3D_ICP_* of the call (mm3d_set_icp_method)
+  // icp_method: MM3D_ICP_* of the call (mm3d_set_icp_method); align: its alignment (mm3d_set_alignment)
+  virtual void begin(size_t n_maps, const mm3d_params *p, int icp_method, const mm3d_alignment_options &align) = 0;
   // map `slot`'s packed upload `raw` (non-empty, on c's stream): the cached bundle, borrowed for the call, or null.  One launch and
   // one wait on c (a second compare-only launch and wait when the digest names another candidate than the slot's last entry).
   virtual const mm3d_map *lookup(Context *c, size_t slot, const mm3d_cloud *raw) = 0;
@@ -45,6 +47,11 @@ struct mm3d_ctx : mm3d::Context {
   // mm3d_set_icp_method: null = the reference's point-to-point ICP.  Not owned (a process-wide object of icp_plane.hip's that
   // holds no state); set on the context and its helpers alike, and copied to helpers that mm3d_set_streams makes later.
   const mm3d::IcpMethodBase *icp_method = nullptr;
+  // mm3d_set_alignment: null = the reference's SAC-IA.  Not owned (a process-wide object of align_prerej.hip's that holds no
+  // state); set, with the options, on the context and its helpers alike, and copied to helpers that mm3d_set_streams makes later.
+  const mm3d::AlignMethodBase *align_method = nullptr;
+  mm3d_alignment_options align_options{MM3D_ALIGN_SAC_IA, 1 << 16, 10, 0.9, 0.25};
+  mm3d_alignment_stats last_align_stats{0, 0, 0, -1, 0, 0};
   // mm3d_set_streams: helper contexts (one HIP stream + one host thread each while a call is running)
   // that mm3d_estimate_maps_transforms deals maps and pairs to; owned by this context
   std::vector<mm3d_ctx *> helpers;
@@ -290,6 +297,19 @@ struct IcpMethodBase {
   // icp_score_batch with this method's ICP
   virtual void score_batch(Context *c, IcpScoreJob *jobs, int n_jobs, bool run_icp, double max_corr_dist, int max_iterations, double eps,
                            bool want_score, double score_max_distance) const = 0;
+};
+struct PairFront;
+// The initial alignment of a context's pair stage under SAC_IA (mm3d_set_alignment; the one concrete class is
+// align_prerej.hip's).  Like IcpMethodBase, the drivers in capi.cpp only see this interface, so the host code links without
+// the new kernels (tests/host_san); a null pointer on the context means the reference's SAC-IA.
+struct AlignMethodBase {
+  virtual ~AlignMethodBase() = default;
+  // the target-side structures a pair reads of a map's keypoints (mm3d_map_prepare)
+  virtual void prepare(Context *c, const mm3d_cloud *kp, double inlier_distance) const = 0;
+  // estimate_pair_front's SAC_IA branch with this method: f.dT0 / f.on_device, or the identity in f.T0
+  virtual void front(Context *c, const mm3d_alignment_options &o, unsigned seed, const mm3d_cloud *skp, const mm3d_desc *sd,
+                     const mm3d_cloud *tkp, const mm3d_desc *td, double inlier_distance, PairFront &f,
+                     mm3d_alignment_stats *stats) const = 0;
 };
 struct PairCounts { int n_correspondences = 0, n_inliers = 0, icp_correspondences = 0; };
 // ICP (optional) from a guess on the device (guess_dev != null) or on the host, then transformScore
