@@ -168,6 +168,26 @@ void mm3d_debug_sacia_stats(long long out[4], int reset, int collect);
  * does not bind (dispatch_descriptors.h:44-46 binds SHOT1344) but BASELINE.json configs[3] names: idx / d2 receive na x k
  * nearest target rows in FLANN's (distance, index) order, exact */
 int mm3d_debug_desc_knn(mm3d_ctx *ctx, const float *a, size_t na, const float *b, size_t nb, int dim, int k, int *idx, float *d2);
+/* test hook: the exact nearest-neighbour search behind mm3d_estimate_transform_icp and mm3d_transform_score (csrc/nn_search_body.hpp),
+ * point by point.  Every source point is carried by the column-major T and searched in `target` within `range`, read as
+ * convention 0: a distance, ICP's max_correspondence_distance; 1: mm3d_transform_score's max_distance, compared with the
+ * SQUARED distance.  The largest squared distance in range, the search radius, the grid cell and the ring limit are derived
+ * as those two entry points derive them.  split: 1 = one work item per wave, 4 = one per block (the library picks by the
+ * source's size; here it is forced).  Per source point, in the caller's order: idx = the nearest target point's index (ties:
+ * the lowest) or -1 for nothing in range and for a non-finite source point, d2 = the float squared distance the search holds,
+ * +inf where idx is -1.  info (optional) receives what was derived; cell = 0 and n_items = 0 when there was nothing to
+ * search (an empty or all-non-finite cloud). */
+typedef struct mm3d_nn_search_info {
+  float max_d2;        /* d2 <= max_d2 is in range */
+  float rmax;          /* the radius the search proves */
+  float cell;          /* the target grid's cell */
+  float origin[3];     /* the grid's corner: the target's bounding-box minimum */
+  int dims[3];         /* cells per axis */
+  int max_ring;        /* a query whose cell is farther than this from every occupied cell (max-norm, in cells) is not searched */
+  int n_items;         /* work items (<= 64 source points each) of the source */
+} mm3d_nn_search_info;
+int mm3d_debug_nn_search(mm3d_ctx *ctx, const mm3d_cloud *source, const mm3d_cloud *target, const float T[16], double range,
+                         int convention, int split, int *idx, float *d2, mm3d_nn_search_info *info);
 /* SAC-IA draws from libc rand() in the reference (process-global, glibc seed 1).  The context
  * carries its own replay of that generator; mm3d_srand re-seeds it (srand semantics). */
 void mm3d_srand(mm3d_ctx *ctx, unsigned seed);

@@ -127,6 +127,17 @@ class _View(C.Structure):
     _fields_ = [("points", C.c_void_p), ("n", C.c_size_t), ("stride", C.c_size_t), ("rgba_offset", C.c_size_t)]
 
 
+class NnSearchInfo(C.Structure):
+    """mm3d_nn_search_info: what mm3d_debug_nn_search derived from its range and the target."""
+    _fields_ = [("max_d2", C.c_float), ("rmax", C.c_float), ("cell", C.c_float), ("origin", C.c_float * 3),
+                ("dims", C.c_int * 3), ("max_ring", C.c_int), ("n_items", C.c_int)]
+
+    def as_dict(self):
+        return dict(max_d2=np.float32(self.max_d2), rmax=np.float32(self.rmax), cell=np.float32(self.cell),
+                    origin=np.array(self.origin[:], dtype=np.float32), dims=tuple(self.dims[:]), max_ring=int(self.max_ring),
+                    n_items=int(self.n_items))
+
+
 _LIB = None
 
 
@@ -465,6 +476,21 @@ class Context:
             C.c_double(max_correspondence_distance), int(max_iterations), C.c_size_t(matching_k),
             C.c_double(transform_epsilon), T.ctypes.data_as(C.c_void_p)))
         return _Tout(T)
+
+    def debugNnSearch(self, source_points, target_points, transform, range, convention, split):
+        """mm3d_debug_nn_search: the ICP / score nearest-neighbour search point by point.  convention 0 reads `range` as ICP's
+        max_correspondence_distance, 1 as transformScore's max_distance (compared with the squared distance); split 1 or 4 is
+        forced.  Returns (idx int32[n], d2 float32[n], info dict) in the source's own order: idx -1 and d2 +inf for nothing
+        in range and for non-finite source points."""
+        n = len(source_points)
+        idx = np.zeros(max(n, 1), dtype=np.int32)
+        d2 = np.zeros(max(n, 1), dtype=np.float32)
+        t = _T(transform)
+        info = NnSearchInfo()
+        self._ck(lib().mm3d_debug_nn_search(self._h, source_points._h, target_points._h, t.ctypes.data_as(C.c_void_p),
+                                            C.c_double(range), int(convention), int(split), idx.ctypes.data_as(C.c_void_p),
+                                            d2.ctypes.data_as(C.c_void_p), C.byref(info)))
+        return idx[:n], d2[:n], info.as_dict()
 
     def transformScore(self, source_points, target_points, transform, max_distance) -> float:
         t = _T(transform)

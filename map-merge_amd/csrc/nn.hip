@@ -21,6 +21,7 @@
 // icp_corr_reduce (this search + 17 double partial sums per block through wave shuffles) and
 // icp_finalize (Umeyama by 3x3 Jacobi SVD, accumulate, PCL's convergence tests, all on the device).
 // Algorithmic traffic: 12 B per source point per iteration.
+#include "capi_guard.hpp"
 #include "nn_core.hpp"
 
 namespace mm3d {
@@ -101,6 +102,41 @@ k_nn_wave(const NnJob *__restrict__ jobs, float max_d2, float rmax)
     double v = 0.0;
     if (MODE == 0 || k >= 15) v = red[0][k] + red[1][k] + red[2][k] + red[3][k];
     partials[(size_t)bid * kAcc + k] = v;
+  }
+}
+
+// The search alone, per point (test hook mm3d_debug_nn_search): nn_search_body.hpp's keyed search (MODE 0) for one job, and
+// each valid lane's result -- the winner's original index and the d2 the lane holds, or -1 / +inf -- stored at the source
+// point's ORIGINAL index (src[i].w).  A third compile of the shared body (the same tokens, its own machine code); the
+// tests tie k_nn_wave's sums to what it returns.
+template <int SPLIT>
+__global__ void __launch_bounds__(256) MM3D_NN_ATTR
+k_nn_probe(const NnJob *__restrict__ jobs, float max_d2, float rmax, int *__restrict__ out_idx, float *__restrict__ out_d2)
+{
+  constexpr int MODE = 0;
+  const NnJob &job = jobs[0];
+  if ((int)blockIdx.x >= job.nblocks) return;
+  const float4 *__restrict__ src = job.src;
+  const int2 *__restrict__ items = job.items;
+  const int n_items = job.n_items;
+  const GridView g = job.g;
+  const float *__restrict__ Tc = job.Tc;
+  const int max_ring = job.max_ring;
+  __shared__ float Ts[16];
+  __shared__ __attribute__((aligned(16))) float s_cx[4][kTile], s_cy[4][kTile], s_cz[4][kTile];
+  __shared__ __attribute__((aligned(16))) unsigned s_cw[4][kTile];
+  __shared__ int s_off[4][kRows];
+  __shared__ int s_beg[4][kRows];
+  __shared__ unsigned long long s_merge[SPLIT == 4 ? 4 : 1][64];
+  if (threadIdx.x < 16) Ts[threadIdx.x] = Tc[threadIdx.x];
+  __syncthreads();
+#include "nn_search_body.hpp"
+  if (SPLIT == 4 && wave != 0) return;     // the four waves hold the same result
+  if (valid) {
+    const int o = __float_as_int(src[i].w);
+    const bool found = (unsigned)bkey != 0xffffffffu;
+    out_idx[o] = found ? (int)(unsigned)bkey : -1;
+    out_d2[o] = found ? best : INFINITY;
   }
 }
 
@@ -239,6 +275,28 @@ static float nn_cell_for(double radius)
   return cell;
 }
 
+// What a search derives from its range: the largest squared distance that is still a correspondence, the radius the
+// search has to prove (with the slack that covers its own rounding) and the radius the target's grid is built for.
+struct NnRange { float max_d2, rmax; double radius; };
+// ICP: max_corr_dist is a distance.  (double)d2 > max_dist_sqr rejects: accept d2 <= largest float not above max_dist_sqr
+static NnRange nn_range_icp(double max_corr_dist)
+{
+  const double max_dist_sqr = max_corr_dist * max_corr_dist;
+  float max_d2 = (float)max_dist_sqr;
+  if ((double)max_d2 > max_dist_sqr) max_d2 = std::nextafterf(max_d2, -INFINITY);
+  return {max_d2, (float)(max_corr_dist * 1.0001 + 1e-5), max_corr_dist};
+}
+// score: max_range_ is compared with the SQUARED distance (PCL quirk), so the search radius is sqrt(max_distance)
+static NnRange nn_range_score(double max_distance)
+{
+  const double radius = std::sqrt(max_distance > 0 ? max_distance : 0.0);
+  float max_d2 = (float)max_distance;
+  if ((double)max_d2 > max_distance) max_d2 = std::nextafterf(max_d2, -INFINITY);
+  return {max_d2, (float)(radius * 1.0001 + 1e-5), radius};
+}
+// rings of cells (around a query's own cell) beyond which the distance transform need not tell cells apart
+static int nn_max_ring(float rmax, const Grid &g) { return (int)std::ceil(rmax / g.cell) + 1; }
+
 // One work item per block (k_nn_wave's SPLIT 4) when the source has too few items to keep the chip busy with one
 // wave each: 256 CUs x 4 SIMDs take 1024 waves before any two share a SIMD.  Measured on MI355X, pairs/s with
 // the split off / on: 16 x 100 k points (1.3 k items) 1765 / 1823, 4 x 200 k (2.5 k items) 245 / 257,
@@ -270,18 +328,11 @@ static void icp_batch(Context *c, IcpScoreJob *jobs, int n_jobs, bool run_icp, d
   static_assert(offsetof(IcpState, T) == 0, "the score kernel reads T at the head of the state");
   c->last_icp_iterations = 0;
   c->last_icp_converged = 0;
-  const double score_radius = std::sqrt(score_max_distance > 0 ? score_max_distance : 0.0);
-  // ICP search parameters
-  const double max_dist_sqr = max_corr_dist * max_corr_dist;
-  // (double)d2 > max_dist_sqr rejects: accept d2 <= largest float not above max_dist_sqr
-  float max_d2 = (float)max_dist_sqr;
-  if ((double)max_d2 > max_dist_sqr) max_d2 = std::nextafterf(max_d2, -INFINITY);
-  const float rmax = (float)(max_corr_dist * 1.0001 + 1e-5);
-  // score search parameters: max_range_ is compared with the SQUARED distance (PCL quirk), so the
-  // search radius is sqrt(max_distance)
-  float s_max_d2 = (float)score_max_distance;
-  if ((double)s_max_d2 > score_max_distance) s_max_d2 = std::nextafterf(s_max_d2, -INFINITY);
-  const float s_rmax = (float)(score_radius * 1.0001 + 1e-5);
+  // the ICP's and the score's search parameters
+  const NnRange icp_range = nn_range_icp(max_corr_dist), score_range = nn_range_score(score_max_distance);
+  const double score_radius = score_range.radius;
+  const float max_d2 = icp_range.max_d2, rmax = icp_range.rmax;
+  const float s_max_d2 = score_range.max_d2, s_rmax = score_range.rmax;
 
   struct Live { int job; const float4 *sp; int ns, n_items; const Grid *tg, *sg; int max_ring, s_ring; };
   std::vector<Live> live;
@@ -307,9 +358,9 @@ static void icp_batch(Context *c, IcpScoreJob *jobs, int n_jobs, bool run_icp, d
     if (plane && tg && (!J.tgt_normals || J.tgt_normals->n != J.tgt->n))
       throw Error(MM3D_EINVAL, "point-to-plane ICP: the target's normals do not match its points");
     Live L{j, sp, ns, J.src->n_wave_items, tg, sg, 0, 0};
-    L.max_ring = tg ? (int)std::ceil(rmax / tg->cell) + 1 : 0;
+    L.max_ring = tg ? nn_max_ring(rmax, *tg) : 0;
     if (tg) grid_ensure_dt(c, *tg, L.max_ring);
-    L.s_ring = sg ? (int)std::ceil(s_rmax / sg->cell) + 1 : 0;
+    L.s_ring = sg ? nn_max_ring(s_rmax, *sg) : 0;
     if (sg) grid_ensure_dt(c, *sg, L.s_ring);
     live.push_back(L);
   }
@@ -476,16 +527,13 @@ IcpResult icp(Context *c, const mm3d_cloud *src, const mm3d_cloud *tgt, const fl
 double transform_score(Context *c, const mm3d_cloud *src, const mm3d_cloud *tgt, const float T[16], double max_distance)
 {
   if (src->n == 0 || tgt->n == 0) return DBL_MAX;
-  // max_range_ is compared with the SQUARED distance (PCL quirk): search radius sqrt(max_distance)
-  const double radius = std::sqrt(max_distance > 0 ? max_distance : 0.0);
-  const Grid &tg = cloud_grid(c, tgt, nn_cell_for(radius));
+  const NnRange range = nn_range_score(max_distance);
+  const Grid &tg = cloud_grid(c, tgt, nn_cell_for(range.radius));
   int ns = 0;
   const float4 *sp = morton_source(c, src, ns);
   if (ns == 0 || tg.n == 0) return DBL_MAX;
-  float max_d2 = (float)max_distance;
-  if ((double)max_d2 > max_distance) max_d2 = std::nextafterf(max_d2, -INFINITY);
-  const float rmax = (float)(radius * 1.0001 + 1e-5);
-  const int max_ring = (int)std::ceil(rmax / tg.cell) + 1;
+  const float max_d2 = range.max_d2, rmax = range.rmax;
+  const int max_ring = nn_max_ring(rmax, tg);
   grid_ensure_dt(c, tg, max_ring);
   const int n_items = src->n_wave_items;
   const bool split = nn_split_items(n_items);
@@ -522,6 +570,71 @@ double transform_score(Context *c, const mm3d_cloud *src, const mm3d_cloud *tgt,
   return ho[1] > 0.0 ? ho[0] / ho[1] : DBL_MAX;
 }
 
+// mm3d_debug_nn_search: range, cell, ring and distance transform as icp_batch (convention 0) or transform_score (1) derive
+// them, the source in its Hilbert order and work items as every search takes it, one launch of k_nn_probe with the split forced
+static void debug_nn_search(Context *c, const mm3d_cloud *src, const mm3d_cloud *tgt, const float T[16], double range, int convention,
+                            int split, int *idx, float *d2, mm3d_nn_search_info *info)
+{
+  const NnRange r = convention == 0 ? nn_range_icp(range) : nn_range_score(range);
+  mm3d_nn_search_info I;
+  memset(&I, 0, sizeof(I));
+  I.max_d2 = r.max_d2;
+  I.rmax = r.rmax;
+  std::vector<int> h_idx(src->n, -1);
+  std::vector<float> h_d2(src->n, INFINITY);
+  int ns = 0;
+  const float4 *sp = (src->n && tgt->n) ? morton_source(c, src, ns) : nullptr;
+  const Grid *tg = ns ? &cloud_grid(c, tgt, nn_cell_for(r.radius)) : nullptr;
+  if (tg && tg->n) {
+    const int max_ring = nn_max_ring(r.rmax, *tg);
+    grid_ensure_dt(c, *tg, max_ring);
+    const int n_items = src->n_wave_items;
+    const unsigned nblocks = split == 4 ? (unsigned)n_items : div_up(n_items, 4);
+    I.cell = tg->cell;
+    I.max_ring = max_ring;
+    for (int a = 0; a < 3; ++a) { I.dims[a] = tg->dims[a]; I.origin[a] = tg->mn[a]; }
+    I.n_items = n_items;
+    DevBuf<int> d_idx(c, src->n);
+    DevBuf<float> d_d2(c, src->n), dT(c, 16);
+    DevBuf<NnJob> d_job(c, 1);
+    char *pinned = (char *)c->pin(256 + sizeof(NnJob));
+    float *hT = (float *)pinned;
+    NnJob *hj = (NnJob *)(pinned + 256);
+    memcpy(hT, T, 64);
+    NnJob q;
+    memset(&q, 0, sizeof(q));
+    q.src = sp;
+    q.items = (const int2 *)src->wave_items.get();
+    q.n_items = n_items;
+    q.nblocks = (int)nblocks;
+    q.split = split == 4 ? 1 : 0;
+    q.g = tg->view();
+    q.tgt_ref = (const float4 *)tgt->pts.get();
+    q.Tc = dT.get();
+    q.max_ring = max_ring;
+    *hj = q;
+    // (non-finite source points are in no work item: they keep -1 / +inf)
+    MM3D_HIP(hipMemcpyAsync(d_idx.get(), h_idx.data(), src->n * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    MM3D_HIP(hipMemcpyAsync(d_d2.get(), h_d2.data(), src->n * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    MM3D_HIP(hipMemcpyAsync(dT.get(), hT, 64, hipMemcpyHostToDevice, c->stream));
+    MM3D_HIP(hipMemcpyAsync(d_job.get(), hj, sizeof(NnJob), hipMemcpyHostToDevice, c->stream));
+    if (split == 4)
+      MM3D_LAUNCH(c, "debug_nn_search", ns * 24.0, (k_nn_probe<4>), dim3(nblocks), dim3(256), 0, (const NnJob *)d_job.get(), r.max_d2, r.rmax,
+                  d_idx.get(), d_d2.get());
+    else
+      MM3D_LAUNCH(c, "debug_nn_search", ns * 24.0, (k_nn_probe<1>), dim3(nblocks), dim3(256), 0, (const NnJob *)d_job.get(), r.max_d2, r.rmax,
+                  d_idx.get(), d_d2.get());
+    MM3D_HIP(hipMemcpyAsync(h_idx.data(), d_idx.get(), src->n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    MM3D_HIP(hipMemcpyAsync(h_d2.data(), d_d2.get(), src->n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    c->sync();
+  }
+  if (src->n) {
+    memcpy(idx, h_idx.data(), src->n * sizeof(int));
+    memcpy(d2, h_d2.data(), src->n * sizeof(float));
+  }
+  if (info) *info = I;
+}
+
 #ifdef MM3D_NN_STATS
 extern "C" void mm3d_debug_nn_stats(unsigned long long *out, int reset)
 {
@@ -538,13 +651,23 @@ void prepare_pair_search(Context *c, const mm3d_cloud *points, double max_corr_d
   if (points->n == 0) return;
   int ns = 0;
   (void)morton_source(c, points, ns);
-  const double radii[2] = {max_corr_dist, std::sqrt(score_max_distance > 0 ? score_max_distance : 0.0)};
-  for (double radius : radii) {
-    const Grid &g = cloud_grid(c, points, nn_cell_for(radius));
+  const NnRange ranges[2] = {nn_range_icp(max_corr_dist), nn_range_score(score_max_distance)};
+  for (const NnRange &range : ranges) {
+    const Grid &g = cloud_grid(c, points, nn_cell_for(range.radius));
     if (g.n == 0) continue;
-    const float rmax = (float)(radius * 1.0001 + 1e-5);
-    grid_ensure_dt(c, g, (int)std::ceil(rmax / g.cell) + 1);
+    grid_ensure_dt(c, g, nn_max_ring(range.rmax, g));
   }
 }
 
 }  // namespace mm3d
+
+// the C entry point of the search probe (include/mm3d.h) lives with its kernel, like fpfh.hip's mm3d_debug_pair_bins: the
+// host-only builds of the library link capi.cpp without this file
+extern "C" int mm3d_debug_nn_search(mm3d_ctx *ctx, const mm3d_cloud *source, const mm3d_cloud *target, const float T[16], double range,
+                                    int convention, int split, int *idx, float *d2, mm3d_nn_search_info *info)
+{
+  if (!source || !target || !T || (convention != 0 && convention != 1) || (split != 1 && split != 4)) return MM3D_EINVAL;
+  if (!(range >= 0.0) || !std::isfinite(range)) return MM3D_EINVAL;
+  if (source->n && (!idx || !d2)) return MM3D_EINVAL;
+  return mm3d::guarded(ctx, [&] { mm3d::debug_nn_search(ctx, source, target, T, range, convention, split, idx, d2, info); });
+}

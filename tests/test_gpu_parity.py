@@ -539,6 +539,24 @@ def _small_rot(ax, ay, az, t):
     return T
 
 
+def _assert_same_double_sum(ctx, ca, cb, T, max_distance, got, ref):
+    """The device and the oracle sum the SAME float d2 in double, each in its own order, and divide by the same count.  The
+    exactly rounded sum of the per-point d2 (test hook mm3d_debug_nn_search; tests/test_gpu_nn_search.py checks those bits against
+    a brute force) over the count is within (count + 2) 2^-53 relative of ANY such sum -- the worst case of a double sum of
+    `count` non-negative terms, plus the division -- so both values must be that close to it; DBL_MAX exactly for count 0."""
+    import math
+    _, d2, _ = ctx.debugNnSearch(ca, cb, T, max_distance, 1, 4)
+    terms = d2[np.isfinite(d2)].astype(np.float64)
+    count = len(terms)
+    if count == 0:
+        assert got == ref == np.finfo(np.float64).max, (max_distance, got, ref)
+        return
+    exact = math.fsum(terms) / count
+    bound = (count + 2) * 2.0 ** -53 * exact
+    assert abs(ref - exact) <= bound, ("oracle", max_distance, ref, exact, count)
+    assert abs(got - exact) <= bound, ("device", max_distance, got, exact, count)
+
+
 def test_transform_score(ctx, po, scene, synth):
     a, b = scene
     gt = synth.relative_gt(a["T"], b["T"]).astype(np.float32)
@@ -546,12 +564,12 @@ def test_transform_score(ctx, po, scene, synth):
     for T in (gt, np.eye(4, dtype=np.float32), (gt @ _small_rot(0.02, -0.01, 0.05, [0.2, 0.1, 0.0])).astype(np.float32)):
         ref = po.transform_score(a["filt"], b["filt"], T, 1.0)
         got = ctx.transformScore(ca, cb, T, 1.0)
-        assert got == pytest.approx(ref, rel=1e-6), (got, ref)   # double sum of identical float d2
+        _assert_same_double_sum(ctx, ca, cb, T, 1.0, got, ref)
     # nothing in range -> DBL_MAX; zero transform is scored like any other matrix
     far = np.eye(4, dtype=np.float32); far[0, 3] = 1e4
     assert ctx.transformScore(ca, cb, far, 1.0) == po.transform_score(a["filt"], b["filt"], far, 1.0) == np.finfo(np.float64).max
     z = np.zeros((4, 4), dtype=np.float32)
-    assert ctx.transformScore(ca, cb, z, 1.0) == pytest.approx(po.transform_score(a["filt"], b["filt"], z, 1.0), rel=1e-6)
+    _assert_same_double_sum(ctx, ca, cb, z, 1.0, ctx.transformScore(ca, cb, z, 1.0), po.transform_score(a["filt"], b["filt"], z, 1.0))
 
 
 def test_nearest_neighbour_search_over_ranges(ctx, po, scene, synth):
@@ -567,10 +585,7 @@ def test_nearest_neighbour_search_over_ranges(ctx, po, scene, synth):
         for T in poses:
             ref = po.transform_score(a["filt"], b["filt"], T, max_distance)
             got = ctx.transformScore(ca, cb, T, max_distance)
-            if ref == np.finfo(np.float64).max:
-                assert got == ref, (max_distance, got)
-            else:
-                assert got == pytest.approx(ref, rel=1e-6), (max_distance, got, ref)
+            _assert_same_double_sum(ctx, ca, cb, T, max_distance, got, ref)
     for max_corr in (0.1, 2.0):
         guess = (gt @ _small_rot(0.02, -0.01, 0.04, [0.2, -0.1, 0.05])).astype(np.float32)
         T_ref, it_ref = po.icp(a["filt"], b["filt"], guess, max_corr, 0.5, 30, 1e-6)
