@@ -12,6 +12,42 @@
 //   includes this header once), then link with -lmm3d.
 #pragma once
 
+#include <cmath>
+#include <cstdlib>
+#include <stdexcept>
+#include <string>
+
+#include "mm3d.h"
+
+namespace map_merge_3d
+{
+namespace mm3d_shim
+{
+// MM3D_KEYPOINTS=uniform or uniform:<leaf in metres>: the estimation context's maps take uniform keypoints instead of the
+// reference's detectors (mm3d_set_keypoints; without a leaf, the library's default fraction of descriptor_radius); reference
+// or unset keeps the detectors.  Anything else throws, as a malformed MM3D_ICP or MM3D_ALIGN does.  (Outside the guard below:
+// it needs neither PCL nor ROS, so it is checked where the rest of this header cannot be compiled.)
+inline mm3d_keypoint_options parse_keypoints(const char *value)
+{
+  mm3d_keypoint_options o;
+  o.source = MM3D_KEYPOINTS_REFERENCE;
+  o.leaf = 0.0;
+  const std::string v = value ? value : "";
+  if (v.empty() || v == "reference") return o;
+  bool ok = v.compare(0, 7, "uniform") == 0 && (v.size() == 7 || v[7] == ':');
+  if (ok && v.size() > 7) {
+    const char *s = v.c_str() + 8;
+    char *end = nullptr;
+    o.leaf = std::strtod(s, &end);
+    ok = end != s && *end == '\0' && std::isfinite(o.leaf) && o.leaf > 0.0;
+  }
+  if (!ok) throw std::runtime_error("mm3d: MM3D_KEYPOINTS must be reference, uniform or uniform:<leaf in metres>, not '" + v + "'");
+  o.source = MM3D_KEYPOINTS_UNIFORM;
+  return o;
+}
+}  // namespace mm3d_shim
+}  // namespace map_merge_3d
+
 #if defined(__has_include)
 #if __has_include(<pcl/point_cloud.h>) && __has_include(<map_merge_3d/map_merging.h>)
 #define MM3D_SHIM_AVAILABLE 1
@@ -89,7 +125,9 @@ inline mm3d_ctx *ctx()
   // set as well this throws rather than quietly running point-to-point.
   // MM3D_ALIGN=prerejective: under SAC_IA the pair stage's initial alignment is the prerejective one (mm3d_set_alignment), with
   // MM3D_ALIGN_SAMPLES=<draws> if given; sac_ia or unset keeps the reference's.  Not available on a device list either.
+  // MM3D_KEYPOINTS=uniform[:<leaf>]: parse_keypoints above; it works on a device list too.
   static mm3d_ctx *c = [] {
+    const mm3d_keypoint_options keypoints = parse_keypoints(std::getenv("MM3D_KEYPOINTS"));
     const char *al = std::getenv("MM3D_ALIGN");
     const std::string align = al ? al : "";
     if (!align.empty() && align != "sac_ia" && align != "prerejective")
@@ -119,6 +157,8 @@ inline mm3d_ctx *ctx()
       if (mm3d_set_alignment(e, &o) != MM3D_OK)
         throw std::runtime_error("mm3d: MM3D_ALIGN=prerejective was refused (MM3D_ALIGN_SAMPLES must be 1 .. 2^30)");
     }
+    if (keypoints.source != MM3D_KEYPOINTS_REFERENCE && mm3d_set_keypoints(e, &keypoints) != MM3D_OK)
+      throw std::runtime_error("mm3d: MM3D_KEYPOINTS was refused (the leaf must be a positive float with a finite reciprocal)");
     return e;
   }();
   return c;

@@ -328,6 +328,32 @@ int mm3d_get_alignment(const mm3d_ctx *ctx, mm3d_alignment_options *options);   
 /* The alignment of the last pair that mm3d_pair_estimate or the one-stream mm3d_estimate_maps_transforms ran with
  * MM3D_ALIGN_PREREJECTIVE on this context (all zero, winner_h -1, before the first).  MM3D_EINVAL for NULL. */
 int mm3d_last_alignment_stats(const mm3d_ctx *ctx, mm3d_alignment_stats *stats);
+/* Where the whole-map calls take a map's keypoints from (off the reference's path; MM3D_KEYPOINTS_REFERENCE, the reference's
+ * detectKeypoints(params.keypoint_type), by default).  With MM3D_KEYPOINTS_UNIFORM every place that runs detectKeypoints
+ * behind a whole-map call -- mm3d_map_features, mm3d_estimate_maps_transforms on one stream or many, on a device list
+ * (mm3d_create_devices) and mm3d_shard_begin -- takes mm3d_uniform_keypoints(the filtered points, leaf) instead: no detector,
+ * an evenly spaced subset of the cloud (what PCL's own alignment tutorials describe with pcl::UniformSampling), so that a map
+ * without colour or corners still has keypoints and two independent samplings of one surface have keypoints within about one
+ * leaf of each other.  params.keypoint_type and params.keypoint_threshold are then not read (values outside the enum still
+ * answer MM3D_EINVAL); mm3d_params does not change.  The normals come from their stand-alone launch (SIFT's fused first octave
+ * does not run); descriptors, their pruning of the keypoints, either estimation method, either alignment and either ICP are
+ * the existing code on the new keypoint cloud.  The stand-alone mm3d_detect_keypoints is untouched.
+ *   - leaf > 0: the spacing in metres; 0: params.descriptor_radius / 2 (DESIGN.md section 7d has the measurement).
+ *   - The setting reaches the context's mm3d_set_streams helpers in either order of the two calls, and every device of a
+ *     device-list context; only a map's features change, and those travel in the bundles, so device lists and shards carry it.
+ *     Every rank of a sharded call must use the same setting.  Results are bit-identical for every stream count, driver and
+ *     cache setting.
+ *   - The map cache's map key holds (source, leaf): a bundle of one source is never served to the other. */
+typedef enum { MM3D_KEYPOINTS_REFERENCE = 0, MM3D_KEYPOINTS_UNIFORM = 1 } mm3d_keypoint_source;
+typedef struct mm3d_keypoint_options {
+  int source;                 /* MM3D_KEYPOINTS_* */
+  double leaf;                /* > 0; 0 = descriptor_radius / 2, see above */
+} mm3d_keypoint_options;
+void mm3d_keypoint_options_default(mm3d_keypoint_options *o);     /* source MM3D_KEYPOINTS_REFERENCE, leaf 0 */
+/* MM3D_EINVAL: ctx or options NULL, an unknown source, a leaf that is neither 0 nor one mm3d_uniform_keypoints takes (the
+ * value is checked whatever the source). */
+int mm3d_set_keypoints(mm3d_ctx *ctx, const mm3d_keypoint_options *options);
+int mm3d_get_keypoints(const mm3d_ctx *ctx, mm3d_keypoint_options *options);        /* MM3D_EINVAL for NULL */
 
 /* ---- cloud objects -------------------------------------------------------------------- */
 int mm3d_cloud_create(mm3d_ctx *ctx, const void *points, size_t n, size_t stride, size_t rgba_offset,
@@ -365,6 +391,28 @@ int mm3d_compute_normals(mm3d_ctx *ctx, const mm3d_cloud *in, double radius, mm3
 int mm3d_detect_keypoints(mm3d_ctx *ctx, const mm3d_cloud *points, const mm3d_normals *normals,
                           int type, double threshold, double radius, double resolution,
                           mm3d_cloud **keypoints);
+/* Uniform keypoints (not a reference function; mm3d_set_keypoints puts it behind the whole-map calls): a subset of the
+ * records of `points`, unchanged (x, y, z and the rgba bits), in ascending input index -- of every occupied voxel of the
+ * GLOBAL lattice of side leaf (anchored at the origin, not at the cloud's minimum) the point nearest the voxel's centre.
+ * To the operation, every one a single IEEE float operation rounded to nearest, nothing contracted:
+ *   - leaf_f = (float)leaf, inv = 1.0f / leaf_f.
+ *   - A point is finite when x, y and z are.  Non-finite points are never keypoints and belong to no voxel.
+ *   - The voxel of a finite point is (i, j, k) = (floorf(x * inv), floorf(y * inv), floorf(z * inv)), as downSample forms
+ *     its keys.  The three are kept as the floats floorf returns (integer-valued, -0.0f equal to 0.0f; +-inf when the
+ *     product overflows).
+ *   - cx = (i + 0.5f) * leaf_f (one add, one multiply), likewise cy, cz; dx = x - cx, dy, dz;
+ *     d2 = (dx * dx + dy * dy) + dz * dz.  d2 is >= +0 or +inf, never NaN.
+ *   - The keypoint of an occupied voxel is its point with the smallest d2, ties to the smallest input index: the minimum of
+ *     the 64-bit keys float_bits(d2) << 32 | index.
+ *   - Extent rule, as VoxelGrid's: with d_a = (max index - min index) + 1 over the finite points on
+ *     axis a, if d_x * d_y * d_z is not <= INT32_MAX (an infinite index included), every finite point is a keypoint.
+ *   - MM3D_EINVAL: a NULL argument; leaf not finite or <= 0, or leaf_f or inv not a positive finite float (a leaf below
+ *     about 3e-39 or above 3.4e38).  An empty cloud gives an empty cloud and MM3D_OK.
+ * No parity with pcl::UniformSampling is claimed: PCL 1.8 takes the point nearest the integer voxel INDEX (i, j, k) read as
+ * a position, not nearest a centre, and anchors its lattice at the cloud's minimum; the rule above is deliberately the
+ * sensible one (audit row 16a).  The result does not depend on launch geometry or on the order in which
+ * anything arrives: all minima are integer minima.  One host wait, for the keypoint count. */
+int mm3d_uniform_keypoints(mm3d_ctx *ctx, const mm3d_cloud *points, double leaf, mm3d_cloud **out);
 /* The Harris response of every point (HarrisKeypoint3D::responseHarris, what detectKeypoints(HARRIS)
  * thresholds and suppresses); dst receives mm3d_cloud_size(points) floats. */
 int mm3d_harris_response(mm3d_ctx *ctx, const mm3d_cloud *points, const mm3d_normals *normals, double radius,

@@ -79,6 +79,24 @@ class AlignmentOptions(C.Structure):
             setattr(self, k, int(v) if k in ("method", "samples", "k") else float(v))
 
 
+class KeypointSource(enum.IntEnum):  # mm3d_keypoint_source (not a reference enum)
+    REFERENCE = 0
+    UNIFORM = 1
+
+
+class KeypointOptions(C.Structure):
+    """mm3d_keypoint_options (mm3d_set_keypoints); the defaults are mm3d_keypoint_options_default's."""
+    _fields_ = [("source", C.c_int), ("leaf", C.c_double)]
+
+    def __init__(self, **kw):
+        super().__init__()
+        lib().mm3d_keypoint_options_default(C.byref(self))
+        for k, v in kw.items():
+            if k not in dict(self._fields_):
+                raise TypeError("unknown keypoint option " + k)
+            setattr(self, k, int(v) if k == "source" else float(v))
+
+
 class AlignmentStats(C.Structure):
     """mm3d_alignment_stats"""
     _fields_ = [("draws", C.c_longlong), ("survivors", C.c_longlong), ("hypotheses_scored", C.c_longlong),
@@ -300,6 +318,17 @@ class Context:
         self._ck(lib().mm3d_last_alignment_stats(self._h, C.byref(st)))
         return st.as_dict()
 
+    def setKeypoints(self, options=None, **kw):
+        """mm3d_set_keypoints: where the whole-map calls take a map's keypoints from.  A KeypointOptions, or its fields as
+        keywords (source=KeypointSource.UNIFORM, leaf=... in metres; 0 = the default fraction of descriptor_radius)."""
+        o = options if options is not None else KeypointOptions(**kw)
+        self._ck(lib().mm3d_set_keypoints(self._h, C.byref(o)))
+
+    def getKeypoints(self) -> "KeypointOptions":
+        o = KeypointOptions()
+        self._ck(lib().mm3d_get_keypoints(self._h, C.byref(o)))
+        return o
+
     def synchronize(self):
         self._ck(lib().mm3d_synchronize(self._h))
 
@@ -355,6 +384,12 @@ class Context:
         self._ck(lib().mm3d_detect_keypoints(self._h, points._h, normals._h if normals is not None else None,
                                              int(type), C.c_double(threshold), C.c_double(radius),
                                              C.c_double(resolution), C.byref(h)))
+        return Cloud(self, h)
+
+    def uniformKeypoints(self, points: "Cloud", leaf: float) -> "Cloud":
+        """mm3d_uniform_keypoints: of every occupied voxel of the global lattice of side leaf, the point nearest its centre."""
+        h = C.c_void_p()
+        self._ck(lib().mm3d_uniform_keypoints(self._h, points._h, C.c_double(leaf), C.byref(h)))
         return Cloud(self, h)
 
     def siftCertOctave(self, points: "Cloud", min_scale: float, octave: int):

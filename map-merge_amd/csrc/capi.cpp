@@ -222,6 +222,8 @@ static void set_streams_one(mm3d_ctx *ctx, int n_streams)
     h->icp_method = ctx->icp_method;                    // (mm3d_set_icp_method before mm3d_set_streams)
     h->align_method = ctx->align_method;                // (mm3d_set_alignment likewise)
     h->align_options = ctx->align_options;
+    h->keypoint_source = ctx->keypoint_source;          // (mm3d_set_keypoints likewise)
+    h->keypoint_options = ctx->keypoint_options;
     ctx->helpers.push_back(h);
   }
 }
@@ -615,6 +617,8 @@ int mm3d_transform_score(mm3d_ctx *ctx, const mm3d_cloud *source, const mm3d_clo
 }
 
 // ---------------------------------------------------------------- map bundles
+// mm3d_set_keypoints with leaf = 0: the leaf is descriptor_radius over this (DESIGN.md section 7d has the measurement)
+static constexpr double kUniformLeafDivisor = 2.0;
 // wait = false: the caller goes on in the same stream (map_prepare_impl) and waits once, there
 static mm3d_map *map_features_impl(mm3d_ctx *ctx, const mm3d_cloud *raw, const mm3d_params *p, bool wait = true)
 {
@@ -629,7 +633,13 @@ static mm3d_map *map_features_impl(mm3d_ctx *ctx, const mm3d_cloud *raw, const m
   // neighbour list over a ball that contains the normals': the two stages share that launch (sift.hip), same bits.
   std::unique_ptr<mm3d_normals> nrm;
   std::unique_ptr<mm3d_cloud> kp;
-  if (p->keypoint_type == MM3D_KP_HARRIS) {
+  if (ctx->keypoint_source) {
+    // mm3d_set_keypoints: no detector runs (keypoint_type and keypoint_threshold are not read); the normals come from their
+    // stand-alone launch, since SIFT's fused first octave does not run
+    nrm.reset(compute_normals(ctx, filt.get(), p->normal_radius));
+    const double leaf = ctx->keypoint_options.leaf > 0.0 ? ctx->keypoint_options.leaf : p->descriptor_radius / kUniformLeafDivisor;
+    kp.reset(ctx->keypoint_source->keypoints(ctx, filt.get(), leaf));
+  } else if (p->keypoint_type == MM3D_KP_HARRIS) {
     nrm.reset(compute_normals(ctx, filt.get(), p->normal_radius));
     kp.reset(detect_keypoints_harris(ctx, filt.get(), nrm.get(), p->keypoint_threshold, p->normal_radius));
   } else {
@@ -2098,7 +2108,8 @@ int mm3d_estimate_maps_transforms(mm3d_ctx *ctx, const mm3d_cloud_view *clouds, 
       bool ok = false;
       ~CacheCall() { if (c && !ok) c->abort(); }
     } cache_call{ctx->map_cache};
-    if (ctx->map_cache) ctx->map_cache->begin(n, params, ctx->icp_method ? ctx->icp_method->method() : MM3D_ICP_POINT_TO_POINT, ctx->align_options);
+    if (ctx->map_cache) ctx->map_cache->begin(n, params, ctx->icp_method ? ctx->icp_method->method() : MM3D_ICP_POINT_TO_POINT, ctx->align_options,
+                                                  ctx->keypoint_options);
     if (!ctx->helpers.empty())
       estimate_maps_streams(ctx, clouds, n, params, out_T, n_out, pairs_out, n_pairs_out);
     else

@@ -31,11 +31,14 @@ struct KeyBuilder {
 };
 
 // what map_features_impl and map_prepare_impl read
-std::string feature_key(const mm3d_params *p)
+std::string feature_key(const mm3d_params *p, const mm3d_keypoint_options &kp)
 {
   KeyBuilder k;
   k.f64(p->resolution).f64(p->descriptor_radius).i32(p->outliers_min_neighbours).f64(p->normal_radius).i32(p->keypoint_type)
       .f64(p->keypoint_threshold).i32(p->descriptor_type).f64(p->max_correspondence_distance).i32(p->estimation_method);
+  // where the keypoints come from (mm3d_set_keypoints): a bundle of the reference's detectors is never a uniform one's, nor
+  // one of another leaf (0 = the default, a function of descriptor_radius above; not read under the reference's detectors)
+  k.i32(kp.source).f64(kp.source == MM3D_KEYPOINTS_UNIFORM ? kp.leaf : 0.0);
   return k.s;
 }
 
@@ -125,11 +128,12 @@ class MapCache final : public MapCacheBase {
       for (long long &c : counters_) c = 0;
   }
 
-  void begin(size_t n_maps, const mm3d_params *p, int icp_method, const mm3d_alignment_options &align) override
+  void begin(size_t n_maps, const mm3d_params *p, int icp_method, const mm3d_alignment_options &align,
+             const mm3d_keypoint_options &keypoints) override
   {
     std::lock_guard<std::mutex> lk(mu_);
     reset_call_locked();
-    fkey_ = feature_key(p);
+    fkey_ = feature_key(p, keypoints);
     pkey_ = pair_params_key(p, icp_method, align);
     sac_ia_ = p->estimation_method == MM3D_EST_SAC_IA;
     prerej_ = sac_ia_ && align.method == MM3D_ALIGN_PREREJECTIVE;

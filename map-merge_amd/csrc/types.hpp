@@ -16,6 +16,7 @@ namespace mm3d {
 struct DeviceSet;
 struct IcpMethodBase;
 struct AlignMethodBase;
+struct KeypointSourceBase;
 
 // The feature / pair cache of mm3d_estimate_maps_transforms (mm3d_set_map_cache; the concrete class is map_cache.cpp's).  The
 // drivers in capi.cpp only see this interface, so the host code links without it (tests/host_san).  One call at a time -- the
@@ -23,8 +24,10 @@ struct AlignMethodBase;
 // abort (it did not: the cache is left exactly as it was before the call).
 struct MapCacheBase {
   virtual ~MapCacheBase() = default;
-  // icp_method: MM3D_ICP_* of the call (mm3d_set_icp_method); align: its alignment (mm3d_set_alignment)
-  virtual void begin(size_t n_maps, const mm3d_params *p, int icp_method, const mm3d_alignment_options &align) = 0;
+  // icp_method: MM3D_ICP_* of the call (mm3d_set_icp_method); align: its alignment (mm3d_set_alignment); keypoints: where its
+  // maps' keypoints come from (mm3d_set_keypoints)
+  virtual void begin(size_t n_maps, const mm3d_params *p, int icp_method, const mm3d_alignment_options &align,
+                     const mm3d_keypoint_options &keypoints) = 0;
   // map `slot`'s packed upload `raw` (non-empty, on c's stream): the cached bundle, borrowed for the call, or null.  One launch and
   // one wait on c (a second compare-only launch and wait when the digest names another candidate than the slot's last entry).
   virtual const mm3d_map *lookup(Context *c, size_t slot, const mm3d_cloud *raw) = 0;
@@ -52,6 +55,11 @@ struct mm3d_ctx : mm3d::Context {
   const mm3d::AlignMethodBase *align_method = nullptr;
   mm3d_alignment_options align_options{MM3D_ALIGN_SAC_IA, 1 << 16, 10, 0.9, 0.25};
   mm3d_alignment_stats last_align_stats{0, 0, 0, -1, 0, 0};
+  // mm3d_set_keypoints: null = the reference's detectors (params.keypoint_type).  Not owned (a process-wide object of
+  // keypoints_uniform.hip's that holds no state); set, with the options, on the context, its helpers and its peers alike, and
+  // copied to helpers that mm3d_set_streams makes later.
+  const mm3d::KeypointSourceBase *keypoint_source = nullptr;
+  mm3d_keypoint_options keypoint_options{MM3D_KEYPOINTS_REFERENCE, 0.0};
   // mm3d_set_streams: helper contexts (one HIP stream + one host thread each while a call is running)
   // that mm3d_estimate_maps_transforms deals maps and pairs to; owned by this context
   std::vector<mm3d_ctx *> helpers;
@@ -310,6 +318,15 @@ struct AlignMethodBase {
   virtual void front(Context *c, const mm3d_alignment_options &o, unsigned seed, const mm3d_cloud *skp, const mm3d_desc *sd,
                      const mm3d_cloud *tkp, const mm3d_desc *td, double inlier_distance, PairFront &f,
                      mm3d_alignment_stats *stats) const = 0;
+};
+// Where a whole-map call takes a map's keypoints from instead of detectKeypoints (mm3d_set_keypoints; the one concrete class
+// is keypoints_uniform.hip's).  Like IcpMethodBase, the drivers in capi.cpp only see this interface, so the host code links
+// without the new kernels (tests/host_san); a null pointer on the context means the reference's detectors.
+struct KeypointSourceBase {
+  virtual ~KeypointSourceBase() = default;
+  virtual int source() const = 0;                        // MM3D_KEYPOINTS_*
+  // the keypoints of the filtered cloud `points`, a new cloud complete on c's stream (one wait: its size)
+  virtual mm3d_cloud *keypoints(Context *c, const mm3d_cloud *points, double leaf) const = 0;
 };
 struct PairCounts { int n_correspondences = 0, n_inliers = 0, icp_correspondences = 0; };
 // ICP (optional) from a guess on the device (guess_dev != null) or on the host, then transformScore
