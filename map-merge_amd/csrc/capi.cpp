@@ -6,7 +6,6 @@
 #include <condition_variable>
 #include <cstdlib>
 #include <exception>
-#include <functional>
 #include <thread>
 #include <sstream>
 #include <string>
@@ -619,8 +618,19 @@ int mm3d_transform_score(mm3d_ctx *ctx, const mm3d_cloud *source, const mm3d_clo
 // ---------------------------------------------------------------- map bundles
 // mm3d_set_keypoints with leaf = 0: the leaf is descriptor_radius over this (DESIGN.md section 7d has the measurement)
 static constexpr double kUniformLeafDivisor = 2.0;
+// a caller's view of a map, uploaded; a null / empty map (robot subscribed but no message yet) counts as "no keypoints"
+static std::unique_ptr<mm3d_cloud> cloud_from_view(mm3d_ctx *c, const mm3d_cloud_view &v)
+{
+  return std::unique_ptr<mm3d_cloud>(cloud_from_memory(c, v.points, v.points ? v.n : 0, v.stride ? v.stride : 16, v.stride ? v.rgba_offset : 12));
+}
+static std::unique_ptr<mm3d_map> make_map(std::unique_ptr<mm3d_cloud> points, std::unique_ptr<mm3d_cloud> keypoints, std::unique_ptr<mm3d_desc> desc)
+{
+  std::unique_ptr<mm3d_map> m(new mm3d_map());
+  m->points = points.release(); m->keypoints = keypoints.release(); m->desc = desc.release();
+  return m;
+}
 // wait = false: the caller goes on in the same stream (map_prepare_impl) and waits once, there
-static mm3d_map *map_features_impl(mm3d_ctx *ctx, const mm3d_cloud *raw, const mm3d_params *p, bool wait = true)
+static std::unique_ptr<mm3d_map> map_features_impl(mm3d_ctx *ctx, const mm3d_cloud *raw, const mm3d_params *p, bool wait = true)
 {
   if (p->keypoint_type != MM3D_KP_SIFT && p->keypoint_type != MM3D_KP_HARRIS) throw Error(MM3D_EINVAL, "invalid keypoint type");
   if (p->descriptor_type < 0 || p->descriptor_type >= 6) throw Error(MM3D_EINVAL, "unknown descriptor type");   // dispatch_descriptors.h:63
@@ -657,10 +667,7 @@ static mm3d_map *map_features_impl(mm3d_ctx *ctx, const mm3d_cloud *raw, const m
                                   : p->descriptor_type == MM3D_DESC_SHOT ? compute_shot(ctx, filt.get(), nrm.get(), kp.get(), p->descriptor_radius)
                                                                          : compute_fpfh(ctx, filt.get(), nrm.get(), kp.get(), p->descriptor_radius));
   if (wait) ctx->sync();
-  auto *m = new mm3d_map();
-  m->points = filt.release();
-  m->keypoints = kp.release();
-  m->desc = desc.release();
+  std::unique_ptr<mm3d_map> m = make_map(std::move(filt), std::move(kp), std::move(desc));
   if (ctx->icp_method) m->normals = std::move(nrm);    // point-to-plane ICP reads them (mm3d_set_icp_method)
   return m;
 }
@@ -669,7 +676,7 @@ int mm3d_map_features(mm3d_ctx *ctx, const mm3d_cloud *raw, const mm3d_params *p
 {
   if (!raw || !params || !out) return MM3D_EINVAL;
   *out = nullptr;
-  return guarded(ctx, [&] { *out = map_features_impl(ctx, raw, params); });
+  return guarded(ctx, [&] { *out = map_features_impl(ctx, raw, params).release(); });
 }
 
 const mm3d_cloud *mm3d_map_points(const mm3d_map *m) { return m ? m->points : nullptr; }
@@ -680,9 +687,7 @@ int mm3d_map_from_parts(mm3d_ctx *ctx, mm3d_cloud *points, mm3d_cloud *keypoints
 {
   if (!ctx || !points || !keypoints || !desc || !out) return MM3D_EINVAL;
   if (keypoints->n != desc->n) return MM3D_EINVAL;
-  auto *m = new mm3d_map();
-  m->points = points; m->keypoints = keypoints; m->desc = desc;
-  *out = m;
+  *out = make_map(std::unique_ptr<mm3d_cloud>(points), std::unique_ptr<mm3d_cloud>(keypoints), std::unique_ptr<mm3d_desc>(desc)).release();
   return MM3D_OK;
 }
 
@@ -708,8 +713,43 @@ void mm3d_map_free(mm3d_ctx *ctx, mm3d_map *m)
   if (!ctx || !m) return;
   std::lock_guard<std::mutex> lock(ctx->mu);
   (void)stream_wait(ctx->stream);
-  delete m->points; delete m->keypoints; delete m->desc;
   delete m;
+}
+
+// Context::private_objects for a scope: what is built inside is the context's alone until the builder has drained the stream
+// itself, so no waits for other contexts' sake while it is built (Context::settle)
+namespace {
+struct PrivateObjects {
+  mm3d_ctx *c;
+  explicit PrivateObjects(mm3d_ctx *c_) : c(c_) { c->private_objects = true; }
+  PrivateObjects(const PrivateObjects &) = delete;
+  ~PrivateObjects() { c->private_objects = false; }
+};
+}  // namespace
+
+// A map built and prepared on one worker's context, for a driver that publishes it afterwards: nobody else sees it before
+// map_prepare_impl's full wait -- which also looks at the error flags the kernels left -- and a throw strands nothing.
+static std::unique_ptr<mm3d_map> build_private_map(mm3d_ctx *c, const mm3d_cloud *raw, const mm3d_params *p)
+{
+  PrivateObjects priv(c);
+  std::unique_ptr<mm3d_map> m = map_features_impl(c, raw, p, false);
+  map_prepare_impl(c, m.get(), p);                     // (ends in that wait)
+  return m;
+}
+
+// A map another device owns, for the SOURCE role on context c (as mm3d_shard_unpack): bundle and source-side structures
+// straight from the owner's memory, then whatever of the query orders / host copy did not come with the clone
+static std::unique_ptr<mm3d_map> pull_map_from_peer(mm3d_ctx *c, const mm3d_map *src, int src_device)
+{
+  PrivateObjects priv(c);                              // (nobody sees the copy before the wait below)
+  std::unique_ptr<mm3d_cloud> pts(cloud_clone_from_peer(c, src->points, src_device));
+  std::unique_ptr<mm3d_cloud> kp(cloud_clone_from_peer(c, src->keypoints, src_device));
+  std::unique_ptr<mm3d_desc> desc(desc_clone_from_peer(c, src->desc, src_device));
+  if (pts->n) cloud_hilbert(c, pts.get());
+  if (kp->n) cloud_hilbert(c, kp.get());
+  (void)cloud_host(c, kp.get());
+  c->sync();
+  return make_map(std::move(pts), std::move(kp), std::move(desc));
 }
 
 // The normals point-to-plane ICP reads of a pair's target map: a map that mm3d_map_prepare did not give them (a map made
@@ -789,6 +829,23 @@ static size_t pair_batch_knob()
     return (size_t)std::min<long>(std::max<long>(b, 1), 32);      // (32: the largest batch ever run)
   }();
   return v;
+}
+// How large a batch, of `avail` pairs that can start now on S streams: round 4 measured take = avail / (share * S) on the headline
+// (16 streams, 120 pairs trickling in behind the feature stage): share 4 / 2 / 1 / 0.5 / 0.25 / 0.125 -> 989 / 990 / 1004 / 1013 /
+// 1021 / 1022 map-pairs/s.  The pair stage's kernels are latency-bound and only four run at a time (hardware queues), so a launch
+// that serves four pairs costs little more queue time than one that serves one; with share 2 most batches were a single pair.
+// (The cap is an experiment knob: 8 / 16 / 32 the same.)
+static size_t pair_batch_take(size_t avail, size_t S)
+{
+  return std::min(pair_batch_knob(), std::max<size_t>(1, (size_t)((double)avail / (pair_share_knob() * (double)S))));
+}
+// every pair of n maps, in the order of the reference's loop (map_merging.cpp:256-269)
+static std::vector<std::pair<size_t, size_t>> all_pairs(size_t n)
+{
+  std::vector<std::pair<size_t, size_t>> all;
+  for (size_t i = 0; i + 1 < n; ++i)
+    for (size_t j = i + 1; j < n; ++j) all.emplace_back(i, j);
+  return all;
 }
 
 // Several pairs on one context: the initial estimates one after the other (each from its own generator state),
@@ -920,9 +977,7 @@ static void estimate_maps_streams(mm3d_ctx *ctx, const mm3d_cloud_view *clouds, 
     const long v = std::atol(e);
     if (v >= 1) F = std::min<size_t>(S, (size_t)v);
   }
-  std::vector<std::pair<size_t, size_t>> all;
-  for (size_t i = 0; i + 1 < n; ++i)
-    for (size_t j = i + 1; j < n; ++j) all.emplace_back(i, j);
+  const std::vector<std::pair<size_t, size_t>> all = all_pairs(n);
   std::vector<mm3d_map *> maps(n, nullptr);
   // mm3d_set_map_cache: maps[i] is the cache's (a hit, or a miss handed over once built) where borrowed[i] is set
   MapCacheBase *const cache = ctx->map_cache;
@@ -933,7 +988,7 @@ static void estimate_maps_streams(mm3d_ctx *ctx, const mm3d_cloud_view *clouds, 
     ~MapsGuard()
     {
       for (size_t i = 0; i < m.size(); ++i)
-        if (m[i] && !borrowed[i]) { delete m[i]->points; delete m[i]->keypoints; delete m[i]->desc; delete m[i]; }
+        if (!borrowed[i]) delete m[i];
     }
   } maps_guard{maps, borrowed};
   std::vector<mm3d_pair_result> rec(all.size());
@@ -1008,13 +1063,7 @@ static void estimate_maps_streams(mm3d_ctx *ctx, const mm3d_cloud_view *clouds, 
       if (avail) {
         // a batch shares its TARGET (the pairs (i, t) of one t): one descriptor search for the sampled rows of all
         // its sources, and one target grid under every search of the batch
-        // How large a batch: round 4 measured take = avail / (share * S) on the headline (16 streams, 120 pairs trickling in behind
-        // the feature stage): share 4 / 2 / 1 / 0.5 / 0.25 / 0.125 -> 989 / 990 / 1004 / 1013 / 1021 / 1022 map-pairs/s.  The pair
-        // stage's kernels are latency-bound and only four run at a time (hardware queues), so a launch that serves four pairs
-        // costs little more queue time than one that serves one; with share 2 most batches were a single pair.
-        const double share = pair_share_knob();
-        const size_t cap = pair_batch_knob();              // (experiment knob: 8 / 16 / 32 the same)
-        const size_t take = std::min(cap, std::max<size_t>(1, (size_t)((double)avail / (share * (double)S))));
+        const size_t take = pair_batch_take(avail, S);
         size_t target = n;
         for (size_t q = 0; q < P && out.size() < take; ++q)
           if (!claimed[q] && all[q].first < prefix && ready[all[q].second] && (target == n || all[q].second == target)) {
@@ -1038,10 +1087,7 @@ static void estimate_maps_streams(mm3d_ctx *ctx, const mm3d_cloud_view *clouds, 
           if (abort || next_map >= n) break;
           i = next_map++;
         }
-        // a null / empty map (robot subscribed but no message yet) counts as "no keypoints"
-        std::unique_ptr<mm3d_cloud> raw(cloud_from_memory(c, clouds[i].points, clouds[i].points ? clouds[i].n : 0,
-                                                          clouds[i].stride ? clouds[i].stride : 16,
-                                                          clouds[i].stride ? clouds[i].rgba_offset : 12));
+        std::unique_ptr<mm3d_cloud> raw = cloud_from_view(c, clouds[i]);
         if (cache && raw->n > 0) {
           // an unchanged map: its bundle is published at once, nothing else runs on the device for it
           if (const mm3d_map *hit = cache->lookup(c, i, raw.get())) {
@@ -1059,16 +1105,7 @@ static void estimate_maps_streams(mm3d_ctx *ctx, const mm3d_cloud_view *clouds, 
             continue;
           }
         }
-        // owned here until it is published: a throw from map_prepare_impl must not strand the map's buffers
-        struct MapFree {
-          void operator()(mm3d_map *x) const { delete x->points; delete x->keypoints; delete x->desc; delete x; }
-        };
-        // the map is this worker's alone until it is published: no waits for other contexts' sake while it is built
-        // (Context::settle), one full wait -- which also looks at the recorded error flags -- before it is published
-        c->private_objects = true;
-        std::unique_ptr<mm3d_map, MapFree> held(map_features_impl(c, raw.get(), params, false));
-        map_prepare_impl(c, held.get(), params);        // (ends in that wait)
-        c->private_objects = false;
+        std::unique_ptr<mm3d_map> held = build_private_map(c, raw.get(), params);   // this worker's alone until it is published
         const bool keep = cache && raw->n > 0;
         {
           std::lock_guard<std::mutex> lk(mu);
@@ -1174,8 +1211,7 @@ struct mm3d_shard {
   std::vector<mm3d_map *> maps;
   ~mm3d_shard()
   {
-    for (mm3d_map *x : maps)
-      if (x) { delete x->points; delete x->keypoints; delete x->desc; delete x; }
+    for (mm3d_map *x : maps) delete x;
   }
 };
 
@@ -1204,7 +1240,6 @@ static void on_streams(mm3d_ctx *ctx, Fn &&fn)
       cs[w]->sync();
     } catch (...) {
       failed.store(true);
-      cs[w]->private_objects = false;
       std::lock_guard<std::mutex> lk(mu);
       if (!first_error) first_error = std::current_exception();
     }
@@ -1233,15 +1268,9 @@ static mm3d_shard *shard_begin_impl(mm3d_ctx *ctx, const mm3d_cloud_view *clouds
       const size_t k = next.fetch_add(1);
       if (k >= mine.size() || failed.load()) break;
       const size_t i = mine[k];
-      std::unique_ptr<mm3d_cloud> raw(cloud_from_memory(c, clouds[i].points, clouds[i].points ? clouds[i].n : 0,
-                                                        clouds[i].stride ? clouds[i].stride : 16,
-                                                        clouds[i].stride ? clouds[i].rgba_offset : 12));
-      // nobody else sees the map before on_streams has drained every stream: no waits for other contexts' sake
-      c->private_objects = true;
-      mm3d_map *m = map_features_impl(c, raw.get(), params, false);
-      sh->maps[i] = m;                         // (distinct slots: no lock needed; the shard owns it from here)
-      map_prepare_impl(c, m, params);          // this rank is the map's target-side owner; ends in a full wait, which also
-      c->private_objects = false;              // looks at the error flags the kernels left
+      std::unique_ptr<mm3d_cloud> raw = cloud_from_view(c, clouds[i]);
+      // this rank is the map's target-side owner; nobody else sees the map before on_streams has drained every stream
+      sh->maps[i] = build_private_map(c, raw.get(), params).release();   // (distinct slots: no lock needed; the shard owns it from here)
     }
   });
   return sh.release();
@@ -1361,7 +1390,7 @@ int mm3d_shard_pack(mm3d_shard *sh, size_t map, void *dst)
 }
 
 // one received bundle -> a map in the source role, on context c (copies, a short wait for the 256-byte header and ONE for the rest; no kernel unless the owner sent no orders)
-static mm3d_map *map_from_bundle(mm3d_ctx *c, const void *src, uint64_t n_points, uint64_t n_keypoints, int descriptor_type)
+static std::unique_ptr<mm3d_map> map_from_bundle(mm3d_ctx *c, const void *src, uint64_t n_points, uint64_t n_keypoints, int descriptor_type)
 {
   const char *s = static_cast<const char *>(src);
   const int dim = mm3d_descriptor_dim(descriptor_type);
@@ -1412,9 +1441,7 @@ static mm3d_map *map_from_bundle(mm3d_ctx *c, const void *src, uint64_t n_points
   if (pts->n) cloud_hilbert(c, pts.get());
   if (kp->n) cloud_hilbert(c, kp.get());
   c->sync();
-  auto *m = new mm3d_map();
-  m->points = pts.release(); m->keypoints = kp.release(); m->desc = desc.release();
-  return m;
+  return make_map(std::move(pts), std::move(kp), std::move(desc));
 }
 
 int mm3d_shard_unpack(mm3d_shard *sh, size_t map, const void *src, uint64_t n_points, uint64_t n_keypoints)
@@ -1425,7 +1452,7 @@ int mm3d_shard_unpack(mm3d_shard *sh, size_t map, const void *src, uint64_t n_po
   return guarded(ctx, [&] {
     // source role only: the query orders of ICP / score and of SAC-IA's scoring, and the host copy of the
     // keypoints that the rand() replay reads; target-side structures are the owner's business
-    sh->maps[map] = map_from_bundle(ctx, src, n_points, n_keypoints, sh->params.descriptor_type);
+    sh->maps[map] = map_from_bundle(ctx, src, n_points, n_keypoints, sh->params.descriptor_type).release();
   });
 }
 
@@ -1445,10 +1472,8 @@ int mm3d_shard_unpack_many(mm3d_shard *sh, size_t count, const size_t *maps, con
         if (k >= count || failed.load()) break;
         const size_t i = maps[k];
         if (sh->maps[i]) continue;                    // an owned map is already here
-        c->private_objects = true;                    // nobody sees the map before this worker's waits
-        mm3d_map *m = map_from_bundle(c, srcs[k], n_points[k], n_keypoints[k], sh->params.descriptor_type);   // source role only, as in mm3d_shard_unpack
-        c->private_objects = false;
-        sh->maps[i] = m;                              // distinct slots
+        PrivateObjects priv(c);                       // nobody sees the map before this worker's waits
+        sh->maps[i] = map_from_bundle(c, srcs[k], n_points[k], n_keypoints[k], sh->params.descriptor_type).release();   // source role only, as in mm3d_shard_unpack; distinct slots
       }
     });
   });
@@ -1463,9 +1488,8 @@ static void shard_pairs_impl(mm3d_shard *sh, mm3d_pair_result *pairs, unsigned c
   // the live pairs in the reference's order, and the generator state before each of them (the draws of a pair
   // depend on its source keypoints only: every rank replays the whole stream on the host, ~30 us per pair)
   std::vector<std::pair<size_t, size_t>> live;
-  for (size_t i = 0; i + 1 < sh->n; ++i)
-    for (size_t j = i + 1; j < sh->n; ++j)
-      if (sh->maps[i]->keypoints->n > 0 && sh->maps[j]->keypoints->n > 0) live.emplace_back(i, j);
+  for (const auto &ij : all_pairs(sh->n))
+    if (sh->maps[ij.first]->keypoints->n > 0 && sh->maps[ij.second]->keypoints->n > 0) live.push_back(ij);
   const size_t P = live.size();
   *n_pairs = P;
   if (P > capacity) throw Error(MM3D_ECAPACITY, "mm3d_shard_pairs: room for every live pair is needed");
@@ -1495,8 +1519,7 @@ static void shard_pairs_impl(mm3d_shard *sh, mm3d_pair_result *pairs, unsigned c
   // batches of pairs with the same target (pairs_estimate_batch), at most kPairBatch of them and not so many that
   // a stream runs dry: every map exists already, so the whole list can be cut up front
   const size_t S = ctx->helpers.size() + 1;
-  const double share = pair_share_knob();                  // (as claim_pairs above)
-  const size_t take = std::min(pair_batch_knob(), std::max<size_t>(1, (size_t)((double)todo.size() / (share * (double)S))));
+  const size_t take = pair_batch_take(todo.size(), S);
   std::stable_sort(todo.begin(), todo.end(), [&](size_t a, size_t b) { return live[a].second < live[b].second; });
   std::vector<std::pair<size_t, size_t>> batches;           // [first, last) into todo
   for (size_t a = 0; a < todo.size();) {
@@ -1550,29 +1573,23 @@ static void estimate_maps_sequential(mm3d_ctx *ctx, const mm3d_cloud_view *cloud
   auto since_start = [&] { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count(); };
   ctx->last_points.assign(n, 0);
   ctx->last_keypoints.assign(n, 0);
-  std::vector<std::unique_ptr<mm3d_map, std::function<void(mm3d_map *)>>> maps;
-  auto del = [](mm3d_map *m) { if (m) { delete m->points; delete m->keypoints; delete m->desc; delete m; } };
-  auto borrow = [](mm3d_map *) {};                     // a bundle of the map cache's (mm3d_set_map_cache)
+  std::vector<const mm3d_map *> maps(n, nullptr);       // every map of the call; those the map cache does not hold
+  std::vector<std::unique_ptr<mm3d_map>> owned(n);      // (mm3d_set_map_cache) are `owned`, and go when the call ends
   MapCacheBase *const cache = ctx->map_cache;
   for (size_t i = 0; i < n; ++i) {
-    // a null / empty map (robot subscribed but no message yet) counts as "no keypoints"
-    std::unique_ptr<mm3d_cloud> raw(cloud_from_memory(ctx, clouds[i].points, clouds[i].points ? clouds[i].n : 0,
-                                                      clouds[i].stride ? clouds[i].stride : 16,
-                                                      clouds[i].stride ? clouds[i].rgba_offset : 12));
-    const mm3d_map *hit = cache && raw->n > 0 ? cache->lookup(ctx, i, raw.get()) : nullptr;
-    if (hit) {
-      maps.emplace_back(const_cast<mm3d_map *>(hit), borrow);
-    } else {
-      maps.emplace_back(map_features_impl(ctx, raw.get(), params), del);
-      map_prepare_impl(ctx, maps.back().get(), params);   // search structures and k-NN target operands, once per map
+    std::unique_ptr<mm3d_cloud> raw = cloud_from_view(ctx, clouds[i]);
+    maps[i] = cache && raw->n > 0 ? cache->lookup(ctx, i, raw.get()) : nullptr;
+    if (!maps[i]) {
+      owned[i] = map_features_impl(ctx, raw.get(), params);
+      map_prepare_impl(ctx, owned[i].get(), params);      // search structures and k-NN target operands, once per map
+      maps[i] = owned[i].get();
       if (cache && raw->n > 0) {                          // built from the same upload: the cache takes it and the map
-        cache->insert(i, std::move(raw), maps.back().get());
-        mm3d_map *m = maps.back().release();
-        maps.back() = std::unique_ptr<mm3d_map, std::function<void(mm3d_map *)>>(m, borrow);
+        cache->insert(i, std::move(raw), owned[i].get());
+        (void)owned[i].release();
       }
     }
-    ctx->last_points[i] = maps.back()->points->n;
-    ctx->last_keypoints[i] = maps.back()->keypoints->n;
+    ctx->last_points[i] = maps[i]->points->n;
+    ctx->last_keypoints[i] = maps[i]->keypoints->n;
   }
   ctx->last_features_s = since_start();
   std::vector<mm3d_pair_result> pairs;
@@ -1585,7 +1602,7 @@ static void estimate_maps_sequential(mm3d_ctx *ctx, const mm3d_cloud_view *cloud
         pairs.push_back(r);
       }
   for (auto &r : pairs) {
-    const mm3d_map *ms = maps[r.source_idx].get(), *mt = maps[r.target_idx].get();
+    const mm3d_map *ms = maps[r.source_idx], *mt = maps[r.target_idx];
     if (cache && cache->pair_lookup(r.source_idx, r.target_idx, ctx->rnd, &r)) {
       // reused: the generator still moves on by the draws the pair would have taken
       pair_rand_replay(ctx->rnd, replay_method(ctx, params), cloud_host(ctx, ms->keypoints), params->inlier_threshold, params->max_iterations);
@@ -1615,6 +1632,21 @@ static void estimate_maps_sequential(mm3d_ctx *ctx, const mm3d_cloud_view *cloud
 //   4. ONE RCCL all-gather of the 104-byte pair records (devices.cpp::gather_pair_records), then the pose graph on the host.
 // Same bits as one device: the ownership only decides where a map or a pair is computed.
 namespace {
+bool devices_debug()
+{
+  static const bool dbg = [] { const char *e = getenv("MM3D_DEVICES_DEBUG"); return e && atoi(e); }();
+  return dbg;
+}
+// after a failed run: every stream of every device is drained before the shards (and their maps) go
+void drain_devices(const std::vector<mm3d_ctx *> &roots, int restore_device)
+{
+  for (mm3d_ctx *r : roots) {
+    (void)hipSetDevice(r->device);
+    (void)stream_wait(r->stream);
+    for (mm3d_ctx *h : r->helpers) (void)stream_wait(h->stream);
+  }
+  (void)hipSetDevice(restore_device);
+}
 // a barrier the device threads can leave through a failure: whoever throws releases the others, who then throw too
 struct FailBarrier {
   std::mutex mu;
@@ -1661,9 +1693,6 @@ static void devices_run_staged(mm3d_ctx *ctx, DevicesRun &R, const mm3d_cloud_vi
 {
   std::vector<mm3d_ctx *> &roots = R.roots;
   const size_t D = R.D, n = R.n;
-  auto &sh = R.sh; auto &rec = R.rec; auto &mine = R.mine; auto &np = R.np;
-  auto &t_feat = R.t_feat; auto &t_exch = R.t_exch; auto &t_pairs = R.t_pairs;
-  auto since_start = [&] { return R.since_start(); };
   FailBarrier bar(D);
   std::mutex err_mu;
   std::exception_ptr first_error;
@@ -1676,13 +1705,13 @@ static void devices_run_staged(mm3d_ctx *ctx, DevicesRun &R, const mm3d_cloud_vi
     if (d > 0) peer_lock = std::unique_lock<std::mutex>(root->mu);
     try {
       if (hipSetDevice(root->device) != hipSuccess) throw Error(MM3D_EDEVICE, "hipSetDevice failed");
-      sh[d].reset(shard_begin_impl(root, clouds, n, params, (int)d, (int)D));
-      t_feat[d] = since_start();
+      R.sh[d].reset(shard_begin_impl(root, clouds, n, params, (int)d, (int)D));
+      R.t_feat[d] = R.since_start();
       bar.wait();                                         // every owner's maps exist and its streams are drained
       // the other devices' maps: bundle + source-side structures straight from the owner's memory, dealt to this device's streams
       std::vector<size_t> theirs;
       for (size_t i = 0; i < n; ++i)
-        if (!sh[d]->maps[i]) theirs.push_back(i);
+        if (!R.sh[d]->maps[i]) theirs.push_back(i);
       std::atomic<size_t> next{0};
       on_streams(root, [&](size_t, mm3d_ctx *c, const std::atomic<bool> &failed) {
         for (;;) {
@@ -1690,29 +1719,15 @@ static void devices_run_staged(mm3d_ctx *ctx, DevicesRun &R, const mm3d_cloud_vi
           if (k >= theirs.size() || failed.load()) break;
           const size_t i = theirs[k];
           const size_t o = (size_t)mm3d_shard_map_owner(i, (int)D);
-          const mm3d_map *src = sh[o]->maps[i];
-          const int src_dev = roots[o]->device;
-          c->private_objects = true;
-          std::unique_ptr<mm3d_cloud> pts(cloud_clone_from_peer(c, src->points, src_dev));
-          std::unique_ptr<mm3d_cloud> kp(cloud_clone_from_peer(c, src->keypoints, src_dev));
-          std::unique_ptr<mm3d_desc> desc(desc_clone_from_peer(c, src->desc, src_dev));
-          // source role only (as mm3d_shard_unpack): whatever of the query orders / host copy did not come with the clone
-          if (pts->n) cloud_hilbert(c, pts.get());
-          if (kp->n) cloud_hilbert(c, kp.get());
-          (void)cloud_host(c, kp.get());
-          c->private_objects = false;
-          c->sync();
-          auto *m = new mm3d_map();
-          m->points = pts.release(); m->keypoints = kp.release(); m->desc = desc.release();
-          sh[d]->maps[i] = m;                             // distinct slots; nobody reads another device's non-owned slots
+          // distinct slots; nobody reads another device's non-owned slots
+          R.sh[d]->maps[i] = pull_map_from_peer(c, R.sh[o]->maps[i], roots[o]->device).release();
         }
       });
-      t_exch[d] = since_start();
-      shard_pairs_impl(sh[d].get(), rec[d].data(), mine[d].data(), max_pairs, &np[d]);
-      t_pairs[d] = since_start();
-      static const bool dbg = [] { const char *e = getenv("MM3D_DEVICES_DEBUG"); return e && atoi(e); }();
-      if (dbg) fprintf(stderr, "mm3d devices (staged): dev%zu features %.2f ms, pulls done %.2f ms, pairs done %.2f ms (its own replay of every pair inside)\n", d,
-                       1e3 * t_feat[d], 1e3 * t_exch[d], 1e3 * t_pairs[d]);
+      R.t_exch[d] = R.since_start();
+      shard_pairs_impl(R.sh[d].get(), R.rec[d].data(), R.mine[d].data(), max_pairs, &R.np[d]);
+      R.t_pairs[d] = R.since_start();
+      if (devices_debug()) fprintf(stderr, "mm3d devices (staged): dev%zu features %.2f ms, pulls done %.2f ms, pairs done %.2f ms (its own replay of every pair inside)\n", d,
+                                   1e3 * R.t_feat[d], 1e3 * R.t_exch[d], 1e3 * R.t_pairs[d]);
       // an owner's maps are read by its peers' pulls: nobody leaves (and nothing is freed) before everybody has pulled
       bar.wait();
     } catch (...) {
@@ -1729,12 +1744,7 @@ static void devices_run_staged(mm3d_ctx *ctx, DevicesRun &R, const mm3d_cloud_vi
   }
   (void)hipSetDevice(ctx->device);
   if (first_error) {
-    for (size_t d = 0; d < D; ++d) {                      // drain before the shards (and their maps) go
-      (void)hipSetDevice(roots[d]->device);
-      (void)stream_wait(roots[d]->stream);
-      for (mm3d_ctx *h : roots[d]->helpers) (void)stream_wait(h->stream);
-    }
-    (void)hipSetDevice(ctx->device);
+    drain_devices(roots, ctx->device);
     std::rethrow_exception(first_error);
   }
 }
@@ -1755,9 +1765,7 @@ static bool devices_run_pipelined(mm3d_ctx *ctx, DevicesRun &R, const mm3d_cloud
 {
   std::vector<mm3d_ctx *> &roots = R.roots;
   const size_t D = R.D, n = R.n;
-  std::vector<std::pair<size_t, size_t>> all;
-  for (size_t i = 0; i + 1 < n; ++i)
-    for (size_t j = i + 1; j < n; ++j) all.emplace_back(i, j);
+  const std::vector<std::pair<size_t, size_t>> all = all_pairs(n);
   const size_t P = all.size();
   for (size_t d = 0; d < D; ++d) {
     R.sh[d].reset(new mm3d_shard());
@@ -1817,9 +1825,6 @@ static bool devices_run_pipelined(mm3d_ctx *ctx, DevicesRun &R, const mm3d_cloud
       cv.notify_all();
     }
   };
-  struct MapFree {
-    void operator()(mm3d_map *x) const { delete x->points; delete x->keypoints; delete x->desc; delete x; }
-  };
   auto device_body = [&](size_t d) {
     mm3d_ctx *root = roots[d];
     std::unique_lock<std::mutex> peer_lock;
@@ -1836,14 +1841,11 @@ static bool devices_run_pipelined(mm3d_ctx *ctx, DevicesRun &R, const mm3d_cloud
             if (abort || failed.load() || next_own[d] >= own_maps[d].size()) break;
             i = own_maps[d][next_own[d]++];
           }
-          std::unique_ptr<mm3d_cloud> raw(cloud_from_memory(c, clouds[i].points, clouds[i].points ? clouds[i].n : 0,
-                                                            clouds[i].stride ? clouds[i].stride : 16,
-                                                            clouds[i].stride ? clouds[i].rgba_offset : 12));
-          c->private_objects = true;
-          std::unique_ptr<mm3d_map, MapFree> held(map_features_impl(c, raw.get(), params, false));
-          map_prepare_impl(c, held.get(), params);          // this device is the map's target-side owner; ends in a full wait:
-          raw.reset();                                      // the map is complete in this device's memory BEFORE anybody is told
-          c->private_objects = false;
+          std::unique_ptr<mm3d_cloud> raw = cloud_from_view(c, clouds[i]);
+          // this device is the map's target-side owner; the build ends in a full wait: the map is complete in this device's
+          // memory BEFORE anybody is told
+          std::unique_ptr<mm3d_map> held = build_private_map(c, raw.get(), params);
+          raw.reset();
           {
             std::lock_guard<std::mutex> lk(mu);
             R.sh[d]->maps[i] = held.release();
@@ -1876,7 +1878,7 @@ static bool devices_run_pipelined(mm3d_ctx *ctx, DevicesRun &R, const mm3d_cloud
                 if (q <= known && have[d][all[q].first] && have[d][all[q].second]) ++avail;
               }
               if (avail) {
-                const size_t take = std::min(pair_batch_knob(), std::max<size_t>(1, (size_t)((double)avail / (pair_share_knob() * (double)S))));
+                const size_t take = pair_batch_take(avail, S);
                 size_t target = n;
                 for (size_t q : todo[d]) {
                   if (batch.size() >= take) break;
@@ -1896,22 +1898,11 @@ static bool devices_run_pipelined(mm3d_ctx *ctx, DevicesRun &R, const mm3d_cloud
           }
           if (pull != n) {
             const size_t o = (size_t)mm3d_shard_map_owner(pull, (int)D);
-            const mm3d_map *src = R.sh[o]->maps[pull];    // (published: complete, and not freed before every thread has joined)
-            const int src_dev = roots[o]->device;
-            c->private_objects = true;
-            std::unique_ptr<mm3d_cloud> pts(cloud_clone_from_peer(c, src->points, src_dev));
-            std::unique_ptr<mm3d_cloud> kp(cloud_clone_from_peer(c, src->keypoints, src_dev));
-            std::unique_ptr<mm3d_desc> desc(desc_clone_from_peer(c, src->desc, src_dev));
-            if (pts->n) cloud_hilbert(c, pts.get());
-            if (kp->n) cloud_hilbert(c, kp.get());
-            (void)cloud_host(c, kp.get());
-            c->private_objects = false;
-            c->sync();
-            auto *m = new mm3d_map();
-            m->points = pts.release(); m->keypoints = kp.release(); m->desc = desc.release();
+            // (the owner's copy is published: complete, and not freed before every thread has joined)
+            std::unique_ptr<mm3d_map> m = pull_map_from_peer(c, R.sh[o]->maps[pull], roots[o]->device);
             {
               std::lock_guard<std::mutex> lk(mu);
-              R.sh[d]->maps[pull] = m;
+              R.sh[d]->maps[pull] = m.release();
               have[d][pull] = 1;
               R.t_exch[d] = std::max(R.t_exch[d], R.since_start());
             }
@@ -1951,16 +1942,10 @@ static bool devices_run_pipelined(mm3d_ctx *ctx, DevicesRun &R, const mm3d_cloud
   }
   (void)hipSetDevice(ctx->device);
   if (first_error) {
-    for (size_t d = 0; d < D; ++d) {                      // drain before the shards (and their maps) go
-      (void)hipSetDevice(roots[d]->device);
-      (void)stream_wait(roots[d]->stream);
-      for (mm3d_ctx *h : roots[d]->helpers) (void)stream_wait(h->stream);
-    }
-    (void)hipSetDevice(ctx->device);
+    drain_devices(roots, ctx->device);
     std::rethrow_exception(first_error);
   }
-  static const bool dbg = [] { const char *e = getenv("MM3D_DEVICES_DEBUG"); return e && atoi(e); }();
-  if (dbg) {
+  if (devices_debug()) {
     fprintf(stderr, "mm3d devices (pipelined): %zu devices, %zu maps, %zu pairs; ONE rand() table: %.2f ms of replay on one host thread, complete %.2f ms into the call "
             "(0 ms of replay on the devices' threads);", D, n, P, 1e3 * fill_busy_s, 1e3 * fill_done_s);
     for (size_t d = 0; d < D; ++d) fprintf(stderr, " dev%zu last map %.2f last pull %.2f last pair %.2f ms;", d, 1e3 * R.t_feat[d], 1e3 * R.t_exch[d], 1e3 * R.t_pairs[d]);
@@ -2036,27 +2021,24 @@ static void estimate_maps_devices(mm3d_ctx *ctx, const mm3d_cloud_view *clouds, 
     }
   }
   if (!ran) devices_run_staged(ctx, R, clouds, params, max_pairs);
-  auto &sh = R.sh; auto &rec = R.rec; auto &mine = R.mine; auto &np = R.np;
-  auto &t_feat = R.t_feat; auto &t_exch = R.t_exch; auto &t_pairs = R.t_pairs;
-  auto since_start = [&] { return R.since_start(); };
   ctx->last_points.assign(n, 0);
   ctx->last_keypoints.assign(n, 0);
   for (size_t i = 0; i < n; ++i) {
-    ctx->last_points[i] = sh[0]->maps[i]->points->n;
-    ctx->last_keypoints[i] = sh[0]->maps[i]->keypoints->n;
+    ctx->last_points[i] = R.sh[0]->maps[i]->points->n;
+    ctx->last_keypoints[i] = R.sh[0]->maps[i]->keypoints->n;
   }
-  ctx->last_features_s = *std::max_element(t_feat.begin(), t_feat.end());
-  ctx->last_exchange_s = *std::max_element(t_exch.begin(), t_exch.end());
-  ctx->last_pairs_s = *std::max_element(t_pairs.begin(), t_pairs.end());
+  ctx->last_features_s = *std::max_element(R.t_feat.begin(), R.t_feat.end());
+  ctx->last_exchange_s = *std::max_element(R.t_exch.begin(), R.t_exch.end());
+  ctx->last_pairs_s = *std::max_element(R.t_pairs.begin(), R.t_pairs.end());
   // the gather: rank d sends the records of its own pairs, in pair order, padded to the largest rank's count
-  const size_t P = np[0];
+  const size_t P = R.np[0];
   for (size_t d = 1; d < D; ++d)
-    if (np[d] != P) throw Error(MM3D_EDEVICE, "estimate_maps_devices: the devices disagree on the live pairs");
+    if (R.np[d] != P) throw Error(MM3D_EDEVICE, "estimate_maps_devices: the devices disagree on the live pairs");
   std::vector<std::vector<mm3d_pair_result>> send(D);
   std::vector<std::vector<size_t>> which(D);
   for (size_t d = 0; d < D; ++d)
     for (size_t q = 0; q < P; ++q)
-      if (mine[d][q]) { send[d].push_back(rec[d][q]); which[d].push_back(q); }
+      if (R.mine[d][q]) { send[d].push_back(R.rec[d][q]); which[d].push_back(q); }
   size_t slots = 0;
   for (size_t d = 0; d < D; ++d) slots = std::max(slots, send[d].size());
   std::vector<mm3d_pair_result> gathered;
@@ -2073,14 +2055,14 @@ static void estimate_maps_devices(mm3d_ctx *ctx, const mm3d_cloud_view *clouds, 
   // the shards (maps on every device) go now; every stream was drained by its device's thread
   for (size_t d = 0; d < D; ++d) {
     (void)hipSetDevice(roots[d]->device);
-    sh[d].reset();
+    R.sh[d].reset();
   }
   (void)hipSetDevice(ctx->device);
   if (pairs_out) std::memcpy(pairs_out, pairs.data(), pairs.size() * sizeof(mm3d_pair_result));
   if (n_pairs_out) *n_pairs_out = pairs.size();
   const int st = global_transforms(pairs.data(), pairs.size(), params->confidence_threshold, n, out_T, n_out);
   if (st != MM3D_OK) throw Error(st, "computeGlobalTransforms failed");
-  ctx->last_total_s = since_start();
+  ctx->last_total_s = R.since_start();
 }
 
 // ---------------------------------------------------------------- map_merging.h

@@ -81,10 +81,7 @@ struct Entry {
   Entry() = default;
   Entry(const Entry &) = delete;
   Entry &operator=(const Entry &) = delete;
-  ~Entry()
-  {
-    if (map) { delete map->points; delete map->keypoints; delete map->desc; delete map; }
-  }
+  ~Entry() { delete map; }
   size_t bytes() const
   {
     return raw->pts.size() * 16 + cloud_bytes(map->points) + cloud_bytes(map->keypoints) + desc_bytes(map->desc) +

@@ -175,12 +175,17 @@ struct mm3d_desc {
   mm3d::DevBuf<float> rf;
 };
 
+// A map owns its parts: whoever holds the map frees all of them with `delete m` (mm3d_map_from_parts adopts the caller's).
 struct mm3d_map {
   mm3d_cloud *points = nullptr;
   mm3d_cloud *keypoints = nullptr;
   mm3d_desc *desc = nullptr;
   // the points' normals (normal_radius), kept for point-to-plane ICP only (mm3d_set_icp_method): null otherwise
   std::unique_ptr<mm3d_normals> normals;
+  mm3d_map() = default;
+  mm3d_map(const mm3d_map &) = delete;
+  mm3d_map &operator=(const mm3d_map &) = delete;
+  ~mm3d_map() { delete points; delete keypoints; delete desc; }
 };
 
 namespace mm3d {

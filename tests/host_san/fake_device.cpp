@@ -115,6 +115,9 @@ mm3d_normals *compute_normals(Context *c, const mm3d_cloud *in, double)
 void normals_of_items(Context *, const mm3d_cloud *, const Grid &, double, const int *, const int *, int, float4 *) {}
 mm3d_cloud *detect_keypoints_sift(Context *c, const mm3d_cloud *points, double, int, int, double, double normals_radius, mm3d_normals **normals_out, float)
 {
+  // TEST KNOB: the map whose filtered cloud has this many points FAILS (a host exception, while other maps are built or exist)
+  if (const char *e = getenv("MM3D_FAKE_FAIL_POINTS"))
+    if ((size_t)atol(e) == points->n) throw Error(MM3D_EDEVICE, "fake device: the keypoint detector failed (MM3D_FAKE_FAIL_POINTS)");
   if (normals_out) *normals_out = compute_normals(c, points, normals_radius);
   // TEST KNOB: the map whose filtered cloud has this many points is LATE (its owner publishes it long after the others)
   if (const char *e = getenv("MM3D_FAKE_LATE_POINTS"))

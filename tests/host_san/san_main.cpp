@@ -2,13 +2,16 @@
 // layer: mm3d_estimate_maps_transforms on 1 and 16 streams (same bits required), both estimation methods, every descriptor
 // type's table entry, the shard driver for a world of 3 ranks emulated in one process, the device-list driver (mm3d_create_devices: 1, 2 and 3
 // fake devices and the duplicate-device hook, the pair records through the fake RCCL), composeMaps, the stage-by-stage
-// calls, parameter parsing, the degenerate inputs of the reference's gtests and the error paths.  Built with
+// calls, parameter parsing, the degenerate inputs of the reference's gtests and the error paths (a map that fails while it is
+// built among them: MM3D_FAKE_FAIL_POINTS).  Built with
 // -fsanitize=thread or -fsanitize=address,undefined by tests/host_san/build.sh; exit code 0 = the checks passed and no
 // sanitizer spoke.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <algorithm>
 #include <cstring>
+#include <string>
 #include <thread>
 #include <vector>
 
@@ -179,6 +182,15 @@ int main()
     std::vector<float> Ta(ns * 16), Tb(ns * 16);
     std::vector<mm3d_pair_result> Pa(mp), Pb(mp);
     size_t na = 0, npa = 0, nb = 0, npb = 0;
+    // how many points a map has after the (fake) filters: the key of the fake device's late and fail knobs
+    auto filtered_points = [&](size_t map) {
+      mm3d_cloud *raw = nullptr, *down = nullptr;
+      CHECK(mm3d_cloud_create(ctx, small[map].data(), small[map].size(), sizeof(Pt), 12, &raw) == MM3D_OK);
+      CHECK(mm3d_downsample(ctx, raw, p.resolution, &down) == MM3D_OK);
+      const std::string size = std::to_string(mm3d_cloud_size(down));
+      mm3d_cloud_free(ctx, raw); mm3d_cloud_free(ctx, down);
+      return size;
+    };
     CHECK(mm3d_set_streams(ctx, 1) == MM3D_OK);
     mm3d_srand(ctx, 1);
     CHECK(mm3d_estimate_maps_transforms(ctx, sv.data(), ns, &p, Ta.data(), &na, Pa.data(), &npa) == MM3D_OK && npa == 19 * 18 / 2);
@@ -210,15 +222,7 @@ int main()
       CHECK(mm3d_set_streams(ctx, 2) == MM3D_OK);
       mm3d_srand(ctx, 1);
       CHECK(mm3d_estimate_maps_transforms(ctx, sv.data(), ns, &p, Ta.data(), &na, Pa.data(), &npa) == MM3D_OK && npa == 20 * 19 / 2);
-      {
-        mm3d_cloud *raw = nullptr, *down = nullptr;               // how many points map 7 has after the (fake) filters: the late knob's key
-        CHECK(mm3d_cloud_create(ctx, small[7].data(), small[7].size(), sizeof(Pt), 12, &raw) == MM3D_OK);
-        CHECK(mm3d_downsample(ctx, raw, p.resolution, &down) == MM3D_OK);
-        char buf[32];
-        std::snprintf(buf, sizeof buf, "%zu", mm3d_cloud_size(down));
-        setenv("MM3D_FAKE_LATE_POINTS", buf, 1);
-        mm3d_cloud_free(ctx, raw); mm3d_cloud_free(ctx, down);
-      }
+      setenv("MM3D_FAKE_LATE_POINTS", filtered_points(7).c_str(), 1);
       mm3d_srand(dc, 1);
       for (int rep = 0; rep < 2; ++rep) {
         CHECK(mm3d_estimate_maps_transforms(dc, sv.data(), ns, &p, Tb.data(), &nb, Pb.data(), &npb) == MM3D_OK);
@@ -232,6 +236,32 @@ int main()
       unsetenv("MM3D_FAKE_LATE_POINTS");
       mm3d_destroy(dc);
     }
+    // the same twenty maps on ONE device, 1 stream and 3, with map 7 FAILING in the (fake) keypoint detector while its
+    // neighbours are being built or exist: the call comes back with a status -- every map built so far freed once (the
+    // sanitizers watch) -- and the same context then gives, from the same seed, the bits of a fresh one
+    setenv("MM3D_FAKE_DEVICES", "1", 1);
+    for (int streams : {1, 3}) {
+      mm3d_ctx *fc = nullptr, *fresh = nullptr;
+      CHECK(mm3d_create(0, &fc) == MM3D_OK && mm3d_create(0, &fresh) == MM3D_OK);
+      if (!fc || !fresh) continue;
+      CHECK(mm3d_set_streams(fc, streams) == MM3D_OK && mm3d_set_streams(fresh, streams) == MM3D_OK);
+      setenv("MM3D_FAKE_FAIL_POINTS", filtered_points(7).c_str(), 1);
+      mm3d_srand(fc, 1);
+      const int st = mm3d_estimate_maps_transforms(fc, sv.data(), ns, &p, Ta.data(), &na, Pa.data(), &npa);
+      unsetenv("MM3D_FAKE_FAIL_POINTS");
+      CHECK(st != MM3D_OK && std::strlen(mm3d_last_error(fc)) > 0);
+      std::memset(Pa.data(), 0, Pa.size() * sizeof(mm3d_pair_result));
+      std::memset(Pb.data(), 0, Pb.size() * sizeof(mm3d_pair_result));
+      mm3d_srand(fc, 1);
+      mm3d_srand(fresh, 1);
+      CHECK(mm3d_estimate_maps_transforms(fc, sv.data(), ns, &p, Ta.data(), &na, Pa.data(), &npa) == MM3D_OK);
+      CHECK(mm3d_estimate_maps_transforms(fresh, sv.data(), ns, &p, Tb.data(), &nb, Pb.data(), &npb) == MM3D_OK);
+      CHECK(na == nb && npa == npb && npa > 0 && std::memcmp(Ta.data(), Tb.data(), na * 16 * sizeof(float)) == 0);
+      CHECK(std::memcmp(Pa.data(), Pb.data(), std::min(npa, npb) * sizeof(mm3d_pair_result)) == 0);
+      mm3d_destroy(fc);
+      mm3d_destroy(fresh);
+    }
+    setenv("MM3D_FAKE_DEVICES", "3", 1);
   }
 
   // degenerate inputs of the reference's gtests (R/test/test_map_merging.cpp:9-40) and the error paths

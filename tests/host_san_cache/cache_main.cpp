@@ -6,6 +6,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <string>
 #include <vector>
 
 #include "../../include/mm3d.h"
@@ -135,6 +136,16 @@ static void sequence(int streams, int method)
   setenv("MM3D_FAKE_DIGEST_FAIL_POINTS", "1111", 1);
   CHECK(run(cached, bad, p).status == MM3D_EDEVICE);
   unsetenv("MM3D_FAKE_DIGEST_FAIL_POINTS");
+  {
+    // the same call failing one stage later: that map misses, and the (fake) keypoint detector throws while it is built
+    mm3d_cloud *raw = nullptr, *down = nullptr;
+    CHECK(mm3d_cloud_create(plain, bad[2].data(), bad[2].size(), sizeof(Pt), 12, &raw) == MM3D_OK);
+    CHECK(mm3d_downsample(plain, raw, p.resolution, &down) == MM3D_OK);
+    setenv("MM3D_FAKE_FAIL_POINTS", std::to_string(mm3d_cloud_size(down)).c_str(), 1);
+    mm3d_cloud_free(plain, raw); mm3d_cloud_free(plain, down);
+    CHECK(run(cached, bad, p).status == MM3D_EDEVICE);
+    unsetenv("MM3D_FAKE_FAIL_POINTS");
+  }
   CHECK(mm3d_map_cache_stats(cached, after, 0) == MM3D_OK);
   CHECK(std::memcmp(before, after, sizeof(before)) == 0);
   P = lockstep(cached, plain, clouds, p, st, 1);               // (the first call's generator state again: SAC_IA's pairs too)
