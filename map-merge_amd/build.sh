@@ -9,7 +9,8 @@ FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-ma
 BUILD=${BUILD_DIR:-build}
 OUT=${OUT:-libmm3d.so}
 mkdir -p $BUILD
-SRCS="libm_debug.hip grid.hip filters.hip normals.hip sift.hip harris.hip fpfh.hip pfh.hip rsd.hip shot.hip sc3d.hip desc_knn.hip registration.hip nn.hip icp_plane.hip align_prerej.hip keypoints_uniform.hip runtime.cpp linalg.cpp host_pipeline.cpp map_cache.hip devices.cpp capi.cpp map_cache.cpp"
+. csrc/host_sources.sh    # MM3D_HOST_SOURCES: the files without a kernel
+SRCS="libm_debug.hip grid.hip filters.hip normals.hip sift.hip harris.hip fpfh.hip pfh.hip rsd.hip shot.hip sc3d.hip desc_knn.hip registration.hip nn.hip icp_plane.hip align_prerej.hip keypoints_uniform.hip map_cache.hip $MM3D_HOST_SOURCES map_cache.cpp"
 OBJS=""
 pids=()
 for s in $SRCS; do

@@ -1,17 +1,12 @@
 // capi.cpp -- the extern "C" boundary of libmm3d.so (include/mm3d.h).  Nothing throws across it.
 #include <algorithm>
-#include <atomic>
-#include <cfloat>
-#include <chrono>
-#include <condition_variable>
 #include <cstdlib>
-#include <exception>
-#include <thread>
 #include <sstream>
 #include <string>
 
 #include "device_util.hpp"
 #include "capi_guard.hpp"
+#include "drivers.hpp"
 
 using namespace mm3d;
 
@@ -412,19 +407,6 @@ int mm3d_desc_download_frames(mm3d_ctx *ctx, const mm3d_desc *d, float *dst)
     ctx->sync();
   });
 }
-static mm3d_desc *desc_from_memory(mm3d_ctx *ctx, const float *data, size_t n, int descriptor_type)
-{
-  const int dim = mm3d_descriptor_dim(descriptor_type);
-  if (dim < 0) throw Error(MM3D_EINVAL, "unknown descriptor type");
-  std::unique_ptr<mm3d_desc> r(new mm3d_desc());
-  r->n = n; r->dim = dim; r->type = descriptor_type;
-  r->data = DevBuf<float>(ctx, n * dim);
-  if (n) {
-    MM3D_HIP(hipMemcpyAsync(r->data.get(), data, n * dim * sizeof(float), hipMemcpyDefault, ctx->stream));
-    ctx->sync();
-  }
-  return r.release();
-}
 
 int mm3d_debug_desc_knn(mm3d_ctx *ctx, const float *a, size_t na, const float *b, size_t nb, int dim, int k, int *idx, float *d2)
 {
@@ -616,62 +598,6 @@ int mm3d_transform_score(mm3d_ctx *ctx, const mm3d_cloud *source, const mm3d_clo
 }
 
 // ---------------------------------------------------------------- map bundles
-// mm3d_set_keypoints with leaf = 0: the leaf is descriptor_radius over this (DESIGN.md section 7d has the measurement)
-static constexpr double kUniformLeafDivisor = 2.0;
-// a caller's view of a map, uploaded; a null / empty map (robot subscribed but no message yet) counts as "no keypoints"
-static std::unique_ptr<mm3d_cloud> cloud_from_view(mm3d_ctx *c, const mm3d_cloud_view &v)
-{
-  return std::unique_ptr<mm3d_cloud>(cloud_from_memory(c, v.points, v.points ? v.n : 0, v.stride ? v.stride : 16, v.stride ? v.rgba_offset : 12));
-}
-static std::unique_ptr<mm3d_map> make_map(std::unique_ptr<mm3d_cloud> points, std::unique_ptr<mm3d_cloud> keypoints, std::unique_ptr<mm3d_desc> desc)
-{
-  std::unique_ptr<mm3d_map> m(new mm3d_map());
-  m->points = points.release(); m->keypoints = keypoints.release(); m->desc = desc.release();
-  return m;
-}
-// wait = false: the caller goes on in the same stream (map_prepare_impl) and waits once, there
-static std::unique_ptr<mm3d_map> map_features_impl(mm3d_ctx *ctx, const mm3d_cloud *raw, const mm3d_params *p, bool wait = true)
-{
-  if (p->keypoint_type != MM3D_KP_SIFT && p->keypoint_type != MM3D_KP_HARRIS) throw Error(MM3D_EINVAL, "invalid keypoint type");
-  if (p->descriptor_type < 0 || p->descriptor_type >= 6) throw Error(MM3D_EINVAL, "unknown descriptor type");   // dispatch_descriptors.h:63
-  std::unique_ptr<mm3d_cloud> down(downsample(ctx, raw, p->resolution));
-  // NB: the outlier radius is the DESCRIPTOR radius (map_merging.cpp:219-220)
-  std::unique_ptr<mm3d_cloud> filt(remove_outliers(ctx, down.get(), p->descriptor_radius, p->outliers_min_neighbours));
-  down.reset();
-  // computeSurfaceNormals, then detectKeypoints(points, normals, type, keypoint_threshold, normal_radius, resolution)
-  // (map_merging.cpp:225-233).  SIFT does not read the normals, and its first octave builds every point's sorted
-  // neighbour list over a ball that contains the normals': the two stages share that launch (sift.hip), same bits.
-  std::unique_ptr<mm3d_normals> nrm;
-  std::unique_ptr<mm3d_cloud> kp;
-  if (ctx->keypoint_source) {
-    // mm3d_set_keypoints: no detector runs (keypoint_type and keypoint_threshold are not read); the normals come from their
-    // stand-alone launch, since SIFT's fused first octave does not run
-    nrm.reset(compute_normals(ctx, filt.get(), p->normal_radius));
-    const double leaf = ctx->keypoint_options.leaf > 0.0 ? ctx->keypoint_options.leaf : p->descriptor_radius / kUniformLeafDivisor;
-    kp.reset(ctx->keypoint_source->keypoints(ctx, filt.get(), leaf));
-  } else if (p->keypoint_type == MM3D_KP_HARRIS) {
-    nrm.reset(compute_normals(ctx, filt.get(), p->normal_radius));
-    kp.reset(detect_keypoints_harris(ctx, filt.get(), nrm.get(), p->keypoint_threshold, p->normal_radius));
-  } else {
-    mm3d_normals *n_out = nullptr;
-    static const bool share_grid = [] { const char *e = getenv("MM3D_SIFT_NO_SHARED_GRID"); return !(e && atoi(e)); }();   // A/B knob
-    // (every descriptor searches `filt` on a grid of descriptor_radius / 2 cells: the first octave uses that one too)
-    kp.reset(detect_keypoints_sift(ctx, filt.get(), p->resolution, 3, 3, p->keypoint_threshold, p->normal_radius, &n_out,
-                                   share_grid ? (float)(p->descriptor_radius * 0.5) : 0.0f));
-    nrm.reset(n_out);
-  }
-  std::unique_ptr<mm3d_desc> desc(p->descriptor_type == MM3D_DESC_PFH    ? compute_pfh(ctx, filt.get(), nrm.get(), kp.get(), p->descriptor_radius)
-                                  : p->descriptor_type == MM3D_DESC_SC3D ? compute_sc3d(ctx, filt.get(), nrm.get(), kp.get(), p->descriptor_radius)
-                                  : p->descriptor_type == MM3D_DESC_RSD ? compute_rsd(ctx, filt.get(), nrm.get(), kp.get(), p->descriptor_radius)
-                                  : p->descriptor_type == MM3D_DESC_PFHRGB ? compute_pfhrgb(ctx, filt.get(), nrm.get(), kp.get(), p->descriptor_radius)
-                                  : p->descriptor_type == MM3D_DESC_SHOT ? compute_shot(ctx, filt.get(), nrm.get(), kp.get(), p->descriptor_radius)
-                                                                         : compute_fpfh(ctx, filt.get(), nrm.get(), kp.get(), p->descriptor_radius));
-  if (wait) ctx->sync();
-  std::unique_ptr<mm3d_map> m = make_map(std::move(filt), std::move(kp), std::move(desc));
-  if (ctx->icp_method) m->normals = std::move(nrm);    // point-to-plane ICP reads them (mm3d_set_icp_method)
-  return m;
-}
-
 int mm3d_map_features(mm3d_ctx *ctx, const mm3d_cloud *raw, const mm3d_params *params, mm3d_map **out)
 {
   if (!raw || !params || !out) return MM3D_EINVAL;
@@ -691,17 +617,6 @@ int mm3d_map_from_parts(mm3d_ctx *ctx, mm3d_cloud *points, mm3d_cloud *keypoints
   return MM3D_OK;
 }
 
-static void map_prepare_impl(mm3d_ctx *ctx, mm3d_map *m, const mm3d_params *p)
-{
-  if (ctx->icp_method && !m->normals) m->normals.reset(compute_normals(ctx, m->points, p->normal_radius));
-  prepare_pair_search(ctx, m->points, p->max_correspondence_distance, p->max_correspondence_distance);
-  if (p->estimation_method == MM3D_EST_SAC_IA && ctx->align_method) ctx->align_method->prepare(ctx, m->keypoints, p->max_correspondence_distance);
-  else if (p->estimation_method == MM3D_EST_SAC_IA) prepare_sacia_target(ctx, m->keypoints, (float)p->max_correspondence_distance);
-  desc_knn_prepare_target(ctx, m->desc);
-  (void)cloud_host(ctx, m->keypoints, false);       // (the keypoints' host copy rides on the wait below)
-  ctx->sync();                                       // everything complete, the error flags the kernels left looked at
-}
-
 int mm3d_map_prepare(mm3d_ctx *ctx, mm3d_map *m, const mm3d_params *p)
 {
   if (!m || !p) return MM3D_EINVAL;
@@ -714,209 +629,6 @@ void mm3d_map_free(mm3d_ctx *ctx, mm3d_map *m)
   std::lock_guard<std::mutex> lock(ctx->mu);
   (void)stream_wait(ctx->stream);
   delete m;
-}
-
-// Context::private_objects for a scope: what is built inside is the context's alone until the builder has drained the stream
-// itself, so no waits for other contexts' sake while it is built (Context::settle)
-namespace {
-struct PrivateObjects {
-  mm3d_ctx *c;
-  explicit PrivateObjects(mm3d_ctx *c_) : c(c_) { c->private_objects = true; }
-  PrivateObjects(const PrivateObjects &) = delete;
-  ~PrivateObjects() { c->private_objects = false; }
-};
-}  // namespace
-
-// A map built and prepared on one worker's context, for a driver that publishes it afterwards: nobody else sees it before
-// map_prepare_impl's full wait -- which also looks at the error flags the kernels left -- and a throw strands nothing.
-static std::unique_ptr<mm3d_map> build_private_map(mm3d_ctx *c, const mm3d_cloud *raw, const mm3d_params *p)
-{
-  PrivateObjects priv(c);
-  std::unique_ptr<mm3d_map> m = map_features_impl(c, raw, p, false);
-  map_prepare_impl(c, m.get(), p);                     // (ends in that wait)
-  return m;
-}
-
-// A map another device owns, for the SOURCE role on context c (as mm3d_shard_unpack): bundle and source-side structures
-// straight from the owner's memory, then whatever of the query orders / host copy did not come with the clone
-static std::unique_ptr<mm3d_map> pull_map_from_peer(mm3d_ctx *c, const mm3d_map *src, int src_device)
-{
-  PrivateObjects priv(c);                              // (nobody sees the copy before the wait below)
-  std::unique_ptr<mm3d_cloud> pts(cloud_clone_from_peer(c, src->points, src_device));
-  std::unique_ptr<mm3d_cloud> kp(cloud_clone_from_peer(c, src->keypoints, src_device));
-  std::unique_ptr<mm3d_desc> desc(desc_clone_from_peer(c, src->desc, src_device));
-  if (pts->n) cloud_hilbert(c, pts.get());
-  if (kp->n) cloud_hilbert(c, kp.get());
-  (void)cloud_host(c, kp.get());
-  c->sync();
-  return make_map(std::move(pts), std::move(kp), std::move(desc));
-}
-
-// The normals point-to-plane ICP reads of a pair's target map: a map that mm3d_map_prepare did not give them (a map made
-// while the context was point-to-point, a cached one of such a call, one from parts) gets them on first use -- under its
-// points' lock, complete on the device before anybody else can see them, since other streams may share the map.
-static const mm3d_normals *map_normals(mm3d_ctx *ctx, const mm3d_map *m, const mm3d_params *p)
-{
-  std::lock_guard<std::recursive_mutex> lk(m->points->cache_mu);
-  if (!m->normals) {
-    std::unique_ptr<mm3d_normals> n(compute_normals(ctx, m->points, p->normal_radius));
-    ctx->sync();
-    const_cast<mm3d_map *>(m)->normals = std::move(n);
-  }
-  return m->normals.get();
-}
-
-// The estimation method as the rand() replay sees it: a prerejective alignment (mm3d_set_alignment) draws nothing from rand(),
-// which is MATCHING's case in pair_rand_replay.
-static int replay_method(const mm3d_ctx *ctx, const mm3d_params *p)
-{
-  return ctx->align_method && p->estimation_method == MM3D_EST_SAC_IA ? (int)MM3D_EST_MATCHING : (int)p->estimation_method;
-}
-static bool prerejective(const mm3d_ctx *ctx, const mm3d_params *p) { return ctx->align_method && p->estimation_method == MM3D_EST_SAC_IA; }
-
-struct PairWork { const mm3d_map *s, *t; mm3d_pair_result *out; GlibcRand rnd; };
-static void pairs_estimate_batch(mm3d_ctx *ctx, PairWork *w, size_t n, const mm3d_params *p);
-
-static void pair_estimate_impl(mm3d_ctx *ctx, const mm3d_map *s, const mm3d_map *t, const mm3d_params *p, bool execute,
-                               mm3d_pair_result *out)
-{
-  if (execute && (ctx->icp_method || prerejective(ctx, p))) {
-    // point-to-plane ICP (mm3d_set_icp_method) and the prerejective alignment (mm3d_set_alignment) live in the batch path: a
-    // batch of one, from (and advancing) the context's generator
-    PairWork w{s, t, out, ctx->rnd};
-    pairs_estimate_batch(ctx, &w, 1, p);
-    return;
-  }
-  std::memset(out->transform, 0, sizeof(out->transform));
-  out->confidence = 0.0;
-  out->icp_iterations = 0;
-  out->n_correspondences = out->n_inliers = out->icp_correspondences = 0;
-  if (prerejective(ctx, p)) return;                     // not executed, and nothing to replay (mm3d_set_alignment)
-  // estimateTransform and transformScore of its result (R/src/map_merging.cpp:91-107) as one device
-  // pipeline: the transform never visits the host in between
-  double score = DBL_MAX;
-  PairCounts counts;
-  const int iters = estimate_pair(ctx, s->points, s->keypoints, s->desc, t->points, t->keypoints, t->desc,
-                                  p->estimation_method, p->refine_transform, p->inlier_threshold,
-                                  p->max_correspondence_distance, p->max_iterations, (size_t)p->matching_k,
-                                  p->transform_epsilon, out->transform, execute, true, p->max_correspondence_distance, &score, &counts);
-  if (!execute) return;
-  out->icp_iterations = iters;
-  out->n_correspondences = counts.n_correspondences;
-  out->n_inliers = counts.n_inliers;
-  out->icp_correspondences = counts.icp_correspondences;
-  out->confidence = 1.0 / score;
-}
-
-constexpr size_t kPairBatch = 16;     // pairs whose tails and scoring share launches
-// the two experiment knobs of the pair batches, validated once (a share <= 0 or not a number would divide by zero and cast
-// inf to size_t; a batch cap of 0 would never claim a pair and leave the scheduler waiting for ever)
-static double pair_share_knob()
-{
-  static const double v = [] {
-    const char *e = getenv("MM3D_PAIR_SHARE");
-    double s = e ? atof(e) : 0.25;
-    if (!(s >= 1.0 / 64.0)) s = 1.0 / 64.0;           // (also catches NaN)
-    return std::min(s, 64.0);
-  }();
-  return v;
-}
-static size_t pair_batch_knob()
-{
-  static const size_t v = [] {
-    const char *e = getenv("MM3D_PAIR_BATCH");
-    const long b = e ? atol(e) : (long)kPairBatch;
-    return (size_t)std::min<long>(std::max<long>(b, 1), 32);      // (32: the largest batch ever run)
-  }();
-  return v;
-}
-// How large a batch, of `avail` pairs that can start now on S streams: round 4 measured take = avail / (share * S) on the headline
-// (16 streams, 120 pairs trickling in behind the feature stage): share 4 / 2 / 1 / 0.5 / 0.25 / 0.125 -> 989 / 990 / 1004 / 1013 /
-// 1021 / 1022 map-pairs/s.  The pair stage's kernels are latency-bound and only four run at a time (hardware queues), so a launch
-// that serves four pairs costs little more queue time than one that serves one; with share 2 most batches were a single pair.
-// (The cap is an experiment knob: 8 / 16 / 32 the same.)
-static size_t pair_batch_take(size_t avail, size_t S)
-{
-  return std::min(pair_batch_knob(), std::max<size_t>(1, (size_t)((double)avail / (pair_share_knob() * (double)S))));
-}
-// every pair of n maps, in the order of the reference's loop (map_merging.cpp:256-269)
-static std::vector<std::pair<size_t, size_t>> all_pairs(size_t n)
-{
-  std::vector<std::pair<size_t, size_t>> all;
-  for (size_t i = 0; i + 1 < n; ++i)
-    for (size_t j = i + 1; j < n; ++j) all.emplace_back(i, j);
-  return all;
-}
-
-// Several pairs on one context: the initial estimates one after the other (each from its own generator state),
-// then every pair's ICP + score tail in lockstep, one launch per step for the whole batch (icp_score_batch).
-static void pairs_estimate_batch(mm3d_ctx *ctx, PairWork *w, size_t n, const mm3d_params *p)
-{
-  std::vector<PairFront> fronts(n);
-  std::vector<IcpScoreJob> jobs(n);
-  std::vector<SacPrepared> prepared;
-  for (size_t i = 0; i < n; ++i) {
-    mm3d_pair_result *out = w[i].out;
-    std::memset(out->transform, 0, sizeof(out->transform));
-    out->confidence = 0.0;
-    out->icp_iterations = 0;
-    out->n_correspondences = out->n_inliers = out->icp_correspondences = 0;
-    ctx->rnd = w[i].rnd;
-    if (prerejective(ctx, p)) {
-      // the same inputs, max_correspondence_distance as the inlier distance; the generator's seed, none of its draws
-      ctx->align_method->front(ctx, ctx->align_options, w[i].rnd.seed0, w[i].s->keypoints, w[i].s->desc, w[i].t->keypoints, w[i].t->desc,
-                               p->max_correspondence_distance, fronts[i], &ctx->last_align_stats);
-    } else if (p->estimation_method == MM3D_EST_SAC_IA) {
-      // argument mapping of matching.cpp:243-246: min_sample_distance := inlier_threshold
-      sac_ia_replay(ctx, w[i].s->keypoints, w[i].s->desc, w[i].t->keypoints, w[i].t->desc, p->inlier_threshold, p->max_iterations, true,
-                    fronts[i]);
-      prepared.push_back(SacPrepared{w[i].s->keypoints, w[i].t->keypoints, w[i].s->desc, w[i].t->desc, &fronts[i]});
-    } else {
-      estimate_pair_front(ctx, w[i].s->keypoints, w[i].s->desc, w[i].t->keypoints, w[i].t->desc, p->estimation_method,
-                          p->inlier_threshold, p->max_correspondence_distance, p->max_iterations, (size_t)p->matching_k, true, fronts[i]);
-    }
-  }
-  if (!prepared.empty()) {
-    // the sampled rows of every pair with the same target go through one descriptor search, and the hypotheses of
-    // all the batch's pairs are scored by the same five launches
-    std::stable_sort(prepared.begin(), prepared.end(), [](const SacPrepared &a, const SacPrepared &b) { return a.td < b.td; });
-    std::vector<DevBuf<int>> nn_owners;
-    std::vector<DevBuf<float>> nd_owners;
-    for (size_t a = 0; a < prepared.size();) {
-      size_t b = a;
-      while (b < prepared.size() && prepared[b].td == prepared[a].td) ++b;
-      nn_owners.emplace_back();
-      nd_owners.emplace_back();
-      sac_ia_knn(ctx, &prepared[a], (int)(b - a), nn_owners.back(), nd_owners.back());
-      a = b;
-    }
-    sac_ia_finish(ctx, prepared.data(), (int)prepared.size(), p->max_correspondence_distance);
-  }
-  for (size_t i = 0; i < n; ++i) {
-    jobs[i].src = w[i].s->points;
-    jobs[i].tgt = w[i].t->points;
-    jobs[i].guess_dev = fronts[i].on_device ? fronts[i].dT0.get() : nullptr;
-    std::memcpy(jobs[i].guess_host, fronts[i].T0, sizeof(fronts[i].T0));
-  }
-  // estimateTransform's ICP and transformScore of its result (R/src/map_merging.cpp:91-107), max_distance = max_correspondence_distance
-  if (ctx->icp_method) {                                // point-to-plane (mm3d_set_icp_method): the targets' normals
-    if (p->refine_transform)
-      for (size_t i = 0; i < n; ++i) jobs[i].tgt_normals = map_normals(ctx, w[i].t, p);
-    ctx->icp_method->score_batch(ctx, jobs.data(), (int)n, p->refine_transform != 0, p->max_correspondence_distance, p->max_iterations,
-                                 p->transform_epsilon, true, p->max_correspondence_distance);
-  } else {
-    icp_score_batch(ctx, jobs.data(), (int)n, p->refine_transform != 0, p->max_correspondence_distance, p->max_iterations, p->transform_epsilon,
-                    true, p->max_correspondence_distance);
-  }
-  for (size_t i = 0; i < n; ++i) {
-    mm3d_pair_result *out = w[i].out;
-    std::memcpy(out->transform, jobs[i].out.T, sizeof(out->transform));
-    out->icp_iterations = jobs[i].out.iterations;
-    out->n_correspondences = fronts[i].counts.n_correspondences;
-    out->n_inliers = fronts[i].counts.n_inliers;
-    out->icp_correspondences = jobs[i].out.n_corr;
-    out->confidence = 1.0 / jobs[i].out.score;
-  }
 }
 
 int mm3d_pair_estimate(mm3d_ctx *ctx, const mm3d_map *source, const mm3d_map *target, const mm3d_params *params, int execute,
@@ -933,9 +645,7 @@ int mm3d_pairs_skip(mm3d_ctx *ctx, const mm3d_map *const *sources, const mm3d_ma
     for (size_t i = 0; i < n; ++i) {
       const mm3d_map *s = sources[i], *t = targets[i];
       if (!s || !t) throw Error(MM3D_EINVAL, "null map");
-      if (s->keypoints->n == 0 || t->keypoints->n == 0) continue;      // not a pair (map_merging.cpp:250)
-      pair_rand_replay(ctx->rnd, replay_method(ctx, params), cloud_host(ctx, s->keypoints), params->inlier_threshold,
-                       params->max_iterations);
+      if (is_pair(s, t)) pair_replay_draws(ctx->rnd, ctx, params, cloud_host(ctx, s->keypoints));
     }
   });
 }
@@ -949,1120 +659,6 @@ int mm3d_global_transforms(const mm3d_pair_result *pairs, size_t n_pairs, double
   } catch (...) {
     return MM3D_ENOMEM;
   }
-}
-
-// estimateMapsTransforms over the context's streams (mm3d_set_streams).  The reference's two loops
-// (map_merging.cpp:212-242 per cloud, :256-269 per pair) are dealt to S workers, one context (HIP
-// stream + memory pool) and one host thread each: about 3/4 of them extract features, every worker
-// then claims pairs in the reference's order and waits until both maps of its pair exist.  A map is
-// prepared (map_prepare_impl) before it is published, so pairs only read it.  The reference's single
-// rand() stream is kept by replay: every worker starts from the caller's generator state and replays
-// the draws of the pairs it does not execute (execute = false, host only), so each pair sees exactly
-// the state the sequential loop would give it; worker 0 (the caller's own context) replays to the
-// end, which leaves the caller's generator where the sequential loop would.
-static void estimate_maps_streams(mm3d_ctx *ctx, const mm3d_cloud_view *clouds, size_t n, const mm3d_params *params, float *out_T,
-                                  size_t *n_out, mm3d_pair_result *pairs_out, size_t *n_pairs_out)
-{
-  std::vector<mm3d_ctx *> cs{ctx};
-  cs.insert(cs.end(), ctx->helpers.begin(), ctx->helpers.end());
-  const size_t S = cs.size();
-  // many small maps (at least two per worker): every worker extracts features first, and the pairs then start in
-  // batches; otherwise (few large maps) 3/4 of the workers do, and the others begin with the pairs of the first maps
-  // (measured on 16 x 500 k points with 16 workers, map pairs/s at 6 / 8 / 10 / 12 / 16 feature workers:
-  // 740 / 741 / 736 / 765 / 741;
-  // and three quarters of the maps with 8 x 2 M points: 93.0 pairs/s with 6 feature workers, 91.2 with 12 = all 8 maps at
-  // once; the dense indoor variant 59.0 / 53.9)
-  size_t F = (S <= 4 || n >= 2 * S) ? S : std::max<size_t>(4, std::min(S * 3 / 4, (n * 3 + 3) / 4));
-  if (const char *e = std::getenv("MM3D_FEATURE_WORKERS")) {     // tuning knob: how many workers start on features
-    const long v = std::atol(e);
-    if (v >= 1) F = std::min<size_t>(S, (size_t)v);
-  }
-  const std::vector<std::pair<size_t, size_t>> all = all_pairs(n);
-  std::vector<mm3d_map *> maps(n, nullptr);
-  // mm3d_set_map_cache: maps[i] is the cache's (a hit, or a miss handed over once built) where borrowed[i] is set
-  MapCacheBase *const cache = ctx->map_cache;
-  std::vector<char> borrowed(n, 0);
-  struct MapsGuard {                                    // the maps go when the call ends, whichever way
-    std::vector<mm3d_map *> &m;
-    const std::vector<char> &borrowed;
-    ~MapsGuard()
-    {
-      for (size_t i = 0; i < m.size(); ++i)
-        if (!borrowed[i]) delete m[i];
-    }
-  } maps_guard{maps, borrowed};
-  std::vector<mm3d_pair_result> rec(all.size());
-  std::vector<char> ready(n, 0), done(all.size(), 0);
-  std::mutex mu;
-  std::condition_variable cv;
-  size_t next_map = 0;
-  bool abort = false;
-  std::exception_ptr first_error;
-  const GlibcRand rnd0 = ctx->rnd;
-  const auto t_start = std::chrono::steady_clock::now();
-  auto since_start = [&] { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count(); };
-  ctx->last_points.assign(n, 0);
-  ctx->last_keypoints.assign(n, 0);
-  ctx->last_features_s = ctx->last_total_s = 0.0;
-
-  // The reference's single rand() stream, without serialising the pairs on it: the draws a pair consumes
-  // depend on its SOURCE keypoints only (pair_rand_replay), given that its target has a keypoint at all.
-  // state_at[q] = the generator before pair q; it is advanced pair by pair (once, under rng_mu) as far as
-  // a worker needs it, taking "is pair q live" from the maps that exist and ASSUMING a target that is
-  // still being computed will have keypoints.  A pair can therefore start as soon as its own two maps
-  // and the sources of the rows before it exist -- not only after the last map.  Every assumption is
-  // checked once all maps exist; a wrong one (a map without keypoints, e.g. an untextured cloud) makes
-  // the call redo the pair loop sequentially, which is the reference's loop.
-  const size_t P = all.size();
-  std::vector<GlibcRand> state_at(P + 1, rnd0);
-  std::vector<char> assumed_live(P, 0), claimed(P, 0);
-  size_t known_upto = 0;                                // state_at[0 .. known_upto] are final
-  std::mutex rng_mu;
-  auto wait_ready = [&](size_t i) {
-    std::unique_lock<std::mutex> lk(mu);
-    cv.wait(lk, [&] { return abort || ready[i]; });
-    if (abort) throw Error(MM3D_EDEVICE, "aborted");
-  };
-  auto is_ready = [&](size_t i) { std::lock_guard<std::mutex> lk(mu); return ready[i] != 0; };
-  auto advance_states = [&](size_t p) {                 // make state_at[p] final
-    std::lock_guard<std::mutex> rl(rng_mu);
-    while (known_upto < p) {
-      const size_t q = known_upto, a = all[q].first, b = all[q].second;
-      wait_ready(a);
-      bool live = maps[a]->keypoints->n > 0;
-      if (live) {
-        if (is_ready(b)) live = maps[b]->keypoints->n > 0;
-        else assumed_live[q] = 1;
-      }
-      GlibcRand r = state_at[q];
-      if (live) pair_rand_replay(r, replay_method(ctx, params), cloud_host(cs[0], maps[a]->keypoints), params->inlier_threshold,
-                                 params->max_iterations);
-      state_at[q + 1] = r;
-      known_upto = q + 1;
-    }
-  };
-  // the next pairs to work on: the first unclaimed ones, in the reference's order, whose two maps and all
-  // earlier sources exist (maps finish roughly in index order, so that is rarely a restriction).  A worker takes
-  // its share of what can start right now, up to kPairBatch pairs: their ICP / score tails then run as one batch
-  // (many small maps: thousands of pairs are ready at once and a launch per pair leaves the chip idle), while a
-  // job whose pairs trickle in behind the feature stage keeps dealing them out one by one.
-  auto claim_pairs = [&](std::vector<size_t> &out) -> bool {
-    out.clear();
-    std::unique_lock<std::mutex> lk(mu);
-    for (;;) {
-      if (abort) return false;
-      bool any_left = false;
-      size_t prefix = 0, avail = 0;
-      while (prefix < n && ready[prefix]) ++prefix;      // maps [0, prefix) exist
-      for (size_t q = 0; q < P; ++q) {
-        if (claimed[q]) continue;
-        any_left = true;
-        if (all[q].first < prefix && ready[all[q].second]) ++avail;
-      }
-      if (!any_left) return false;
-      if (avail) {
-        // a batch shares its TARGET (the pairs (i, t) of one t): one descriptor search for the sampled rows of all
-        // its sources, and one target grid under every search of the batch
-        const size_t take = pair_batch_take(avail, S);
-        size_t target = n;
-        for (size_t q = 0; q < P && out.size() < take; ++q)
-          if (!claimed[q] && all[q].first < prefix && ready[all[q].second] && (target == n || all[q].second == target)) {
-            target = all[q].second;
-            claimed[q] = 1;
-            out.push_back(q);
-          }
-        return true;
-      }
-      cv.wait(lk);
-    }
-  };
-  auto worker = [&](size_t w) {
-    mm3d_ctx *c = cs[w];
-    try {
-      if (hipSetDevice(c->device) != hipSuccess) throw Error(MM3D_EDEVICE, "hipSetDevice failed");
-      while (w < F) {
-        size_t i;
-        {
-          std::lock_guard<std::mutex> lk(mu);
-          if (abort || next_map >= n) break;
-          i = next_map++;
-        }
-        std::unique_ptr<mm3d_cloud> raw = cloud_from_view(c, clouds[i]);
-        if (cache && raw->n > 0) {
-          // an unchanged map: its bundle is published at once, nothing else runs on the device for it
-          if (const mm3d_map *hit = cache->lookup(c, i, raw.get())) {
-            raw.reset();
-            {
-              std::lock_guard<std::mutex> lk(mu);
-              maps[i] = const_cast<mm3d_map *>(hit);
-              borrowed[i] = 1;
-              ready[i] = 1;
-              ctx->last_points[i] = hit->points->n;
-              ctx->last_keypoints[i] = hit->keypoints->n;
-              ctx->last_features_s = std::max(ctx->last_features_s, since_start());
-            }
-            cv.notify_all();
-            continue;
-          }
-        }
-        std::unique_ptr<mm3d_map> held = build_private_map(c, raw.get(), params);   // this worker's alone until it is published
-        const bool keep = cache && raw->n > 0;
-        {
-          std::lock_guard<std::mutex> lk(mu);
-          mm3d_map *m = held.release();
-          maps[i] = m;
-          if (keep) {
-            cache->insert(i, std::move(raw), m);         // (the cache owns the map and its raw points from here on)
-            borrowed[i] = 1;
-          }
-          ready[i] = 1;
-          ctx->last_points[i] = m->points->n;
-          ctx->last_keypoints[i] = m->keypoints->n;
-          ctx->last_features_s = std::max(ctx->last_features_s, since_start());
-        }
-        raw.reset();
-        cv.notify_all();
-      }
-      std::vector<size_t> mine, work_q;
-      std::vector<PairWork> work;
-      while (claim_pairs(mine)) {
-        work.clear();
-        work_q.clear();
-        for (size_t p : mine) {
-          const mm3d_map *ms = maps[all[p].first], *mt = maps[all[p].second];
-          if (ms->keypoints->n > 0 && mt->keypoints->n > 0) {
-            advance_states(p);                          // (a reused pair's draws are replayed all the same)
-            rec[p].source_idx = all[p].first;
-            rec[p].target_idx = all[p].second;
-            if (cache && cache->pair_lookup(all[p].first, all[p].second, state_at[p], &rec[p])) continue;
-            work.push_back(PairWork{ms, mt, &rec[p], state_at[p]});
-            work_q.push_back(p);
-          }
-        }
-        if (!work.empty()) pairs_estimate_batch(c, work.data(), work.size(), params);
-        if (cache)
-          for (size_t k = 0; k < work.size(); ++k) cache->pair_insert(all[work_q[k]].first, all[work_q[k]].second, work[k].rnd, *work[k].out);
-        for (size_t p : mine)
-          if (maps[all[p].first]->keypoints->n > 0 && maps[all[p].second]->keypoints->n > 0) done[p] = 1;
-      }
-      // (every map and every batch of pairs ended in a wait that brought its results to the host: nothing is in flight here
-      // unless a kernel left an error flag to be looked at)
-      if (!c->deferred.empty()) c->sync();
-    } catch (...) {
-      std::lock_guard<std::mutex> lk(mu);
-      if (!first_error) first_error = std::current_exception();
-      abort = true;
-      cv.notify_all();
-    }
-  };
-  std::vector<std::thread> threads;
-  for (size_t w = 1; w < S; ++w) threads.emplace_back(worker, w);
-  worker(0);
-  for (auto &t : threads) t.join();
-  // every stream has been synchronised by its worker (or the run was aborted): the maps can go
-  for (size_t w = 0; w < S; ++w) (void)stream_wait(cs[w]->stream);
-  if (first_error) std::rethrow_exception(first_error);
-  // all maps exist now: finish the generator states and check what was assumed about late targets
-  advance_states(P);
-  bool assumptions_hold = true;
-  for (size_t q = 0; q < P; ++q)
-    if (assumed_live[q] && maps[all[q].second]->keypoints->n == 0) assumptions_hold = false;
-  if (assumptions_hold) {
-    ctx->rnd = state_at[P];                             // where the sequential loop leaves the generator
-  } else {
-    // a target turned out to have no keypoints: the states after that pair were positioned wrongly.
-    // Redo the pair loop the reference's way, on the caller's stream.  (The map cache is left out of it: the records it took
-    // above are still right for the states they name.)
-    ctx->rnd = rnd0;
-    std::fill(done.begin(), done.end(), 0);
-    for (size_t q = 0; q < P; ++q) {
-      const mm3d_map *ms = maps[all[q].first], *mt = maps[all[q].second];
-      if (ms->keypoints->n == 0 || mt->keypoints->n == 0) continue;
-      pair_estimate_impl(ctx, ms, mt, params, true, &rec[q]);
-      rec[q].source_idx = all[q].first;
-      rec[q].target_idx = all[q].second;
-      done[q] = 1;
-    }
-    ctx->sync();
-  }
-  std::vector<mm3d_pair_result> pairs;
-  for (size_t p = 0; p < all.size(); ++p)
-    if (done[p]) pairs.push_back(rec[p]);
-  if (pairs_out) std::memcpy(pairs_out, pairs.data(), pairs.size() * sizeof(mm3d_pair_result));
-  if (n_pairs_out) *n_pairs_out = pairs.size();
-  const int st = global_transforms(pairs.data(), pairs.size(), params->confidence_threshold, n, out_T, n_out);
-  if (st != MM3D_OK) throw Error(st, "computeGlobalTransforms failed");
-  ctx->last_total_s = since_start();
-}
-
-// ---------------------------------------------------------------- the same job on N processes (one per GPU)
-// The N > 1 driver, inside the library like the N = 1 one (estimate_maps_streams): the caller (bench.py,
-// one process per GPU) only moves bytes between ranks -- one all-gather of the maps' feature bundles, one
-// all-gather of the pair records.  A rank extracts the features of the maps it owns (on its streams),
-// receives the other maps' bundles, and estimates the pairs whose TARGET it owns, so each rank builds
-// target-side search structures (grids, distance transforms, k-NN operands) for n / world maps only.
-// Owners zig-zag over the ranks (0 1 .. w-1 w-1 .. 1 0 0 1 ..): target j has j pairs, and j and its mirror
-// image share a rank, which evens the pair counts out.
-struct mm3d_shard {
-  mm3d_ctx *ctx = nullptr;
-  int rank = 0, world = 1;
-  size_t n = 0;
-  mm3d_params params{};
-  std::vector<mm3d_map *> maps;
-  ~mm3d_shard()
-  {
-    for (mm3d_map *x : maps) delete x;
-  }
-};
-
-int mm3d_shard_map_owner(size_t map, int world)
-{
-  if (world <= 1) return 0;
-  const size_t j = map % (2 * (size_t)world);
-  return (int)(j < (size_t)world ? j : 2 * (size_t)world - 1 - j);
-}
-
-}  // extern "C" (a template needs C++ linkage)
-// run fn(worker index, context, failed) on the context's streams (the caller's thread is worker 0); the first
-// exception is rethrown.  `failed` is set when any worker has thrown: the others stop taking work.
-template <class Fn>
-static void on_streams(mm3d_ctx *ctx, Fn &&fn)
-{
-  std::vector<mm3d_ctx *> cs{ctx};
-  cs.insert(cs.end(), ctx->helpers.begin(), ctx->helpers.end());
-  std::mutex mu;
-  std::exception_ptr first_error;
-  std::atomic<bool> failed{false};
-  auto body = [&](size_t w) {
-    try {
-      if (hipSetDevice(cs[w]->device) != hipSuccess) throw Error(MM3D_EDEVICE, "hipSetDevice failed");
-      fn(w, cs[w], failed);
-      cs[w]->sync();
-    } catch (...) {
-      failed.store(true);
-      std::lock_guard<std::mutex> lk(mu);
-      if (!first_error) first_error = std::current_exception();
-    }
-  };
-  std::vector<std::thread> threads;
-  for (size_t w = 1; w < cs.size(); ++w) threads.emplace_back(body, w);
-  body(0);
-  for (auto &t : threads) t.join();
-  for (mm3d_ctx *c : cs) (void)stream_wait(c->stream);
-  if (first_error) std::rethrow_exception(first_error);
-}
-extern "C" {
-
-// (no lock, no device selection: the callers -- mm3d_shard_begin under guarded(), estimate_maps_devices on a device's own thread -- did both)
-static mm3d_shard *shard_begin_impl(mm3d_ctx *ctx, const mm3d_cloud_view *clouds, size_t n, const mm3d_params *params, int rank, int world)
-{
-  std::unique_ptr<mm3d_shard> sh(new mm3d_shard());
-  sh->ctx = ctx; sh->rank = rank; sh->world = world; sh->n = n; sh->params = *params;
-  sh->maps.assign(n, nullptr);
-  std::vector<size_t> mine;
-  for (size_t i = 0; i < n; ++i)
-    if (mm3d_shard_map_owner(i, world) == rank) mine.push_back(i);
-  std::atomic<size_t> next{0};
-  on_streams(ctx, [&](size_t, mm3d_ctx *c, const std::atomic<bool> &failed) {
-    for (;;) {
-      const size_t k = next.fetch_add(1);
-      if (k >= mine.size() || failed.load()) break;
-      const size_t i = mine[k];
-      std::unique_ptr<mm3d_cloud> raw = cloud_from_view(c, clouds[i]);
-      // this rank is the map's target-side owner; nobody else sees the map before on_streams has drained every stream
-      sh->maps[i] = build_private_map(c, raw.get(), params).release();   // (distinct slots: no lock needed; the shard owns it from here)
-    }
-  });
-  return sh.release();
-}
-
-int mm3d_shard_begin(mm3d_ctx *ctx, const mm3d_cloud_view *clouds, size_t n, const mm3d_params *params, int rank, int world,
-                     mm3d_shard **out)
-{
-  if (!ctx || !params || !out || (n && !clouds) || world < 1 || rank < 0 || rank >= world) return MM3D_EINVAL;
-  *out = nullptr;
-  return guarded(ctx, [&] {
-    if (ctx->icp_method) throw Error(MM3D_EUNSUPPORTED, "mm3d_shard_begin: shard bundles carry no normals for point-to-plane ICP");
-    if (ctx->align_method) throw Error(MM3D_EUNSUPPORTED, "mm3d_shard_begin: the ranks' pair loops run SAC-IA, not the prerejective alignment");
-    *out = shard_begin_impl(ctx, clouds, n, params, rank, world);
-  });
-}
-
-int mm3d_shard_bundle_sizes(const mm3d_shard *sh, uint64_t *n_points, uint64_t *n_keypoints)
-{
-  if (!sh || !n_points || !n_keypoints) return MM3D_EINVAL;
-  for (size_t i = 0; i < sh->n; ++i) {
-    const bool own = sh->maps[i] && mm3d_shard_map_owner(i, sh->world) == sh->rank;
-    n_points[i] = own ? sh->maps[i]->points->n : 0;
-    n_keypoints[i] = own ? sh->maps[i]->keypoints->n : 0;
-  }
-  return MM3D_OK;
-}
-
-// A map's bundle (round 5: the source-side structures travel with it).  What a rank does with another rank's map is the SOURCE
-// role: ICP / score / SAC-IA scoring read the cloud in its Hilbert query order through its work items, the rand() replay reads
-// the keypoints on the host.  Until round 5 a rank rebuilt those orders from the points it had received (two Hilbert sorts and a
-// wait per map: 2.3 ms per rank and step at N = 8, with fourteen foreign maps); now the owner -- who has them -- sends them:
-//   header (256 B) | points 16 B x P | keypoints 16 B x K | descriptors 4 B x dim x K |
-//   points in Hilbert order 16 B x P | their work items 8 B x (P / 64 + 16 386) | the same two for the keypoints
-// Every part starts 16-byte aligned and is as large as P and K allow (the sizes are all a receiver knows before the exchange);
-// the header says how much of the Hilbert parts is meant, and carries the bounding boxes.  The order a pair's reductions run in
-// is then the owner's, i.e. the one-process run's, by construction.
-namespace {
-struct BundleHeader {
-  uint64_t magic, n_points, n_keypoints;
-  uint64_t p_finite, p_items, k_finite, k_items;
-  uint32_t p_have, k_have;                   // bounding box + Hilbert copy + items are in the bundle
-  float p_bmin[3], p_bmax[3], k_bmin[3], k_bmax[3];
-  unsigned char pad[256 - 7 * 8 - 2 * 4 - 12 * 4];
-};
-static_assert(sizeof(BundleHeader) == 256, "bundle header");
-constexpr uint64_t kBundleMagic = 0x6d6d33642d623032ull;          // "mm3d-b02"
-// A stack object (a bundle header) is the source / destination of an asynchronous copy: nothing may unwind the frame while
-// that copy can still be in flight.  Armed until the function's own wait.
-struct DrainOnUnwind {
-  Context *c;
-  bool armed = true;
-  ~DrainOnUnwind() { if (armed) (void)stream_wait(c->stream); }
-};
-struct BundleLayout {
-  size_t pts, kp, desc, p_hil, p_items, k_hil, k_items, total, p_item_cap, k_item_cap;
-};
-size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
-BundleLayout bundle_layout(uint64_t P, uint64_t K, int dim)
-{
-  BundleLayout L;
-  L.p_item_cap = (size_t)P / 64 + 16384 + 2;                        // cloud_hilbert's bound (grid.hip)
-  L.k_item_cap = (size_t)K / 64 + 16384 + 2;
-  L.pts = sizeof(BundleHeader);
-  L.kp = L.pts + (size_t)P * 16;
-  L.desc = L.kp + (size_t)K * 16;
-  L.p_hil = up16(L.desc + (size_t)K * (size_t)(dim > 0 ? dim : 0) * 4);
-  L.p_items = L.p_hil + (size_t)P * 16;
-  L.k_hil = up16(L.p_items + L.p_item_cap * sizeof(int2));
-  L.k_items = L.k_hil + (size_t)K * 16;
-  L.total = up16(L.k_items + L.k_item_cap * sizeof(int2));
-  return L;
-}
-}  // namespace
-
-size_t mm3d_shard_bundle_bytes(uint64_t n_points, uint64_t n_keypoints, int descriptor_type)
-{
-  return bundle_layout(n_points, n_keypoints, mm3d_descriptor_dim(descriptor_type)).total;
-}
-
-int mm3d_shard_pack(mm3d_shard *sh, size_t map, void *dst)
-{
-  if (!sh || map >= sh->n || !sh->maps[map] || !dst) return MM3D_EINVAL;
-  mm3d_ctx *ctx = sh->ctx;
-  return guarded(ctx, [&] {
-    const mm3d_map *m = sh->maps[map];
-    char *d = static_cast<char *>(dst);
-    const BundleLayout L = bundle_layout(m->points->n, m->keypoints->n, m->desc->dim);
-    // the query orders exist on the owner as soon as it has played the source role once; a map that has not is ordered now
-    if (m->points->n) cloud_hilbert(ctx, m->points);
-    if (m->keypoints->n) cloud_hilbert(ctx, m->keypoints);
-    // (ordinary memory: the pinned arena may wrap under the copies below, and 256 bytes need no pinning)
-    BundleHeader header;
-    BundleHeader *h = &header;
-    std::memset(h, 0, sizeof(*h));
-    h->magic = kBundleMagic; h->n_points = m->points->n; h->n_keypoints = m->keypoints->n;
-    auto side = [&](const mm3d_cloud *cl, uint64_t &fin, uint64_t &items, uint32_t &have, float *bmin, float *bmax, size_t off_hil,
-                    size_t off_items, size_t item_cap) {
-      have = (cl->n && cl->have_bbox && cl->hil_pts.get() && (size_t)cl->n_wave_items <= item_cap) ? 1u : 0u;
-      if (!have) return;
-      fin = cl->n_finite; items = (uint64_t)cl->n_wave_items;
-      for (int a = 0; a < 3; ++a) { bmin[a] = cl->bmin[a]; bmax[a] = cl->bmax[a]; }
-      if (cl->n_finite) MM3D_HIP(hipMemcpyAsync(d + off_hil, cl->hil_pts.get(), cl->n_finite * 16, hipMemcpyDefault, ctx->stream));
-      if (cl->n_wave_items)
-        MM3D_HIP(hipMemcpyAsync(d + off_items, cl->wave_items.get(), (size_t)cl->n_wave_items * sizeof(int2), hipMemcpyDefault, ctx->stream));
-    };
-    DrainOnUnwind drain{ctx};                 // (`header` is read by the copy queued below)
-    side(m->points, h->p_finite, h->p_items, h->p_have, h->p_bmin, h->p_bmax, L.p_hil, L.p_items, L.p_item_cap);
-    side(m->keypoints, h->k_finite, h->k_items, h->k_have, h->k_bmin, h->k_bmax, L.k_hil, L.k_items, L.k_item_cap);
-    MM3D_HIP(hipMemcpyAsync(d, h, sizeof(*h), hipMemcpyDefault, ctx->stream));
-    if (m->points->n) MM3D_HIP(hipMemcpyAsync(d + L.pts, m->points->pts.get(), m->points->n * 16, hipMemcpyDefault, ctx->stream));
-    if (m->keypoints->n) MM3D_HIP(hipMemcpyAsync(d + L.kp, m->keypoints->pts.get(), m->keypoints->n * 16, hipMemcpyDefault, ctx->stream));
-    if (m->desc->n) MM3D_HIP(hipMemcpyAsync(d + L.desc, m->desc->data.get(), m->desc->n * (size_t)m->desc->dim * 4, hipMemcpyDefault, ctx->stream));
-    ctx->sync();
-    drain.armed = false;
-  });
-}
-
-// one received bundle -> a map in the source role, on context c (copies, a short wait for the 256-byte header and ONE for the rest; no kernel unless the owner sent no orders)
-static std::unique_ptr<mm3d_map> map_from_bundle(mm3d_ctx *c, const void *src, uint64_t n_points, uint64_t n_keypoints, int descriptor_type)
-{
-  const char *s = static_cast<const char *>(src);
-  const int dim = mm3d_descriptor_dim(descriptor_type);
-  const BundleLayout L = bundle_layout(n_points, n_keypoints, dim);
-  // (into ordinary memory: the pinned arena may wrap under cloud_host() below, and 256 bytes need no pinning)
-  BundleHeader header;
-  BundleHeader *h = &header;
-  std::memset(h, 0, sizeof(*h));
-  // the header first, blocking (256 bytes), and checked BEFORE the large copies are queued at sizes the caller supplied
-  if (s) {
-    MM3D_HIP(hipMemcpyAsync(h, s, sizeof(*h), hipMemcpyDefault, c->stream));
-    DrainOnUnwind drain{c};
-    c->sync();
-    drain.armed = false;
-    if (h->magic != kBundleMagic || h->n_points != n_points || h->n_keypoints != n_keypoints)
-      throw Error(MM3D_EINVAL, "mm3d_shard_unpack: not a bundle of this library version, or the sizes do not match it");
-  }
-  std::unique_ptr<mm3d_cloud> pts(cloud_from_memory(c, n_points ? s + L.pts : nullptr, n_points, 16, 12));
-  std::unique_ptr<mm3d_cloud> kp(cloud_from_memory(c, n_keypoints ? s + L.kp : nullptr, n_keypoints, 16, 12));
-  std::unique_ptr<mm3d_desc> desc(desc_from_memory(c, reinterpret_cast<const float *>(s ? s + L.desc : nullptr), n_keypoints, descriptor_type));
-  // the Hilbert parts at their full size (how much of them is meant is in the header, which arrives with the same wait)
-  struct Side { DevBuf<float4> hil; DevBuf<int2> items; };
-  auto grab = [&](uint64_t n, size_t off_hil, size_t off_items, size_t item_cap) {
-    Side sd;
-    if (!n || !s) return sd;
-    sd.hil = DevBuf<float4>(c, n);
-    sd.items = DevBuf<int2>(c, item_cap);
-    MM3D_HIP(hipMemcpyAsync(sd.hil.get(), s + off_hil, (size_t)n * 16, hipMemcpyDefault, c->stream));
-    MM3D_HIP(hipMemcpyAsync(sd.items.get(), s + off_items, item_cap * sizeof(int2), hipMemcpyDefault, c->stream));
-    return sd;
-  };
-  Side ps = grab(n_points, L.p_hil, L.p_items, L.p_item_cap), ks = grab(n_keypoints, L.k_hil, L.k_items, L.k_item_cap);
-  (void)cloud_host(c, kp.get());                      // (the host copy of the keypoints: this is the wait)
-  c->sync();
-  auto adopt = [&](mm3d_cloud *cl, Side &sd, uint32_t have, uint64_t fin, uint64_t items, const float *bmin, const float *bmax, size_t item_cap) {
-    if (!have || !cl->n || fin > cl->n || items > item_cap) return;
-    std::lock_guard<std::recursive_mutex> lk(cl->cache_mu);
-    cl->have_bbox = true;
-    cl->n_finite = (size_t)fin;
-    for (int a = 0; a < 3; ++a) { cl->bmin[a] = bmin[a]; cl->bmax[a] = bmax[a]; }
-    cl->hil_pts = std::move(sd.hil);
-    cl->wave_items = std::move(sd.items);
-    cl->n_wave_items = (int)items;
-  };
-  adopt(pts.get(), ps, h->p_have, h->p_finite, h->p_items, h->p_bmin, h->p_bmax, L.p_item_cap);
-  adopt(kp.get(), ks, h->k_have, h->k_finite, h->k_items, h->k_bmin, h->k_bmax, L.k_item_cap);
-  // (an owner that sent no orders -- an empty or all-NaN cloud -- leaves them to be built here, as before round 5)
-  if (pts->n) cloud_hilbert(c, pts.get());
-  if (kp->n) cloud_hilbert(c, kp.get());
-  c->sync();
-  return make_map(std::move(pts), std::move(kp), std::move(desc));
-}
-
-int mm3d_shard_unpack(mm3d_shard *sh, size_t map, const void *src, uint64_t n_points, uint64_t n_keypoints)
-{
-  if (!sh || map >= sh->n || (!src && (n_points || n_keypoints))) return MM3D_EINVAL;
-  if (sh->maps[map]) return MM3D_OK;               // an owned map is already here
-  mm3d_ctx *ctx = sh->ctx;
-  return guarded(ctx, [&] {
-    // source role only: the query orders of ICP / score and of SAC-IA's scoring, and the host copy of the
-    // keypoints that the rand() replay reads; target-side structures are the owner's business
-    sh->maps[map] = map_from_bundle(ctx, src, n_points, n_keypoints, sh->params.descriptor_type).release();
-  });
-}
-
-// every map another rank owns, on the context's streams (at 8 ranks that is 14 of 16 maps per rank)
-int mm3d_shard_unpack_many(mm3d_shard *sh, size_t count, const size_t *maps, const void *const *srcs, const uint64_t *n_points,
-                           const uint64_t *n_keypoints)
-{
-  if (!sh || (count && (!maps || !srcs || !n_points || !n_keypoints))) return MM3D_EINVAL;
-  mm3d_ctx *ctx = sh->ctx;
-  return guarded(ctx, [&] {
-    for (size_t k = 0; k < count; ++k)
-      if (maps[k] >= sh->n || (!srcs[k] && (n_points[k] || n_keypoints[k]))) throw Error(MM3D_EINVAL, "mm3d_shard_unpack_many: bad item");
-    std::atomic<size_t> next{0};
-    on_streams(ctx, [&](size_t, mm3d_ctx *c, const std::atomic<bool> &failed) {
-      for (;;) {
-        const size_t k = next.fetch_add(1);
-        if (k >= count || failed.load()) break;
-        const size_t i = maps[k];
-        if (sh->maps[i]) continue;                    // an owned map is already here
-        PrivateObjects priv(c);                       // nobody sees the map before this worker's waits
-        sh->maps[i] = map_from_bundle(c, srcs[k], n_points[k], n_keypoints[k], sh->params.descriptor_type).release();   // source role only, as in mm3d_shard_unpack; distinct slots
-      }
-    });
-  });
-}
-
-static void shard_pairs_impl(mm3d_shard *sh, mm3d_pair_result *pairs, unsigned char *mine, size_t capacity, size_t *n_pairs)
-{
-  mm3d_ctx *ctx = sh->ctx;
-  for (size_t i = 0; i < sh->n; ++i)
-    if (!sh->maps[i]) throw Error(MM3D_EINVAL, "mm3d_shard_pairs: a map has neither been computed here nor unpacked");
-  const mm3d_params *params = &sh->params;
-  // the live pairs in the reference's order, and the generator state before each of them (the draws of a pair
-  // depend on its source keypoints only: every rank replays the whole stream on the host, ~30 us per pair)
-  std::vector<std::pair<size_t, size_t>> live;
-  for (const auto &ij : all_pairs(sh->n))
-    if (sh->maps[ij.first]->keypoints->n > 0 && sh->maps[ij.second]->keypoints->n > 0) live.push_back(ij);
-  const size_t P = live.size();
-  *n_pairs = P;
-  if (P > capacity) throw Error(MM3D_ECAPACITY, "mm3d_shard_pairs: room for every live pair is needed");
-  // state_at[q] = the generator before pair q, advanced on demand (under rng_mu) as far as a worker needs it:
-  // the first pairs start at once, the table's tail (~30 us of host work per pair) is filled in while they run
-  std::vector<GlibcRand> state_at(P + 1, ctx->rnd);
-  size_t known_upto = 0;
-  std::mutex rng_mu;
-  std::vector<const std::vector<float4> *> src_kp(sh->n, nullptr);
-  for (size_t i = 0; i < sh->n; ++i) src_kp[i] = &cloud_host(ctx, sh->maps[i]->keypoints);   // (cached at prepare / unpack time)
-  auto advance_states = [&](size_t upto) {
-    std::lock_guard<std::mutex> lk(rng_mu);
-    while (known_upto < upto) {
-      GlibcRand r = state_at[known_upto];
-      pair_rand_replay(r, params->estimation_method, *src_kp[live[known_upto].first], params->inlier_threshold, params->max_iterations);
-      state_at[++known_upto] = r;
-    }
-  };
-  std::vector<size_t> todo;
-  for (size_t q = 0; q < P; ++q) {
-    std::memset(&pairs[q], 0, sizeof(mm3d_pair_result));
-    pairs[q].source_idx = live[q].first;
-    pairs[q].target_idx = live[q].second;
-    mine[q] = mm3d_shard_map_owner(live[q].second, sh->world) == sh->rank ? 1 : 0;
-    if (mine[q]) todo.push_back(q);
-  }
-  // batches of pairs with the same target (pairs_estimate_batch), at most kPairBatch of them and not so many that
-  // a stream runs dry: every map exists already, so the whole list can be cut up front
-  const size_t S = ctx->helpers.size() + 1;
-  const size_t take = pair_batch_take(todo.size(), S);
-  std::stable_sort(todo.begin(), todo.end(), [&](size_t a, size_t b) { return live[a].second < live[b].second; });
-  std::vector<std::pair<size_t, size_t>> batches;           // [first, last) into todo
-  for (size_t a = 0; a < todo.size();) {
-    size_t b = a + 1;
-    while (b < todo.size() && b - a < take && live[todo[b]].second == live[todo[a]].second) ++b;
-    batches.emplace_back(a, b);
-    a = b;
-  }
-  std::atomic<size_t> next{0};
-  on_streams(ctx, [&](size_t, mm3d_ctx *c, const std::atomic<bool> &failed) {
-    std::vector<PairWork> work;
-    for (;;) {
-      const size_t k = next.fetch_add(1);
-      if (k >= batches.size() || failed.load()) break;
-      work.clear();
-      for (size_t e = batches[k].first; e < batches[k].second; ++e) {
-        const size_t q = todo[e];
-        advance_states(q);
-        work.push_back(PairWork{sh->maps[live[q].first], sh->maps[live[q].second], &pairs[q], state_at[q]});
-      }
-      pairs_estimate_batch(c, work.data(), work.size(), params);
-    }
-  });
-  advance_states(P);
-  ctx->rnd = state_at[P];                       // where the reference's sequential loop leaves the generator
-}
-
-int mm3d_shard_pairs(mm3d_shard *sh, mm3d_pair_result *pairs, unsigned char *mine, size_t capacity, size_t *n_pairs)
-{
-  if (!sh || !n_pairs || !pairs || !mine) return MM3D_EINVAL;
-  return guarded(sh->ctx, [&] { shard_pairs_impl(sh, pairs, mine, capacity, n_pairs); });
-}
-
-void mm3d_shard_end(mm3d_shard *sh)
-{
-  if (!sh) return;
-  mm3d_ctx *ctx = sh->ctx;
-  {
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    (void)stream_wait(ctx->stream);
-    for (mm3d_ctx *h : ctx->helpers) (void)stream_wait(h->stream);
-  }
-  delete sh;
-}
-
-// the reference's two loops on ONE stream, in the reference's order (mm3d_set_streams(ctx, 1), the default)
-static void estimate_maps_sequential(mm3d_ctx *ctx, const mm3d_cloud_view *clouds, size_t n, const mm3d_params *params, float *out_T,
-                                     size_t *n_out, mm3d_pair_result *pairs_out, size_t *n_pairs_out)
-{
-  const auto t_start = std::chrono::steady_clock::now();
-  auto since_start = [&] { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count(); };
-  ctx->last_points.assign(n, 0);
-  ctx->last_keypoints.assign(n, 0);
-  std::vector<const mm3d_map *> maps(n, nullptr);       // every map of the call; those the map cache does not hold
-  std::vector<std::unique_ptr<mm3d_map>> owned(n);      // (mm3d_set_map_cache) are `owned`, and go when the call ends
-  MapCacheBase *const cache = ctx->map_cache;
-  for (size_t i = 0; i < n; ++i) {
-    std::unique_ptr<mm3d_cloud> raw = cloud_from_view(ctx, clouds[i]);
-    maps[i] = cache && raw->n > 0 ? cache->lookup(ctx, i, raw.get()) : nullptr;
-    if (!maps[i]) {
-      owned[i] = map_features_impl(ctx, raw.get(), params);
-      map_prepare_impl(ctx, owned[i].get(), params);      // search structures and k-NN target operands, once per map
-      maps[i] = owned[i].get();
-      if (cache && raw->n > 0) {                          // built from the same upload: the cache takes it and the map
-        cache->insert(i, std::move(raw), owned[i].get());
-        (void)owned[i].release();
-      }
-    }
-    ctx->last_points[i] = maps[i]->points->n;
-    ctx->last_keypoints[i] = maps[i]->keypoints->n;
-  }
-  ctx->last_features_s = since_start();
-  std::vector<mm3d_pair_result> pairs;
-  for (size_t i = 0; i + 1 < n; ++i)
-    for (size_t j = i + 1; j < n; ++j)
-      if (maps[i]->keypoints->n > 0 && maps[j]->keypoints->n > 0) {
-        mm3d_pair_result r;
-        std::memset(&r, 0, sizeof(r));
-        r.source_idx = i; r.target_idx = j;
-        pairs.push_back(r);
-      }
-  for (auto &r : pairs) {
-    const mm3d_map *ms = maps[r.source_idx], *mt = maps[r.target_idx];
-    if (cache && cache->pair_lookup(r.source_idx, r.target_idx, ctx->rnd, &r)) {
-      // reused: the generator still moves on by the draws the pair would have taken
-      pair_rand_replay(ctx->rnd, replay_method(ctx, params), cloud_host(ctx, ms->keypoints), params->inlier_threshold, params->max_iterations);
-      continue;
-    }
-    const GlibcRand r0 = ctx->rnd;
-    pair_estimate_impl(ctx, ms, mt, params, true, &r);
-    if (cache) cache->pair_insert(r.source_idx, r.target_idx, r0, r);
-  }
-  if (pairs_out) std::memcpy(pairs_out, pairs.data(), pairs.size() * sizeof(mm3d_pair_result));
-  if (n_pairs_out) *n_pairs_out = pairs.size();
-  int st = global_transforms(pairs.data(), pairs.size(), params->confidence_threshold, n, out_T, n_out);
-  if (st != MM3D_OK) throw Error(st, "computeGlobalTransforms failed");
-  ctx->last_total_s = since_start();
-}
-
-// ---------------------------------------------------------------- the same job on N devices of ONE process
-// estimateMapsTransforms behind the reference's own entry point on a device list (mm3d_create_devices): the reference's
-// caller is one process -- a ROS timer callback, R/src/map_merge_node.cpp:133-153 -- and cannot be relaunched under torchrun.
-// One host thread per device drives that device's root context and its streams through the mm3d_shard_* scheme:
-//   1. features of the maps the device owns (zig-zag ownership, shard_begin_impl) incl. their target-side structures;
-//   2. when every device is done, each PULLS the other maps' bundles and source-side structures from their owners with
-//      hipMemcpyPeerAsync (devices.cpp::cloud_clone_from_peer), dealt to its streams -- xGMI is point to point, every
-//      device reads from up to seven peers at once; nothing is recomputed (the multi-process form re-builds the Hilbert
-//      orders from the bundles: 2.3 ms per rank at N = 8);
-//   3. the pairs whose TARGET the device owns (shard_pairs_impl), every device replaying the reference's single rand() stream;
-//   4. ONE RCCL all-gather of the 104-byte pair records (devices.cpp::gather_pair_records), then the pose graph on the host.
-// Same bits as one device: the ownership only decides where a map or a pair is computed.
-namespace {
-bool devices_debug()
-{
-  static const bool dbg = [] { const char *e = getenv("MM3D_DEVICES_DEBUG"); return e && atoi(e); }();
-  return dbg;
-}
-// after a failed run: every stream of every device is drained before the shards (and their maps) go
-void drain_devices(const std::vector<mm3d_ctx *> &roots, int restore_device)
-{
-  for (mm3d_ctx *r : roots) {
-    (void)hipSetDevice(r->device);
-    (void)stream_wait(r->stream);
-    for (mm3d_ctx *h : r->helpers) (void)stream_wait(h->stream);
-  }
-  (void)hipSetDevice(restore_device);
-}
-// a barrier the device threads can leave through a failure: whoever throws releases the others, who then throw too
-struct FailBarrier {
-  std::mutex mu;
-  std::condition_variable cv;
-  size_t n, waiting = 0, generation = 0;
-  bool failed = false;
-  explicit FailBarrier(size_t n_) : n(n_) {}
-  void wait()
-  {
-    std::unique_lock<std::mutex> lk(mu);
-    if (failed) throw Error(MM3D_EDEVICE, "another device failed");
-    const size_t gen = generation;
-    if (++waiting == n) { waiting = 0; ++generation; cv.notify_all(); return; }
-    cv.wait(lk, [&] { return failed || generation != gen; });
-    if (failed) throw Error(MM3D_EDEVICE, "another device failed");
-  }
-  void fail()
-  {
-    std::lock_guard<std::mutex> lk(mu);
-    failed = true;
-    cv.notify_all();
-  }
-};
-}  // namespace
-
-// ---- one process, several devices --------------------------------------------------------------------------------------
-// What every device of a run shares on the host (one process: one address space).
-struct DevicesRun {
-  std::vector<mm3d_ctx *> roots;
-  size_t D = 0, n = 0;
-  std::vector<std::unique_ptr<mm3d_shard>> sh;            // per device: its own maps and its copies of the others'
-  std::vector<std::vector<mm3d_pair_result>> rec;         // per device, by live-pair number
-  std::vector<std::vector<unsigned char>> mine;
-  std::vector<size_t> np;
-  std::vector<double> t_feat, t_exch, t_pairs;
-  std::chrono::steady_clock::time_point t_start;
-  double since_start() const { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count(); }
-};
-
-// Round 5's form: three lock-step stages -- every device's features, barrier, every device pulls every other map, every
-// device replays the WHOLE rand() stream for itself and runs its pairs, barrier.  Kept as the fallback of the pipelined form
-// below (a map without keypoints falsifies its assumptions) and as its A/B (MM3D_DEVICES_STAGED=1).
-static void devices_run_staged(mm3d_ctx *ctx, DevicesRun &R, const mm3d_cloud_view *clouds, const mm3d_params *params, size_t max_pairs)
-{
-  std::vector<mm3d_ctx *> &roots = R.roots;
-  const size_t D = R.D, n = R.n;
-  FailBarrier bar(D);
-  std::mutex err_mu;
-  std::exception_ptr first_error;
-  for (size_t d = 1; d < D; ++d) roots[d]->rnd = ctx->rnd;        // every device replays the one rand() stream from the caller's state
-  auto body = [&](size_t d) {
-    mm3d_ctx *root = roots[d];
-    // (the peers are reached only through this call, which holds the first context's lock: theirs is taken for the helpers'
-    // sake of invariants only -- nothing else can be using them)
-    std::unique_lock<std::mutex> peer_lock;
-    if (d > 0) peer_lock = std::unique_lock<std::mutex>(root->mu);
-    try {
-      if (hipSetDevice(root->device) != hipSuccess) throw Error(MM3D_EDEVICE, "hipSetDevice failed");
-      R.sh[d].reset(shard_begin_impl(root, clouds, n, params, (int)d, (int)D));
-      R.t_feat[d] = R.since_start();
-      bar.wait();                                         // every owner's maps exist and its streams are drained
-      // the other devices' maps: bundle + source-side structures straight from the owner's memory, dealt to this device's streams
-      std::vector<size_t> theirs;
-      for (size_t i = 0; i < n; ++i)
-        if (!R.sh[d]->maps[i]) theirs.push_back(i);
-      std::atomic<size_t> next{0};
-      on_streams(root, [&](size_t, mm3d_ctx *c, const std::atomic<bool> &failed) {
-        for (;;) {
-          const size_t k = next.fetch_add(1);
-          if (k >= theirs.size() || failed.load()) break;
-          const size_t i = theirs[k];
-          const size_t o = (size_t)mm3d_shard_map_owner(i, (int)D);
-          // distinct slots; nobody reads another device's non-owned slots
-          R.sh[d]->maps[i] = pull_map_from_peer(c, R.sh[o]->maps[i], roots[o]->device).release();
-        }
-      });
-      R.t_exch[d] = R.since_start();
-      shard_pairs_impl(R.sh[d].get(), R.rec[d].data(), R.mine[d].data(), max_pairs, &R.np[d]);
-      R.t_pairs[d] = R.since_start();
-      if (devices_debug()) fprintf(stderr, "mm3d devices (staged): dev%zu features %.2f ms, pulls done %.2f ms, pairs done %.2f ms (its own replay of every pair inside)\n", d,
-                                   1e3 * R.t_feat[d], 1e3 * R.t_exch[d], 1e3 * R.t_pairs[d]);
-      // an owner's maps are read by its peers' pulls: nobody leaves (and nothing is freed) before everybody has pulled
-      bar.wait();
-    } catch (...) {
-      bar.fail();
-      std::lock_guard<std::mutex> lk(err_mu);
-      if (!first_error) first_error = std::current_exception();
-    }
-  };
-  {
-    std::vector<std::thread> threads;
-    for (size_t d = 1; d < D; ++d) threads.emplace_back(body, d);
-    body(0);
-    for (auto &t : threads) t.join();
-  }
-  (void)hipSetDevice(ctx->device);
-  if (first_error) {
-    drain_devices(roots, ctx->device);
-    std::rethrow_exception(first_error);
-  }
-}
-
-// Round 6: the same split -- features by owner, pairs by target owner, peer copies in between -- WITHOUT the lock-step and
-// WITHOUT D private replays of the rand() stream:
-//   * ONE table of generator states (state_at[q] = the state before pair q of the reference's loop), filled once by one host
-//     thread as the sources' keypoints appear (the draws of a pair depend on its source keypoints only) and read by every
-//     device.  Before, each device replayed all n (n - 1) / 2 pairs itself: 8.5 us x 2 016 pairs = 17 ms of serial host work
-//     per device on 64 x 50 k maps, the size of a device's whole pair stage at N = 8 ("host RNG replay dominates").
-//   * per-map readiness: a map is published (a flag under the run's mutex, behind its owner's full stream wait) the moment its
-//     owner has finished it; any device pulls it then (hipMemcpyPeerAsync on its own stream) and starts a pair as soon as the
-//     pair's two maps are on the device and the pair's state is in the table.  Only the end of the call waits for everybody
-//     (an owner's maps are read by its peers' pulls until then).
-// The table assumes that a target which does not exist yet will have keypoints (as estimate_maps_streams does); the
-// assumptions are checked when every map exists.  Returns false when one was wrong: the caller runs the staged form.
-static bool devices_run_pipelined(mm3d_ctx *ctx, DevicesRun &R, const mm3d_cloud_view *clouds, const mm3d_params *params)
-{
-  std::vector<mm3d_ctx *> &roots = R.roots;
-  const size_t D = R.D, n = R.n;
-  const std::vector<std::pair<size_t, size_t>> all = all_pairs(n);
-  const size_t P = all.size();
-  for (size_t d = 0; d < D; ++d) {
-    R.sh[d].reset(new mm3d_shard());
-    R.sh[d]->ctx = roots[d]; R.sh[d]->rank = (int)d; R.sh[d]->world = (int)D; R.sh[d]->n = n; R.sh[d]->params = *params;
-    R.sh[d]->maps.assign(n, nullptr);
-  }
-  std::mutex mu;                                          // guards everything below but the table
-  std::condition_variable cv;
-  std::vector<char> ready(n, 0);                          // map i is published by its owner
-  std::vector<std::vector<char>> pull_claimed(D, std::vector<char>(n, 0)), have(D, std::vector<char>(n, 0));
-  std::vector<char> claimed(P, 0);
-  std::vector<std::vector<size_t>> own_maps(D), todo(D);  // per device: the maps it owns; the pairs whose target it owns
-  std::vector<size_t> next_own(D, 0);
-  for (size_t i = 0; i < n; ++i) own_maps[(size_t)mm3d_shard_map_owner(i, (int)D)].push_back(i);
-  for (size_t q = 0; q < P; ++q) todo[(size_t)mm3d_shard_map_owner(all[q].second, (int)D)].push_back(q);
-  bool abort = false;
-  std::exception_ptr first_error;
-  std::vector<mm3d_pair_result> rec_all(P);
-  std::vector<char> done(P, 0);
-  // the table
-  std::vector<GlibcRand> state_at(P + 1, ctx->rnd);
-  std::vector<char> assumed_live(P, 0);
-  std::atomic<size_t> known_upto{0};                      // state_at[0 .. known_upto] are final
-  double fill_busy_s = 0.0, fill_done_s = 0.0;            // (the filler thread's alone until it is joined)
-  auto fill_table = [&] {
-    try {
-      for (size_t q = 0; q < P; ++q) {
-        const size_t a = all[q].first, b = all[q].second;
-        const mm3d_map *ma = nullptr;
-        bool live = false;
-        {
-          std::unique_lock<std::mutex> lk(mu);
-          cv.wait(lk, [&] { return abort || ready[a]; });
-          if (abort) return;
-          ma = R.sh[(size_t)mm3d_shard_map_owner(a, (int)D)]->maps[a];
-          live = ma->keypoints->n > 0;
-          if (live) {
-            if (ready[b]) live = R.sh[(size_t)mm3d_shard_map_owner(b, (int)D)]->maps[b]->keypoints->n > 0;
-            else assumed_live[q] = 1;
-          }
-        }
-        GlibcRand r = state_at[q];
-        const auto tb = std::chrono::steady_clock::now();
-        // (the host copy of an owner's keypoints was made when the map was prepared: no device is touched here)
-        if (live) pair_rand_replay(r, params->estimation_method, cloud_host(roots[(size_t)mm3d_shard_map_owner(a, (int)D)], ma->keypoints),
-                                   params->inlier_threshold, params->max_iterations);
-        fill_busy_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - tb).count();
-        fill_done_s = R.since_start();
-        state_at[q + 1] = r;
-        known_upto.store(q + 1, std::memory_order_release);
-        if ((q & 7) == 7 || q + 1 == P) { std::lock_guard<std::mutex> lk(mu); cv.notify_all(); }
-      }
-    } catch (...) {
-      std::lock_guard<std::mutex> lk(mu);
-      if (!first_error) first_error = std::current_exception();
-      abort = true;
-      cv.notify_all();
-    }
-  };
-  auto device_body = [&](size_t d) {
-    mm3d_ctx *root = roots[d];
-    std::unique_lock<std::mutex> peer_lock;
-    if (d > 0) peer_lock = std::unique_lock<std::mutex>(root->mu);
-    const size_t S = root->helpers.size() + 1;
-    try {
-      if (hipSetDevice(root->device) != hipSuccess) throw Error(MM3D_EDEVICE, "hipSetDevice failed");
-      on_streams(root, [&](size_t, mm3d_ctx *c, const std::atomic<bool> &failed) {
-        // 1. this device's own maps, in index order
-        for (;;) {
-          size_t i;
-          {
-            std::lock_guard<std::mutex> lk(mu);
-            if (abort || failed.load() || next_own[d] >= own_maps[d].size()) break;
-            i = own_maps[d][next_own[d]++];
-          }
-          std::unique_ptr<mm3d_cloud> raw = cloud_from_view(c, clouds[i]);
-          // this device is the map's target-side owner; the build ends in a full wait: the map is complete in this device's
-          // memory BEFORE anybody is told
-          std::unique_ptr<mm3d_map> held = build_private_map(c, raw.get(), params);
-          raw.reset();
-          {
-            std::lock_guard<std::mutex> lk(mu);
-            R.sh[d]->maps[i] = held.release();
-            have[d][i] = 1;
-            ready[i] = 1;
-            R.t_feat[d] = std::max(R.t_feat[d], R.since_start());
-          }
-          cv.notify_all();
-        }
-        // 2. pulls and pairs, whatever can start
-        std::vector<size_t> batch;
-        std::vector<PairWork> work;
-        for (;;) {
-          size_t pull = n;
-          batch.clear();
-          {
-            std::unique_lock<std::mutex> lk(mu);
-            for (;;) {
-              if (abort || failed.load()) return;
-              // a published map this device does not hold yet: first, it unlocks pairs
-              for (size_t i = 0; i < n && pull == n; ++i)
-                if (ready[i] && !have[d][i] && !pull_claimed[d][i]) pull = i;
-              if (pull != n) { pull_claimed[d][pull] = 1; break; }
-              // pairs of this device whose two maps are here and whose state is in the table: a batch shares its target
-              const size_t known = known_upto.load(std::memory_order_acquire);
-              size_t avail = 0, left = 0;
-              for (size_t q : todo[d]) {
-                if (claimed[q]) continue;
-                ++left;
-                if (q <= known && have[d][all[q].first] && have[d][all[q].second]) ++avail;
-              }
-              if (avail) {
-                const size_t take = pair_batch_take(avail, S);
-                size_t target = n;
-                for (size_t q : todo[d]) {
-                  if (batch.size() >= take) break;
-                  if (claimed[q] || q > known || !have[d][all[q].first] || !have[d][all[q].second]) continue;
-                  if (target != n && all[q].second != target) continue;
-                  target = all[q].second;
-                  claimed[q] = 1;
-                  batch.push_back(q);
-                }
-                break;
-              }
-              bool pulls_left = false;
-              for (size_t i = 0; i < n; ++i) pulls_left = pulls_left || (!have[d][i] && !pull_claimed[d][i]);
-              if (!left && !pulls_left) return;           // nothing more for this worker, ever
-              cv.wait(lk);
-            }
-          }
-          if (pull != n) {
-            const size_t o = (size_t)mm3d_shard_map_owner(pull, (int)D);
-            // (the owner's copy is published: complete, and not freed before every thread has joined)
-            std::unique_ptr<mm3d_map> m = pull_map_from_peer(c, R.sh[o]->maps[pull], roots[o]->device);
-            {
-              std::lock_guard<std::mutex> lk(mu);
-              R.sh[d]->maps[pull] = m.release();
-              have[d][pull] = 1;
-              R.t_exch[d] = std::max(R.t_exch[d], R.since_start());
-            }
-            cv.notify_all();
-            continue;
-          }
-          work.clear();
-          for (size_t q : batch) {
-            const mm3d_map *ms = R.sh[d]->maps[all[q].first], *mt = R.sh[d]->maps[all[q].second];
-            if (ms->keypoints->n > 0 && mt->keypoints->n > 0) {
-              rec_all[q].source_idx = all[q].first;
-              rec_all[q].target_idx = all[q].second;
-              work.push_back(PairWork{ms, mt, &rec_all[q], state_at[q]});
-              done[q] = 1;                                // (distinct q per worker; read after the joins)
-            }
-          }
-          if (!work.empty()) pairs_estimate_batch(c, work.data(), work.size(), params);
-          { std::lock_guard<std::mutex> lk(mu); R.t_pairs[d] = std::max(R.t_pairs[d], R.since_start()); }
-        }
-      });
-    } catch (...) {
-      std::lock_guard<std::mutex> lk(mu);
-      if (!first_error) first_error = std::current_exception();
-      abort = true;
-      cv.notify_all();
-    }
-  };
-  {
-    std::thread filler(fill_table);
-    std::vector<std::thread> threads;
-    for (size_t d = 1; d < D; ++d) threads.emplace_back(device_body, d);
-    device_body(0);
-    for (auto &t : threads) t.join();
-    { std::lock_guard<std::mutex> lk(mu); if (first_error) abort = true; }
-    cv.notify_all();
-    filler.join();
-  }
-  (void)hipSetDevice(ctx->device);
-  if (first_error) {
-    drain_devices(roots, ctx->device);
-    std::rethrow_exception(first_error);
-  }
-  if (devices_debug()) {
-    fprintf(stderr, "mm3d devices (pipelined): %zu devices, %zu maps, %zu pairs; ONE rand() table: %.2f ms of replay on one host thread, complete %.2f ms into the call "
-            "(0 ms of replay on the devices' threads);", D, n, P, 1e3 * fill_busy_s, 1e3 * fill_done_s);
-    for (size_t d = 0; d < D; ++d) fprintf(stderr, " dev%zu last map %.2f last pull %.2f last pair %.2f ms;", d, 1e3 * R.t_feat[d], 1e3 * R.t_exch[d], 1e3 * R.t_pairs[d]);
-    fprintf(stderr, "\n");
-  }
-  // every map exists: were the table's assumptions right?
-  for (size_t q = 0; q < P; ++q)
-    if (assumed_live[q] && R.sh[0]->maps[all[q].second]->keypoints->n == 0) return false;
-  ctx->rnd = state_at[P];                                 // where the reference's sequential loop leaves the generator
-  // the live pairs in the reference's order, per executing device (what the gather sends)
-  size_t nl = 0;
-  for (size_t q = 0; q < P; ++q) {
-    if (!done[q]) continue;
-    const size_t d = (size_t)mm3d_shard_map_owner(all[q].second, (int)D);
-    for (size_t e = 0; e < D; ++e) {
-      R.rec[e][nl] = mm3d_pair_result{};
-      R.rec[e][nl].source_idx = all[q].first; R.rec[e][nl].target_idx = all[q].second;
-      R.mine[e][nl] = e == d ? 1 : 0;
-    }
-    R.rec[d][nl] = rec_all[q];
-    ++nl;
-  }
-  for (size_t d = 0; d < D; ++d) R.np[d] = nl;
-  return true;
-}
-
-static void estimate_maps_devices(mm3d_ctx *ctx, const mm3d_cloud_view *clouds, size_t n, const mm3d_params *params, float *out_T,
-                                  size_t *n_out, mm3d_pair_result *pairs_out, size_t *n_pairs_out)
-{
-  std::vector<mm3d_ctx *> roots{ctx};
-  roots.insert(roots.end(), ctx->peers.begin(), ctx->peers.end());
-  const size_t D = roots.size();
-  const size_t max_pairs = n * (n - 1) / 2;
-  if (D == 1) {
-    // a list of one device: nothing to shard, so the job runs as on a plain context (pipelined over the streams, not in
-    // barriered stages) -- and its pair records still travel through the communicator's all-gather (a world of one), so that
-    // the collective of the path is exercised wherever a device list is used
-    std::vector<mm3d_pair_result> local(std::max<size_t>(max_pairs, 1));
-    size_t np = 0;
-    if (!ctx->helpers.empty()) estimate_maps_streams(ctx, clouds, n, params, out_T, n_out, local.data(), &np);
-    else estimate_maps_sequential(ctx, clouds, n, params, out_T, n_out, local.data(), &np);
-    const double t_before = ctx->last_total_s;
-    std::vector<std::vector<mm3d_pair_result>> send(1);
-    send[0].assign(local.begin(), local.begin() + (ptrdiff_t)np);
-    std::vector<mm3d_pair_result> gathered;
-    ctx->last_gather_s = gather_pair_records(ctx->device_set, roots, send, np, gathered);
-    ctx->last_exchange_s = ctx->last_features_s;
-    ctx->last_pairs_s = t_before;
-    if (pairs_out && np) std::memcpy(pairs_out, gathered.data(), np * sizeof(mm3d_pair_result));
-    if (n_pairs_out) *n_pairs_out = np;
-    const int st = global_transforms(gathered.data(), np, params->confidence_threshold, n, out_T, n_out);   // (from what the gather delivered)
-    if (st != MM3D_OK) throw Error(st, "computeGlobalTransforms failed");
-    ctx->last_total_s = t_before + ctx->last_gather_s;
-    return;
-  }
-  DevicesRun R;
-  R.roots = roots; R.D = D; R.n = n;
-  R.sh.resize(D);
-  R.rec.assign(D, std::vector<mm3d_pair_result>(max_pairs));
-  R.mine.assign(D, std::vector<unsigned char>(max_pairs, 0));
-  R.np.assign(D, 0);
-  R.t_feat.assign(D, 0.0); R.t_exch.assign(D, 0.0); R.t_pairs.assign(D, 0.0);
-  R.t_start = std::chrono::steady_clock::now();
-  static const bool staged_only = [] { const char *e = getenv("MM3D_DEVICES_STAGED"); return e && atoi(e); }();
-  const GlibcRand rnd0 = ctx->rnd;
-  bool ran = false;
-  if (!staged_only) {
-    ran = devices_run_pipelined(ctx, R, clouds, params);
-    if (!ran) {                                           // a map without keypoints: the table was positioned wrongly after it
-      for (size_t d = 0; d < D; ++d) { (void)hipSetDevice(roots[d]->device); R.sh[d].reset(); }
-      (void)hipSetDevice(ctx->device);
-      ctx->rnd = rnd0;
-    }
-  }
-  if (!ran) devices_run_staged(ctx, R, clouds, params, max_pairs);
-  ctx->last_points.assign(n, 0);
-  ctx->last_keypoints.assign(n, 0);
-  for (size_t i = 0; i < n; ++i) {
-    ctx->last_points[i] = R.sh[0]->maps[i]->points->n;
-    ctx->last_keypoints[i] = R.sh[0]->maps[i]->keypoints->n;
-  }
-  ctx->last_features_s = *std::max_element(R.t_feat.begin(), R.t_feat.end());
-  ctx->last_exchange_s = *std::max_element(R.t_exch.begin(), R.t_exch.end());
-  ctx->last_pairs_s = *std::max_element(R.t_pairs.begin(), R.t_pairs.end());
-  // the gather: rank d sends the records of its own pairs, in pair order, padded to the largest rank's count
-  const size_t P = R.np[0];
-  for (size_t d = 1; d < D; ++d)
-    if (R.np[d] != P) throw Error(MM3D_EDEVICE, "estimate_maps_devices: the devices disagree on the live pairs");
-  std::vector<std::vector<mm3d_pair_result>> send(D);
-  std::vector<std::vector<size_t>> which(D);
-  for (size_t d = 0; d < D; ++d)
-    for (size_t q = 0; q < P; ++q)
-      if (R.mine[d][q]) { send[d].push_back(R.rec[d][q]); which[d].push_back(q); }
-  size_t slots = 0;
-  for (size_t d = 0; d < D; ++d) slots = std::max(slots, send[d].size());
-  std::vector<mm3d_pair_result> gathered;
-  ctx->last_gather_s = gather_pair_records(ctx->device_set, roots, send, slots, gathered);
-  std::vector<mm3d_pair_result> pairs(P);
-  std::vector<char> seen(P, 0);
-  for (size_t d = 0; d < D; ++d)
-    for (size_t k = 0; k < which[d].size(); ++k) {
-      pairs[which[d][k]] = gathered[d * slots + k];
-      seen[which[d][k]] = 1;
-    }
-  for (size_t q = 0; q < P; ++q)
-    if (!seen[q]) throw Error(MM3D_EDEVICE, "estimate_maps_devices: a pair has no owner");
-  // the shards (maps on every device) go now; every stream was drained by its device's thread
-  for (size_t d = 0; d < D; ++d) {
-    (void)hipSetDevice(roots[d]->device);
-    R.sh[d].reset();
-  }
-  (void)hipSetDevice(ctx->device);
-  if (pairs_out) std::memcpy(pairs_out, pairs.data(), pairs.size() * sizeof(mm3d_pair_result));
-  if (n_pairs_out) *n_pairs_out = pairs.size();
-  const int st = global_transforms(pairs.data(), pairs.size(), params->confidence_threshold, n, out_T, n_out);
-  if (st != MM3D_OK) throw Error(st, "computeGlobalTransforms failed");
-  ctx->last_total_s = R.since_start();
 }
 
 // ---------------------------------------------------------------- map_merging.h

@@ -2,7 +2,7 @@
 //
 // The reference's caller is ONE process (R/src/map_merge_node.cpp:133-153 calls estimateMapsTransforms from a timer callback;
 // R/src/map_merge_tool.cpp:37-38 from main), so the N-GPU form of the path has to live behind that one call:
-// capi.cpp::estimate_maps_devices runs the mm3d_shard_* scheme with one host thread + stream set per device, and this file
+// driver_devices.cpp::estimate_maps_devices runs the mm3d_shard_* scheme with one host thread + stream set per device, and this file
 // holds the two exchanges between the devices:
 //   * the maps' bundles (filtered cloud, keypoints, descriptors, and the source-side search structures built on them) are
 //     PULLED by every device that does not own the map with hipMemcpyPeerAsync -- point-to-point over xGMI, each device

@@ -1,7 +1,7 @@
 // runtime.cpp -- the host-only runtime of the library: the reference-counted device-memory pool, a context's waits
 // (stream_wait: poll + nap instead of spinning), its pinned arena, the deferred device-side error checks, the kernel
-// profiling scopes and the bookkeeping of the chained scans.  No kernel lives here, so this file -- with capi.cpp,
-// host_pipeline.cpp and linalg.cpp -- is what the host sanitizer build compiles for real (tests/host_san: a fake HIP runtime
+// profiling scopes and the bookkeeping of the chained scans.  No kernel lives here, so this file -- with the others of
+// host_sources.sh (capi.cpp, the drivers, host_pipeline.cpp, linalg.cpp) -- is what the host sanitizer build compiles for real (tests/host_san: a fake HIP runtime
 // and a fake device layer stand in for everything below it; ThreadSanitizer / AddressSanitizer + UBSan).
 #include <hip/hip_runtime.h>
 

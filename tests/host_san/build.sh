@@ -1,5 +1,6 @@
 #!/bin/bash
-# Builds the library's host code -- runtime.cpp, capi.cpp, host_pipeline.cpp, linalg.cpp, devices.cpp, unchanged -- with a sanitizer against
+# Builds the library's host code -- the files of map-merge_amd/csrc/host_sources.sh (runtime.cpp, the extern "C" boundary capi.cpp,
+# pair_estimate.cpp, the driver_*.cpp, host_pipeline.cpp, linalg.cpp, devices.cpp), unchanged -- with a sanitizer against
 # the fake HIP runtime and the fake device layer of this directory, into tests/host_san/_build/san_<kind> (git-ignored):
 #   tests/host_san/build.sh thread | address
 # clang's host pass of the HIP language (--cuda-host-only): the headers' __device__ helpers are parsed, never emitted.
@@ -10,10 +11,11 @@ CSRC=../../map-merge_amd/csrc
 CLANG=${CLANG:-/opt/rocm/lib/llvm/bin/clang++}
 [ "$KIND" = thread ] && SAN="-fsanitize=thread" || SAN="-fsanitize=address,undefined -fno-sanitize-recover=undefined"
 FLAGS="-x hip --cuda-host-only -nogpulib -std=c++17 -O1 -g -fno-omit-frame-pointer -ffp-contract=off -I/opt/rocm/include -I$CSRC -Wno-unused-function -Wno-option-ignored -Wno-unused-command-line-argument $SAN"
+. $CSRC/host_sources.sh
 mkdir -p _build
 objs=""
 pids=()
-for f in $CSRC/runtime.cpp $CSRC/capi.cpp $CSRC/host_pipeline.cpp $CSRC/linalg.cpp $CSRC/devices.cpp fake_hip.cpp fake_rccl.cpp fake_device.cpp san_main.cpp; do
+for f in $(printf "$CSRC/%s " $MM3D_HOST_SOURCES) fake_hip.cpp fake_rccl.cpp fake_device.cpp san_main.cpp; do
   o=_build/$(basename "${f%.*}")_$KIND.o
   objs="$objs $o"
   ( $CLANG $FLAGS -c "$f" -o "$o" ) &

@@ -1,6 +1,6 @@
 // fake_device.cpp -- TEST INFRASTRUCTURE: host stand-ins for every stage entry point that lives in a .hip file (types.hpp),
 // so that the library's HOST code -- the stream scheduler of mm3d_estimate_maps_transforms, the shard driver, the rand()
-// state table, the SAC-IA / RANSAC replays, the pose graph, the pool and the waits (capi.cpp, host_pipeline.cpp, linalg.cpp,
+// state table, the SAC-IA / RANSAC replays, the pose graph, the pool and the waits (capi.cpp, pair_estimate.cpp, the driver_*.cpp, host_pipeline.cpp, linalg.cpp,
 // runtime.cpp, compiled for real) -- runs under ThreadSanitizer and AddressSanitizer + UBSan without a GPU
 // (tests/test_host_sanitizers.py).  The stages compute cheap deterministic placeholders of the right
 // shapes; their numbers mean nothing, only that they depend on nothing but their inputs -- which lets the driver check that

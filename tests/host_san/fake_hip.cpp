@@ -1,5 +1,5 @@
 // fake_hip.cpp -- TEST INFRASTRUCTURE: a host stand-in for the HIP runtime entry points the library's host code calls, so
-// that runtime.cpp / capi.cpp / host_pipeline.cpp / linalg.cpp run under ThreadSanitizer and AddressSanitizer in a
+// that runtime.cpp / capi.cpp and the drivers / host_pipeline.cpp / linalg.cpp run under ThreadSanitizer and AddressSanitizer in a
 // container without a GPU (tests/test_host_sanitizers.py).  "Device" memory is host memory, streams execute at once on
 // the calling thread.  Nothing here is part of the product; the product links libamdhip64.
 #include <hip/hip_runtime.h>

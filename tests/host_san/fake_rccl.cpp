@@ -1,5 +1,5 @@
 // fake_rccl.cpp -- TEST INFRASTRUCTURE: a host stand-in for the six RCCL entry points devices.cpp calls, so that the
-// multi-device driver (capi.cpp::estimate_maps_devices, devices.cpp::gather_pair_records, compiled for real) runs under
+// multi-device driver (driver_devices.cpp::estimate_maps_devices, devices.cpp::gather_pair_records, compiled for real) runs under
 // ThreadSanitizer and AddressSanitizer without a GPU.  The single-process form only: every rank's ncclAllGather is enqueued
 // inside one ncclGroupStart / ncclGroupEnd pair on one thread and executed at the group's end ("device" memory is host
 // memory, fake_hip.cpp).  Like RCCL, ncclCommInitAll refuses a device twice.  Nothing here is part of the product.

@@ -1,5 +1,5 @@
 // fake_digest.cpp -- TEST INFRASTRUCTURE: a host stand-in for map_cache.hip's cloud_digest_compare (types.hpp), so that the
-// map cache (map_cache.cpp) and the drivers that use it (capi.cpp) run under the sanitizers on tests/host_san's fake device
+// map cache (map_cache.cpp) and the drivers that use it (driver_streams.cpp) run under the sanitizers on tests/host_san's fake device
 // layer, where "device" memory is host memory.  Nothing here is product code.
 #include <cstring>
 

@@ -1,8 +1,9 @@
 """The library's HOST code under ThreadSanitizer and under AddressSanitizer + UndefinedBehaviourSanitizer.
 
-runtime.cpp (pool, waits, profiling scopes), capi.cpp (the stream scheduler of mm3d_estimate_maps_transforms with its worker
-threads and rand() state table, the shard driver, params / enums / error paths), host_pipeline.cpp (RANSAC / SAC-IA replays,
-pair driver, pose graph) and linalg.cpp are compiled UNCHANGED by clang's host pass with the sanitizer on and linked against a
+runtime.cpp (pool, waits, profiling scopes), capi.cpp (params / enums / error paths), pair_estimate.cpp (map builders, pair
+batches), driver_streams.cpp (the stream scheduler of mm3d_estimate_maps_transforms with its worker threads and rand() state
+table), driver_shard.cpp (the shard driver), driver_devices.cpp (the device-list driver), host_pipeline.cpp (RANSAC / SAC-IA
+replays, pair driver, pose graph), linalg.cpp and devices.cpp -- the list of map-merge_amd/csrc/host_sources.sh -- are compiled UNCHANGED by clang's host pass with the sanitizer on and linked against a
 fake HIP runtime and a fake device layer (tests/host_san/: "device" memory is host memory, every stage returns a cheap
 deterministic placeholder).  The driver (tests/host_san/san_main.cpp) runs whole jobs on 1, 3, 5, 8 and 16 streams and on a
 world of three emulated ranks and requires identical bits, plus the degenerate inputs of the reference's gtests

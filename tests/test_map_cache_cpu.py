@@ -1,5 +1,5 @@
 """The map cache of mm3d_estimate_maps_transforms (mm3d_set_map_cache) without a GPU: its four entry points are declared and
-exported and behave on a NULL context, and the cache's HOST code -- map_cache.cpp and the drivers in capi.cpp that use it --
+exported and behave on a NULL context, and the cache's HOST code -- map_cache.cpp and the drivers that use it (driver_streams.cpp) --
 runs under ThreadSanitizer and AddressSanitizer + UBSan on the fake HIP runtime and fake device layer of tests/host_san
 (tests/host_san_cache: repeats, changed, reordered and evicted maps, parameter changes, SAC_IA with and without srand, calls
 that fail half-way; every call bit-equal to a plain context, the counters exact)."""
