@@ -45,6 +45,30 @@ inline mm3d_keypoint_options parse_keypoints(const char *value)
   o.source = MM3D_KEYPOINTS_UNIFORM;
   return o;
 }
+// MM3D_REFINE=ndt or ndt:<resolution in metres>: the estimation context's pair stage refines with NDT in the ICP's place
+// (mm3d_set_refinement; without a resolution, the library's default multiple of params.resolution; the other options keep
+// mm3d_refine_options_default's values); icp or unset keeps the ICP that MM3D_ICP selects.  Anything else throws.
+inline mm3d_refine_options parse_refine(const char *value)
+{
+  mm3d_refine_options o;
+  o.method = MM3D_REFINE_ICP;
+  o.resolution = 0.0;
+  o.neighbours = 7;
+  o.min_points = 6;
+  o.regularisation = 0.01;
+  const std::string v = value ? value : "";
+  if (v.empty() || v == "icp") return o;
+  bool ok = v.compare(0, 3, "ndt") == 0 && (v.size() == 3 || v[3] == ':');
+  if (ok && v.size() > 3) {
+    const char *s = v.c_str() + 4;
+    char *end = nullptr;
+    o.resolution = std::strtod(s, &end);
+    ok = end != s && *end == '\0' && std::isfinite(o.resolution) && o.resolution > 0.0;
+  }
+  if (!ok) throw std::runtime_error("mm3d: MM3D_REFINE must be icp, ndt or ndt:<resolution in metres>, not '" + v + "'");
+  o.method = MM3D_REFINE_NDT;
+  return o;
+}
 }  // namespace mm3d_shim
 }  // namespace map_merge_3d
 
@@ -126,8 +150,12 @@ inline mm3d_ctx *ctx()
   // MM3D_ALIGN=prerejective: under SAC_IA the pair stage's initial alignment is the prerejective one (mm3d_set_alignment), with
   // MM3D_ALIGN_SAMPLES=<draws> if given; sac_ia or unset keeps the reference's.  Not available on a device list either.
   // MM3D_KEYPOINTS=uniform[:<leaf>]: parse_keypoints above; it works on a device list too.
+  // MM3D_REFINE=ndt[:<resolution>]: parse_refine above.  Not available on a device list: ndt with MM3D_DEVICES set as well throws.
   static mm3d_ctx *c = [] {
     const mm3d_keypoint_options keypoints = parse_keypoints(std::getenv("MM3D_KEYPOINTS"));
+    mm3d_refine_options refine = parse_refine(std::getenv("MM3D_REFINE"));
+    if (refine.method == MM3D_REFINE_NDT && std::getenv("MM3D_DEVICES") && *std::getenv("MM3D_DEVICES"))
+      throw std::runtime_error("mm3d: MM3D_REFINE=ndt is not available with MM3D_DEVICES (a device list carries no voxel tables)");
     const char *al = std::getenv("MM3D_ALIGN");
     const std::string align = al ? al : "";
     if (!align.empty() && align != "sac_ia" && align != "prerejective")
@@ -159,6 +187,8 @@ inline mm3d_ctx *ctx()
     }
     if (keypoints.source != MM3D_KEYPOINTS_REFERENCE && mm3d_set_keypoints(e, &keypoints) != MM3D_OK)
       throw std::runtime_error("mm3d: MM3D_KEYPOINTS was refused (the leaf must be a positive float with a finite reciprocal)");
+    if (refine.method != MM3D_REFINE_ICP && mm3d_set_refinement(e, &refine) != MM3D_OK)
+      throw std::runtime_error("mm3d: MM3D_REFINE was refused (the resolution must be a positive float with a finite reciprocal)");
     return e;
   }();
   return c;

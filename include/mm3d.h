@@ -354,6 +354,58 @@ void mm3d_keypoint_options_default(mm3d_keypoint_options *o);     /* source MM3D
  * value is checked whatever the source). */
 int mm3d_set_keypoints(mm3d_ctx *ctx, const mm3d_keypoint_options *options);
 int mm3d_get_keypoints(const mm3d_ctx *ctx, mm3d_keypoint_options *options);        /* MM3D_EINVAL for NULL */
+/* What refines a pair's initial estimate where params.refine_transform is set (off the reference's path; MM3D_REFINE_ICP by
+ * default: the ICP that mm3d_set_icp_method selects, which mm3d_get_icp_method keeps answering whatever the refinement is).
+ * MM3D_REFINE_NDT runs the Normal Distributions Transform in the ICP's place: a Gauss-Newton form of point-to-distribution
+ * NDT (Biber & Strasser 2003; Magnusson 2009).  The target is summarised once per map as one Gaussian per voxel, and a source
+ * point finds its terms by computing an index: no search, and a cost per iteration that does not grow with the target's
+ * density.  The voxel side sets the basin of convergence; max_correspondence_distance is not read by it.  No parity with
+ * pcl::NormalDistributionsTransform is claimed: PCL clamps the covariance's eigenvalues, mixes in the d1 / d2 outlier
+ * constants and steps by a More-Thuente line search; none of that is here (audit row 16b).
+ *   Voxel table of the target.  r_f = (float)resolution, inv = 1.0f / r_f.  The voxel of a finite point is
+ *   (floorf(x * inv), floorf(y * inv), floorf(z * inv)) on the GLOBAL lattice anchored at the origin, as in
+ *   mm3d_uniform_keypoints; non-finite points belong to no voxel.  Per voxel with count >= min_points, everything in double
+ *   over the voxel's points in ascending input index (position l of that order goes to partial sum l mod 64, each partial
+ *   ascending, and the 64 partials are added by a fixed tree): the mean mu; the covariance
+ *   S = sum (p - mu)(p - mu)^T / (count - 1), two-pass; S' = S + regularisation * (trace S / 3) * I; P = S'^-1 by the
+ *   closed-form adjugate.  mu and P are rounded to float once.  The voxel has no Gaussian when count < min_points, when
+ *   trace S is not > 0, or when anything is not finite.
+ *   One iteration.  For every finite source point, s = the point transformed by the current float T (the ICP's float rule).
+ *   For its own voxel -- and, with neighbours = 7, the six face neighbours -- where that voxel has a Gaussian, in double:
+ *   q = s - mu, m = q^T P q, w = exp(-m / 2); a term whose m is not finite adds nothing.  With J = [-[s]x | I] (the
+ *   parametrisation of the point-to-plane row), H = sum w J^T P J, g = -sum w J^T P q, sum w, the number of terms and the
+ *   number of points with at least one term are summed in double in a fixed order (per point first: J^T (sum w P) J and
+ *   -J^T (sum w P q)).  H x = g is solved by point-to-plane's unpivoted LDLt with its degeneracy rule: a pivot at or below
+ *   1e-12 * trace H / 6, or fewer than 6 terms, stops the loop, not converged, with T unchanged.  Tinc = [Rz(x2) Ry(x1) Rx(x0) |
+ *   x3 x4 x5], T <- Tinc * T in float, then DefaultConvergenceCriteria's three tests as the ICP runs them, with
+ *   F = sum w / (number of finite source points) in the place of the mean d2.
+ *   - Applies to the refinement of mm3d_estimate_maps_transforms (one stream or many, with or without the map cache) and of
+ *     mm3d_pair_estimate.  In the pair record icp_iterations is NDT's iteration count, icp_correspondences the number of
+ *     source points that had at least one term in the last iteration, and confidence stays the point-to-point transformScore.
+ *     mm3d_last_icp_iterations / mm3d_last_icp_converged report on NDT runs.
+ *   - resolution > 0: the voxel side in metres; 0: 10 * params.resolution (DESIGN.md section 7e has the measurement).
+ *   - mm3d_map_prepare builds a map's table on an NDT context; a pair whose target has none, or one of other options, builds
+ *     it on first use.  Memory: 48 B per occupied voxel plus 4 B per cell of the voxel bounding box of the finite points,
+ *     cached maps included.  Size limit: that box may hold at most 2^26 cells (MM3D_EUNSUPPORTED from the call beyond it).
+ *   - The setting reaches the context's mm3d_set_streams helpers in either order of the two calls.  Results are bit-identical
+ *     for every stream count, batch, split and cache setting, and through mm3d_estimate_transform_ndt from the same guess.
+ *   - The map cache's pair key holds the method and, under NDT, its four options: records of different refinements are
+ *     never shared. */
+typedef enum { MM3D_REFINE_ICP = 0, MM3D_REFINE_NDT = 1 } mm3d_refine_method;
+typedef struct mm3d_refine_options {
+  int method;                 /* MM3D_REFINE_*; ICP = whatever mm3d_set_icp_method says */
+  double resolution;          /* voxel side in metres, > 0; 0 = 10 * params.resolution, see above */
+  int neighbours;             /* 1: the point's own voxel; 7: it and its six face neighbours */
+  int min_points;             /* a voxel with fewer finite points has no Gaussian; >= 4 */
+  double regularisation;      /* kappa above, 0 < kappa <= 1 */
+} mm3d_refine_options;
+void mm3d_refine_options_default(mm3d_refine_options *o);         /* MM3D_REFINE_ICP, 0, 7, 6, 0.01 */
+/* MM3D_EINVAL: ctx or options NULL, an unknown method, a value outside its range above or a resolution that is neither 0 nor a
+ * positive finite float with a finite reciprocal (the values are checked whatever the method).  MM3D_EUNSUPPORTED:
+ * MM3D_REFINE_NDT on a device-list context (mm3d_create_devices), whose bundles carry no voxel tables -- nor does
+ * mm3d_shard_begin, which returns MM3D_EUNSUPPORTED on an NDT context. */
+int mm3d_set_refinement(mm3d_ctx *ctx, const mm3d_refine_options *options);
+int mm3d_get_refinement(const mm3d_ctx *ctx, mm3d_refine_options *options);        /* MM3D_EINVAL for NULL */
 
 /* ---- cloud objects -------------------------------------------------------------------- */
 int mm3d_cloud_create(mm3d_ctx *ctx, const void *points, size_t n, size_t stride, size_t rgba_offset,
@@ -456,6 +508,20 @@ int mm3d_estimate_transform_icp_plane(mm3d_ctx *ctx, const mm3d_cloud *source, c
                                       const mm3d_normals *target_normals, const float initial_guess[16],
                                       double max_correspondence_distance, int max_iterations, double transformation_epsilon,
                                       float T[16]);
+/* NDT (mm3d_set_refinement states the table and the loop) from initial_guess, whatever the context's setting and
+ * options->method; options->resolution must be > 0 here.  mm3d_last_icp_iterations / mm3d_last_icp_converged report on it; a
+ * degenerate system returns MM3D_OK, not converged, with T = the transform before the degenerate iteration.  MM3D_EINVAL: a
+ * NULL argument, options out of range, a resolution that is not positive and finite; MM3D_EUNSUPPORTED: a target whose voxel
+ * bounding box needs more than 2^26 index cells. */
+int mm3d_estimate_transform_ndt(mm3d_ctx *ctx, const mm3d_cloud *source, const mm3d_cloud *target, const float initial_guess[16],
+                                const mm3d_refine_options *options, int max_iterations, double transformation_epsilon,
+                                float T[16]);
+/* test hook of the above: the target's voxel table in ascending (i, j, k) -- i first --, voxels with and without a Gaussian
+ * alike; at most cap rows of each array.  icov: xx xy xz yy yz zz, zeros when the voxel has no Gaussian (valid = 0).
+ * *n_voxels receives their number, which may exceed cap. */
+int mm3d_debug_ndt_voxels(mm3d_ctx *ctx, const mm3d_cloud *target, const mm3d_refine_options *options, int *ijk /* [cap][3] */,
+                          int *count, float *mean /* [cap][3] */, float *icov /* [cap][6] */, unsigned char *valid, size_t cap,
+                          size_t *n_voxels);
 /* The prerejective alignment (mm3d_set_alignment states it) of two keypoint sets with their descriptors, whatever the
  * context's setting and options->method.  stats may be NULL.  Fewer than three keypoints on either side, or no surviving
  * draw: MM3D_OK, T = identity, converged = 0.  MM3D_EINVAL: a NULL argument, options out of range, inlier_distance not a

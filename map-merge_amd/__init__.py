@@ -97,6 +97,28 @@ class KeypointOptions(C.Structure):
             setattr(self, k, int(v) if k == "source" else float(v))
 
 
+class RefineMethod(enum.IntEnum):   # mm3d_refine_method (not a reference enum)
+    ICP = 0
+    NDT = 1
+
+
+class RefineOptions(C.Structure):
+    """mm3d_refine_options (mm3d_set_refinement); the defaults are mm3d_refine_options_default's."""
+    _fields_ = [("method", C.c_int), ("resolution", C.c_double), ("neighbours", C.c_int), ("min_points", C.c_int),
+                ("regularisation", C.c_double)]
+
+    def __init__(self, **kw):
+        super().__init__()
+        lib().mm3d_refine_options_default(C.byref(self))
+        for k, v in kw.items():
+            if k not in dict(self._fields_):
+                raise TypeError("unknown refinement option " + k)
+            setattr(self, k, int(v) if k in ("method", "neighbours", "min_points") else float(v))
+
+    def as_tuple(self):
+        return (int(self.method), float(self.resolution), int(self.neighbours), int(self.min_points), float(self.regularisation))
+
+
 class AlignmentStats(C.Structure):
     """mm3d_alignment_stats"""
     _fields_ = [("draws", C.c_longlong), ("survivors", C.c_longlong), ("hypotheses_scored", C.c_longlong),
@@ -329,6 +351,18 @@ class Context:
         self._ck(lib().mm3d_get_keypoints(self._h, C.byref(o)))
         return o
 
+    def setRefinement(self, options=None, **kw):
+        """mm3d_set_refinement: what refines a pair's initial estimate.  A RefineOptions, or its fields as keywords
+        (method=RefineMethod.NDT, resolution=... in metres; 0 = the default multiple of params.resolution, neighbours=1 or 7,
+        min_points=..., regularisation=...)."""
+        o = options if options is not None else RefineOptions(**kw)
+        self._ck(lib().mm3d_set_refinement(self._h, C.byref(o)))
+
+    def getRefinement(self) -> "RefineOptions":
+        o = RefineOptions()
+        self._ck(lib().mm3d_get_refinement(self._h, C.byref(o)))
+        return o
+
     def synchronize(self):
         self._ck(lib().mm3d_synchronize(self._h))
 
@@ -500,6 +534,38 @@ class Context:
         self.last_icp_iterations = lib().mm3d_last_icp_iterations(self._h)
         self.last_icp_converged = lib().mm3d_last_icp_converged(self._h)
         return _Tout(T)
+
+    def estimateTransformNDT(self, source_points, target_points, initial_guess, options=None, max_iterations=100,
+                             transformation_epsilon=0.0, **kw):
+        """mm3d_estimate_transform_ndt: NDT from initial_guess, whatever the context's setting (options.resolution > 0)."""
+        o = options if options is not None else RefineOptions(**kw)
+        g = _T(initial_guess)
+        T = np.zeros(16, dtype=np.float32)
+        self._ck(lib().mm3d_estimate_transform_ndt(
+            self._h, source_points._h, target_points._h, g.ctypes.data_as(C.c_void_p), C.byref(o), int(max_iterations),
+            C.c_double(transformation_epsilon), T.ctypes.data_as(C.c_void_p)))
+        self.last_icp_iterations = lib().mm3d_last_icp_iterations(self._h)
+        self.last_icp_converged = lib().mm3d_last_icp_converged(self._h)
+        return _Tout(T)
+
+    def ndtVoxels(self, target_points, options=None, cap=1 << 20, **kw):
+        """mm3d_debug_ndt_voxels: the target's voxel table in ascending (i, j, k) as a dict of arrays -- ijk [n][3], count [n],
+        mean [n][3], icov [n][6] (xx xy xz yy yz zz; zeros when invalid), valid [n] -- and the number of voxels, which may exceed cap."""
+        o = options if options is not None else RefineOptions(**kw)
+        c = max(int(cap), 1)
+        ijk = np.zeros((c, 3), dtype=np.int32)
+        count = np.zeros(c, dtype=np.int32)
+        mean = np.zeros((c, 3), dtype=np.float32)
+        icov = np.zeros((c, 6), dtype=np.float32)
+        valid = np.zeros(c, dtype=np.uint8)
+        n = C.c_size_t()
+        self._ck(lib().mm3d_debug_ndt_voxels(
+            self._h, target_points._h, C.byref(o), ijk.ctypes.data_as(C.c_void_p), count.ctypes.data_as(C.c_void_p),
+            mean.ctypes.data_as(C.c_void_p), icov.ctypes.data_as(C.c_void_p), valid.ctypes.data_as(C.c_void_p), C.c_size_t(int(cap)),
+            C.byref(n)))
+        m = min(int(n.value), int(cap))
+        return dict(ijk=ijk[:m].copy(), count=count[:m].copy(), mean=mean[:m].copy(), icov=icov[:m].copy(),
+                    valid=valid[:m].astype(bool)), int(n.value)
 
     def estimateTransform(self, source_points, source_keypoints, source_descriptors, target_points,
                           target_keypoints, target_descriptors, method, refine, inlier_threshold,

@@ -45,13 +45,18 @@ std::string feature_key(const mm3d_params *p, const mm3d_keypoint_options &kp)
 // what the pair stage reads (pair_estimate_impl / pairs_estimate_batch), and the ICP method (mm3d_set_icp_method): a
 // point-to-point record is never one of point-to-plane's.  (The map key needs no method: the normals point-to-plane keeps are
 // a function of the points and normal_radius.)
-std::string pair_params_key(const mm3d_params *p, int icp_method, const mm3d_alignment_options &align)
+std::string pair_params_key(const mm3d_params *p, int icp_method, const mm3d_alignment_options &align, const mm3d_refine_options &refine)
 {
   KeyBuilder k;
   k.i32(p->estimation_method).i32(p->refine_transform).f64(p->inlier_threshold).f64(p->max_correspondence_distance)
       .i32(p->max_iterations).u64(p->matching_k).f64(p->transform_epsilon).i32(icp_method);
   // the alignment (mm3d_set_alignment): a SAC-IA record is never a prerejective one's, nor one of other options
   k.i32(align.method).i32(align.samples).i32(align.k).f64(align.similarity).f64(align.inlier_fraction);
+  // the refinement (mm3d_set_refinement): an ICP record is never an NDT one's, nor an NDT one that of other options (which the
+  // ICP does not read: whatever they are, its records are shared)
+  const bool ndt = refine.method == MM3D_REFINE_NDT;
+  k.i32(refine.method).f64(ndt ? refine.resolution : 0.0).i32(ndt ? refine.neighbours : 0).i32(ndt ? refine.min_points : 0)
+      .f64(ndt ? refine.regularisation : 0.0);
   return k.s;
 }
 
@@ -85,7 +90,8 @@ struct Entry {
   size_t bytes() const
   {
     return raw->pts.size() * 16 + cloud_bytes(map->points) + cloud_bytes(map->keypoints) + desc_bytes(map->desc) +
-           (map->normals ? map->normals->nrm.size() * 16 : 0);    // (normals: point-to-plane ICP only)
+           (map->normals ? map->normals->nrm.size() * 16 : 0) +   // (normals: point-to-plane ICP only)
+           (map->ndt ? map->ndt->rec.size() * 16 + map->ndt->index.size() * 4 : 0);    // (voxel table: NDT only)
   }
 };
 
@@ -126,12 +132,12 @@ class MapCache final : public MapCacheBase {
   }
 
   void begin(size_t n_maps, const mm3d_params *p, int icp_method, const mm3d_alignment_options &align,
-             const mm3d_keypoint_options &keypoints) override
+             const mm3d_keypoint_options &keypoints, const mm3d_refine_options &refine) override
   {
     std::lock_guard<std::mutex> lk(mu_);
     reset_call_locked();
     fkey_ = feature_key(p, keypoints);
-    pkey_ = pair_params_key(p, icp_method, align);
+    pkey_ = pair_params_key(p, icp_method, align, refine);
     sac_ia_ = p->estimation_method == MM3D_EST_SAC_IA;
     prerej_ = sac_ia_ && align.method == MM3D_ALIGN_PREREJECTIVE;
     slot_entry_.assign(n_maps, 0);

@@ -322,9 +322,13 @@ static void launch_nn(Context *c, const char *name, double bytes, const NnJob *j
 // score is only kept once its ICP has finished (it nearly always has: the reference's epsilon is loose).
 // plane: point-to-plane ICP (icp_plane.hip's icp_plane_step over NnPlaneJobs that carry each target's normals) instead of
 // icp_corr_reduce + icp_finalize; everything else -- states, chunks, waits, the speculative point-to-point score -- is shared.
+// ndt: NDT (ndt.hip's ndt_step over NdtJobs that carry each target's voxel table) in the ICP's place: no grid of the target is
+// read by it, max_corr_dist is not read by it, and its partials are always per block of four work items.
+enum class IcpKind { Point, Plane, Ndt };
 static void icp_batch(Context *c, IcpScoreJob *jobs, int n_jobs, bool run_icp, double max_corr_dist, int max_iterations, double eps,
-                      bool want_score, double score_max_distance, bool plane)
+                      bool want_score, double score_max_distance, IcpKind kind)
 {
+  const bool plane = kind == IcpKind::Plane, ndt = kind == IcpKind::Ndt;
   static_assert(offsetof(IcpState, T) == 0, "the score kernel reads T at the head of the state");
   c->last_icp_iterations = 0;
   c->last_icp_converged = 0;
@@ -341,9 +345,10 @@ static void icp_batch(Context *c, IcpScoreJob *jobs, int n_jobs, bool run_icp, d
     J.out.iterations = 0; J.out.converged = 0; J.out.n_corr = 0; J.out.score = DBL_MAX;
     int ns = 0;
     const float4 *sp = (J.src->n && J.tgt->n) ? morton_source(c, J.src, ns) : nullptr;
-    const Grid *tg = (ns && run_icp) ? &cloud_grid(c, J.tgt, nn_cell_for(max_corr_dist)) : nullptr;
+    const Grid *tg = (ns && run_icp && !ndt) ? &cloud_grid(c, J.tgt, nn_cell_for(max_corr_dist)) : nullptr;
+    const bool ndt_icp = ns && run_icp && ndt;
     const Grid *sg = (ns && want_score) ? &cloud_grid(c, J.tgt, nn_cell_for(score_radius)) : nullptr;
-    if (ns == 0 || (tg && tg->n == 0) || (sg && sg->n == 0) || (!tg && !sg)) {
+    if (ns == 0 || (tg && tg->n == 0) || (sg && sg->n == 0) || (!tg && !sg && !ndt_icp)) {
       // nothing to search: Identity * guess, and the score of an empty search
       if (J.guess_dev) {
         float *hT = (float *)c->pin(256);
@@ -357,6 +362,7 @@ static void icp_batch(Context *c, IcpScoreJob *jobs, int n_jobs, bool run_icp, d
     }
     if (plane && tg && (!J.tgt_normals || J.tgt_normals->n != J.tgt->n))
       throw Error(MM3D_EINVAL, "point-to-plane ICP: the target's normals do not match its points");
+    if (ndt_icp && !J.tgt_ndt) throw Error(MM3D_EINVAL, "NDT: the target has no voxel table");
     Live L{j, sp, ns, J.src->n_wave_items, tg, sg, 0, 0};
     L.max_ring = tg ? nn_max_ring(rmax, *tg) : 0;
     if (tg) grid_ensure_dt(c, *tg, L.max_ring);
@@ -377,14 +383,17 @@ static void icp_batch(Context *c, IcpScoreJob *jobs, int n_jobs, bool run_icp, d
   double icp_bytes = 0.0, score_bytes = 0.0;
   std::vector<unsigned> nb(B);
   // (the ICP partials: kAcc per block, kPlaneAcc for point-to-plane; the score's stay kAcc)
-  const int icp_acc = plane ? kPlaneAcc : kAcc;
+  const int icp_acc = plane ? kPlaneAcc : ndt ? kNdtAcc : kAcc;
   size_t icp_part_total = 0;
+  unsigned ndt_grid_x = 0;
   for (int b = 0; b < B; ++b) {
     nb[b] = split ? (unsigned)live[b].n_items : div_up(live[b].n_items, 4);
     part_total += (size_t)nb[b] * kAcc;
-    icp_part_total += (size_t)nb[b] * icp_acc;
+    const unsigned icp_nb = ndt ? div_up(live[b].n_items, 4) : nb[b];
+    icp_part_total += (size_t)icp_nb * icp_acc;
     grid_x = std::max(grid_x, nb[b]);
-    icp_bytes += live[b].ns * (plane ? 28.0 : 12.0);      // (point-to-plane: + the winner's normal)
+    ndt_grid_x = std::max(ndt_grid_x, icp_nb);
+    icp_bytes += live[b].ns * (plane ? 28.0 : ndt ? 16.0 + 52.0 * jobs[live[b].job].ndt_neighbours : 12.0);   // (point-to-plane: + the winner's normal; NDT: the point, and an index word and a record per voxel)
     score_bytes += live[b].ns * 12.0 + (live[b].sg ? live[b].sg->n * 12.0 : 0.0);
   }
   DevBuf<double> partials(c, icp_part_total), s_partials(c, want_score ? part_total : 1);
@@ -392,15 +401,17 @@ static void icp_batch(Context *c, IcpScoreJob *jobs, int n_jobs, bool run_icp, d
   DevBuf<IcpState> st(c, B);
   DevBuf<NnJob> d_jobs(c, (size_t)2 * B);                 // [0, B): ICP, [B, 2B): score
   DevBuf<NnPlaneJob> d_pjobs(c, plane ? (size_t)B : 1);   // point-to-plane: the ICP jobs with their normals
+  DevBuf<NdtJob> d_njobs(c, ndt ? (size_t)B : 1);         // NDT: the ICP jobs with their voxel tables
 
-  // host images, in the pinned arena: states | ICP jobs | score jobs | scores back | point-to-plane jobs
+  // host images, in the pinned arena: states | ICP jobs | score jobs | scores back | point-to-plane jobs | NDT jobs
   const size_t st_bytes = sizeof(IcpState) * B, job_bytes = sizeof(NnJob) * 2 * B, out_bytes = 16 * (size_t)B;
-  const size_t pjob_bytes = plane ? sizeof(NnPlaneJob) * B : 0;
-  char *pinned = (char *)c->pin(st_bytes + job_bytes + out_bytes + pjob_bytes + 64);
+  const size_t pjob_bytes = plane ? sizeof(NnPlaneJob) * B : 0, njob_bytes = ndt ? sizeof(NdtJob) * B : 0;
+  char *pinned = (char *)c->pin(st_bytes + job_bytes + out_bytes + pjob_bytes + njob_bytes + 64);
   IcpState *hp = (IcpState *)pinned;
   NnJob *hj = (NnJob *)(pinned + ((st_bytes + 15) & ~(size_t)15));
   double *ho = (double *)((char *)hj + job_bytes);
   NnPlaneJob *hpj = (NnPlaneJob *)((char *)ho + out_bytes);
+  NdtJob *hnj = (NdtJob *)((char *)hpj + pjob_bytes);
   size_t off = 0, icp_off = 0;
   for (int b = 0; b < B; ++b) {
     const Live &L = live[b];
@@ -432,15 +443,32 @@ static void icp_batch(Context *c, IcpScoreJob *jobs, int n_jobs, bool run_icp, d
       hpj[b].nn = q;
       hpj[b].nrm = L.tg ? (const float4 *)J.tgt_normals->nrm.get() : nullptr;
     }
+    if (ndt) {
+      NdtJob nj;
+      memset(&nj, 0, sizeof(nj));
+      nj.nn = q;
+      nj.nn.split = 0;
+      nj.nn.nblocks = (int)div_up(L.n_items, 4);
+      if (const NdtTable *t = run_icp ? J.tgt_ndt : nullptr) {
+        nj.rec = (const float4 *)t->rec.get();
+        nj.index = (const int *)t->index.get();
+        nj.inv = t->inv;
+        for (int a = 0; a < 3; ++a) { nj.mn[a] = t->mn[a]; nj.dims[a] = t->dims[a]; }
+      }
+      nj.neighbours = J.ndt_neighbours;
+      nj.n_src = L.ns;
+      hnj[b] = nj;
+    }
     if (L.sg) { q.g = L.sg->view(); q.max_ring = L.s_ring; }
     q.partials = s_partials.get() + (want_score ? off : 0);
     hj[B + b] = q;
     off += (size_t)nb[b] * kAcc;
-    icp_off += (size_t)nb[b] * icp_acc;
+    icp_off += (size_t)(ndt ? div_up(L.n_items, 4) : nb[b]) * icp_acc;
   }
   MM3D_HIP(hipMemcpyAsync(st.get(), hp, st_bytes, hipMemcpyHostToDevice, c->stream));
   MM3D_HIP(hipMemcpyAsync(d_jobs.get(), hj, job_bytes, hipMemcpyHostToDevice, c->stream));
   if (plane) MM3D_HIP(hipMemcpyAsync(d_pjobs.get(), hpj, pjob_bytes, hipMemcpyHostToDevice, c->stream));
+  if (ndt) MM3D_HIP(hipMemcpyAsync(d_njobs.get(), hnj, njob_bytes, hipMemcpyHostToDevice, c->stream));
   for (int b = 0; b < B; ++b)
     if (jobs[live[b].job].guess_dev)
       MM3D_HIP(hipMemcpyAsync(st.get() + b, jobs[live[b].job].guess_dev, 64, hipMemcpyDeviceToDevice, c->stream));
@@ -457,6 +485,10 @@ static void icp_batch(Context *c, IcpScoreJob *jobs, int n_jobs, bool run_icp, d
       for (int k = 0; k < chunk; ++k) {
         if (plane) {
           icp_plane_step(c, d_pjobs.get(), B, grid_x, split, max_d2, rmax, icp_bytes, icp_part_total * 8.0);
+          continue;
+        }
+        if (ndt) {
+          ndt_step(c, d_njobs.get(), B, ndt_grid_x, icp_bytes, icp_part_total * 8.0);
           continue;
         }
         launch_nn<0>(c, "icp_corr_reduce", icp_bytes, d_jobs.get(), B, grid_x, split, max_d2, rmax);
@@ -494,13 +526,19 @@ static void icp_batch(Context *c, IcpScoreJob *jobs, int n_jobs, bool run_icp, d
 void icp_score_batch(Context *c, IcpScoreJob *jobs, int n_jobs, bool run_icp, double max_corr_dist, int max_iterations, double eps,
                      bool want_score, double score_max_distance)
 {
-  icp_batch(c, jobs, n_jobs, run_icp, max_corr_dist, max_iterations, eps, want_score, score_max_distance, false);
+  icp_batch(c, jobs, n_jobs, run_icp, max_corr_dist, max_iterations, eps, want_score, score_max_distance, IcpKind::Point);
 }
 
 void icp_plane_score_batch(Context *c, IcpScoreJob *jobs, int n_jobs, bool run_icp, double max_corr_dist, int max_iterations, double eps,
                            bool want_score, double score_max_distance)
 {
-  icp_batch(c, jobs, n_jobs, run_icp, max_corr_dist, max_iterations, eps, want_score, score_max_distance, true);
+  icp_batch(c, jobs, n_jobs, run_icp, max_corr_dist, max_iterations, eps, want_score, score_max_distance, IcpKind::Plane);
+}
+
+void ndt_score_batch(Context *c, IcpScoreJob *jobs, int n_jobs, bool run_icp, double max_corr_dist, int max_iterations, double eps,
+                     bool want_score, double score_max_distance)
+{
+  icp_batch(c, jobs, n_jobs, run_icp, max_corr_dist, max_iterations, eps, want_score, score_max_distance, IcpKind::Ndt);
 }
 
 PairTail icp_score(Context *c, const mm3d_cloud *src, const mm3d_cloud *tgt, const float *guess_dev, const float guess_host[16],

@@ -136,4 +136,22 @@ constexpr int kPlaneAcc = 30;
 void icp_plane_step(Context *c, const NnPlaneJob *jobs_dev, int count, unsigned grid_x, bool split, float max_d2, float rmax,
                     double bytes, double finalize_bytes);
 
+
+// NDT (ndt.hip): the job's source side and state (nn.g, nn.tgt_ref and nn.max_ring are not read; nn.split is 0: always four work
+// items per block, so nn.partials is [ceil(n_items / 4)][kNdtAcc] whatever the batch), and the target's voxel table
+struct NdtJob {
+  NnJob nn;
+  const float4 *rec;          // NdtTable::rec
+  const int *index;           // NdtTable::index
+  float inv, mn[3];
+  int dims[3];
+  int neighbours;             // 1 or 7
+  int n_src;                  // finite source points: the divisor of the convergence test's mean weight
+};
+// H upper triangle (21) | g (6) | sum w | terms | points with at least one term
+constexpr int kNdtAcc = 30;
+// one NDT iteration of a batch: the lookup + reduction launch, then the solve / accumulate / convergence launch, on the same
+// IcpState protocol as icp_score_batch's
+void ndt_step(Context *c, const NdtJob *jobs_dev, int count, unsigned grid_x, double bytes, double finalize_bytes);
+
 }  // namespace mm3d

@@ -83,6 +83,7 @@ std::unique_ptr<mm3d_map> mm3d::map_features_impl(mm3d_ctx *ctx, const mm3d_clou
 void mm3d::map_prepare_impl(mm3d_ctx *ctx, mm3d_map *m, const mm3d_params *p)
 {
   if (ctx->icp_method && !m->normals) m->normals.reset(compute_normals(ctx, m->points, p->normal_radius));
+  if (ctx->refine_method) ctx->refine_method->prepare_target(ctx, m, p, nullptr);   // NDT's voxel table (mm3d_set_refinement)
   prepare_pair_search(ctx, m->points, p->max_correspondence_distance, p->max_correspondence_distance);
   if (p->estimation_method == MM3D_EST_SAC_IA && ctx->align_method) ctx->align_method->prepare(ctx, m->keypoints, p->max_correspondence_distance);
   else if (p->estimation_method == MM3D_EST_SAC_IA) prepare_sacia_target(ctx, m->keypoints, (float)p->max_correspondence_distance);
@@ -160,8 +161,8 @@ void mm3d::pair_record_init(mm3d_pair_result *r, size_t source, size_t target)
 void mm3d::pair_estimate_impl(mm3d_ctx *ctx, const mm3d_map *s, const mm3d_map *t, const mm3d_params *p, bool execute,
                              mm3d_pair_result *out)
 {
-  if (execute && (ctx->icp_method || prerejective(ctx, p))) {
-    // point-to-plane ICP (mm3d_set_icp_method) and the prerejective alignment (mm3d_set_alignment) live in the batch path: a
+  if (execute && (ctx->icp_method || ctx->refine_method || prerejective(ctx, p))) {
+    // point-to-plane ICP (mm3d_set_icp_method), NDT (mm3d_set_refinement) and the prerejective alignment (mm3d_set_alignment) live in the batch path: a
     // batch of one, from (and advancing) the context's generator
     PairWork w{s, t, out, ctx->rnd};
     pairs_estimate_batch(ctx, &w, 1, p);
@@ -273,7 +274,12 @@ void mm3d::pairs_estimate_batch(mm3d_ctx *ctx, PairWork *w, size_t n, const mm3d
     std::memcpy(jobs[i].guess_host, fronts[i].T0, sizeof(fronts[i].T0));
   }
   // estimateTransform's ICP and transformScore of its result (R/src/map_merging.cpp:91-107), max_distance = max_correspondence_distance
-  if (ctx->icp_method) {                                // point-to-plane (mm3d_set_icp_method): the targets' normals
+  if (ctx->refine_method) {                             // NDT in the ICP's place (mm3d_set_refinement): the targets' voxel tables
+    if (p->refine_transform)
+      for (size_t i = 0; i < n; ++i) ctx->refine_method->prepare_target(ctx, w[i].t, p, &jobs[i]);
+    ctx->refine_method->score_batch(ctx, jobs.data(), (int)n, p->refine_transform != 0, p->max_correspondence_distance, p->max_iterations,
+                                    p->transform_epsilon, true, p->max_correspondence_distance);
+  } else if (ctx->icp_method) {                         // point-to-plane (mm3d_set_icp_method): the targets' normals
     if (p->refine_transform)
       for (size_t i = 0; i < n; ++i) jobs[i].tgt_normals = map_normals(ctx, w[i].t, p);
     ctx->icp_method->score_batch(ctx, jobs.data(), (int)n, p->refine_transform != 0, p->max_correspondence_distance, p->max_iterations,

@@ -25,9 +25,9 @@ struct KeypointSourceBase;
 struct MapCacheBase {
   virtual ~MapCacheBase() = default;
   // icp_method: MM3D_ICP_* of the call (mm3d_set_icp_method); align: its alignment (mm3d_set_alignment); keypoints: where its
-  // maps' keypoints come from (mm3d_set_keypoints)
+  // maps' keypoints come from (mm3d_set_keypoints); refine: what refines its pairs (mm3d_set_refinement)
   virtual void begin(size_t n_maps, const mm3d_params *p, int icp_method, const mm3d_alignment_options &align,
-                     const mm3d_keypoint_options &keypoints) = 0;
+                     const mm3d_keypoint_options &keypoints, const mm3d_refine_options &refine) = 0;
   // map `slot`'s packed upload `raw` (non-empty, on c's stream): the cached bundle, borrowed for the call, or null.  One launch and
   // one wait on c (a second compare-only launch and wait when the digest names another candidate than the slot's last entry).
   virtual const mm3d_map *lookup(Context *c, size_t slot, const mm3d_cloud *raw) = 0;
@@ -60,6 +60,11 @@ struct mm3d_ctx : mm3d::Context {
   // copied to helpers that mm3d_set_streams makes later.
   const mm3d::KeypointSourceBase *keypoint_source = nullptr;
   mm3d_keypoint_options keypoint_options{MM3D_KEYPOINTS_REFERENCE, 0.0};
+  // mm3d_set_refinement: null = the ICP that icp_method selects; otherwise it takes that ICP's place in the pair stage (NDT).
+  // Not owned (a process-wide object of ndt.hip's that holds no state); set, with the options, on the context and its helpers
+  // alike, and copied to helpers that mm3d_set_streams makes later.  icp_method keeps its own value beside it.
+  const mm3d::IcpMethodBase *refine_method = nullptr;
+  mm3d_refine_options refine_options{MM3D_REFINE_ICP, 0.0, 7, 6, 0.01};
   // mm3d_set_streams: helper contexts (one HIP stream + one host thread each while a call is running)
   // that mm3d_estimate_maps_transforms deals maps and pairs to; owned by this context
   std::vector<mm3d_ctx *> helpers;
@@ -122,6 +127,19 @@ struct Grid {
   }
 };
 
+// The target side of NDT (ndt.hip, mm3d_set_refinement): one Gaussian per voxel of the global lattice, and a dense index over
+// the voxel bounding box of the finite points, so that a lookup is one load.  48 B per occupied voxel plus 4 B per index cell.
+struct NdtTable {
+  double resolution = 0.0, regularisation = 0.0;   // what it was built with (a map's table is rebuilt when these change)
+  int min_points = 0;
+  float inv = 0.f;                                 // 1.0f / (float)resolution
+  float mn[3] = {0, 0, 0};                         // the smallest voxel index per axis (an integer-valued float)
+  int dims[3] = {0, 0, 0};                         // index cells per axis; cell ((i * dims[1]) + j) * dims[2] + k
+  int n_voxels = 0;
+  DevBuf<float4> rec;      // [n_voxels][3], ascending (i, j, k): {mean, valid} {P xx xy xz yy} {P yz zz, count bits, 0}
+  DevBuf<int> index;       // [dims[0] * dims[1] * dims[2]]: the voxel's record, -1 = empty
+};
+
 }  // namespace mm3d
 
 struct mm3d_cloud {
@@ -182,6 +200,9 @@ struct mm3d_map {
   mm3d_desc *desc = nullptr;
   // the points' normals (normal_radius), kept for point-to-plane ICP only (mm3d_set_icp_method): null otherwise
   std::unique_ptr<mm3d_normals> normals;
+  // the points' voxel Gaussians, kept for NDT only (mm3d_set_refinement): null otherwise.  Made and replaced under the
+  // points' cache_mu (mm3d_map_prepare, or a pair's first use of the map as a target).
+  std::unique_ptr<mm3d::NdtTable> ndt;
   mm3d_map() = default;
   mm3d_map(const mm3d_map &) = delete;
   mm3d_map &operator=(const mm3d_map &) = delete;
@@ -295,13 +316,19 @@ struct IcpScoreJob {
   PairTail out{};
   bool closed = false;
   const mm3d_normals *tgt_normals = nullptr;   // point-to-plane ICP: the target's normals, in its order
+  const NdtTable *tgt_ndt = nullptr;           // NDT: the target's voxel table, and how many voxels a point reads (1 or 7)
+  int ndt_neighbours = 7;
 };
 void icp_score_batch(Context *c, IcpScoreJob *jobs, int n_jobs, bool run_icp, double max_corr_dist, int max_iterations, double eps,
                      bool want_score, double score_max_distance);
 // the same with point-to-plane ICP (icp_plane.hip's kernels; every job's tgt_normals set).  The score stays point-to-point.
 void icp_plane_score_batch(Context *c, IcpScoreJob *jobs, int n_jobs, bool run_icp, double max_corr_dist, int max_iterations, double eps,
                            bool want_score, double score_max_distance);
-// The ICP method of a context's pair stage (mm3d_set_icp_method; the one concrete class is icp_plane.hip's).  Like MapCacheBase,
+// the same with NDT in the ICP's place (ndt.hip's kernels; every job's tgt_ndt set); max_corr_dist is read by the score only
+void ndt_score_batch(Context *c, IcpScoreJob *jobs, int n_jobs, bool run_icp, double max_corr_dist, int max_iterations, double eps,
+                     bool want_score, double score_max_distance);
+// The ICP method of a context's pair stage (mm3d_set_icp_method: icp_plane.hip's class) or what takes its place
+// (mm3d_set_refinement: ndt.hip's).  Like MapCacheBase,
 // the drivers in capi.cpp only see this interface, so the host code links without the new kernels (tests/host_san); a null
 // pointer on the context means the reference's point-to-point ICP (icp_score_batch).
 struct IcpMethodBase {
@@ -310,6 +337,9 @@ struct IcpMethodBase {
   // icp_score_batch with this method's ICP
   virtual void score_batch(Context *c, IcpScoreJob *jobs, int n_jobs, bool run_icp, double max_corr_dist, int max_iterations, double eps,
                            bool want_score, double score_max_distance) const = 0;
+  // what the method keeps on a target map beyond its search structures (NDT's voxel table): made when missing or stale,
+  // complete on the device before anybody else can see it, and bound to `job` when there is one
+  virtual void prepare_target(mm3d_ctx *, const mm3d_map *, const mm3d_params *, IcpScoreJob *) const {}
 };
 struct PairFront;
 // The initial alignment of a context's pair stage under SAC_IA (mm3d_set_alignment; the one concrete class is
