@@ -69,6 +69,27 @@ inline mm3d_refine_options parse_refine(const char *value)
   o.method = MM3D_REFINE_NDT;
   return o;
 }
+// MM3D_COARSE=correlative or correlative:<cell in metres>: the estimation context's pairs take their initial estimate from the
+// correlative yaw / shift search (mm3d_set_coarse_alignment; without a cell, the library's default multiple of
+// params.resolution; the other options keep mm3d_coarse_options_default's values); none or unset keeps the estimate that
+// estimation_method and MM3D_ALIGN select.  Anything else throws.
+inline mm3d_coarse_options parse_coarse(const char *value)
+{
+  mm3d_coarse_options o;
+  mm3d_coarse_options_default(&o);
+  const std::string v = value ? value : "";
+  if (v.empty() || v == "none") return o;
+  bool ok = v.compare(0, 11, "correlative") == 0 && (v.size() == 11 || v[11] == ':');
+  if (ok && v.size() > 11) {
+    const char *s = v.c_str() + 12;
+    char *end = nullptr;
+    o.cell = std::strtod(s, &end);
+    ok = end != s && *end == '\0' && std::isfinite(o.cell) && o.cell > 0.0;
+  }
+  if (!ok) throw std::runtime_error("mm3d: MM3D_COARSE must be none, correlative or correlative:<cell in metres>, not '" + v + "'");
+  o.method = MM3D_COARSE_CORRELATIVE;
+  return o;
+}
 }  // namespace mm3d_shim
 }  // namespace map_merge_3d
 
@@ -151,7 +172,11 @@ inline mm3d_ctx *ctx()
   // MM3D_ALIGN_SAMPLES=<draws> if given; sac_ia or unset keeps the reference's.  Not available on a device list either.
   // MM3D_KEYPOINTS=uniform[:<leaf>]: parse_keypoints above; it works on a device list too.
   // MM3D_REFINE=ndt[:<resolution>]: parse_refine above.  Not available on a device list: ndt with MM3D_DEVICES set as well throws.
+  // MM3D_COARSE=correlative[:<cell>]: parse_coarse above.  Not available on a device list: correlative with MM3D_DEVICES set as well throws.
   static mm3d_ctx *c = [] {
+    const mm3d_coarse_options coarse = parse_coarse(std::getenv("MM3D_COARSE"));
+    if (coarse.method == MM3D_COARSE_CORRELATIVE && std::getenv("MM3D_DEVICES") && *std::getenv("MM3D_DEVICES"))
+      throw std::runtime_error("mm3d: MM3D_COARSE=correlative is not available with MM3D_DEVICES (a device list carries no signatures)");
     const mm3d_keypoint_options keypoints = parse_keypoints(std::getenv("MM3D_KEYPOINTS"));
     mm3d_refine_options refine = parse_refine(std::getenv("MM3D_REFINE"));
     if (refine.method == MM3D_REFINE_NDT && std::getenv("MM3D_DEVICES") && *std::getenv("MM3D_DEVICES"))
@@ -189,6 +214,8 @@ inline mm3d_ctx *ctx()
       throw std::runtime_error("mm3d: MM3D_KEYPOINTS was refused (the leaf must be a positive float with a finite reciprocal)");
     if (refine.method != MM3D_REFINE_ICP && mm3d_set_refinement(e, &refine) != MM3D_OK)
       throw std::runtime_error("mm3d: MM3D_REFINE was refused (the resolution must be a positive float with a finite reciprocal)");
+    if (coarse.method != MM3D_COARSE_NONE && mm3d_set_coarse_alignment(e, &coarse) != MM3D_OK)
+      throw std::runtime_error("mm3d: MM3D_COARSE was refused (the cell must be a positive float with a finite reciprocal)");
     return e;
   }();
   return c;

@@ -649,6 +649,118 @@ int mm3d_profile_entry(mm3d_ctx *ctx, int i, const char **name, double *total_ms
                        double *algorithmic_bytes);
 int mm3d_synchronize(mm3d_ctx *ctx);
 
+/* ---- correlative coarse alignment ------------------------------------------------------- */
+/* Where a pair's INITIAL estimate comes from (off the reference's path; MM3D_COARSE_NONE by default: whatever
+ * params.estimation_method and mm3d_set_alignment say).  MM3D_COARSE_CORRELATIVE reads no keypoint and no descriptor: the
+ * maps come from robots that know gravity, so the unknown part of a pair's pose is close to a yaw and a shift in the plane.
+ * EVERY yaw and shift is scored on a coarse 2-D occupancy of the vertical structure (walls: points whose normal is near
+ * horizontal), the best few are refined on the fine grid, and height and residual tilt are read off the two ground surfaces.
+ * Nothing is drawn at random; all scores are integer counts, so the result does not depend on launch geometry or arrival
+ * order.  No such estimator is in PCL or in the reference: no parity is claimed (audit row 16c).
+ * To the operation -- every float step is a single IEEE operation rounded to nearest, nothing contracted:
+ *   Signature of a map (once per map and option set).  c = (float)cell, inv = 1.0f / c.  A point counts when x, y, z and
+ *   the three components of its normal are finite.  Its 2-D cell is (i, j) = (floorf(x * inv), floorf(y * inv)) on the
+ *   GLOBAL lattice anchored at the origin.  A fine STRUCTURE cell has >= min_points counted points with
+ *   fabsf(n_z) <= (float)wall_nz; a GROUND cell has >= min_points counted points with fabsf(n_z) >= (float)ground_nz, and its
+ *   height is the mean z in double over those points in ascending input index (position l of that order goes to partial
+ *   sum l mod 64, each partial ascending, and the 64 partials are added by the fixed tree of the NDT voxel table), rounded to
+ *   float once.  The COARSE structure cells are the distinct (floor(i / F), floor(j / F)) of the structure cells (floor
+ *   division, F = cell_factor).  All lists ascend in (i, j), i first.  For the target role the structure cells are also kept
+ *   as a dense map DILATED by one cell (a cell is set when it or one of its 8 neighbours is a structure cell), beside a
+ *   dense map of the ground heights.  Size limit: the 2-D box of the counted points' cells may hold at most 2^24 cells.
+ *   Coarse vote.  cs[k] = (float)cos(2 pi k / yaw_steps), sn[k] = (float)sin(2 pi k / yaw_steps), the angle and the
+ *   functions evaluated in double on the host.  C = c * (float)F, invC = 1.0f / C, G = yaw_factor, Q = yaw_steps / G.  For
+ *   every coarse yaw index q (k = q G), every source coarse cell (I, J) with centre p = (((float)I + 0.5f) * C,
+ *   ((float)J + 0.5f) * C) and every target coarse cell with centre t formed alike: r = (cs px - sn py, sn px + cs py),
+ *   d = t - r, (u, v) = (floorf(dx * invC + 0.5f), floorf(dy * invC + 0.5f)), acc[q][u][v] += 1.  The accumulator spans a
+ *   box of (u, v) that the two maps' cell boxes bound, U x V cells; Q U V may be at most 2^26 (MM3D_EUNSUPPORTED beyond).
+ *   Candidates.  A cell is a candidate when it has >= 1 vote and no OTHER cell of its 3 x 3 x 3 neighbourhood (cyclic in q,
+ *   clipped in u and v) has more votes, or as many and a lower linear index (q U + u') V + v' (u', v' counted from the box's
+ *   minimum).  The `candidates` best are kept: votes descending, then linear index ascending.
+ *   Fine score.  For every kept candidate (rank order), every g in [-G, G] (k = (q G + g) mod yaw_steps) and every (a, b) in
+ *   [-F, F]^2 the shift is s = ((float)(u F + a) * c, (float)(v F + b) * c) and the score is the number of source fine
+ *   structure cells (i, j) whose centre p = (((float)i + 0.5f) * c, ((float)j + 0.5f) * c), rotated to r as above and
+ *   shifted, x' = rx + sx, y' = ry + sy, falls in a set cell (floorf(x' * inv), floorf(y' * inv)) of the target's dilated
+ *   map.  The winner is the highest score, ties to the lowest (rank, g, a, b).  candidates (2G + 1) (2F + 1)^2 must stay below
+ *   2^31 (MM3D_EUNSUPPORTED beyond).
+ *   Height and tilt.  At the winner every source ground cell's centre is carried over the same way; where
+ *   (floorf(x' * inv), floorf(y' * inv)) is a ground cell of the target, d = (double)h_target - (double)h_source.  With n such
+ *   cells, position l of the source's list order goes to partial sum l mod 256, each partial ascending, and the partials are
+ *   added by a fixed tree, all in double: n, sums of x', y', x'x', x'y', y'y', d, x'd, y'd.  With n >= 16 the 3 x 3 normal
+ *   equations of d ~ alpha x' + beta y' + gamma (unknowns in that order) are solved by an unpivoted LDLt; a pivot at or below
+ *   1e-12 * trace / 3 (the rule of the point-to-plane solve) makes the system degenerate.  A degenerate system, n < 16, a
+ *   result that is not finite or a slope sqrt(alpha^2 + beta^2) above tan 20 deg gives alpha = beta = 0 and gamma = the
+ *   mean d (0 with n = 0).
+ *   Transform.  In double: T = Trans(0, 0, gamma) * Rx(atan beta) * Ry(-atan alpha) * [Rz | s], Rz from the table's floats
+ *   (cs[k], sn[k]) of the winner, cos(atan a) = 1 / sqrt(1 + a^2) and sin(atan a) = a / sqrt(1 + a^2); the third row of
+ *   Rx Ry is then (alpha, beta sqrt(1 + alpha^2), 1) / (sqrt(1 + alpha^2) sqrt(1 + beta^2)): the fitted plane to first order, and the
+ *   refinement takes the rest.  Rounded to a float 4 x 4 once (column-major, as every transform of this header).
+ *   Outcome.  converged = (double)score >= accept_fraction * (double)source_cells.  A winner that is not converged is still
+ *   handed on, as the prerejective alignment does.  No structure cell on either side: the identity, converged = 0, yaw_index -1.
+ *   - Behind the whole-map calls: with MM3D_COARSE_CORRELATIVE a pair's initial estimate is this one, whatever
+ *     params.estimation_method and mm3d_set_alignment say -- mm3d_estimate_maps_transforms on one stream or many, with or
+ *     without the map cache, and mm3d_pair_estimate.  The pair goes on to the configured refinement and to its record as
+ *     after SAC-IA; n_correspondences and n_inliers are 0.  Nothing is taken from the rand() replay:
+ *     mm3d_pair_estimate(execute = 0) and mm3d_pairs_skip advance nothing.  A map's features are still computed, and which
+ *     pairs are live does not change.
+ *   - cell > 0: the fine cell side in metres; 0: 5 * params.resolution.
+ *   - mm3d_map_prepare makes a map's signature from the normals the map build has anyway; a pair whose map has none, or one
+ *     of other options, makes it on first use (a map without normals gets them as point-to-plane's targets do).
+ *   - The setting reaches the context's mm3d_set_streams helpers in either order of the two calls.  Results are bit-identical
+ *     for every stream count, batch and cache setting, and through mm3d_estimate_transform_correlative on the same inputs.
+ *   - The map cache's pair key holds the method and, under it, every option. */
+typedef enum { MM3D_COARSE_NONE = 0, MM3D_COARSE_CORRELATIVE = 1 } mm3d_coarse_method;
+typedef struct mm3d_coarse_options {
+  int method;            /* MM3D_COARSE_* */
+  double cell;           /* fine cell side in metres, > 0; 0 = 5 * params.resolution */
+  int cell_factor;       /* F: a coarse cell is F x F fine cells, 1 .. 16 */
+  int yaw_steps;         /* fine yaw steps per turn, 8 .. 7200 */
+  int yaw_factor;        /* G: a coarse yaw step is G fine ones; yaw_steps % G == 0 */
+  int candidates;        /* coarse maxima that are refined, 1 .. 1024 */
+  double wall_nz;        /* a point is structure when |n_z| <= wall_nz, 0 .. 1 */
+  double ground_nz;      /* a point is ground when |n_z| >= ground_nz, wall_nz < ground_nz <= 1 */
+  int min_points;        /* points of a class a cell needs, >= 1 */
+  double accept_fraction;/* converged when score >= accept_fraction * source structure cells, 0 .. 1 */
+} mm3d_coarse_options;
+typedef struct mm3d_coarse_stats {
+  int source_cells, target_cells;   /* fine structure cells */
+  int coarse_votes;                 /* of the winner's candidate */
+  int candidates;                   /* refined */
+  int score;                        /* the winner's */
+  int yaw_index;                    /* fine step, 0 .. yaw_steps-1; -1: none */
+  int ground_pairs;                 /* cells in the plane fit */
+  int converged;
+} mm3d_coarse_stats;
+void mm3d_coarse_options_default(mm3d_coarse_options *o);   /* NONE, 0, 4, 720, 6, 32, 0.5, 0.9, 3, 0.25 */
+/* MM3D_EINVAL: ctx or options NULL, an unknown method, a value outside its range above, a cell that is neither 0 nor a
+ * positive finite float with a finite reciprocal (the values are checked whatever the method).  MM3D_EUNSUPPORTED:
+ * MM3D_COARSE_CORRELATIVE on a device-list context (mm3d_create_devices), whose bundles carry no signatures -- nor does
+ * mm3d_shard_begin, which returns MM3D_EUNSUPPORTED on a correlative context. */
+int mm3d_set_coarse_alignment(mm3d_ctx *ctx, const mm3d_coarse_options *options);
+int mm3d_get_coarse_alignment(const mm3d_ctx *ctx, mm3d_coarse_options *options);   /* MM3D_EINVAL for NULL */
+/* of the most recent correlative alignment this context ran (a pair of a whole-map call on one stream, or the call below) */
+int mm3d_last_coarse_stats(const mm3d_ctx *ctx, mm3d_coarse_stats *stats);
+/* The correlative alignment of two clouds with their normals (one per point, in its order), whatever the context's setting
+ * and options->method; options->cell must be > 0 here.  stats may be NULL.  MM3D_EINVAL: a NULL argument, options out of
+ * range, normals whose count differs from their cloud's; MM3D_EUNSUPPORTED: a size limit above. */
+int mm3d_estimate_transform_correlative(mm3d_ctx *ctx, const mm3d_cloud *source, const mm3d_normals *source_normals,
+                                        const mm3d_cloud *target, const mm3d_normals *target_normals,
+                                        const mm3d_coarse_options *options, float T[16], mm3d_coarse_stats *stats);
+/* test hook: a map's signature.  structure [cap][3] = (i, j, count), ground [cap][3] = (i, j, count) with ground_height
+ * [cap], coarse [cap][2] = (I, J), each ascending in (i, j); at most cap rows of each (arrays may be NULL with cap = 0).
+ * n[3] receives the three counts, which may exceed cap. */
+int mm3d_debug_correlative_signature(mm3d_ctx *ctx, const mm3d_cloud *points, const mm3d_normals *normals,
+                                     const mm3d_coarse_options *options, int *structure, int *ground, float *ground_height,
+                                     int *coarse, size_t cap, size_t n[3]);
+/* test hook: the search of a pair.  frame[5] = {Q, u_min, v_min, U, V}; acc (may be NULL) receives the U x V accumulator
+ * of coarse yaw index q when acc_cap >= U V; cands [cand_cap][4] = (q, u, v, votes) in rank order, u and v as the rule
+ * counts them (not from the box's minimum); scores [cand_cap][2G+1][2F+1][2F+1] the fine score cube of each; *n_cands the
+ * number refined, at most options->candidates.  A pair without structure cells: frame all 0, *n_cands = 0. */
+int mm3d_debug_correlative_votes(mm3d_ctx *ctx, const mm3d_cloud *source, const mm3d_normals *source_normals,
+                                 const mm3d_cloud *target, const mm3d_normals *target_normals,
+                                 const mm3d_coarse_options *options, int q, int frame[5], int *acc, size_t acc_cap, int *cands,
+                                 int *scores, size_t cand_cap, size_t *n_cands);
+
 #ifdef __cplusplus
 }
 #endif

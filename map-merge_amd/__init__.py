@@ -119,6 +119,39 @@ class RefineOptions(C.Structure):
         return (int(self.method), float(self.resolution), int(self.neighbours), int(self.min_points), float(self.regularisation))
 
 
+class CoarseMethod(enum.IntEnum):   # mm3d_coarse_method (not a reference enum)
+    NONE = 0
+    CORRELATIVE = 1
+
+
+class CoarseOptions(C.Structure):
+    """mm3d_coarse_options (mm3d_set_coarse_alignment); the defaults are mm3d_coarse_options_default's."""
+    _fields_ = [("method", C.c_int), ("cell", C.c_double), ("cell_factor", C.c_int), ("yaw_steps", C.c_int), ("yaw_factor", C.c_int),
+                ("candidates", C.c_int), ("wall_nz", C.c_double), ("ground_nz", C.c_double), ("min_points", C.c_int),
+                ("accept_fraction", C.c_double)]
+
+    def __init__(self, **kw):
+        super().__init__()
+        lib().mm3d_coarse_options_default(C.byref(self))
+        kinds = dict(self._fields_)
+        for k, v in kw.items():
+            if k not in kinds:
+                raise TypeError("unknown coarse alignment option " + k)
+            setattr(self, k, int(v) if kinds[k] is C.c_int else float(v))
+
+    def as_tuple(self):
+        return tuple(int(getattr(self, k)) if t is C.c_int else float(getattr(self, k)) for k, t in self._fields_)
+
+
+class CoarseStats(C.Structure):
+    """mm3d_coarse_stats"""
+    _fields_ = [("source_cells", C.c_int), ("target_cells", C.c_int), ("coarse_votes", C.c_int), ("candidates", C.c_int),
+                ("score", C.c_int), ("yaw_index", C.c_int), ("ground_pairs", C.c_int), ("converged", C.c_int)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 class AlignmentStats(C.Structure):
     """mm3d_alignment_stats"""
     _fields_ = [("draws", C.c_longlong), ("survivors", C.c_longlong), ("hypotheses_scored", C.c_longlong),
@@ -363,6 +396,22 @@ class Context:
         self._ck(lib().mm3d_get_refinement(self._h, C.byref(o)))
         return o
 
+    def setCoarseAlignment(self, options=None, **kw):
+        """mm3d_set_coarse_alignment: what replaces a pair's initial estimate.  A CoarseOptions, or its fields as keywords
+        (method=CoarseMethod.CORRELATIVE, cell=... in metres; 0 = the default multiple of params.resolution, ...)."""
+        o = options if options is not None else CoarseOptions(**kw)
+        self._ck(lib().mm3d_set_coarse_alignment(self._h, C.byref(o)))
+
+    def getCoarseAlignment(self) -> "CoarseOptions":
+        o = CoarseOptions()
+        self._ck(lib().mm3d_get_coarse_alignment(self._h, C.byref(o)))
+        return o
+
+    def lastCoarseStats(self) -> dict:
+        st = CoarseStats()
+        self._ck(lib().mm3d_last_coarse_stats(self._h, C.byref(st)))
+        return st.as_dict()
+
     def synchronize(self):
         self._ck(lib().mm3d_synchronize(self._h))
 
@@ -566,6 +615,54 @@ class Context:
         m = min(int(n.value), int(cap))
         return dict(ijk=ijk[:m].copy(), count=count[:m].copy(), mean=mean[:m].copy(), icov=icov[:m].copy(),
                     valid=valid[:m].astype(bool)), int(n.value)
+
+    def estimateTransformCorrelative(self, source_points, source_normals, target_points, target_normals, options=None, **kw):
+        """mm3d_estimate_transform_correlative: (T, stats dict), whatever the context's setting (options.cell > 0)."""
+        o = options if options is not None else CoarseOptions(**kw)
+        T = np.zeros(16, dtype=np.float32)
+        st = CoarseStats()
+        self._ck(lib().mm3d_estimate_transform_correlative(
+            self._h, source_points._h, source_normals._h, target_points._h, target_normals._h, C.byref(o),
+            T.ctypes.data_as(C.c_void_p), C.byref(st)))
+        return _Tout(T), st.as_dict()
+
+    def correlativeSignature(self, points, normals, options=None, cap=1 << 20, **kw):
+        """mm3d_debug_correlative_signature: a dict of structure [n][3] (i, j, count), ground [n][3], ground_height [n] and
+        coarse [n][2], each ascending in (i, j)."""
+        o = options if options is not None else CoarseOptions(**kw)
+        c = max(int(cap), 1)
+        st = np.zeros((c, 3), dtype=np.int32)
+        gr = np.zeros((c, 3), dtype=np.int32)
+        gh = np.zeros(c, dtype=np.float32)
+        co = np.zeros((c, 2), dtype=np.int32)
+        n = (C.c_size_t * 3)()
+        self._ck(lib().mm3d_debug_correlative_signature(
+            self._h, points._h, normals._h, C.byref(o), st.ctypes.data_as(C.c_void_p), gr.ctypes.data_as(C.c_void_p),
+            gh.ctypes.data_as(C.c_void_p), co.ctypes.data_as(C.c_void_p), C.c_size_t(c), n))
+        if max(n) > c:
+            raise RuntimeError("correlativeSignature: more cells than cap")
+        return dict(structure=st[:n[0]].copy(), ground=gr[:n[1]].copy(), ground_height=gh[:n[1]].copy(), coarse=co[:n[2]].copy())
+
+    def correlativeVotes(self, source_points, source_normals, target_points, target_normals, q, options=None, **kw):
+        """mm3d_debug_correlative_votes: a dict of frame (Q, u_min, v_min, U, V), acc [U][V] of coarse yaw index q, cands
+        [n][4] (q, u, v, votes) in rank order and scores [n][2G+1][2F+1][2F+1]."""
+        o = options if options is not None else CoarseOptions(**kw)
+        frame = (C.c_int * 5)()
+        n = C.c_size_t()
+        K, W, GW = int(o.candidates), 2 * int(o.cell_factor) + 1, 2 * int(o.yaw_factor) + 1
+        cands = np.zeros((K, 4), dtype=np.int32)
+        scores = np.zeros((K, GW, W, W), dtype=np.int32)
+        args = (self._h, source_points._h, source_normals._h, target_points._h, target_normals._h, C.byref(o), int(q), frame)
+        self._ck(lib().mm3d_debug_correlative_votes(*args, None, C.c_size_t(0), cands.ctypes.data_as(C.c_void_p),
+                                                    scores.ctypes.data_as(C.c_void_p), C.c_size_t(K), C.byref(n)))
+        U, V = int(frame[3]), int(frame[4])
+        acc = np.zeros((U, V), dtype=np.int32)
+        if U * V:
+            self._ck(lib().mm3d_debug_correlative_votes(*args, acc.ctypes.data_as(C.c_void_p), C.c_size_t(U * V),
+                                                        cands.ctypes.data_as(C.c_void_p), scores.ctypes.data_as(C.c_void_p),
+                                                        C.c_size_t(K), C.byref(n)))
+        m = int(n.value)
+        return dict(frame=tuple(int(x) for x in frame), acc=acc, cands=cands[:m].copy(), scores=scores[:m].copy())
 
     def estimateTransform(self, source_points, source_keypoints, source_descriptors, target_points,
                           target_keypoints, target_descriptors, method, refine, inlier_threshold,

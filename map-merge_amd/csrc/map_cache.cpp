@@ -45,7 +45,8 @@ std::string feature_key(const mm3d_params *p, const mm3d_keypoint_options &kp)
 // what the pair stage reads (pair_estimate_impl / pairs_estimate_batch), and the ICP method (mm3d_set_icp_method): a
 // point-to-point record is never one of point-to-plane's.  (The map key needs no method: the normals point-to-plane keeps are
 // a function of the points and normal_radius.)
-std::string pair_params_key(const mm3d_params *p, int icp_method, const mm3d_alignment_options &align, const mm3d_refine_options &refine)
+std::string pair_params_key(const mm3d_params *p, int icp_method, const mm3d_alignment_options &align, const mm3d_refine_options &refine,
+                            const mm3d_coarse_options &coarse)
 {
   KeyBuilder k;
   k.i32(p->estimation_method).i32(p->refine_transform).f64(p->inlier_threshold).f64(p->max_correspondence_distance)
@@ -57,6 +58,12 @@ std::string pair_params_key(const mm3d_params *p, int icp_method, const mm3d_ali
   const bool ndt = refine.method == MM3D_REFINE_NDT;
   k.i32(refine.method).f64(ndt ? refine.resolution : 0.0).i32(ndt ? refine.neighbours : 0).i32(ndt ? refine.min_points : 0)
       .f64(ndt ? refine.regularisation : 0.0);
+  // the coarse alignment (mm3d_set_coarse_alignment): a correlative record is never one of the descriptor estimates, nor one of
+  // other options (which nothing else reads: whatever they are, the other records are shared)
+  const bool corr = coarse.method == MM3D_COARSE_CORRELATIVE;
+  k.i32(coarse.method).f64(corr ? coarse.cell : 0.0).i32(corr ? coarse.cell_factor : 0).i32(corr ? coarse.yaw_steps : 0)
+      .i32(corr ? coarse.yaw_factor : 0).i32(corr ? coarse.candidates : 0).f64(corr ? coarse.wall_nz : 0.0)
+      .f64(corr ? coarse.ground_nz : 0.0).i32(corr ? coarse.min_points : 0).f64(corr ? coarse.accept_fraction : 0.0);
   return k.s;
 }
 
@@ -91,7 +98,9 @@ struct Entry {
   {
     return raw->pts.size() * 16 + cloud_bytes(map->points) + cloud_bytes(map->keypoints) + desc_bytes(map->desc) +
            (map->normals ? map->normals->nrm.size() * 16 : 0) +   // (normals: point-to-plane ICP only)
-           (map->ndt ? map->ndt->rec.size() * 16 + map->ndt->index.size() * 4 : 0);    // (voxel table: NDT only)
+           (map->ndt ? map->ndt->rec.size() * 16 + map->ndt->index.size() * 4 : 0) +   // (voxel table: NDT only)
+           (map->coarse ? (map->coarse->scells.size() + map->coarse->gcells.size()) * 16 + map->coarse->ccells.size() * 8 +
+                              map->coarse->dil.size() + map->coarse->gh.size() * 4 : 0);   // (signature: correlative alignment only)
   }
 };
 
@@ -132,13 +141,14 @@ class MapCache final : public MapCacheBase {
   }
 
   void begin(size_t n_maps, const mm3d_params *p, int icp_method, const mm3d_alignment_options &align,
-             const mm3d_keypoint_options &keypoints, const mm3d_refine_options &refine) override
+             const mm3d_keypoint_options &keypoints, const mm3d_refine_options &refine, const mm3d_coarse_options &coarse) override
   {
     std::lock_guard<std::mutex> lk(mu_);
     reset_call_locked();
     fkey_ = feature_key(p, keypoints);
-    pkey_ = pair_params_key(p, icp_method, align, refine);
-    sac_ia_ = p->estimation_method == MM3D_EST_SAC_IA;
+    pkey_ = pair_params_key(p, icp_method, align, refine, coarse);
+    // (the correlative alignment reads neither the generator nor its seed: no state in its pairs' keys)
+    sac_ia_ = p->estimation_method == MM3D_EST_SAC_IA && coarse.method != MM3D_COARSE_CORRELATIVE;
     prerej_ = sac_ia_ && align.method == MM3D_ALIGN_PREREJECTIVE;
     slot_entry_.assign(n_maps, 0);
     slot_digest_.assign(n_maps, {0ull, 0ull});

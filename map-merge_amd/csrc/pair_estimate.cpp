@@ -76,7 +76,7 @@ std::unique_ptr<mm3d_map> mm3d::map_features_impl(mm3d_ctx *ctx, const mm3d_clou
                                                                          : compute_fpfh(ctx, filt.get(), nrm.get(), kp.get(), p->descriptor_radius));
   if (wait) ctx->sync();
   std::unique_ptr<mm3d_map> m = make_map(std::move(filt), std::move(kp), std::move(desc));
-  if (ctx->icp_method) m->normals = std::move(nrm);    // point-to-plane ICP reads them (mm3d_set_icp_method)
+  if (ctx->icp_method || ctx->coarse_method) m->normals = std::move(nrm);    // point-to-plane ICP reads them (mm3d_set_icp_method), and the correlative signature
   return m;
 }
 
@@ -84,6 +84,7 @@ void mm3d::map_prepare_impl(mm3d_ctx *ctx, mm3d_map *m, const mm3d_params *p)
 {
   if (ctx->icp_method && !m->normals) m->normals.reset(compute_normals(ctx, m->points, p->normal_radius));
   if (ctx->refine_method) ctx->refine_method->prepare_target(ctx, m, p, nullptr);   // NDT's voxel table (mm3d_set_refinement)
+  if (ctx->coarse_method) ctx->coarse_method->prepare(ctx, m, p);                   // the correlative signature (mm3d_set_coarse_alignment)
   prepare_pair_search(ctx, m->points, p->max_correspondence_distance, p->max_correspondence_distance);
   if (p->estimation_method == MM3D_EST_SAC_IA && ctx->align_method) ctx->align_method->prepare(ctx, m->keypoints, p->max_correspondence_distance);
   else if (p->estimation_method == MM3D_EST_SAC_IA) prepare_sacia_target(ctx, m->keypoints, (float)p->max_correspondence_distance);
@@ -132,12 +133,16 @@ static const mm3d_normals *map_normals(mm3d_ctx *ctx, const mm3d_map *m, const m
 }
 
 // The estimation method as the rand() replay sees it: a prerejective alignment (mm3d_set_alignment) draws nothing from rand(),
-// which is MATCHING's case in pair_rand_replay.
+// which is MATCHING's case in pair_rand_replay; nor does the correlative alignment (mm3d_set_coarse_alignment).
 static int replay_method(const mm3d_ctx *ctx, const mm3d_params *p)
 {
+  if (ctx->coarse_method) return (int)MM3D_EST_MATCHING;
   return ctx->align_method && p->estimation_method == MM3D_EST_SAC_IA ? (int)MM3D_EST_MATCHING : (int)p->estimation_method;
 }
-static bool prerejective(const mm3d_ctx *ctx, const mm3d_params *p) { return ctx->align_method && p->estimation_method == MM3D_EST_SAC_IA; }
+static bool prerejective(const mm3d_ctx *ctx, const mm3d_params *p)
+{
+  return !ctx->coarse_method && ctx->align_method && p->estimation_method == MM3D_EST_SAC_IA;
+}
 void mm3d::pair_replay_draws(GlibcRand &rnd, const mm3d_ctx *ctx, const mm3d_params *p, const std::vector<float4> &skp_host)
 {
   pair_rand_replay(rnd, replay_method(ctx, p), skp_host, p->inlier_threshold, p->max_iterations);
@@ -161,7 +166,7 @@ void mm3d::pair_record_init(mm3d_pair_result *r, size_t source, size_t target)
 void mm3d::pair_estimate_impl(mm3d_ctx *ctx, const mm3d_map *s, const mm3d_map *t, const mm3d_params *p, bool execute,
                              mm3d_pair_result *out)
 {
-  if (execute && (ctx->icp_method || ctx->refine_method || prerejective(ctx, p))) {
+  if (execute && (ctx->icp_method || ctx->refine_method || ctx->coarse_method || prerejective(ctx, p))) {
     // point-to-plane ICP (mm3d_set_icp_method), NDT (mm3d_set_refinement) and the prerejective alignment (mm3d_set_alignment) live in the batch path: a
     // batch of one, from (and advancing) the context's generator
     PairWork w{s, t, out, ctx->rnd};
@@ -169,7 +174,7 @@ void mm3d::pair_estimate_impl(mm3d_ctx *ctx, const mm3d_map *s, const mm3d_map *
     return;
   }
   clear_estimate(out);
-  if (prerejective(ctx, p)) return;                     // not executed, and nothing to replay (mm3d_set_alignment)
+  if (ctx->coarse_method || prerejective(ctx, p)) return;   // not executed, and nothing to replay (mm3d_set_alignment, mm3d_set_coarse_alignment)
   // estimateTransform and transformScore of its result (R/src/map_merging.cpp:91-107) as one device
   // pipeline: the transform never visits the host in between
   double score = DBL_MAX;
@@ -237,7 +242,10 @@ void mm3d::pairs_estimate_batch(mm3d_ctx *ctx, PairWork *w, size_t n, const mm3d
     mm3d_pair_result *out = w[i].out;
     clear_estimate(out);
     ctx->rnd = w[i].rnd;
-    if (prerejective(ctx, p)) {
+    if (ctx->coarse_method) {
+      // no keypoints, no descriptors, nothing of the generator: the two maps' signatures
+      ctx->coarse_method->front(ctx, w[i].s, w[i].t, p, fronts[i], &ctx->last_coarse_stats);
+    } else if (prerejective(ctx, p)) {
       // the same inputs, max_correspondence_distance as the inlier distance; the generator's seed, none of its draws
       ctx->align_method->front(ctx, ctx->align_options, w[i].rnd.seed0, w[i].s->keypoints, w[i].s->desc, w[i].t->keypoints, w[i].t->desc,
                                p->max_correspondence_distance, fronts[i], &ctx->last_align_stats);

@@ -17,6 +17,7 @@ struct DeviceSet;
 struct IcpMethodBase;
 struct AlignMethodBase;
 struct KeypointSourceBase;
+struct CoarseMethodBase;
 
 // The feature / pair cache of mm3d_estimate_maps_transforms (mm3d_set_map_cache; the concrete class is map_cache.cpp's).  The
 // drivers in capi.cpp only see this interface, so the host code links without it (tests/host_san).  One call at a time -- the
@@ -26,8 +27,9 @@ struct MapCacheBase {
   virtual ~MapCacheBase() = default;
   // icp_method: MM3D_ICP_* of the call (mm3d_set_icp_method); align: its alignment (mm3d_set_alignment); keypoints: where its
   // maps' keypoints come from (mm3d_set_keypoints); refine: what refines its pairs (mm3d_set_refinement)
+  // coarse: what replaces its pairs' initial estimate (mm3d_set_coarse_alignment)
   virtual void begin(size_t n_maps, const mm3d_params *p, int icp_method, const mm3d_alignment_options &align,
-                     const mm3d_keypoint_options &keypoints, const mm3d_refine_options &refine) = 0;
+                     const mm3d_keypoint_options &keypoints, const mm3d_refine_options &refine, const mm3d_coarse_options &coarse) = 0;
   // map `slot`'s packed upload `raw` (non-empty, on c's stream): the cached bundle, borrowed for the call, or null.  One launch and
   // one wait on c (a second compare-only launch and wait when the digest names another candidate than the slot's last entry).
   virtual const mm3d_map *lookup(Context *c, size_t slot, const mm3d_cloud *raw) = 0;
@@ -65,6 +67,12 @@ struct mm3d_ctx : mm3d::Context {
   // alike, and copied to helpers that mm3d_set_streams makes later.  icp_method keeps its own value beside it.
   const mm3d::IcpMethodBase *refine_method = nullptr;
   mm3d_refine_options refine_options{MM3D_REFINE_ICP, 0.0, 7, 6, 0.01};
+  // mm3d_set_coarse_alignment: null = the initial estimate that estimation_method and align_method select; otherwise it
+  // takes their place in the pair stage (align_correlative.hip).  Not owned (a process-wide object that holds no state); set,
+  // with the options, on the context and its helpers alike, and copied to helpers that mm3d_set_streams makes later.
+  const mm3d::CoarseMethodBase *coarse_method = nullptr;
+  mm3d_coarse_options coarse_options{MM3D_COARSE_NONE, 0.0, 4, 720, 6, 32, 0.5, 0.9, 3, 0.25};
+  mm3d_coarse_stats last_coarse_stats{0, 0, 0, 0, 0, -1, 0, 0};
   // mm3d_set_streams: helper contexts (one HIP stream + one host thread each while a call is running)
   // that mm3d_estimate_maps_transforms deals maps and pairs to; owned by this context
   std::vector<mm3d_ctx *> helpers;
@@ -140,6 +148,23 @@ struct NdtTable {
   DevBuf<int> index;       // [dims[0] * dims[1] * dims[2]]: the voxel's record, -1 = empty
 };
 
+// What the correlative alignment keeps of a map (align_correlative.hip, mm3d_set_coarse_alignment): the 2-D cells of its
+// vertical structure and of its ground on the global lattice, as lists for the source role and as dense maps over the cell box
+// of its counted points, padded by one cell, for the target role.
+struct CoarseSignature {
+  mm3d_coarse_options opt{};                       // what it was made with, cell resolved (a map's is remade when these change)
+  float c = 0.f, inv = 0.f;                        // (float)cell, 1.0f / c
+  int n_struct = 0, n_ground = 0;                  // fine structure cells, ground cells
+  int mn[2] = {0, 0}, dims[2] = {0, 0};            // the dense frame: cell (i, j) is word (i - mn[0]) * dims[1] + (j - mn[1])
+  int cmn[2] = {0, 0}, cdims[2] = {0, 0};          // the frame of the coarse cells
+  DevBuf<int4> scells;     // [n_struct] (i, j, count, 0), ascending (i, j)
+  DevBuf<int4> gcells;     // [n_ground] (i, j, count, height bits)
+  DevBuf<int2> ccells;     // coarse cells (I, J), ascending; their number is n_coarse[0], on the device
+  DevBuf<int> n_coarse;
+  DevBuf<unsigned char> dil;   // dense: the structure cells dilated by one cell
+  DevBuf<float> gh;            // dense: a ground cell's height, NaN elsewhere
+};
+
 }  // namespace mm3d
 
 struct mm3d_cloud {
@@ -203,6 +228,9 @@ struct mm3d_map {
   // the points' voxel Gaussians, kept for NDT only (mm3d_set_refinement): null otherwise.  Made and replaced under the
   // points' cache_mu (mm3d_map_prepare, or a pair's first use of the map as a target).
   std::unique_ptr<mm3d::NdtTable> ndt;
+  // the points' correlative signature, kept for mm3d_set_coarse_alignment only: null otherwise.  Made and replaced under the
+  // points' cache_mu (mm3d_map_prepare, or a pair's first use of the map); the normals above are kept for it too.
+  std::unique_ptr<mm3d::CoarseSignature> coarse;
   mm3d_map() = default;
   mm3d_map(const mm3d_map &) = delete;
   mm3d_map &operator=(const mm3d_map &) = delete;
@@ -362,6 +390,17 @@ struct KeypointSourceBase {
   virtual int source() const = 0;                        // MM3D_KEYPOINTS_*
   // the keypoints of the filtered cloud `points`, a new cloud complete on c's stream (one wait: its size)
   virtual mm3d_cloud *keypoints(Context *c, const mm3d_cloud *points, double leaf) const = 0;
+};
+// What takes the place of a pair's initial estimate (mm3d_set_coarse_alignment; the one concrete class is
+// align_correlative.hip's).  Like AlignMethodBase, the drivers only see this interface, so the host code links without the
+// new kernels (tests/host_san); a null pointer on the context means the estimate that estimation_method selects.
+struct CoarseMethodBase {
+  virtual ~CoarseMethodBase() = default;
+  // the map's signature at the context's options (and the normals it is made from): made when missing or stale, under the
+  // points' lock and complete on the device before anybody else can see it
+  virtual void prepare(mm3d_ctx *ctx, const mm3d_map *m, const mm3d_params *p) const = 0;
+  // the pair's initial estimate: f.dT0 / f.on_device, or the identity in f.T0
+  virtual void front(mm3d_ctx *ctx, const mm3d_map *s, const mm3d_map *t, const mm3d_params *p, PairFront &f, mm3d_coarse_stats *stats) const = 0;
 };
 struct PairCounts { int n_correspondences = 0, n_inliers = 0, icp_correspondences = 0; };
 // ICP (optional) from a guess on the device (guess_dev != null) or on the host, then transformScore
