@@ -90,6 +90,37 @@ inline mm3d_coarse_options parse_coarse(const char *value)
   o.method = MM3D_COARSE_CORRELATIVE;
   return o;
 }
+// MM3D_CONFIDENCE=overlap or overlap:<voxel in metres>: the estimation context's pair records carry the overlap confidence, a
+// fraction in [0, 1] that confidence_threshold is then compared with (mm3d_set_confidence; without a voxel, the library's
+// default multiple of params.resolution; the other options keep mm3d_confidence_options_default's values); none or unset
+// keeps the reference's 1 / transformScore.  Anything else throws.
+inline mm3d_confidence_options parse_confidence(const char *value)
+{
+  mm3d_confidence_options o;
+  o.method = MM3D_CONFIDENCE_REFERENCE;
+  o.voxel = 0.0;
+  o.min_points = 8;
+  o.min_overlap = 0.05;
+  o.view_margin = 0;
+  const std::string v = value ? value : "";
+  if (v.empty() || v == "none") return o;
+  bool ok = v.compare(0, 7, "overlap") == 0 && (v.size() == 7 || v[7] == ':');
+  if (ok && v.size() > 7) {
+    const char *s = v.c_str() + 8;
+    char *end = nullptr;
+    o.voxel = std::strtod(s, &end);
+    ok = end != s && *end == '\0' && std::isfinite(o.voxel) && o.voxel > 0.0;
+  }
+  if (!ok) throw std::runtime_error("mm3d: MM3D_CONFIDENCE must be none, overlap or overlap:<voxel in metres>, not '" + v + "'");
+  o.method = MM3D_CONFIDENCE_OVERLAP;
+  return o;
+}
+// Not available on a device list (its bundles carry no tables): overlap with MM3D_DEVICES set as well throws.
+inline void check_confidence_devices(const mm3d_confidence_options &o, const char *devices)
+{
+  if (o.method == MM3D_CONFIDENCE_OVERLAP && devices && *devices)
+    throw std::runtime_error("mm3d: MM3D_CONFIDENCE=overlap is not available with MM3D_DEVICES (a device list carries no tables)");
+}
 }  // namespace mm3d_shim
 }  // namespace map_merge_3d
 
@@ -173,7 +204,10 @@ inline mm3d_ctx *ctx()
   // MM3D_KEYPOINTS=uniform[:<leaf>]: parse_keypoints above; it works on a device list too.
   // MM3D_REFINE=ndt[:<resolution>]: parse_refine above.  Not available on a device list: ndt with MM3D_DEVICES set as well throws.
   // MM3D_COARSE=correlative[:<cell>]: parse_coarse above.  Not available on a device list: correlative with MM3D_DEVICES set as well throws.
+  // MM3D_CONFIDENCE=overlap[:<voxel>]: parse_confidence above.  Not available on a device list: overlap with MM3D_DEVICES set as well throws.
   static mm3d_ctx *c = [] {
+    const mm3d_confidence_options confidence = parse_confidence(std::getenv("MM3D_CONFIDENCE"));
+    check_confidence_devices(confidence, std::getenv("MM3D_DEVICES"));
     const mm3d_coarse_options coarse = parse_coarse(std::getenv("MM3D_COARSE"));
     if (coarse.method == MM3D_COARSE_CORRELATIVE && std::getenv("MM3D_DEVICES") && *std::getenv("MM3D_DEVICES"))
       throw std::runtime_error("mm3d: MM3D_COARSE=correlative is not available with MM3D_DEVICES (a device list carries no signatures)");
@@ -216,6 +250,8 @@ inline mm3d_ctx *ctx()
       throw std::runtime_error("mm3d: MM3D_REFINE was refused (the resolution must be a positive float with a finite reciprocal)");
     if (coarse.method != MM3D_COARSE_NONE && mm3d_set_coarse_alignment(e, &coarse) != MM3D_OK)
       throw std::runtime_error("mm3d: MM3D_COARSE was refused (the cell must be a positive float with a finite reciprocal)");
+    if (confidence.method != MM3D_CONFIDENCE_REFERENCE && mm3d_set_confidence(e, &confidence) != MM3D_OK)
+      throw std::runtime_error("mm3d: MM3D_CONFIDENCE was refused (the voxel must be a positive float with a finite reciprocal)");
     return e;
   }();
   return c;

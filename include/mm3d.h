@@ -761,6 +761,78 @@ int mm3d_debug_correlative_votes(mm3d_ctx *ctx, const mm3d_cloud *source, const 
                                  const mm3d_coarse_options *options, int q, int frame[5], int *acc, size_t acc_cap, int *cands,
                                  int *scores, size_t cand_cap, size_t *n_cands);
 
+/* ---- overlap confidence (off the reference's path) ---------------------------------------
+ * What a pair record's `confidence` is.  MM3D_CONFIDENCE_REFERENCE (the default) is the reference's 1 / transformScore, bit
+ * for bit as before.  MM3D_CONFIDENCE_OVERLAP replaces it by a two-way voxel agreement of the two maps under the pair's
+ * transform: search-free (one index computation and two loads per point), normalised to the overlap, and integer-valued up
+ * to one final division.  It has no PCL counterpart and claims no parity (audit row 16d; section 7g).
+ * THIS CONFIDENCE LIVES IN [0, 1]: params.confidence_threshold is then a fraction, not a reciprocal mean squared distance.
+ *   Lattice.  r_f = (float)voxel, inv = 1.0f / r_f.  The voxel of a coordinate x is (int)floorf(x * inv) (one float multiply)
+ *   on the GLOBAL lattice anchored at the origin, as in mm3d_set_refinement and mm3d_uniform_keypoints.  Per axis, brick
+ *   b = v >> 2 and view cell c = v >> 3 (arithmetic shifts: floor division).
+ *   Table of a map, from its finite points only, once per map and option set:
+ *     occ(v):  some finite point lies in voxel v.
+ *     near(v): occ(u) for some u with max|u - v| <= 1 (the 27 voxels around v).
+ *     cnt(c):  the number of finite points whose view cell is c;  seen(c) = cnt(c) >= min_points.
+ *     view(c): view_margin = 0: seen(c);  view_margin = 1: seen(c') for some c' with max|c' - c| <= 1.
+ *   Storage is dense over the brick box of the finite points: per axis bricks [(v_lo - 1) >> 2, (v_hi + 1) >> 2], v_lo / v_hi
+ *   the voxels of the cloud's bounding box minimum / maximum.  One uint64 word per brick holds its 4 x 4 x 4 voxels of near:
+ *   voxel (i, j, k) is bit (i&3) | ((j&3)<<2) | ((k&3)<<4) of word ((bi-b0i)*nj + (bj-b0j))*nk + (bk-b0k).  One byte per view
+ *   cell holds view, over the view cells [b0 >> 1, b1 >> 1] that the brick box touches, widened by one cell on every side
+ *   when view_margin = 1, in the same (i-major) order.  Everything outside the two boxes reads as 0.  Memory: 8 B per brick
+ *   plus 1 B per view cell, cached maps included.  Limits, decided before anything is allocated, both MM3D_EUNSUPPORTED: more
+ *   than 2^24 words; a voxel index of magnitude >= 2^30.
+ *   One direction A -> B under a float matrix M.  For every finite point p of A: s = M p by the ICP's float rule (unfused
+ *   multiplies and adds, x then y then z then the translation).  A point with a non-finite s, or with |s * inv| >= 2^30 on
+ *   any axis, counts for nothing.  Otherwise v = its voxel; if view_B(v >> 3): in += 1, and if in addition near_B(v): hit += 1.
+ *   Two directions.  source -> target uses M = T.  target -> source uses the rigid inverse, formed on the host in double from
+ *   T's float entries: R' = R^T, t'_r = -((R_0r t_0 + R_1r t_1) + R_2r t_2), rounded to float once, last row 0 0 0 1.  A T with
+ *   a non-finite entry, or the all-zero matrix, gives all counts 0 and confidence 0.
+ *   Confidence.  n_s, n_t = the finite point counts.  It is 0.0 when in_st == 0, in_ts == 0,
+ *   (double)in_st < min_overlap * (double)n_s or (double)in_ts < min_overlap * (double)n_t; otherwise
+ *   min((double)hit_st / (double)in_st, (double)hit_ts / (double)in_ts).
+ *   - voxel: 0, or a positive finite float with a finite reciprocal; 0 means 2 * params.resolution.  min_points >= 1.
+ *     0 <= min_overlap <= 1.  view_margin 0 or 1.
+ *   - Applies to mm3d_estimate_maps_transforms (one stream or many, with or without the map cache) and mm3d_pair_estimate:
+ *     the record's confidence is the overlap confidence at the record's transform; every other field is what it would have
+ *     been, and nothing is taken from the rand() replay.  The reference's transformScore is then not run at all.
+ *   - mm3d_map_prepare builds a map's table on an overlap context; a pair needs BOTH maps' tables, and either is built on first
+ *     use when missing or made with other options.
+ *   - The setting reaches the context's mm3d_set_streams helpers in either order of the two calls.  All counts are integer
+ *     sums: identical for every launch shape, batch, stream count and cache setting, and through mm3d_transform_overlap.
+ *   - The map cache's pair key holds the method and, under overlap, its four options. */
+typedef enum { MM3D_CONFIDENCE_REFERENCE = 0, MM3D_CONFIDENCE_OVERLAP = 1 } mm3d_confidence_method;
+typedef struct mm3d_confidence_options {
+  int method;            /* MM3D_CONFIDENCE_* */
+  double voxel;          /* voxel side in metres, > 0; 0 = 2 * params.resolution */
+  int min_points;        /* a view cell with fewer finite points has not been seen; >= 1 */
+  double min_overlap;    /* the share of a map's finite points that must fall in the other's view, 0 .. 1 */
+  int view_margin;       /* 0: a view cell counts when seen; 1: when it or one of its 26 neighbours is */
+} mm3d_confidence_options;
+typedef struct mm3d_overlap_stats {
+  long long points_st, in_st, hit_st;   /* source -> target: finite source points, in the target's view, near a target voxel */
+  long long points_ts, in_ts, hit_ts;   /* target -> source */
+  double confidence;
+} mm3d_overlap_stats;
+void mm3d_confidence_options_default(mm3d_confidence_options *o);   /* REFERENCE, 0, 8, 0.05, 0 */
+/* MM3D_EINVAL: ctx or options NULL, an unknown method, a value outside its range above (the values are checked whatever the
+ * method).  MM3D_EUNSUPPORTED: MM3D_CONFIDENCE_OVERLAP on a device-list context (mm3d_create_devices), whose bundles carry
+ * no tables -- nor does mm3d_shard_begin, which returns MM3D_EUNSUPPORTED on an overlap context. */
+int mm3d_set_confidence(mm3d_ctx *ctx, const mm3d_confidence_options *options);
+int mm3d_get_confidence(const mm3d_ctx *ctx, mm3d_confidence_options *options);      /* MM3D_EINVAL for NULL */
+/* of the most recent pair this context scored itself (the last pair of a whole-map call on one stream, or the call below) */
+int mm3d_last_confidence_stats(const mm3d_ctx *ctx, mm3d_overlap_stats *stats);
+/* The overlap confidence of two clouds under T (column-major, as in the pair record), whatever the context's setting and
+ * options->method; options->voxel must be > 0 here.  Builds throw-away tables.  stats receives the counts and the
+ * confidence.  MM3D_EINVAL: a NULL argument, options out of range; MM3D_EUNSUPPORTED: a limit above. */
+int mm3d_transform_overlap(mm3d_ctx *ctx, const mm3d_cloud *source, const mm3d_cloud *target, const float T[16],
+                           const mm3d_confidence_options *options, mm3d_overlap_stats *stats);
+/* test hook: a cloud's table.  box[12] = brick box minimum (3) and extent (3), view box minimum (3) and extent (3); words
+ * receives the near words when word_cap >= their number, view the bytes when view_cap >= theirs (either may be NULL with a
+ * cap of 0).  A cloud without a finite point: box all 0. */
+int mm3d_debug_overlap_table(mm3d_ctx *ctx, const mm3d_cloud *cloud, const mm3d_confidence_options *options, int box[12],
+                             unsigned long long *words, size_t word_cap, unsigned char *view, size_t view_cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -152,6 +152,38 @@ class CoarseStats(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class ConfidenceMethod(enum.IntEnum):   # mm3d_confidence_method (not a reference enum)
+    REFERENCE = 0
+    OVERLAP = 1
+
+
+class ConfidenceOptions(C.Structure):
+    """mm3d_confidence_options (mm3d_set_confidence); the defaults are mm3d_confidence_options_default's."""
+    _fields_ = [("method", C.c_int), ("voxel", C.c_double), ("min_points", C.c_int), ("min_overlap", C.c_double),
+                ("view_margin", C.c_int)]
+
+    def __init__(self, **kw):
+        super().__init__()
+        lib().mm3d_confidence_options_default(C.byref(self))
+        kinds = dict(self._fields_)
+        for k, v in kw.items():
+            if k not in kinds:
+                raise TypeError("unknown confidence option " + k)
+            setattr(self, k, int(v) if kinds[k] is C.c_int else float(v))
+
+    def as_tuple(self):
+        return tuple(int(getattr(self, k)) if t is C.c_int else float(getattr(self, k)) for k, t in self._fields_)
+
+
+class OverlapStats(C.Structure):
+    """mm3d_overlap_stats"""
+    _fields_ = [("points_st", C.c_longlong), ("in_st", C.c_longlong), ("hit_st", C.c_longlong), ("points_ts", C.c_longlong),
+                ("in_ts", C.c_longlong), ("hit_ts", C.c_longlong), ("confidence", C.c_double)]
+
+    def as_dict(self):
+        return {k: (float if t is C.c_double else int)(getattr(self, k)) for k, t in self._fields_}
+
+
 class AlignmentStats(C.Structure):
     """mm3d_alignment_stats"""
     _fields_ = [("draws", C.c_longlong), ("survivors", C.c_longlong), ("hypotheses_scored", C.c_longlong),
@@ -412,6 +444,23 @@ class Context:
         self._ck(lib().mm3d_last_coarse_stats(self._h, C.byref(st)))
         return st.as_dict()
 
+    def setConfidence(self, options=None, **kw):
+        """mm3d_set_confidence: what a pair record's confidence is.  A ConfidenceOptions, or its fields as keywords
+        (method=ConfidenceMethod.OVERLAP, voxel=... in metres; 0 = the default multiple of params.resolution, min_points=...,
+        min_overlap=..., view_margin=0 or 1).  Under OVERLAP the confidence lives in [0, 1]."""
+        o = options if options is not None else ConfidenceOptions(**kw)
+        self._ck(lib().mm3d_set_confidence(self._h, C.byref(o)))
+
+    def getConfidence(self) -> "ConfidenceOptions":
+        o = ConfidenceOptions()
+        self._ck(lib().mm3d_get_confidence(self._h, C.byref(o)))
+        return o
+
+    def lastConfidenceStats(self) -> dict:
+        st = OverlapStats()
+        self._ck(lib().mm3d_last_confidence_stats(self._h, C.byref(st)))
+        return st.as_dict()
+
     def synchronize(self):
         self._ck(lib().mm3d_synchronize(self._h))
 
@@ -663,6 +712,30 @@ class Context:
                                                         C.c_size_t(K), C.byref(n)))
         m = int(n.value)
         return dict(frame=tuple(int(x) for x in frame), acc=acc, cands=cands[:m].copy(), scores=scores[:m].copy())
+
+    def transformOverlap(self, source_points, target_points, transform, options=None, **kw) -> dict:
+        """mm3d_transform_overlap: the overlap confidence of two clouds under `transform` (4 x 4) and its six counts, whatever
+        the context's setting (options.voxel > 0)."""
+        o = options if options is not None else ConfidenceOptions(**kw)
+        T = _T(transform)
+        st = OverlapStats()
+        self._ck(lib().mm3d_transform_overlap(self._h, source_points._h, target_points._h, T.ctypes.data_as(C.c_void_p), C.byref(o),
+                                              C.byref(st)))
+        return st.as_dict()
+
+    def debugOverlapTable(self, points, options=None, **kw) -> dict:
+        """mm3d_debug_overlap_table: brick0 / bricks / view0 / views (3 ints each), words uint64 [bricks] and view uint8
+        [views], both i-major."""
+        o = options if options is not None else ConfidenceOptions(**kw)
+        box = (C.c_int * 12)()
+        self._ck(lib().mm3d_debug_overlap_table(self._h, points._h, C.byref(o), box, None, C.c_size_t(0), None, C.c_size_t(0)))
+        b = [int(x) for x in box]
+        words = np.zeros(tuple(b[3:6]), dtype=np.uint64)
+        view = np.zeros(tuple(b[9:12]), dtype=np.uint8)
+        if words.size:
+            self._ck(lib().mm3d_debug_overlap_table(self._h, points._h, C.byref(o), box, words.ctypes.data_as(C.c_void_p),
+                                                    C.c_size_t(words.size), view.ctypes.data_as(C.c_void_p), C.c_size_t(view.size)))
+        return dict(brick0=tuple(b[0:3]), bricks=tuple(b[3:6]), view0=tuple(b[6:9]), views=tuple(b[9:12]), words=words, view=view)
 
     def estimateTransform(self, source_points, source_keypoints, source_descriptors, target_points,
                           target_keypoints, target_descriptors, method, refine, inlier_threshold,

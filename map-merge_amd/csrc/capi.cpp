@@ -222,6 +222,8 @@ static void set_streams_one(mm3d_ctx *ctx, int n_streams)
     h->refine_options = ctx->refine_options;
     h->coarse_method = ctx->coarse_method;              // (mm3d_set_coarse_alignment likewise)
     h->coarse_options = ctx->coarse_options;
+    h->confidence_method = ctx->confidence_method;      // (mm3d_set_confidence likewise)
+    h->confidence_options = ctx->confidence_options;
     ctx->helpers.push_back(h);
   }
 }
@@ -691,7 +693,7 @@ int mm3d_estimate_maps_transforms(mm3d_ctx *ctx, const mm3d_cloud_view *clouds, 
       ~CacheCall() { if (c && !ok) c->abort(); }
     } cache_call{ctx->map_cache};
     if (ctx->map_cache) ctx->map_cache->begin(n, params, ctx->icp_method ? ctx->icp_method->method() : MM3D_ICP_POINT_TO_POINT, ctx->align_options,
-                                                  ctx->keypoint_options, ctx->refine_options, ctx->coarse_options);
+                                                  ctx->keypoint_options, ctx->refine_options, ctx->coarse_options, ctx->confidence_options);
     if (!ctx->helpers.empty())
       estimate_maps_streams(ctx, clouds, n, params, out_T, n_out, pairs_out, n_pairs_out);
     else

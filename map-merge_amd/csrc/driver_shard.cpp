@@ -57,6 +57,7 @@ int mm3d_shard_begin(mm3d_ctx *ctx, const mm3d_cloud_view *clouds, size_t n, con
   *out = nullptr;
   return guarded(ctx, [&] {
     if (ctx->icp_method) throw Error(MM3D_EUNSUPPORTED, "mm3d_shard_begin: shard bundles carry no normals for point-to-plane ICP");
+    if (ctx->confidence_method) throw Error(MM3D_EUNSUPPORTED, "mm3d_shard_begin: shard bundles carry no tables for the overlap confidence");
     if (ctx->coarse_method) throw Error(MM3D_EUNSUPPORTED, "mm3d_shard_begin: shard bundles carry no signatures for the correlative alignment");
     if (ctx->refine_method) throw Error(MM3D_EUNSUPPORTED, "mm3d_shard_begin: shard bundles carry no voxel tables for NDT");
     if (ctx->align_method) throw Error(MM3D_EUNSUPPORTED, "mm3d_shard_begin: the ranks' pair loops run SAC-IA, not the prerejective alignment");

@@ -46,7 +46,7 @@ std::string feature_key(const mm3d_params *p, const mm3d_keypoint_options &kp)
 // point-to-point record is never one of point-to-plane's.  (The map key needs no method: the normals point-to-plane keeps are
 // a function of the points and normal_radius.)
 std::string pair_params_key(const mm3d_params *p, int icp_method, const mm3d_alignment_options &align, const mm3d_refine_options &refine,
-                            const mm3d_coarse_options &coarse)
+                            const mm3d_coarse_options &coarse, const mm3d_confidence_options &conf)
 {
   KeyBuilder k;
   k.i32(p->estimation_method).i32(p->refine_transform).f64(p->inlier_threshold).f64(p->max_correspondence_distance)
@@ -64,6 +64,11 @@ std::string pair_params_key(const mm3d_params *p, int icp_method, const mm3d_ali
   k.i32(coarse.method).f64(corr ? coarse.cell : 0.0).i32(corr ? coarse.cell_factor : 0).i32(corr ? coarse.yaw_steps : 0)
       .i32(corr ? coarse.yaw_factor : 0).i32(corr ? coarse.candidates : 0).f64(corr ? coarse.wall_nz : 0.0)
       .f64(corr ? coarse.ground_nz : 0.0).i32(corr ? coarse.min_points : 0).f64(corr ? coarse.accept_fraction : 0.0);
+  // the confidence (mm3d_set_confidence): a record with the reference's confidence is never one with the overlap confidence,
+  // nor an overlap one that of other options (which the reference's does not read: whatever they are, its records are shared)
+  const bool ovl = conf.method == MM3D_CONFIDENCE_OVERLAP;
+  k.i32(conf.method).f64(ovl ? conf.voxel : 0.0).i32(ovl ? conf.min_points : 0).f64(ovl ? conf.min_overlap : 0.0)
+      .i32(ovl ? conf.view_margin : 0);
   return k.s;
 }
 
@@ -100,7 +105,8 @@ struct Entry {
            (map->normals ? map->normals->nrm.size() * 16 : 0) +   // (normals: point-to-plane ICP only)
            (map->ndt ? map->ndt->rec.size() * 16 + map->ndt->index.size() * 4 : 0) +   // (voxel table: NDT only)
            (map->coarse ? (map->coarse->scells.size() + map->coarse->gcells.size()) * 16 + map->coarse->ccells.size() * 8 +
-                              map->coarse->dil.size() + map->coarse->gh.size() * 4 : 0);   // (signature: correlative alignment only)
+                              map->coarse->dil.size() + map->coarse->gh.size() * 4 : 0) +   // (signature: correlative alignment only)
+           (map->overlap ? map->overlap->near.size() * 8 + map->overlap->view.size() : 0);   // (table: overlap confidence only)
   }
 };
 
@@ -141,12 +147,13 @@ class MapCache final : public MapCacheBase {
   }
 
   void begin(size_t n_maps, const mm3d_params *p, int icp_method, const mm3d_alignment_options &align,
-             const mm3d_keypoint_options &keypoints, const mm3d_refine_options &refine, const mm3d_coarse_options &coarse) override
+             const mm3d_keypoint_options &keypoints, const mm3d_refine_options &refine, const mm3d_coarse_options &coarse,
+             const mm3d_confidence_options &confidence) override
   {
     std::lock_guard<std::mutex> lk(mu_);
     reset_call_locked();
     fkey_ = feature_key(p, keypoints);
-    pkey_ = pair_params_key(p, icp_method, align, refine, coarse);
+    pkey_ = pair_params_key(p, icp_method, align, refine, coarse, confidence);
     // (the correlative alignment reads neither the generator nor its seed: no state in its pairs' keys)
     sac_ia_ = p->estimation_method == MM3D_EST_SAC_IA && coarse.method != MM3D_COARSE_CORRELATIVE;
     prerej_ = sac_ia_ && align.method == MM3D_ALIGN_PREREJECTIVE;

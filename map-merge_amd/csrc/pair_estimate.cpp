@@ -85,6 +85,7 @@ void mm3d::map_prepare_impl(mm3d_ctx *ctx, mm3d_map *m, const mm3d_params *p)
   if (ctx->icp_method && !m->normals) m->normals.reset(compute_normals(ctx, m->points, p->normal_radius));
   if (ctx->refine_method) ctx->refine_method->prepare_target(ctx, m, p, nullptr);   // NDT's voxel table (mm3d_set_refinement)
   if (ctx->coarse_method) ctx->coarse_method->prepare(ctx, m, p);                   // the correlative signature (mm3d_set_coarse_alignment)
+  if (ctx->confidence_method) ctx->confidence_method->prepare(ctx, m, p);           // the overlap table (mm3d_set_confidence)
   prepare_pair_search(ctx, m->points, p->max_correspondence_distance, p->max_correspondence_distance);
   if (p->estimation_method == MM3D_EST_SAC_IA && ctx->align_method) ctx->align_method->prepare(ctx, m->keypoints, p->max_correspondence_distance);
   else if (p->estimation_method == MM3D_EST_SAC_IA) prepare_sacia_target(ctx, m->keypoints, (float)p->max_correspondence_distance);
@@ -166,9 +167,9 @@ void mm3d::pair_record_init(mm3d_pair_result *r, size_t source, size_t target)
 void mm3d::pair_estimate_impl(mm3d_ctx *ctx, const mm3d_map *s, const mm3d_map *t, const mm3d_params *p, bool execute,
                              mm3d_pair_result *out)
 {
-  if (execute && (ctx->icp_method || ctx->refine_method || ctx->coarse_method || prerejective(ctx, p))) {
-    // point-to-plane ICP (mm3d_set_icp_method), NDT (mm3d_set_refinement) and the prerejective alignment (mm3d_set_alignment) live in the batch path: a
-    // batch of one, from (and advancing) the context's generator
+  if (execute && (ctx->icp_method || ctx->refine_method || ctx->coarse_method || ctx->confidence_method || prerejective(ctx, p))) {
+    // point-to-plane ICP (mm3d_set_icp_method), NDT (mm3d_set_refinement), the prerejective alignment (mm3d_set_alignment) and the
+    // overlap confidence (mm3d_set_confidence) live in the batch path: a batch of one, from (and advancing) the context's generator
     PairWork w{s, t, out, ctx->rnd};
     pairs_estimate_batch(ctx, &w, 1, p);
     return;
@@ -282,19 +283,21 @@ void mm3d::pairs_estimate_batch(mm3d_ctx *ctx, PairWork *w, size_t n, const mm3d
     std::memcpy(jobs[i].guess_host, fronts[i].T0, sizeof(fronts[i].T0));
   }
   // estimateTransform's ICP and transformScore of its result (R/src/map_merging.cpp:91-107), max_distance = max_correspondence_distance
+  // (under mm3d_set_confidence nobody reads that score: it is not launched, and the ICP's states come back as they would have)
+  const bool want_score = !ctx->confidence_method;
   if (ctx->refine_method) {                             // NDT in the ICP's place (mm3d_set_refinement): the targets' voxel tables
     if (p->refine_transform)
       for (size_t i = 0; i < n; ++i) ctx->refine_method->prepare_target(ctx, w[i].t, p, &jobs[i]);
     ctx->refine_method->score_batch(ctx, jobs.data(), (int)n, p->refine_transform != 0, p->max_correspondence_distance, p->max_iterations,
-                                    p->transform_epsilon, true, p->max_correspondence_distance);
+                                    p->transform_epsilon, want_score, p->max_correspondence_distance);
   } else if (ctx->icp_method) {                         // point-to-plane (mm3d_set_icp_method): the targets' normals
     if (p->refine_transform)
       for (size_t i = 0; i < n; ++i) jobs[i].tgt_normals = map_normals(ctx, w[i].t, p);
     ctx->icp_method->score_batch(ctx, jobs.data(), (int)n, p->refine_transform != 0, p->max_correspondence_distance, p->max_iterations,
-                                 p->transform_epsilon, true, p->max_correspondence_distance);
+                                 p->transform_epsilon, want_score, p->max_correspondence_distance);
   } else {
     icp_score_batch(ctx, jobs.data(), (int)n, p->refine_transform != 0, p->max_correspondence_distance, p->max_iterations, p->transform_epsilon,
-                    true, p->max_correspondence_distance);
+                    want_score, p->max_correspondence_distance);
   }
   for (size_t i = 0; i < n; ++i) {
     mm3d_pair_result *out = w[i].out;
@@ -304,6 +307,13 @@ void mm3d::pairs_estimate_batch(mm3d_ctx *ctx, PairWork *w, size_t n, const mm3d
     out->n_inliers = fronts[i].counts.n_inliers;
     out->icp_correspondences = jobs[i].out.n_corr;
     out->confidence = 1.0 / jobs[i].out.score;
+  }
+  if (ctx->confidence_method) {
+    // the transforms are on the host: both maps' tables (made on first use), one launch and one wait for the whole batch
+    std::vector<ConfidencePair> cp(n);
+    for (size_t i = 0; i < n; ++i) cp[i] = ConfidencePair{w[i].s, w[i].t, w[i].out->transform, 0.0};
+    ctx->confidence_method->score(ctx, cp.data(), n, p, &ctx->last_confidence_stats);
+    for (size_t i = 0; i < n; ++i) w[i].out->confidence = cp[i].confidence;
   }
 }
 

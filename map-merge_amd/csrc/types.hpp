@@ -18,6 +18,7 @@ struct IcpMethodBase;
 struct AlignMethodBase;
 struct KeypointSourceBase;
 struct CoarseMethodBase;
+struct ConfidenceMethodBase;
 
 // The feature / pair cache of mm3d_estimate_maps_transforms (mm3d_set_map_cache; the concrete class is map_cache.cpp's).  The
 // drivers in capi.cpp only see this interface, so the host code links without it (tests/host_san).  One call at a time -- the
@@ -27,9 +28,11 @@ struct MapCacheBase {
   virtual ~MapCacheBase() = default;
   // icp_method: MM3D_ICP_* of the call (mm3d_set_icp_method); align: its alignment (mm3d_set_alignment); keypoints: where its
   // maps' keypoints come from (mm3d_set_keypoints); refine: what refines its pairs (mm3d_set_refinement)
-  // coarse: what replaces its pairs' initial estimate (mm3d_set_coarse_alignment)
+  // coarse: what replaces its pairs' initial estimate (mm3d_set_coarse_alignment); confidence: what their records' confidence
+  // is (mm3d_set_confidence)
   virtual void begin(size_t n_maps, const mm3d_params *p, int icp_method, const mm3d_alignment_options &align,
-                     const mm3d_keypoint_options &keypoints, const mm3d_refine_options &refine, const mm3d_coarse_options &coarse) = 0;
+                     const mm3d_keypoint_options &keypoints, const mm3d_refine_options &refine, const mm3d_coarse_options &coarse,
+                     const mm3d_confidence_options &confidence) = 0;
   // map `slot`'s packed upload `raw` (non-empty, on c's stream): the cached bundle, borrowed for the call, or null.  One launch and
   // one wait on c (a second compare-only launch and wait when the digest names another candidate than the slot's last entry).
   virtual const mm3d_map *lookup(Context *c, size_t slot, const mm3d_cloud *raw) = 0;
@@ -73,6 +76,12 @@ struct mm3d_ctx : mm3d::Context {
   const mm3d::CoarseMethodBase *coarse_method = nullptr;
   mm3d_coarse_options coarse_options{MM3D_COARSE_NONE, 0.0, 4, 720, 6, 32, 0.5, 0.9, 3, 0.25};
   mm3d_coarse_stats last_coarse_stats{0, 0, 0, 0, 0, -1, 0, 0};
+  // mm3d_set_confidence: null = the reference's 1 / transformScore; otherwise it replaces a pair record's confidence after the
+  // pair stage (confidence_overlap.hip).  Not owned (a process-wide object that holds no state); set, with the options, on the
+  // context and its helpers alike, and copied to helpers that mm3d_set_streams makes later.
+  const mm3d::ConfidenceMethodBase *confidence_method = nullptr;
+  mm3d_confidence_options confidence_options{MM3D_CONFIDENCE_REFERENCE, 0.0, 8, 0.05, 0};
+  mm3d_overlap_stats last_confidence_stats{0, 0, 0, 0, 0, 0, 0.0};
   // mm3d_set_streams: helper contexts (one HIP stream + one host thread each while a call is running)
   // that mm3d_estimate_maps_transforms deals maps and pairs to; owned by this context
   std::vector<mm3d_ctx *> helpers;
@@ -165,6 +174,20 @@ struct CoarseSignature {
   DevBuf<float> gh;            // dense: a ground cell's height, NaN elsewhere
 };
 
+// What the overlap confidence keeps of a map (confidence_overlap.hip, mm3d_set_confidence): which voxels of the global lattice
+// lie within one voxel of a point, one bit each in 4 x 4 x 4 bricks, and which 8-voxel view cells the map has seen, one byte
+// each; both dense over the brick box of the finite points.  8 B per brick plus 1 B per view cell.
+struct OverlapTable {
+  double voxel = 0.0;                              // what it was built with (a map's table is rebuilt when these change)
+  int min_points = 0, view_margin = 0;
+  float inv = 0.f;                                 // 1.0f / (float)voxel
+  int b0[3] = {0, 0, 0}, nb[3] = {0, 0, 0};        // the brick box: minimum and extent; word ((bi-b0i) * nb[1] + (bj-b0j)) * nb[2] + (bk-b0k)
+  int c0[3] = {0, 0, 0}, nc[3] = {0, 0, 0};        // the view-cell box, in the same order
+  size_t n_finite = 0;                             // the cloud's finite points
+  DevBuf<unsigned long long> near;                 // [nb[0] * nb[1] * nb[2]]
+  DevBuf<unsigned char> view;                      // [nc[0] * nc[1] * nc[2]]
+};
+
 }  // namespace mm3d
 
 struct mm3d_cloud {
@@ -231,6 +254,9 @@ struct mm3d_map {
   // the points' correlative signature, kept for mm3d_set_coarse_alignment only: null otherwise.  Made and replaced under the
   // points' cache_mu (mm3d_map_prepare, or a pair's first use of the map); the normals above are kept for it too.
   std::unique_ptr<mm3d::CoarseSignature> coarse;
+  // the points' overlap table, kept for mm3d_set_confidence only: null otherwise.  Made and replaced under the points'
+  // cache_mu (mm3d_map_prepare, or a pair's first use of the map, in either role).
+  std::unique_ptr<mm3d::OverlapTable> overlap;
   mm3d_map() = default;
   mm3d_map(const mm3d_map &) = delete;
   mm3d_map &operator=(const mm3d_map &) = delete;
@@ -401,6 +427,19 @@ struct CoarseMethodBase {
   virtual void prepare(mm3d_ctx *ctx, const mm3d_map *m, const mm3d_params *p) const = 0;
   // the pair's initial estimate: f.dT0 / f.on_device, or the identity in f.T0
   virtual void front(mm3d_ctx *ctx, const mm3d_map *s, const mm3d_map *t, const mm3d_params *p, PairFront &f, mm3d_coarse_stats *stats) const = 0;
+};
+// What a pair record's confidence is when it is not the reference's (mm3d_set_confidence; the one concrete class is
+// confidence_overlap.hip's).  Like CoarseMethodBase, the drivers and pair_estimate.cpp only see this interface, so the host
+// code links without the new kernels (tests/host_san); a null pointer on the context means 1 / transformScore.
+struct ConfidencePair { const mm3d_map *s, *t; const float *T; double confidence; };   // T: the pair's transform on the host, 16 floats
+struct ConfidenceMethodBase {
+  virtual ~ConfidenceMethodBase() = default;
+  // the map's table at the context's options: made when missing or stale, under the points' lock and complete on the device
+  // before anybody else can see it
+  virtual void prepare(mm3d_ctx *ctx, const mm3d_map *m, const mm3d_params *p) const = 0;
+  // the confidences of a batch of pairs at their host transforms: one launch, one wait; stats (may be null) receives the
+  // last pair's counts
+  virtual void score(mm3d_ctx *ctx, ConfidencePair *pairs, size_t n, const mm3d_params *p, mm3d_overlap_stats *stats) const = 0;
 };
 struct PairCounts { int n_correspondences = 0, n_inliers = 0, icp_correspondences = 0; };
 // ICP (optional) from a guess on the device (guess_dev != null) or on the host, then transformScore
