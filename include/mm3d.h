@@ -140,6 +140,16 @@ int mm3d_debug_libm(mm3d_ctx *ctx, int fn, const float *x, const float *y, int n
  * of the SPFH's exact pair features, their branch (0 no switch, 1 switched, 2 f4 == 0: the oracle's mo_pair_features code),
  * the exact path's three bins, the certified path's (pair_bins_fast) ok flag and its three bins (csrc/fpfh.hip) */
 int mm3d_debug_pair_bins(mm3d_ctx *ctx, const float *p1, const float *n1, const float *p2, const float *n2, int n, int *out);
+/* test hook: every wave-wide reduction / scan of csrc/device_util.hpp (DPP / permlane network) next to the shuffle loop it
+ * replaced (kept in csrc/libm_debug.hip), on the same input: n elements (a multiple of 256: whole blocks of four waves), every
+ * lane's result of the new form in out_new and of the old one in out_old, element type as the input's.
+ * op 0 wave_sum(double), 1 wave_sum(float), 2 wave_sum(int) -- lane 0 of every wave holds the sum;
+ * op 3 wave_min_int, 4 wave_max_int, 5 wave_min_f, 6 wave_max_f, 8 wave_min_u64 (uint64) -- every lane holds the result;
+ * op 7 wave_scan_incl(int), the inclusive prefix sum. */
+/* test hook: SAC-IA's error kernel takes k source keypoints per thread (1, 2, 4 or 8) in every launch from now on, whatever
+ * its size; 0: chosen by the launch's size again; negative: no change.  Returns the count large launches use. */
+int mm3d_debug_sacia_queries_per_thread(int k);
+int mm3d_debug_wave_primitives(mm3d_ctx *ctx, int op, const void *in, int n, void *out_new, void *out_old);
 /*
  * test hooks of the certified SIFT decision (csrc/sift_cert.hpp; the later octaves of detectKeypoints(SIFT),
  * R/src/features.cpp:45-62): the unsorted scale space of octave `octave` (0-based) on `points` -- val[5 i + s] and

@@ -296,6 +296,12 @@ def sacia_stats(reset=False, collect=-1):
     return list(out)
 
 
+def sacia_queries_per_thread(k=-1):
+    """mm3d_debug_sacia_queries_per_thread: force SAC-IA's error kernel to k source keypoints per thread (1, 2, 4, 8; 0: by
+    the launch's size again; negative: leave as it is).  Returns the count large launches use."""
+    return int(lib().mm3d_debug_sacia_queries_per_thread(int(k)))
+
+
 class Context:
     """One registration engine on one GPU (mm3d_ctx) -- or, with `devices`, on a list of GPUs of this one process
     (mm3d_create_devices): estimateMapsTransforms then shards over them inside the library and gathers the pair
@@ -747,6 +753,17 @@ class Context:
             C.c_double(max_correspondence_distance), int(max_iterations), C.c_size_t(matching_k),
             C.c_double(transform_epsilon), T.ctypes.data_as(C.c_void_p)))
         return _Tout(T)
+
+    def debugWavePrimitives(self, op, values):
+        """mm3d_debug_wave_primitives: one wave reduction / scan of device_util.hpp and the shuffle loop it replaced on the
+        same input (a multiple of 256 elements; float64 for op 0, float32 for 1, 5, 6, uint64 for 8, int32 otherwise).
+        Returns (new, old), every lane's result."""
+        dt = {0: np.float64, 1: np.float32, 5: np.float32, 6: np.float32, 8: np.uint64}.get(int(op), np.int32)
+        v = np.ascontiguousarray(values, dtype=dt)
+        new, old = np.empty_like(v), np.empty_like(v)
+        self._ck(lib().mm3d_debug_wave_primitives(self._h, int(op), v.ctypes.data_as(C.c_void_p), len(v),
+                                                  new.ctypes.data_as(C.c_void_p), old.ctypes.data_as(C.c_void_p)))
+        return new, old
 
     def debugNnSearch(self, source_points, target_points, transform, range, convention, split):
         """mm3d_debug_nn_search: the ICP / score nearest-neighbour search point by point.  convention 0 reads `range` as ICP's

@@ -287,7 +287,6 @@ constexpr int kThetaExtra = 6;
 constexpr int kFilterCap = 512;
 
 __device__ __forceinline__ unsigned knn_ordered_bits(float v);
-__device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v);
 template <int kD>
 __device__ __forceinline__ void knn_exact_range_row(const float (&x)[kD], float U, int row, const float *__restrict__ B, int nb, int k,
                                                     const uint32_t *__restrict__ nsort, const uint32_t *__restrict__ nperm, int lane,
@@ -564,12 +563,7 @@ k_knn_rerank(const float *__restrict__ A, int na, const float *__restrict__ B, i
   float kth = INFINITY;
   for (int o = 0; o < k; ++o) {
     const unsigned long long key = ((unsigned long long)__float_as_uint(bd[0]) << 32) | (unsigned)bi[0];
-    unsigned long long best = key;
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) {
-      const unsigned long long other = __shfl_xor(best, s, kWave);
-      best = other < best ? other : best;
-    }
+    const unsigned long long best = wave_min_u64(key);
     const float d = __uint_as_float((unsigned)(best >> 32));
     if (lane == 0) {
       idx[(size_t)a * k + o] = d < INFINITY ? (int)(unsigned)(best & 0xffffffffull) : -1;
@@ -1065,15 +1059,6 @@ __device__ __forceinline__ unsigned knn_ordered_bits(float v)
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
-__device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v)
-{
-#pragma unroll
-  for (int s = 32; s > 0; s >>= 1) {
-    const unsigned long long o = __shfl_xor(v, s, kWave);
-    v = o < v ? o : v;
-  }
-  return v;
-}
 
 // One wave per query row.  An exact distance costs a 1344-term chain per candidate, so only the
 // candidates that can still be among the k nearest are re-ranked:

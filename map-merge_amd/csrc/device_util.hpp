@@ -148,51 +148,119 @@ __device__ __forceinline__ bool acos_abs_greater(float a1, float a2)
 // builtin takes the i1 as it is (the comparison's own lane mask).
 __device__ __forceinline__ unsigned long long ballot(bool p) { return __builtin_amdgcn_ballot_w64(p); }
 
-// ---- wave / block reductions -------------------------------------------------------------------
+// ---- wave reductions and scans on the DPP / permlane network --------------------------------------------
+// Six dependent VALU operations instead of six ds_bpermute round trips through the LDS pipe (~80
+// cycles against ~440, and nothing queued behind the other kernels' LDS traffic).  A DPP read from a disabled lane does
+// not return what a shuffle returns: every function here must be called in wave-uniform control flow with all 64 lanes
+// enabled (every call site does: DESIGN.md section 5 lists what was read).  The shuffle loops these replaced live on in
+// libm_debug.hip, where tests/test_gpu_wave_primitives.py holds the two against each other.
+template <int CTRL, int ROWMASK = 0xf, int BANKMASK = 0xf>
+__device__ __forceinline__ int dpp_i(int old, int v)                  // lanes without a source (or masked off) get `old`
+{
+  return __builtin_amdgcn_update_dpp(old, v, CTRL, ROWMASK, BANKMASK, false);
+}
+template <int CTRL, int ROWMASK = 0xf>
+__device__ __forceinline__ float dpp_f(float v) { return __int_as_float(dpp_i<CTRL, ROWMASK>(__float_as_int(v), __float_as_int(v))); }
+template <int CTRL>
+__device__ __forceinline__ double dpp_d(double v)
+{
+  const long long b = __double_as_longlong(v);
+  const int lo = (int)b, hi = (int)(b >> 32);
+  const unsigned l2 = (unsigned)dpp_i<CTRL>(lo, lo), h2 = (unsigned)dpp_i<CTRL>(hi, hi);
+  return __longlong_as_double((long long)(((unsigned long long)h2 << 32) | l2));
+}
+// lane l < 32 receives lane l + 32's word (v_permlane32_swap: the upper half of one operand against the lower half of the
+// other); lane l of rows 0 and 2 receives lane l + 16's (v_permlane16_swap: odd rows against even rows).  The other lanes
+// receive their own word.
+__device__ __forceinline__ unsigned lane_plus32(unsigned v) { return __builtin_amdgcn_permlane32_swap(v, v, false, false)[1]; }
+__device__ __forceinline__ unsigned lane_plus16(unsigned v) { return __builtin_amdgcn_permlane16_swap(v, v, false, false)[1]; }
+template <unsigned (*SWAP)(unsigned)>
+__device__ __forceinline__ double swap_d(double v)
+{
+  const unsigned long long b = (unsigned long long)__double_as_longlong(v);
+  return __longlong_as_double((long long)(((unsigned long long)SWAP((unsigned)(b >> 32)) << 32) | SWAP((unsigned)b)));
+}
+
+// Inclusive prefix sum: row shifts inside the rows of 16 lanes, then the two row broadcasts.
+__device__ __forceinline__ int wave_scan_incl(int v)
+{
+  v += dpp_i<0x111>(0, v);            // row_shr:1
+  v += dpp_i<0x112>(0, v);            // row_shr:2
+  v += dpp_i<0x114>(0, v);            // row_shr:4
+  v += dpp_i<0x118>(0, v);            // row_shr:8
+  v += dpp_i<0x142, 0xa>(0, v);       // row_bcast:15 into rows 1, 3
+  v += dpp_i<0x143, 0xc>(0, v);       // row_bcast:31 into rows 2, 3
+  return v;
+}
+
+// Floating-point sums: lane 0 holds the result (no other lane does).  The pairs and their order are those of
+// "v += shuffle_down(v, o)" for o = 32, 16, 8, 4, 2, 1, which these functions replaced: lane l adds lane l + o's value to
+// its own, so lane 0's bits are what they always were.  Distances 32 and 16 cross rows (permlane swaps), 8 .. 1 are row_shl.
 __device__ __forceinline__ double wave_sum(double v)
 {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, kWave);
+  v += swap_d<lane_plus32>(v);
+  v += swap_d<lane_plus16>(v);
+  v += dpp_d<0x108>(v);
+  v += dpp_d<0x104>(v);
+  v += dpp_d<0x102>(v);
+  v += dpp_d<0x101>(v);
   return v;
 }
 __device__ __forceinline__ float wave_sum(float v)
 {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, kWave);
+  v += __uint_as_float(lane_plus32(__float_as_uint(v)));
+  v += __uint_as_float(lane_plus16(__float_as_uint(v)));
+  v += dpp_f<0x108>(v);
+  v += dpp_f<0x104>(v);
+  v += dpp_f<0x102>(v);
+  v += dpp_f<0x101>(v);
   return v;
 }
-__device__ __forceinline__ int wave_sum(int v)
-{
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, kWave);
-  return v;
-}
+// Integer reductions are free in their order: reduce towards lane 63, read it into a scalar.  Wave-uniform results.
+__device__ __forceinline__ int wave_sum(int v) { return __builtin_amdgcn_readlane(wave_scan_incl(v), 63); }
 
+#define MM3D_WAVE_REDUCE(v, OP, DPP)                                                                           \
+  v = OP(v, DPP<0x111>(v)); v = OP(v, DPP<0x112>(v)); v = OP(v, DPP<0x114>(v)); v = OP(v, DPP<0x118>(v));      \
+  v = OP(v, DPP<0x142, 0xa>(v)); v = OP(v, DPP<0x143, 0xc>(v))
+template <int CTRL, int ROWMASK = 0xf>
+__device__ __forceinline__ int dpp_own_i(int v) { return dpp_i<CTRL, ROWMASK>(v, v); }
 __device__ __forceinline__ int wave_min_int(int v)
 {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, kWave));
-  return v;
+  MM3D_WAVE_REDUCE(v, min, dpp_own_i);
+  return __builtin_amdgcn_readlane(v, 63);
 }
 __device__ __forceinline__ int wave_max_int(int v)
 {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, kWave));
-  return v;
+  MM3D_WAVE_REDUCE(v, max, dpp_own_i);
+  return __builtin_amdgcn_readlane(v, 63);
 }
-
+// Float minima and maxima: fminf / fmaxf order -0 below +0 and drop a NaN against a number, so the result does not depend
+// on the pairing; every lane receives lane 63's bits (the shuffle butterfly these replaced left the same bits in every lane).
 __device__ __forceinline__ float wave_min_f(float v)
 {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o, kWave));
-  return v;
+  MM3D_WAVE_REDUCE(v, fminf, dpp_f);
+  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
 }
 __device__ __forceinline__ float wave_max_f(float v)
 {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, kWave));
-  return v;
+  MM3D_WAVE_REDUCE(v, fmaxf, dpp_f);
+  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
 }
+// 64-bit key minimum (integer keys: any order), wave-uniform
+__device__ __forceinline__ unsigned long long dpp_u64_min(unsigned long long v, unsigned long long o) { return o < v ? o : v; }
+template <int CTRL, int ROWMASK = 0xf>
+__device__ __forceinline__ unsigned long long dpp_own_u64(unsigned long long v)
+{
+  const int lo = (int)(unsigned)v, hi = (int)(unsigned)(v >> 32);
+  return ((unsigned long long)(unsigned)dpp_i<CTRL, ROWMASK>(hi, hi) << 32) | (unsigned)dpp_i<CTRL, ROWMASK>(lo, lo);
+}
+__device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v)
+{
+  MM3D_WAVE_REDUCE(v, dpp_u64_min, dpp_own_u64);
+  return ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), 63) << 32) |
+         (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, 63);
+}
+#undef MM3D_WAVE_REDUCE
 
 // LDS written by some lanes of a wave and read by others of the SAME wave: order the accesses for
 // the compiler; the hardware executes one wave's DS operations in order.
@@ -253,13 +321,8 @@ __device__ __forceinline__ void wave_stream_box(const GridView &g, int x0, int x
       b = g.cell_start[row + x0];
       len = g.cell_start[row + x1 + 1] - b;
     }
-    int incl = len;
-#pragma unroll
-    for (int o = 1; o < kWave; o <<= 1) {
-      const int t = __shfl_up(incl, o, kWave);
-      if (lane >= o) incl += t;
-    }
-    const int total = __shfl(incl, kWave - 1, kWave);
+    const int incl = wave_scan_incl(len);
+    const int total = __builtin_amdgcn_readlane(incl, kWave - 1);
     wave_lds_fence();                 // readers of the previous tile / offsets are done
     s_off[lane] = incl - len;
     s_beg[lane] = b;

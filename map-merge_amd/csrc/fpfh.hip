@@ -341,13 +341,8 @@ k_spfh(const float4 *__restrict__ q_pts, const int2 *__restrict__ items, int n_i
           MM3D_SPFH_STAT(2, __popc(all[0]) + __popc(all[1]));
           MM3D_SPFH_STAT(3, mine);
           // number the wave's hits: exclusive prefix of the per-lane counts
-          int incl = mine;
-#pragma unroll
-          for (int o = 1; o < kWave; o <<= 1) {
-            const int t = __shfl_up(incl, o, kWave);
-            if (lane >= o) incl += t;
-          }
-          const int total = __shfl(incl, kWave - 1, kWave);
+          const int incl = wave_scan_incl(mine);
+          const int total = __builtin_amdgcn_readlane(incl, kWave - 1);
           const int first = incl - mine;
           for (int base = 0; base < total; base += kSpfhPool) {   // one chunk unless nearly every lane hits every candidate
             {

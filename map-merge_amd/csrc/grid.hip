@@ -54,12 +54,7 @@ k_scan_int(const int *__restrict__ in, int *__restrict__ out, size_t n, unsigned
   for (int k = 0; k < kScanItems; ++k) sum += v[k];
   // block-wide exclusive scan of the per-thread sums
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int incl = sum;
-#pragma unroll
-  for (int o = 1; o < kWave; o <<= 1) {
-    const int t = __shfl_up(incl, o, kWave);
-    if (lane >= o) incl += t;
-  }
+  const int incl = wave_scan_incl(sum);
   if (lane == kWave - 1) s_wave[wave] = incl;
   __syncthreads();
   int wave_off = 0;
@@ -84,7 +79,6 @@ k_scan_int(const int *__restrict__ in, int *__restrict__ out, size_t n, unsigned
       prefix += wave_sum(take);
       if (first >= 0) break;
     }
-    prefix = __shfl(prefix, 0, kWave);
     if (lane == 0) {
       __hip_atomic_store(&status[tile], tag | (2ull << 32) | (unsigned)(prefix + total), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       s_prefix = prefix;
@@ -228,11 +222,7 @@ __global__ void k_bbox(const float4 *__restrict__ pts, size_t n, unsigned *__res
     }
   }
 #pragma unroll
-  for (int a = 0; a < 3; ++a)
-    for (int o = 32; o > 0; o >>= 1) {
-      mn[a] = fminf(mn[a], __shfl_down(mn[a], o, kWave));
-      mx[a] = fmaxf(mx[a], __shfl_down(mx[a], o, kWave));
-    }
+  for (int a = 0; a < 3; ++a) { mn[a] = wave_min_f(mn[a]); mx[a] = wave_max_f(mx[a]); }
   cnt = wave_sum(cnt);
   // one set of atomics per block (the seven words are shared by the whole grid)
   __shared__ float smn[4][3], smx[4][3];

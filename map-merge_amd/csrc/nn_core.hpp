@@ -88,18 +88,9 @@ struct NnJob {
   int max_ring;
 };
 
-__device__ __forceinline__ int wave_min_i(int v)
-{
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, kWave));
-  return v;
-}
-__device__ __forceinline__ int wave_max_i(int v)
-{
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, kWave));
-  return v;
-}
+// (wave-uniform, in a scalar register: device_util.hpp's DPP reductions)
+__device__ __forceinline__ int wave_min_i(int v) { return wave_min_int(v); }
+__device__ __forceinline__ int wave_max_i(int v) { return wave_max_int(v); }
 // LDS written by some lanes of a wave and read by others: order the accesses for the compiler;
 // the hardware executes one wave's DS operations in order.
 __device__ __forceinline__ void wave_lds_sync()

@@ -1,7 +1,9 @@
 // nn_search_body.hpp -- the body of the wave-cooperative exact nearest-neighbour search (nn.hip's header comment), included
-// TEXTUALLY inside a kernel's body: by k_nn_wave (nn.hip) and k_icp_plane_wave (icp_plane.hip).  A shared device function
-// would be the usual way, but it changes how the compiler schedules k_nn_wave, and that kernel's machine code is fixed
-// (its counters are recorded against it); the same tokens in the same place compile to the same code.
+// TEXTUALLY inside a kernel's body: by k_nn_wave and k_nn_probe (nn.hip) and k_icp_plane_wave (icp_plane.hip).  A shared
+// device function would be the usual way, but it changes how the compiler schedules k_nn_wave; the same tokens in the same
+// place compile to the same code, so the recorded counters of k_nn_wave (profiles/) describe all three.  Its wave-wide
+// minima, maxima and prefix scans run on the DPP network (device_util.hpp): they sit at the top level of the pass and
+// chunk loops, whose bounds are wave-uniform, with all 64 lanes enabled.
 //
 // Expects in scope: template parameters MODE (0: keyed search, 1: distance only) and SPLIT (1 or 4); `job` (its nblocks),
 // src, items, n_items, g, max_ring, Ts (the transform, in LDS, synchronised), max_d2, rmax, and the LDS arrays s_cx, s_cy,
@@ -186,13 +188,8 @@
       int mine = 0;
 #pragma unroll
       for (int u = 0; u < kRowsPerLane; ++u) { hl[u] -= hb[u]; mine += hl[u]; }
-      int incl = mine;
-#pragma unroll
-      for (int o = 1; o < kWave; o <<= 1) {
-        const int t = __shfl_up(incl, o, kWave);
-        if (lane >= o) incl += t;
-      }
-      const int total = __shfl(incl, kWave - 1, kWave);
+      const int incl = wave_scan_incl(mine);
+      const int total = __builtin_amdgcn_readlane(incl, kWave - 1);
       MM3D_STAT(2, 1);
       MM3D_STAT(3, total);
       MM3D_STAT(5, min(nspans - r0, kRows));

@@ -106,10 +106,13 @@ __global__ void k_sacia_models(const SacJob *__restrict__ jobs, int H)
 #define MM3D_SAC_SUB 1
 #endif
 constexpr int kSacSub = MM3D_SAC_SUB;
-__device__ __forceinline__ float sacia_term(const GridView &g, const float *Tl, const float4 s, float thresh, float radius)
+// In two steps, so that a thread with several queries can have all their span headers in flight before it scans the first:
+// sacia_locate transforms the keypoint and reads its cell's span, sacia_scan walks it.
+struct SacQuery { float3 p; int b, e; float slack; bool inside; };
+__device__ __forceinline__ SacQuery sacia_locate(const GridView &g, const float *Tl, const float4 s)
 {
-  const float3 p = xform(Tl, s.x, s.y, s.z);
-  float best = INFINITY;
+  SacQuery q;
+  q.p = xform(Tl, s.x, s.y, s.z);
   // 500 x K_s queries per pair against the same K_t targets: the stencil walk is taken out of the
   // query.  The target grid (cell = radius / kSacSub) carries, per cell, the merged list of the block
   // of cells the radius can reach (grid_ensure_nblists), ascending in distance from the cell centre.
@@ -117,18 +120,27 @@ __device__ __forceinline__ float sacia_term(const GridView &g, const float *Tl, 
   // query's own, exceeds min(best so far, radius): nothing later can be nearer.  An empty
   // span is the "nothing in range" answer most wrong hypotheses get.  The minimum itself is taken
   // over exact float distances, so the order of the scan does not show in the result.
-  const int cx = cell_floor(p.x, g.minx, g.inv), cy = cell_floor(p.y, g.miny, g.inv), cz = cell_floor(p.z, g.minz, g.inv);
-  const bool inside = cx >= 0 && cx < g.dx && cy >= 0 && cy < g.dy && cz >= 0 && cz < g.dz;
-  if (inside) {
-    const size_t c = ((size_t)cz * g.dy + cy) * g.dx + cx;
-    const int b = g.nb_start[c], e = g.nb_start[c + 1];
-    // |q - e| >= |e - centre| - |q - centre| for every entry e; 1e-3 cell covers the rounding of both terms
-    const float ox = p.x - (g.minx + ((float)cx + 0.5f) * g.cell), oy = p.y - (g.miny + ((float)cy + 0.5f) * g.cell);
-    const float oz = p.z - (g.minz + ((float)cz + 0.5f) * g.cell);
-    const float slack = sqrtf(ox * ox + oy * oy + oz * oz) + 1e-3f * g.cell;
+  const int cx = cell_floor(q.p.x, g.minx, g.inv), cy = cell_floor(q.p.y, g.miny, g.inv), cz = cell_floor(q.p.z, g.minz, g.inv);
+  q.inside = cx >= 0 && cx < g.dx && cy >= 0 && cy < g.dy && cz >= 0 && cz < g.dz;
+  // (a query outside the grid reads cell 0's header and ignores it: the load then waits for no branch)
+  const size_t c = q.inside ? ((size_t)cz * g.dy + cy) * g.dx + cx : 0;
+  q.b = g.nb_start[c];
+  q.e = g.nb_start[c + 1];
+  // |q - e| >= |e - centre| - |q - centre| for every entry e; 1e-3 cell covers the rounding of both terms
+  const float ox = q.p.x - (g.minx + ((float)cx + 0.5f) * g.cell), oy = q.p.y - (g.miny + ((float)cy + 0.5f) * g.cell);
+  const float oz = q.p.z - (g.minz + ((float)cz + 0.5f) * g.cell);
+  q.slack = sqrtf(ox * ox + oy * oy + oz * oz) + 1e-3f * g.cell;
+  return q;
+}
+__device__ __forceinline__ float sacia_scan(const GridView &g, const SacQuery &q, float thresh, float radius)
+{
+  const float3 p = q.p;
+  float best = INFINITY;
+  if (q.inside) {
+    const int e = q.e;
     float want = thresh;                              // squared distance still worth finding
     // four loads in flight per step; min is idempotent, so the tail just re-reads the last point
-    for (int j = b; j < e; j += 4) {
+    for (int j = q.b; j < e; j += 4) {
       const int last = e - 1;
       const float4 q0 = g.nb_pts[j];
       const float4 q1 = g.nb_pts[min(j + 1, last)];
@@ -138,17 +150,21 @@ __device__ __forceinline__ float sacia_term(const GridView &g, const float *Tl, 
       const float d2 = dist2(p.x, p.y, p.z, q2.x, q2.y, q2.z), d3 = dist2(p.x, p.y, p.z, q3.x, q3.y, q3.z);
       best = fminf(best, fminf(fminf(d0, d1), fminf(d2, d3)));
       want = fminf(want, best);
-      const float lb = q3.w - slack;
+      const float lb = q3.w - q.slack;
       if (lb > 0.0f && lb * lb > want) break;
     }
   } else {
     // outside the grid: clipped stencil walk
-    for_each_candidate(g, p.x, p.y, p.z, radius, [&](const float4 &q) {
-      best = fminf(best, dist2(p.x, p.y, p.z, q.x, q.y, q.z));
+    for_each_candidate(g, p.x, p.y, p.z, radius, [&](const float4 &t) {
+      best = fminf(best, dist2(p.x, p.y, p.z, t.x, t.y, t.z));
       return true;
     });
   }
   return (best <= thresh) ? best / thresh : 1.0f;
+}
+__device__ __forceinline__ float sacia_term(const GridView &g, const float *Tl, const float4 s, float thresh, float radius)
+{
+  return sacia_scan(g, sacia_locate(g, Tl, s), thresh, radius);
 }
 
 // Every (hypothesis, keypoint) term, summed per hypothesis in double and counted when it is not 1.0f: what the certified pick
@@ -156,25 +172,45 @@ __device__ __forceinline__ float sacia_term(const GridView &g, const float *Tl, 
 // cells: similar span lengths, shared cache lines).  Until round 6 the terms were WRITTEN, E[h][i], 31 MB per headline pair
 // in scattered 4-byte stores, for the float chains to read back; the chains that still run recompute theirs (k_sacia_exact):
 // the kernel alone 0.55 -> 0.42 ms per batch of three headline pairs, the headline + 3 %.
+// A thread takes K keypoints of its hypothesis (tile blockIdx.x = 256 K consecutive queries, thread t the queries t, t + 256,
+// ...): it has its K keypoints, then its K span headers in flight together, adds its terms up privately, and the wave
+// reduces once per K queries -- one model load, one reduction, one barrier and one pair of atomics where there were K.
+template <int K>
 __global__ void __launch_bounds__(256)
 k_sacia_err(const SacJob *__restrict__ jobs, int h_first, float thresh, float radius)
 {
   const SacJob &J = jobs[blockIdx.z];
   const int ns = J.ns;
-  if ((int)(blockIdx.x * blockDim.x) >= ns) return;   // (the grid is as wide as the batch's largest pair)
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  const bool valid = i < ns;
+  const int i0 = (int)blockIdx.x * (256 * K);
+  if (i0 >= ns) return;                               // (the grid is as wide as the batch's largest pair)
   const int h = h_first + (int)blockIdx.y;            // uniform: the model sits in scalar registers
   const float *T = J.T_all + (size_t)h * 16;
   float Tl[16];
 #pragma unroll
   for (int k = 0; k < 16; ++k) Tl[k] = T[k];
-  const float e_term = valid ? sacia_term(J.g, Tl, J.skp_q[i], thresh, radius) : 0.0f;
+  float4 s[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    const int i = i0 + k * 256 + (int)threadIdx.x;
+    s[k] = J.skp_q[i < ns ? i : i0];                  // (past the end: a query that is not counted)
+  }
+  SacQuery q[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) q[k] = sacia_locate(J.g, Tl, s[k]);
   // for the certified pick: the terms' sum in double (any order) and how many terms are not exactly 1.0f
+  double sum = 0.0;
+  int part = 0;
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    const bool valid = i0 + k * 256 + (int)threadIdx.x < ns;
+    const float e_term = valid ? sacia_scan(J.g, q[k], thresh, radius) : 0.0f;
+    sum += (double)e_term;
+    part += (valid && e_term != 1.0f) ? 1 : 0;
+  }
   __shared__ double s_sum[4];
   __shared__ int s_part[4];
-  const double ws = wave_sum((double)e_term);
-  const int part = __popcll(ballot(valid && e_term != 1.0f));
+  const double ws = wave_sum(sum);
+  part = wave_sum(part);
   if ((threadIdx.x & 63) == 0) { s_sum[threadIdx.x >> 6] = ws; s_part[threadIdx.x >> 6] = part; }
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -182,6 +218,22 @@ k_sacia_err(const SacJob *__restrict__ jobs, int h_first, float thresh, float ra
     const int pt = s_part[0] + s_part[1] + s_part[2] + s_part[3];
     if (pt) atomicAdd(&J.n_part[h], pt);
   }
+}
+// Queries per thread: kSacK where the launch still has tiles enough to fill the chip, one otherwise.
+#ifndef MM3D_SAC_K
+#define MM3D_SAC_K 4
+#endif
+constexpr int kSacK = MM3D_SAC_K;
+constexpr long long kSacMinTiles = 256 * 8;           // 256 CUs, eight resident blocks each
+// (forced: the A/B knob MM3D_SAC_K, or the test hook mm3d_debug_sacia_queries_per_thread; 1, 2, 4 or 8, anything else: by size)
+static std::atomic<int> g_sacia_k{[] { const char *e = getenv("MM3D_SAC_K"); return e ? atoi(e) : 0; }()};
+static int sacia_queries_per_thread(long long ns_total, int hn)
+{
+  const int knob = g_sacia_k.load();
+  if (knob == 1 || knob == 2 || knob == 4 || knob == 8) return knob;
+  int k = kSacK;
+  while (k > 1 && div_up(ns_total, 256 * k) * hn < kSacMinTiles) k >>= 1;
+  return k;
 }
 
 // The certified pick.  SampleConsensusInitialAlignment keeps the hypothesis with the lowest error sum -- "if (i_iter == 0 ||
@@ -339,6 +391,7 @@ void sacia_score_batch(Context *c, const SacPair *pairs, int n, int H, float cor
   MM3D_HIP(hipMemsetAsync(cert.get(), 0, per_pair * (size_t)n, c->stream));
   SacJob *hj = (SacJob *)c->pin(sizeof(SacJob) * (size_t)n);
   int max_ns = 0;
+  long long sum_ns = 0;
   double err_bytes = 0.0;
   for (int i = 0; i < n; ++i) {
     const SacPair &P = pairs[i];
@@ -368,6 +421,7 @@ void sacia_score_batch(Context *c, const SacPair *pairs, int n, int H, float cor
     q.cls = cp + (size_t)H * 16 + sizeof(SacCtl);
     hj[i] = q;
     max_ns = std::max(max_ns, ns);
+    sum_ns += ns;
     err_bytes += (double)ns * H * 4.0 + ns * 16.0;          // (SURVEY 8d's figure: 4 B per (hypothesis, keypoint))
   }
   DevBuf<SacJob> d_jobs(c, (size_t)n);
@@ -376,7 +430,15 @@ void sacia_score_batch(Context *c, const SacPair *pairs, int n, int H, float cor
   MM3D_LAUNCH(c, "sacia_models", n * H * 88.0, k_sacia_models, dim3(div_up(H, 64), n), dim3(64), 0, dj, H);
   for (int h0 = 0; h0 < H; h0 += 65535) {               // gridDim.y holds at most 65535 hypotheses
     const int hn = std::min(65535, H - h0);
-    MM3D_LAUNCH(c, "sacia_err", err_bytes * hn / H, k_sacia_err, dim3(div_up(max_ns, 256), hn, n), dim3(256), 0, dj, h0, corr_thresh, radius);
+    const double bytes = err_bytes * hn / H;
+    switch (sacia_queries_per_thread(sum_ns, hn)) {
+#define MM3D_SAC_ERR(K_) case K_: MM3D_LAUNCH(c, "sacia_err", bytes, (k_sacia_err<K_>), dim3(div_up(max_ns, 256 * K_), hn, n), dim3(256), 0, dj, h0, corr_thresh, radius); break
+      MM3D_SAC_ERR(8);
+      MM3D_SAC_ERR(4);
+      MM3D_SAC_ERR(2);
+      default: MM3D_SAC_ERR(1);
+#undef MM3D_SAC_ERR
+    }
   }
   // "if (i_iter == 0 || error < lowest_error)": the first minimum, picked on the device -- certified from the sums in
   // double where that decides it (nearly always: one candidate, no chain), from the CPU path's float chains of the
@@ -420,11 +482,7 @@ __global__ void __launch_bounds__(64) k_sacia_pick(const SacJob *__restrict__ jo
         best = key < best ? key : best;
       }
     }
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) {
-      const unsigned long long other = __shfl_xor(best, s, kWave);
-      best = other < best ? other : best;
-    }
+    best = wave_min_u64(best);                           // (e0 is the same in every lane: all 64 are here)
   }
   const int h = (e0 == e0) ? (int)(unsigned)(best & 0xffffffffull) : 0;
   if (lane < 16) T_best[lane] = T_all[(size_t)h * 16 + lane];
@@ -432,3 +490,10 @@ __global__ void __launch_bounds__(64) k_sacia_pick(const SacJob *__restrict__ jo
 
 
 }  // namespace mm3d
+
+// test hook (include/mm3d.h): lives with the kernel it steers, so the host-only builds of the library link without it
+extern "C" int mm3d_debug_sacia_queries_per_thread(int k)
+{
+  if (k >= 0) mm3d::g_sacia_k = k;
+  return mm3d::kSacK;
+}

@@ -33,11 +33,7 @@ struct BoxAcc {
     __shared__ float s_mn[4][3], s_mx[4][3];
     __shared__ int s_cnt[4];
 #pragma unroll
-    for (int a = 0; a < 3; ++a)
-      for (int o = 32; o > 0; o >>= 1) {
-        mn[a] = fminf(mn[a], __shfl_down(mn[a], o, kWave));
-        mx[a] = fmaxf(mx[a], __shfl_down(mx[a], o, kWave));
-      }
+    for (int a = 0; a < 3; ++a) { mn[a] = wave_min_f(mn[a]); mx[a] = wave_max_f(mx[a]); }
     const int total = wave_sum(cnt);
     const int lane = threadIdx.x & 63, wave = (threadIdx.x >> 6) & 3;
     if (lane == 0) {
@@ -102,12 +98,7 @@ k_scan_fused(size_t n, unsigned long long *status, unsigned *ticket, unsigned ti
 #pragma unroll
   for (int k = 0; k < kScanItems; ++k) sum += v[k];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int incl = sum;
-#pragma unroll
-  for (int o = 1; o < kWave; o <<= 1) {
-    const int t = __shfl_up(incl, o, kWave);
-    if (lane >= o) incl += t;
-  }
+  const int incl = wave_scan_incl(sum);
   if (lane == kWave - 1) s_wave[wave] = incl;
   __syncthreads();
   int wave_off = 0;
@@ -133,7 +124,6 @@ k_scan_fused(size_t n, unsigned long long *status, unsigned *ticket, unsigned ti
       prefix += wave_sum(take);
       if (first >= 0) break;
     }
-    prefix = __shfl(prefix, 0, kWave);
     if (lane == 0) {
       __hip_atomic_store(&status[tile], tag | (2ull << 32) | (unsigned)(prefix + total), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       s_prefix = prefix;

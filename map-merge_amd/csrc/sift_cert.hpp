@@ -115,9 +115,9 @@ k_sift_dog_fast(const float4 *__restrict__ q_pts, const int2 *__restrict__ items
     const int2 it = items[S.item];
     const bool live = lane < it.y;
     const float4 q = live ? q_pts[it.x + lane] : make_float4(kSnbFar, kSnbFar, kSnbFar, 0.0f);
-    const float lx = snb_min_f_dpp(live ? q.x : INFINITY), hx = snb_max_f_dpp(live ? q.x : -INFINITY);
-    const float ly = snb_min_f_dpp(live ? q.y : INFINITY), hy = snb_max_f_dpp(live ? q.y : -INFINITY);
-    const float lz = snb_min_f_dpp(live ? q.z : INFINITY), hz = snb_max_f_dpp(live ? q.z : -INFINITY);
+    const float lx = wave_min_f(live ? q.x : INFINITY), hx = wave_max_f(live ? q.x : -INFINITY);
+    const float ly = wave_min_f(live ? q.y : INFINITY), hy = wave_max_f(live ? q.y : -INFINITY);
+    const float lz = wave_min_f(live ? q.z : INFINITY), hz = wave_max_f(live ? q.z : -INFINITY);
     const int x0 = max(cell_floor(lx - ri, g.minx, g.inv), 0), x1 = min(cell_floor(hx + ri, g.minx, g.inv), g.dx - 1);
     const int y0 = max(cell_floor(ly - ri, g.miny, g.inv), 0), y1 = min(cell_floor(hy + ri, g.miny, g.inv), g.dy - 1);
     const int z0 = max(cell_floor(lz - ri, g.minz, g.inv), 0), z1 = min(cell_floor(hz + ri, g.minz, g.inv), g.dz - 1);
@@ -181,7 +181,7 @@ k_sift_dog_fast(const float4 *__restrict__ q_pts, const int2 *__restrict__ items
         b = g.cell_start[row + x0];
         len = g.cell_start[row + x1 + 1] - b;
       }
-      const int incl = snb_scan_dpp(len);
+      const int incl = wave_scan_incl(len);
       const int total = __builtin_amdgcn_readlane(incl, 63);
       wave_lds_fence();
       w_off[lane] = incl - len;
@@ -386,7 +386,7 @@ k_sift_reject(const float4 *__restrict__ q_pts, const int2 *__restrict__ items, 
     const int self = __float_as_int(qa.w);
     const unsigned c0 = live ? cls[self] : 0u;
     const float r2q = (live && (c0 & 7u)) ? rlo2[self] : 0.0f;      // (a point without a candidate scale asks for nothing)
-    const float r2max = snb_max_f_dpp(r2q);
+    const float r2max = wave_max_f(r2q);
     if (r2max > 0.0f) {                            // block-uniform
       // own intervals; the box of the queries that ask, grown by the largest reject radius
       float lo_p[3], hi_p[3];
@@ -396,9 +396,9 @@ k_sift_reject(const float4 *__restrict__ q_pts, const int2 *__restrict__ items, 
         if (live) cert_interval(dogv[(size_t)self * kCertDog + s + 1], dogb[(size_t)self * kCertDog + s + 1], lo_p[s], hi_p[s]);
       }
       const bool ask = r2q > 0.0f;
-      const float lx = snb_min_f_dpp(ask ? qa.x : INFINITY), hx = snb_max_f_dpp(ask ? qa.x : -INFINITY);
-      const float ly = snb_min_f_dpp(ask ? qa.y : INFINITY), hy = snb_max_f_dpp(ask ? qa.y : -INFINITY);
-      const float lz = snb_min_f_dpp(ask ? qa.z : INFINITY), hz = snb_max_f_dpp(ask ? qa.z : -INFINITY);
+      const float lx = wave_min_f(ask ? qa.x : INFINITY), hx = wave_max_f(ask ? qa.x : -INFINITY);
+      const float ly = wave_min_f(ask ? qa.y : INFINITY), hy = wave_max_f(ask ? qa.y : -INFINITY);
+      const float lz = wave_min_f(ask ? qa.z : INFINITY), hz = wave_max_f(ask ? qa.z : -INFINITY);
       const float ri = sqrtf(r2max) * 1.0001f + 1e-4f;
       const int x0 = max(cell_floor(lx - ri, g.minx, g.inv), 0), x1 = min(cell_floor(hx + ri, g.minx, g.inv), g.dx - 1);
       const int y0 = max(cell_floor(ly - ri, g.miny, g.inv), 0), y1 = min(cell_floor(hy + ri, g.miny, g.inv), g.dy - 1);
@@ -417,7 +417,7 @@ k_sift_reject(const float4 *__restrict__ q_pts, const int2 *__restrict__ items, 
           b = g.cell_start[row + x0];
           len = g.cell_start[row + x1 + 1] - b;
         }
-        const int incl = snb_scan_dpp(len);
+        const int incl = wave_scan_incl(len);
         const int total = __builtin_amdgcn_readlane(incl, 63);
         wave_lds_fence();
         w_off[lane] = incl - len;
@@ -548,17 +548,6 @@ __global__ void k_sift_collect_ids(const unsigned char *__restrict__ sel, unsign
   if (i < n && (sel[i] & mask)) ids[atomicAdd(n_ids, 1)] = i;
 }
 
-__device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v)
-{
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)v, o, 64), hi = (unsigned)__shfl_xor((int)(unsigned)(v >> 32), o, 64);
-    const unsigned long long w = ((unsigned long long)hi << 32) | lo;
-    v = w < v ? w : v;
-  }
-  return v;
-}
-
 // findScaleSpaceExtrema on intervals for ONE point per wave, the lanes over the candidates.  What is left after
 // k_sift_reject is a few thousand scattered points per octave (the keypoints themselves, near misses, open comparisons);
 // compact runs of them do not exist any more, and a block that grows rings around a single point is a long chain of
@@ -615,8 +604,7 @@ k_sift_extrema_one(const int *__restrict__ ids, const int *__restrict__ n_ids_de
             cnt += dist2(q.x, q.y, q.z, cd.x, cd.y, cd.z) <= r2 ? 1 : 0;
           }
         }
-        cnt = wave_sum(cnt);
-        cnt = __shfl(cnt, 0, 64);
+        cnt = wave_sum(cnt);                     // (wave-uniform)
         if (cnt >= kk0) break;
       }
       r2q = r2;
@@ -657,7 +645,7 @@ k_sift_extrema_one(const int *__restrict__ ids, const int *__restrict__ n_ids_de
           b = g.cell_start[row + x0];
           len = g.cell_start[row + x1 + 1] - b;
         }
-        const int incl = snb_scan_dpp(len);
+        const int incl = wave_scan_incl(len);
         const int total = __builtin_amdgcn_readlane(incl, 63);
         wave_lds_fence();
         w_off[lane] = incl - len;
@@ -725,7 +713,6 @@ k_sift_extrema_one(const int *__restrict__ ids, const int *__restrict__ n_ids_de
         cc_min[s] = wave_sum(cc_min[s]); cp_min[s] = wave_sum(cp_min[s]);
         cc_max[s] = wave_sum(cc_max[s]); cp_max[s] = wave_sum(cp_max[s]);
       }
-      cg = __shfl(cg, 0, 64);
       const int kk = g.n < kCertKnn ? g.n : kCertKnn;
       const bool proven = cg >= kk;              // (the unsorted pass counted them with the same test: always)
       bool any_open = !proven;
@@ -733,7 +720,7 @@ k_sift_extrema_one(const int *__restrict__ ids, const int *__restrict__ n_ids_de
 #pragma unroll
       for (int s = 0; s < 3; ++s) {
         if (!(cand & (1u << s))) continue;
-        const int ccn = __shfl(cc_min[s], 0, 64), cpn = __shfl(cp_min[s], 0, 64), ccx = __shfl(cc_max[s], 0, 64), cpx = __shfl(cp_max[s], 0, 64);
+        const int ccn = cc_min[s], cpn = cp_min[s], ccx = cc_max[s], cpx = cp_max[s];   // (wave_sum's results are wave-uniform)
         // per side: 0 no (a certain violator among the 25 nearest), 2 open (a possible one among them), 1 yes
         const int st_min = (vc_min[s] != ~0ull && ccn < kk) ? 0 : ((vp_min[s] != ~0ull && cpn < kk) ? 2 : 1);
         const int st_max = (vc_max[s] != ~0ull && ccx < kk) ? 0 : ((vp_max[s] != ~0ull && cpx < kk) ? 2 : 1);

@@ -121,61 +121,6 @@ struct SnbCtl {
   int error;                // the fallback's "one query alone overflows the scratch" word
 };
 
-// ---- wave-wide scan / reductions on the DPP network ------------------------------------------------------
-// Row shifts inside the rows of 16 lanes, then the two row broadcasts: six dependent VALU operations, ~80
-// cycles, where six ds_bpermute shuffles take ~440 (scripts/micro/lat.hip checks them against a sequential
-// loop and times both).
-__device__ __forceinline__ int snb_scan_dpp(int v)                    // inclusive sum
-{
-  v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, false);     // row_shr:1
-  v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, false);     // row_shr:2
-  v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, false);     // row_shr:4
-  v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, false);     // row_shr:8
-  v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);     // row_bcast:15 into rows 1, 3
-  v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);     // row_bcast:31 into rows 2, 3
-  return v;
-}
-template <int CTRL, int ROWMASK>
-__device__ __forceinline__ int snb_dpp_i(int v)                       // lanes without a source keep their own value
-{
-  return __builtin_amdgcn_update_dpp(v, v, CTRL, ROWMASK, 0xf, false);
-}
-__device__ __forceinline__ int snb_max_dpp(int v)                     // wave-uniform result
-{
-  v = max(v, snb_dpp_i<0x111, 0xf>(v));
-  v = max(v, snb_dpp_i<0x112, 0xf>(v));
-  v = max(v, snb_dpp_i<0x114, 0xf>(v));
-  v = max(v, snb_dpp_i<0x118, 0xf>(v));
-  v = max(v, snb_dpp_i<0x142, 0xa>(v));
-  v = max(v, snb_dpp_i<0x143, 0xc>(v));
-  return __builtin_amdgcn_readlane(v, 63);
-}
-template <int CTRL, int ROWMASK>
-__device__ __forceinline__ float snb_dpp_f(float v)
-{
-  return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), CTRL, ROWMASK, 0xf, false));
-}
-__device__ __forceinline__ float snb_min_f_dpp(float v)               // wave-uniform result
-{
-  v = fminf(v, snb_dpp_f<0x111, 0xf>(v));
-  v = fminf(v, snb_dpp_f<0x112, 0xf>(v));
-  v = fminf(v, snb_dpp_f<0x114, 0xf>(v));
-  v = fminf(v, snb_dpp_f<0x118, 0xf>(v));
-  v = fminf(v, snb_dpp_f<0x142, 0xa>(v));
-  v = fminf(v, snb_dpp_f<0x143, 0xc>(v));
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
-}
-__device__ __forceinline__ float snb_max_f_dpp(float v)
-{
-  v = fmaxf(v, snb_dpp_f<0x111, 0xf>(v));
-  v = fmaxf(v, snb_dpp_f<0x112, 0xf>(v));
-  v = fmaxf(v, snb_dpp_f<0x114, 0xf>(v));
-  v = fmaxf(v, snb_dpp_f<0x118, 0xf>(v));
-  v = fmaxf(v, snb_dpp_f<0x142, 0xa>(v));
-  v = fmaxf(v, snb_dpp_f<0x143, 0xc>(v));
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
-}
-
 __device__ __forceinline__ int snb_mbcnt(unsigned long long m, int base)   // base + number of set bits of m below this lane
 {
   return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, (unsigned)base));
@@ -220,7 +165,7 @@ __device__ __forceinline__ void snb_stage(const GridView &g, SnbLds<Cfg> &S, int
       b = g.cell_start[row + x0];
       len = g.cell_start[row + x1 + 1] - b;
     }
-    const int incl = snb_scan_dpp(len);
+    const int incl = wave_scan_incl(len);
     const int total = __builtin_amdgcn_readlane(incl, 63);
     int *w_off = W.off(), *w_beg = W.beg();
     wave_lds_fence();
@@ -368,12 +313,12 @@ __device__ __forceinline__ int snb_sort_one(SnbLds<Cfg> &S, SnbWave<Cfg> &W, flo
       sum += cnt;
       mx = max(mx, cnt);
     }
-    const int incl = snb_scan_dpp(sum);
+    const int incl = wave_scan_incl(sum);
     const unsigned ex = (unsigned)(incl - sum);
 #pragma unroll
     for (int k = 0; k < WPL; ++k) W.hist[lane * WPL + k] = wd[k] + ex;
     if (lane == kWave - 1) W.hist[NB] = (unsigned)incl;         // start of the bucket past the last = nh
-    mb = snb_max_dpp(mx);
+    mb = wave_max_int(mx);
   }
   wave_lds_fence();
   SNB_TOCK(6, t_c);
@@ -568,9 +513,9 @@ __device__ __forceinline__ int snb_stage_queries(const GridView &g, SnbLds<Cfg> 
   const bool live = lane < count;
   const float4 qa = q_pts[first + (live ? lane : 0)];
   if (wave == 0 && live) S.qpts[lane] = qa;
-  const float lx = snb_min_f_dpp(live ? qa.x : INFINITY), hx = snb_max_f_dpp(live ? qa.x : -INFINITY);
-  const float ly = snb_min_f_dpp(live ? qa.y : INFINITY), hy = snb_max_f_dpp(live ? qa.y : -INFINITY);
-  const float lz = snb_min_f_dpp(live ? qa.z : INFINITY), hz = snb_max_f_dpp(live ? qa.z : -INFINITY);
+  const float lx = wave_min_f(live ? qa.x : INFINITY), hx = wave_max_f(live ? qa.x : -INFINITY);
+  const float ly = wave_min_f(live ? qa.y : INFINITY), hy = wave_max_f(live ? qa.y : -INFINITY);
+  const float lz = wave_min_f(live ? qa.z : INFINITY), hz = wave_max_f(live ? qa.z : -INFINITY);
   const int x0 = max(cell_floor(lx - ri, g.minx, g.inv), 0), x1 = min(cell_floor(hx + ri, g.minx, g.inv), g.dx - 1);
   const int y0 = max(cell_floor(ly - ri, g.miny, g.inv), 0), y1 = min(cell_floor(hy + ri, g.miny, g.inv), g.dy - 1);
   const int z0 = max(cell_floor(lz - ri, g.minz, g.inv), 0), z1 = min(cell_floor(hz + ri, g.minz, g.inv), g.dz - 1);

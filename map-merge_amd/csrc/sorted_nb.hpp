@@ -170,12 +170,7 @@ __device__ __forceinline__ int sn_build_lists(const GridView &g, SnLds &L, float
   for (int p = 0; p < n_q; ++p) {
     const unsigned w = L.cnt[p][lane];
     const int c0 = (int)(w & 0xffffu), c1 = (int)(w >> 16);
-    int incl = c0 + c1;
-#pragma unroll
-    for (int o = 1; o < kWave; o <<= 1) {
-      const int t = __shfl_up(incl, o, kWave);
-      if (lane >= o) incl += t;
-    }
+    const int incl = wave_scan_incl(c0 + c1);
     const int excl = incl - c0 - c1;
     const int m = __builtin_amdgcn_readlane(incl, kWave - 1);
     const bool ok = fit == p && total + m <= kSnEntries && m <= 0xffff;
