@@ -33,6 +33,8 @@
 #include <cstring>
 
 #include "capi_guard.hpp"
+#include "drivers.hpp"
+#include "map_kept.hpp"
 #include "icp_solve6.hpp"
 #include "scan_fused.hpp"
 
@@ -701,31 +703,19 @@ mm3d_coarse_options corr_resolved(const mm3d_coarse_options &o, const mm3d_param
 }
 
 struct CoarseCorrelative final : CoarseMethodBase {
-  // The map's signature at the context's options: made when the map has none (a map made while the context had no coarse
-  // alignment, a cached one of such a call, one from parts) or one of other options -- under its points' lock, complete on
-  // the device before anybody else can see it, since other streams may share the map.  So are the normals it is made from.
+  // the map's signature at the context's options, and the normals it is made from (map_kept.hpp)
   const CoarseSignature *signature(mm3d_ctx *ctx, const mm3d_map *m, const mm3d_params *p) const
   {
-    const mm3d_coarse_options o = corr_resolved(ctx->coarse_options, p);
-    std::lock_guard<std::recursive_mutex> lk(m->points->cache_mu);
-    mm3d_map *mm = const_cast<mm3d_map *>(m);
-    if (!m->normals) {
-      std::unique_ptr<mm3d_normals> n(compute_normals(ctx, m->points, p->normal_radius));
-      ctx->sync();
-      mm->normals = std::move(n);
-    }
-    if (!m->coarse || !corr_same_options(m->coarse->opt, o)) {
-      std::unique_ptr<CoarseSignature> made = corr_build_signature(ctx, m->points, m->normals.get(), o);
-      ctx->sync();
-      mm->coarse = std::move(made);
-    }
-    return m->coarse.get();
+    const mm3d_coarse_options o = corr_resolved(ctx->sel.coarse_options, p);
+    return map_kept(
+        ctx, m, &mm3d_map::coarse, [&](const CoarseSignature &h) { return corr_same_options(h.opt, o); },
+        [&] { return corr_build_signature(ctx, m->points, map_normals(ctx, m, p), o); });
   }
   void prepare(mm3d_ctx *ctx, const mm3d_map *m, const mm3d_params *p) const override { (void)signature(ctx, m, p); }
   void front(mm3d_ctx *ctx, const mm3d_map *s, const mm3d_map *t, const mm3d_params *p, PairFront &f, mm3d_coarse_stats *stats) const override
   {
     const CoarseSignature *S = signature(ctx, s, p), *T = signature(ctx, t, p);
-    corr_align(ctx, corr_resolved(ctx->coarse_options, p), *S, *T, f, stats);
+    corr_align(ctx, corr_resolved(ctx->sel.coarse_options, p), *S, *T, f, stats);
   }
 };
 const CoarseCorrelative g_correlative;
@@ -751,41 +741,22 @@ using namespace mm3d;
 
 extern "C" {
 
-void mm3d_coarse_options_default(mm3d_coarse_options *o)
-{
-  if (!o) return;
-  o->method = MM3D_COARSE_NONE;
-  o->cell = 0.0;
-  o->cell_factor = 4;
-  o->yaw_steps = 720;
-  o->yaw_factor = 6;
-  o->candidates = 32;
-  o->wall_nz = 0.5;
-  o->ground_nz = 0.9;
-  o->min_points = 3;
-  o->accept_fraction = 0.25;
-}
-
 int mm3d_set_coarse_alignment(mm3d_ctx *ctx, const mm3d_coarse_options *options)
 {
   if (!ctx || !corr_options_ok(options)) return MM3D_EINVAL;
   if (options->cell != 0.0 && !corr_cell_ok(options->cell)) return MM3D_EINVAL;     // (also catches NaN)
   std::lock_guard<std::mutex> lock(ctx->mu);        // (no call is running while the method changes)
-  if (ctx->device_set && options->method == MM3D_COARSE_CORRELATIVE) {
-    ctx->err = "mm3d_set_coarse_alignment: the correlative alignment is not available on a device-list context";
+  const bool corr = options->method == MM3D_COARSE_CORRELATIVE;
+  if (corr && refused_on_device_list(ctx, "mm3d_set_coarse_alignment: the correlative alignment is not available on a device-list context"))
     return MM3D_EUNSUPPORTED;
-  }
-  const CoarseMethodBase *m = options->method == MM3D_COARSE_CORRELATIVE ? &g_correlative : nullptr;
-  ctx->coarse_method = m;
-  ctx->coarse_options = *options;
-  for (mm3d_ctx *h : ctx->helpers) { h->coarse_method = m; h->coarse_options = *options; }
+  select_stages(ctx, false, [&](StageSelection &s) { s.coarse = corr ? &g_correlative : nullptr; s.coarse_options = *options; });
   return MM3D_OK;
 }
 
 int mm3d_get_coarse_alignment(const mm3d_ctx *ctx, mm3d_coarse_options *options)
 {
   if (!ctx || !options) return MM3D_EINVAL;
-  *options = ctx->coarse_options;
+  *options = ctx->sel.coarse_options;
   return MM3D_OK;
 }
 

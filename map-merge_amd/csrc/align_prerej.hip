@@ -26,6 +26,7 @@
 #include <cstring>
 
 #include "capi_guard.hpp"
+#include "drivers.hpp"
 #include "device_util.hpp"
 #include "linalg_shared.hpp"
 
@@ -484,35 +485,21 @@ using namespace mm3d;
 
 extern "C" {
 
-void mm3d_alignment_options_default(mm3d_alignment_options *o)
-{
-  if (!o) return;
-  o->method = MM3D_ALIGN_SAC_IA;
-  o->samples = 1 << 16;
-  o->k = 10;
-  o->similarity = 0.9;
-  o->inlier_fraction = 0.25;
-}
-
 int mm3d_set_alignment(mm3d_ctx *ctx, const mm3d_alignment_options *options)
 {
   if (!ctx || !options_ok(options)) return MM3D_EINVAL;
   std::lock_guard<std::mutex> lock(ctx->mu);        // (no call is running while the method changes)
-  if (ctx->device_set && options->method == MM3D_ALIGN_PREREJECTIVE) {
-    ctx->err = "mm3d_set_alignment: prerejective alignment is not available on a device-list context";
+  const bool prerej = options->method == MM3D_ALIGN_PREREJECTIVE;
+  if (prerej && refused_on_device_list(ctx, "mm3d_set_alignment: prerejective alignment is not available on a device-list context"))
     return MM3D_EUNSUPPORTED;
-  }
-  const AlignMethodBase *m = options->method == MM3D_ALIGN_PREREJECTIVE ? &g_prerejective : nullptr;
-  ctx->align_method = m;
-  ctx->align_options = *options;
-  for (mm3d_ctx *h : ctx->helpers) { h->align_method = m; h->align_options = *options; }
+  select_stages(ctx, false, [&](StageSelection &s) { s.align = prerej ? &g_prerejective : nullptr; s.align_options = *options; });
   return MM3D_OK;
 }
 
 int mm3d_get_alignment(const mm3d_ctx *ctx, mm3d_alignment_options *options)
 {
   if (!ctx || !options) return MM3D_EINVAL;
-  *options = ctx->align_options;
+  *options = ctx->sel.align_options;
   return MM3D_OK;
 }
 

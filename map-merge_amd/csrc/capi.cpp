@@ -28,6 +28,33 @@ int from_string(const char *s, const char *const *names, int n)
 
 }  // namespace
 
+mm3d::StageSelection::StageSelection()
+{
+  mm3d_alignment_options_default(&align_options);
+  mm3d_keypoint_options_default(&keypoint_options);
+  mm3d_refine_options_default(&refine_options);
+  mm3d_coarse_options_default(&coarse_options);
+  mm3d_confidence_options_default(&confidence_options);
+}
+
+void mm3d::select_stages(mm3d_ctx *ctx, bool peers_follow, const std::function<void(StageSelection &)> &edit)
+{
+  auto one = [&](mm3d_ctx *root) {
+    edit(root->sel);
+    for (mm3d_ctx *h : root->helpers) h->sel = root->sel;
+  };
+  one(ctx);
+  if (peers_follow)
+    for (mm3d_ctx *p : ctx->peers) one(p);            // (every device of an mm3d_create_devices context)
+}
+
+bool mm3d::refused_on_device_list(mm3d_ctx *ctx, const char *text)
+{
+  if (!ctx->device_set) return false;
+  ctx->err = text;
+  return true;
+}
+
 extern "C" {
 
 // ---------------------------------------------------------------- enums / params
@@ -137,6 +164,28 @@ size_t mm3d_params_to_string(const mm3d_params *p, char *buf, size_t cap)
   return str.size() + 1;
 }
 
+// ---------------------------------------------------------------- the opt-in stages' options and their record
+void mm3d_alignment_options_default(mm3d_alignment_options *o)
+{
+  if (o) *o = mm3d_alignment_options{MM3D_ALIGN_SAC_IA, 1 << 16, 10, 0.9, 0.25};
+}
+void mm3d_keypoint_options_default(mm3d_keypoint_options *o)
+{
+  if (o) *o = mm3d_keypoint_options{MM3D_KEYPOINTS_REFERENCE, 0.0};
+}
+void mm3d_refine_options_default(mm3d_refine_options *o)
+{
+  if (o) *o = mm3d_refine_options{MM3D_REFINE_ICP, 0.0, 7, 6, 0.01};
+}
+void mm3d_coarse_options_default(mm3d_coarse_options *o)
+{
+  if (o) *o = mm3d_coarse_options{MM3D_COARSE_NONE, 0.0, 4, 720, 6, 32, 0.5, 0.9, 3, 0.25};
+}
+void mm3d_confidence_options_default(mm3d_confidence_options *o)
+{
+  if (o) *o = mm3d_confidence_options{MM3D_CONFIDENCE_REFERENCE, 0.0, 8, 0.05, 0};
+}
+
 // ---------------------------------------------------------------- context
 static std::string &create_error()
 {
@@ -213,17 +262,7 @@ static void set_streams_one(mm3d_ctx *ctx, int n_streams)
     mm3d_ctx *h = nullptr;
     const int st = mm3d_create(ctx->device, &h);
     if (st != MM3D_OK) throw Error(st, "mm3d_set_streams: could not create a helper context");
-    h->icp_method = ctx->icp_method;                    // (mm3d_set_icp_method before mm3d_set_streams)
-    h->align_method = ctx->align_method;                // (mm3d_set_alignment likewise)
-    h->align_options = ctx->align_options;
-    h->keypoint_source = ctx->keypoint_source;          // (mm3d_set_keypoints likewise)
-    h->keypoint_options = ctx->keypoint_options;
-    h->refine_method = ctx->refine_method;              // (mm3d_set_refinement likewise)
-    h->refine_options = ctx->refine_options;
-    h->coarse_method = ctx->coarse_method;              // (mm3d_set_coarse_alignment likewise)
-    h->coarse_options = ctx->coarse_options;
-    h->confidence_method = ctx->confidence_method;      // (mm3d_set_confidence likewise)
-    h->confidence_options = ctx->confidence_options;
+    h->sel = ctx->sel;                                  // (whatever was selected before mm3d_set_streams)
     ctx->helpers.push_back(h);
   }
 }
@@ -692,8 +731,7 @@ int mm3d_estimate_maps_transforms(mm3d_ctx *ctx, const mm3d_cloud_view *clouds, 
       bool ok = false;
       ~CacheCall() { if (c && !ok) c->abort(); }
     } cache_call{ctx->map_cache};
-    if (ctx->map_cache) ctx->map_cache->begin(n, params, ctx->icp_method ? ctx->icp_method->method() : MM3D_ICP_POINT_TO_POINT, ctx->align_options,
-                                                  ctx->keypoint_options, ctx->refine_options, ctx->coarse_options, ctx->confidence_options);
+    if (ctx->map_cache) ctx->map_cache->begin(n, params, ctx->sel);
     if (!ctx->helpers.empty())
       estimate_maps_streams(ctx, clouds, n, params, out_T, n_out, pairs_out, n_pairs_out);
     else

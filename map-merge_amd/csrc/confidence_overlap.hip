@@ -20,6 +20,8 @@
 #include <cstring>
 
 #include "capi_guard.hpp"
+#include "drivers.hpp"
+#include "map_kept.hpp"
 #include "device_util.hpp"
 
 namespace mm3d {
@@ -332,22 +334,15 @@ void ovl_count(Context *c, const OvlSide *src, const OvlSide *tgt, const float *
 }
 
 struct ConfidenceOverlap final : ConfidenceMethodBase {
-  // The map's table at the context's options: made when the map has none (a map made while the context used the reference's
-  // confidence, a cached one of such a call, one from parts) or one of other options -- under its points' lock, complete on the
-  // device before anybody else can see it, since other streams may share the map.
+  // the map's table at the context's options (map_kept.hpp)
   const OverlapTable *table(mm3d_ctx *ctx, const mm3d_map *m, const mm3d_params *p) const
   {
-    const mm3d_confidence_options &o = ctx->confidence_options;
+    const mm3d_confidence_options &o = ctx->sel.confidence_options;
     const double voxel = o.voxel > 0.0 ? o.voxel : kOvlDefaultMultiple * p->resolution;
-    std::lock_guard<std::recursive_mutex> lk(m->points->cache_mu);
-    const OverlapTable *t = m->overlap.get();
-    if (!t || t->voxel != voxel || t->min_points != o.min_points || t->view_margin != o.view_margin) {
-      std::unique_ptr<OverlapTable> made = ovl_build_table(ctx, m->points, voxel, o.min_points, o.view_margin);
-      ctx->sync();
-      const_cast<mm3d_map *>(m)->overlap = std::move(made);
-      t = m->overlap.get();
-    }
-    return t;
+    return map_kept(
+        ctx, m, &mm3d_map::overlap,
+        [&](const OverlapTable &h) { return h.voxel == voxel && h.min_points == o.min_points && h.view_margin == o.view_margin; },
+        [&] { return ovl_build_table(ctx, m->points, voxel, o.min_points, o.view_margin); });
   }
   void prepare(mm3d_ctx *ctx, const mm3d_map *m, const mm3d_params *p) const override { (void)table(ctx, m, p); }
   void score(mm3d_ctx *ctx, ConfidencePair *pairs, size_t n, const mm3d_params *p, mm3d_overlap_stats *stats) const override
@@ -360,19 +355,12 @@ struct ConfidenceOverlap final : ConfidenceMethodBase {
       T[i] = pairs[i].T;
     }
     std::vector<mm3d_overlap_stats> out(n);
-    ovl_count(ctx, src.data(), tgt.data(), T.data(), n, ctx->confidence_options.min_overlap, out.data());
+    ovl_count(ctx, src.data(), tgt.data(), T.data(), n, ctx->sel.confidence_options.min_overlap, out.data());
     for (size_t i = 0; i < n; ++i) pairs[i].confidence = out[i].confidence;
     if (stats && n) *stats = out[n - 1];
   }
 };
 const ConfidenceOverlap g_overlap;
-
-void set_on(mm3d_ctx *c, const ConfidenceMethodBase *m, const mm3d_confidence_options &o)
-{
-  c->confidence_method = m;
-  c->confidence_options = o;
-  for (mm3d_ctx *h : c->helpers) { h->confidence_method = m; h->confidence_options = o; }
-}
 
 }  // namespace
 
@@ -382,33 +370,22 @@ using namespace mm3d;
 
 extern "C" {
 
-void mm3d_confidence_options_default(mm3d_confidence_options *o)
-{
-  if (!o) return;
-  o->method = MM3D_CONFIDENCE_REFERENCE;
-  o->voxel = 0.0;
-  o->min_points = 8;
-  o->min_overlap = 0.05;
-  o->view_margin = 0;
-}
-
 int mm3d_set_confidence(mm3d_ctx *ctx, const mm3d_confidence_options *options)
 {
   if (!ctx || !ovl_options_ok(options)) return MM3D_EINVAL;
   if (options->voxel != 0.0 && !ovl_voxel_ok(options->voxel)) return MM3D_EINVAL;     // (also catches NaN)
   std::lock_guard<std::mutex> lock(ctx->mu);        // (no call is running while the method changes)
-  if (ctx->device_set && options->method == MM3D_CONFIDENCE_OVERLAP) {
-    ctx->err = "mm3d_set_confidence: the overlap confidence is not available on a device-list context";
+  const bool ovl = options->method == MM3D_CONFIDENCE_OVERLAP;
+  if (ovl && refused_on_device_list(ctx, "mm3d_set_confidence: the overlap confidence is not available on a device-list context"))
     return MM3D_EUNSUPPORTED;
-  }
-  set_on(ctx, options->method == MM3D_CONFIDENCE_OVERLAP ? &g_overlap : nullptr, *options);
+  select_stages(ctx, false, [&](StageSelection &s) { s.confidence = ovl ? &g_overlap : nullptr; s.confidence_options = *options; });
   return MM3D_OK;
 }
 
 int mm3d_get_confidence(const mm3d_ctx *ctx, mm3d_confidence_options *options)
 {
   if (!ctx || !options) return MM3D_EINVAL;
-  *options = ctx->confidence_options;
+  *options = ctx->sel.confidence_options;
   return MM3D_OK;
 }
 

@@ -56,11 +56,12 @@ int mm3d_shard_begin(mm3d_ctx *ctx, const mm3d_cloud_view *clouds, size_t n, con
   if (!ctx || !params || !out || (n && !clouds) || world < 1 || rank < 0 || rank >= world) return MM3D_EINVAL;
   *out = nullptr;
   return guarded(ctx, [&] {
-    if (ctx->icp_method) throw Error(MM3D_EUNSUPPORTED, "mm3d_shard_begin: shard bundles carry no normals for point-to-plane ICP");
-    if (ctx->confidence_method) throw Error(MM3D_EUNSUPPORTED, "mm3d_shard_begin: shard bundles carry no tables for the overlap confidence");
-    if (ctx->coarse_method) throw Error(MM3D_EUNSUPPORTED, "mm3d_shard_begin: shard bundles carry no signatures for the correlative alignment");
-    if (ctx->refine_method) throw Error(MM3D_EUNSUPPORTED, "mm3d_shard_begin: shard bundles carry no voxel tables for NDT");
-    if (ctx->align_method) throw Error(MM3D_EUNSUPPORTED, "mm3d_shard_begin: the ranks' pair loops run SAC-IA, not the prerejective alignment");
+    const StageSelection &sel = ctx->sel;
+    if (sel.icp) throw Error(MM3D_EUNSUPPORTED, "mm3d_shard_begin: shard bundles carry no normals for point-to-plane ICP");
+    if (sel.confidence) throw Error(MM3D_EUNSUPPORTED, "mm3d_shard_begin: shard bundles carry no tables for the overlap confidence");
+    if (sel.coarse) throw Error(MM3D_EUNSUPPORTED, "mm3d_shard_begin: shard bundles carry no signatures for the correlative alignment");
+    if (sel.refine) throw Error(MM3D_EUNSUPPORTED, "mm3d_shard_begin: shard bundles carry no voxel tables for NDT");
+    if (sel.align) throw Error(MM3D_EUNSUPPORTED, "mm3d_shard_begin: the ranks' pair loops run SAC-IA, not the prerejective alignment");
     *out = shard_begin_impl(ctx, clouds, n, params, rank, world);
   });
 }

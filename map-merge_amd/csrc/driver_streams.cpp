@@ -38,12 +38,12 @@ void mm3d::estimate_maps_streams(mm3d_ctx *ctx, const mm3d_cloud_view *clouds, s
     if (v >= 1) F = std::min<size_t>(S, (size_t)v);
   }
   const std::vector<std::pair<size_t, size_t>> all = all_pairs(n);
-  std::vector<mm3d_map *> maps(n, nullptr);
+  std::vector<const mm3d_map *> maps(n, nullptr);
   // mm3d_set_map_cache: maps[i] is the cache's (a hit, or a miss handed over once built) where borrowed[i] is set
   MapCacheBase *const cache = ctx->map_cache;
   std::vector<char> borrowed(n, 0);
   struct MapsGuard {                                    // the maps go when the call ends, whichever way
-    std::vector<mm3d_map *> &m;
+    std::vector<const mm3d_map *> &m;
     const std::vector<char> &borrowed;
     ~MapsGuard()
     {
@@ -152,7 +152,7 @@ void mm3d::estimate_maps_streams(mm3d_ctx *ctx, const mm3d_cloud_view *clouds, s
             raw.reset();
             {
               std::lock_guard<std::mutex> lk(mu);
-              maps[i] = const_cast<mm3d_map *>(hit);
+              maps[i] = hit;
               borrowed[i] = 1;
               ready[i] = 1;
               record_map_sizes(ctx, i, hit);

@@ -19,6 +19,8 @@
 #include <cmath>
 
 #include "capi_guard.hpp"
+#include "drivers.hpp"
+#include "map_kept.hpp"
 #include "icp_solve6.hpp"
 #include "nn_core.hpp"
 
@@ -192,6 +194,11 @@ struct IcpPointToPlane final : IcpMethodBase {
   {
     icp_plane_score_batch(c, jobs, n_jobs, run_icp, max_corr_dist, max_iterations, eps, want_score, score_max_distance);
   }
+  void prepare_target(mm3d_ctx *ctx, const mm3d_map *m, const mm3d_params *p, IcpScoreJob *job) const override
+  {
+    const mm3d_normals *n = map_normals(ctx, m, p);
+    if (job) job->tgt_normals = n;
+  }
 };
 const IcpPointToPlane g_point_to_plane;
 }  // namespace
@@ -206,20 +213,15 @@ int mm3d_set_icp_method(mm3d_ctx *ctx, int method)
 {
   if (!ctx || (method != MM3D_ICP_POINT_TO_POINT && method != MM3D_ICP_POINT_TO_PLANE)) return MM3D_EINVAL;
   std::lock_guard<std::mutex> lock(ctx->mu);        // (no call is running while the method changes)
-  if (ctx->device_set) {
-    ctx->err = "mm3d_set_icp_method: not available on a device-list context";
-    return MM3D_EUNSUPPORTED;
-  }
-  const IcpMethodBase *m = method == MM3D_ICP_POINT_TO_PLANE ? &g_point_to_plane : nullptr;
-  ctx->icp_method = m;
-  for (mm3d_ctx *h : ctx->helpers) h->icp_method = m;
+  if (refused_on_device_list(ctx, "mm3d_set_icp_method: not available on a device-list context")) return MM3D_EUNSUPPORTED;
+  select_stages(ctx, false, [&](StageSelection &s) { s.icp = method == MM3D_ICP_POINT_TO_PLANE ? &g_point_to_plane : nullptr; });
   return MM3D_OK;
 }
 
 int mm3d_get_icp_method(const mm3d_ctx *ctx)
 {
   if (!ctx) return MM3D_EINVAL;
-  return ctx->icp_method ? ctx->icp_method->method() : MM3D_ICP_POINT_TO_POINT;
+  return ctx->sel.icp_method();
 }
 
 int mm3d_estimate_transform_icp_plane(mm3d_ctx *ctx, const mm3d_cloud *source, const mm3d_cloud *target, const mm3d_normals *target_normals,

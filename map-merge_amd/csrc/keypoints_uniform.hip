@@ -19,6 +19,7 @@
 #include <cstring>
 
 #include "capi_guard.hpp"
+#include "drivers.hpp"
 #include "device_util.hpp"
 #include "scan_fused.hpp"
 
@@ -216,13 +217,6 @@ bool options_ok(const mm3d_keypoint_options *o)
   return o->leaf == 0.0 || ukp_leaf_ok(o->leaf);
 }
 
-void set_on(mm3d_ctx *c, const KeypointSourceBase *s, const mm3d_keypoint_options &o)
-{
-  c->keypoint_source = s;
-  c->keypoint_options = o;
-  for (mm3d_ctx *h : c->helpers) { h->keypoint_source = s; h->keypoint_options = o; }
-}
-
 }  // namespace
 
 }  // namespace mm3d
@@ -238,27 +232,22 @@ int mm3d_uniform_keypoints(mm3d_ctx *ctx, const mm3d_cloud *points, double leaf,
   return guarded(ctx, [&] { *out = uniform_keypoints(ctx, points, leaf); });
 }
 
-void mm3d_keypoint_options_default(mm3d_keypoint_options *o)
-{
-  if (!o) return;
-  o->source = MM3D_KEYPOINTS_REFERENCE;
-  o->leaf = 0.0;
-}
-
 int mm3d_set_keypoints(mm3d_ctx *ctx, const mm3d_keypoint_options *options)
 {
   if (!ctx || !options_ok(options)) return MM3D_EINVAL;
   std::lock_guard<std::mutex> lock(ctx->mu);        // (no call is running while the source changes)
-  const KeypointSourceBase *s = options->source == MM3D_KEYPOINTS_UNIFORM ? &g_uniform : nullptr;
-  set_on(ctx, s, *options);
-  for (mm3d_ctx *p : ctx->peers) set_on(p, s, *options);            // (every device of an mm3d_create_devices context)
+  // (features travel in the bundles, so device lists carry the option: the peers follow)
+  select_stages(ctx, true, [&](StageSelection &s) {
+    s.keypoints = options->source == MM3D_KEYPOINTS_UNIFORM ? &g_uniform : nullptr;
+    s.keypoint_options = *options;
+  });
   return MM3D_OK;
 }
 
 int mm3d_get_keypoints(const mm3d_ctx *ctx, mm3d_keypoint_options *options)
 {
   if (!ctx || !options) return MM3D_EINVAL;
-  *options = ctx->keypoint_options;
+  *options = ctx->sel.keypoint_options;
   return MM3D_OK;
 }
 

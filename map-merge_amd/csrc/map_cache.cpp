@@ -31,8 +31,9 @@ struct KeyBuilder {
 };
 
 // what map_features_impl and map_prepare_impl read
-std::string feature_key(const mm3d_params *p, const mm3d_keypoint_options &kp)
+std::string feature_key(const mm3d_params *p, const StageSelection &sel)
 {
+  const mm3d_keypoint_options &kp = sel.keypoint_options;
   KeyBuilder k;
   k.f64(p->resolution).f64(p->descriptor_radius).i32(p->outliers_min_neighbours).f64(p->normal_radius).i32(p->keypoint_type)
       .f64(p->keypoint_threshold).i32(p->descriptor_type).f64(p->max_correspondence_distance).i32(p->estimation_method);
@@ -45,12 +46,15 @@ std::string feature_key(const mm3d_params *p, const mm3d_keypoint_options &kp)
 // what the pair stage reads (pair_estimate_impl / pairs_estimate_batch), and the ICP method (mm3d_set_icp_method): a
 // point-to-point record is never one of point-to-plane's.  (The map key needs no method: the normals point-to-plane keeps are
 // a function of the points and normal_radius.)
-std::string pair_params_key(const mm3d_params *p, int icp_method, const mm3d_alignment_options &align, const mm3d_refine_options &refine,
-                            const mm3d_coarse_options &coarse, const mm3d_confidence_options &conf)
+std::string pair_params_key(const mm3d_params *p, const StageSelection &sel)
 {
+  const mm3d_alignment_options &align = sel.align_options;
+  const mm3d_refine_options &refine = sel.refine_options;
+  const mm3d_coarse_options &coarse = sel.coarse_options;
+  const mm3d_confidence_options &conf = sel.confidence_options;
   KeyBuilder k;
   k.i32(p->estimation_method).i32(p->refine_transform).f64(p->inlier_threshold).f64(p->max_correspondence_distance)
-      .i32(p->max_iterations).u64(p->matching_k).f64(p->transform_epsilon).i32(icp_method);
+      .i32(p->max_iterations).u64(p->matching_k).f64(p->transform_epsilon).i32(sel.icp_method());
   // the alignment (mm3d_set_alignment): a SAC-IA record is never a prerejective one's, nor one of other options
   k.i32(align.method).i32(align.samples).i32(align.k).f64(align.similarity).f64(align.inlier_fraction);
   // the refinement (mm3d_set_refinement): an ICP record is never an NDT one's, nor an NDT one that of other options (which the
@@ -146,17 +150,15 @@ class MapCache final : public MapCacheBase {
       for (long long &c : counters_) c = 0;
   }
 
-  void begin(size_t n_maps, const mm3d_params *p, int icp_method, const mm3d_alignment_options &align,
-             const mm3d_keypoint_options &keypoints, const mm3d_refine_options &refine, const mm3d_coarse_options &coarse,
-             const mm3d_confidence_options &confidence) override
+  void begin(size_t n_maps, const mm3d_params *p, const StageSelection &sel) override
   {
     std::lock_guard<std::mutex> lk(mu_);
     reset_call_locked();
-    fkey_ = feature_key(p, keypoints);
-    pkey_ = pair_params_key(p, icp_method, align, refine, coarse, confidence);
+    fkey_ = feature_key(p, sel);
+    pkey_ = pair_params_key(p, sel);
     // (the correlative alignment reads neither the generator nor its seed: no state in its pairs' keys)
-    sac_ia_ = p->estimation_method == MM3D_EST_SAC_IA && coarse.method != MM3D_COARSE_CORRELATIVE;
-    prerej_ = sac_ia_ && align.method == MM3D_ALIGN_PREREJECTIVE;
+    sac_ia_ = p->estimation_method == MM3D_EST_SAC_IA && sel.coarse_options.method != MM3D_COARSE_CORRELATIVE;
+    prerej_ = sac_ia_ && sel.align_options.method == MM3D_ALIGN_PREREJECTIVE;
     slot_entry_.assign(n_maps, 0);
     slot_digest_.assign(n_maps, {0ull, 0ull});
     staged_.reserve(n_maps);             // (insert never reallocates: it cannot fail once it owns a map)

@@ -27,6 +27,8 @@
 #include <cstring>
 
 #include "capi_guard.hpp"
+#include "drivers.hpp"
+#include "map_kept.hpp"
 #include "icp_solve6.hpp"
 #include "nn_core.hpp"
 #include "scan_fused.hpp"
@@ -412,32 +414,19 @@ struct RefineNdt final : IcpMethodBase {
   {
     ndt_score_batch(c, jobs, n_jobs, run_icp, max_corr_dist, max_iterations, eps, want_score, score_max_distance);
   }
-  // The map's table at the context's options: made when the map has none (a map made while the context refined with ICP, a
-  // cached one of such a call, one from parts) or one of other options -- under its points' lock, complete on the device
-  // before anybody else can see it, since other streams may share the map.
+  // the map's table at the context's options (map_kept.hpp)
   void prepare_target(mm3d_ctx *ctx, const mm3d_map *m, const mm3d_params *p, IcpScoreJob *job) const override
   {
-    const mm3d_refine_options &o = ctx->refine_options;
+    const mm3d_refine_options &o = ctx->sel.refine_options;
     const double res = o.resolution > 0.0 ? o.resolution : kNdtDefaultMultiple * p->resolution;
-    std::lock_guard<std::recursive_mutex> lk(m->points->cache_mu);
-    const NdtTable *t = m->ndt.get();
-    if (!t || t->resolution != res || t->min_points != o.min_points || t->regularisation != o.regularisation) {
-      std::unique_ptr<NdtTable> made = ndt_build_table(ctx, m->points, res, o.min_points, o.regularisation);
-      ctx->sync();
-      const_cast<mm3d_map *>(m)->ndt = std::move(made);
-      t = m->ndt.get();
-    }
+    const NdtTable *t = map_kept(
+        ctx, m, &mm3d_map::ndt,
+        [&](const NdtTable &h) { return h.resolution == res && h.min_points == o.min_points && h.regularisation == o.regularisation; },
+        [&] { return ndt_build_table(ctx, m->points, res, o.min_points, o.regularisation); });
     if (job) { job->tgt_ndt = t; job->ndt_neighbours = o.neighbours; }
   }
 };
 const RefineNdt g_ndt;
-
-void set_on(mm3d_ctx *c, const IcpMethodBase *m, const mm3d_refine_options &o)
-{
-  c->refine_method = m;
-  c->refine_options = o;
-  for (mm3d_ctx *h : c->helpers) { h->refine_method = m; h->refine_options = o; }
-}
 
 }  // namespace
 
@@ -453,33 +442,21 @@ using namespace mm3d;
 
 extern "C" {
 
-void mm3d_refine_options_default(mm3d_refine_options *o)
-{
-  if (!o) return;
-  o->method = MM3D_REFINE_ICP;
-  o->resolution = 0.0;
-  o->neighbours = 7;
-  o->min_points = 6;
-  o->regularisation = 0.01;
-}
-
 int mm3d_set_refinement(mm3d_ctx *ctx, const mm3d_refine_options *options)
 {
   if (!ctx || !ndt_options_ok(options)) return MM3D_EINVAL;
   if (options->resolution != 0.0 && !ndt_resolution_ok(options->resolution)) return MM3D_EINVAL;     // (also catches NaN)
   std::lock_guard<std::mutex> lock(ctx->mu);        // (no call is running while the method changes)
-  if (ctx->device_set && options->method == MM3D_REFINE_NDT) {
-    ctx->err = "mm3d_set_refinement: NDT is not available on a device-list context";
-    return MM3D_EUNSUPPORTED;
-  }
-  set_on(ctx, options->method == MM3D_REFINE_NDT ? &g_ndt : nullptr, *options);
+  const bool ndt = options->method == MM3D_REFINE_NDT;
+  if (ndt && refused_on_device_list(ctx, "mm3d_set_refinement: NDT is not available on a device-list context")) return MM3D_EUNSUPPORTED;
+  select_stages(ctx, false, [&](StageSelection &s) { s.refine = ndt ? &g_ndt : nullptr; s.refine_options = *options; });
   return MM3D_OK;
 }
 
 int mm3d_get_refinement(const mm3d_ctx *ctx, mm3d_refine_options *options)
 {
   if (!ctx || !options) return MM3D_EINVAL;
-  *options = ctx->refine_options;
+  *options = ctx->sel.refine_options;
   return MM3D_OK;
 }
 

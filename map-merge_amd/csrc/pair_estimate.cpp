@@ -51,12 +51,12 @@ std::unique_ptr<mm3d_map> mm3d::map_features_impl(mm3d_ctx *ctx, const mm3d_clou
   // neighbour list over a ball that contains the normals': the two stages share that launch (sift.hip), same bits.
   std::unique_ptr<mm3d_normals> nrm;
   std::unique_ptr<mm3d_cloud> kp;
-  if (ctx->keypoint_source) {
+  if (ctx->sel.keypoints) {
     // mm3d_set_keypoints: no detector runs (keypoint_type and keypoint_threshold are not read); the normals come from their
     // stand-alone launch, since SIFT's fused first octave does not run
     nrm.reset(compute_normals(ctx, filt.get(), p->normal_radius));
-    const double leaf = ctx->keypoint_options.leaf > 0.0 ? ctx->keypoint_options.leaf : p->descriptor_radius / kUniformLeafDivisor;
-    kp.reset(ctx->keypoint_source->keypoints(ctx, filt.get(), leaf));
+    const double leaf = ctx->sel.keypoint_options.leaf > 0.0 ? ctx->sel.keypoint_options.leaf : p->descriptor_radius / kUniformLeafDivisor;
+    kp.reset(ctx->sel.keypoints->keypoints(ctx, filt.get(), leaf));
   } else if (p->keypoint_type == MM3D_KP_HARRIS) {
     nrm.reset(compute_normals(ctx, filt.get(), p->normal_radius));
     kp.reset(detect_keypoints_harris(ctx, filt.get(), nrm.get(), p->keypoint_threshold, p->normal_radius));
@@ -76,18 +76,19 @@ std::unique_ptr<mm3d_map> mm3d::map_features_impl(mm3d_ctx *ctx, const mm3d_clou
                                                                          : compute_fpfh(ctx, filt.get(), nrm.get(), kp.get(), p->descriptor_radius));
   if (wait) ctx->sync();
   std::unique_ptr<mm3d_map> m = make_map(std::move(filt), std::move(kp), std::move(desc));
-  if (ctx->icp_method || ctx->coarse_method) m->normals = std::move(nrm);    // point-to-plane ICP reads them (mm3d_set_icp_method), and the correlative signature
+  if (ctx->sel.icp || ctx->sel.coarse) m->normals = std::move(nrm);    // point-to-plane ICP reads them (mm3d_set_icp_method), and the correlative signature
   return m;
 }
 
 void mm3d::map_prepare_impl(mm3d_ctx *ctx, mm3d_map *m, const mm3d_params *p)
 {
-  if (ctx->icp_method && !m->normals) m->normals.reset(compute_normals(ctx, m->points, p->normal_radius));
-  if (ctx->refine_method) ctx->refine_method->prepare_target(ctx, m, p, nullptr);   // NDT's voxel table (mm3d_set_refinement)
-  if (ctx->coarse_method) ctx->coarse_method->prepare(ctx, m, p);                   // the correlative signature (mm3d_set_coarse_alignment)
-  if (ctx->confidence_method) ctx->confidence_method->prepare(ctx, m, p);           // the overlap table (mm3d_set_confidence)
+  const StageSelection &sel = ctx->sel;
+  if (sel.icp) sel.icp->prepare_target(ctx, m, p, nullptr);            // the normals (mm3d_set_icp_method): no wait when the map has them
+  if (sel.refine) sel.refine->prepare_target(ctx, m, p, nullptr);      // NDT's voxel table (mm3d_set_refinement)
+  if (sel.coarse) sel.coarse->prepare(ctx, m, p);                      // the correlative signature (mm3d_set_coarse_alignment)
+  if (sel.confidence) sel.confidence->prepare(ctx, m, p);              // the overlap table (mm3d_set_confidence)
   prepare_pair_search(ctx, m->points, p->max_correspondence_distance, p->max_correspondence_distance);
-  if (p->estimation_method == MM3D_EST_SAC_IA && ctx->align_method) ctx->align_method->prepare(ctx, m->keypoints, p->max_correspondence_distance);
+  if (p->estimation_method == MM3D_EST_SAC_IA && sel.align) sel.align->prepare(ctx, m->keypoints, p->max_correspondence_distance);
   else if (p->estimation_method == MM3D_EST_SAC_IA) prepare_sacia_target(ctx, m->keypoints, (float)p->max_correspondence_distance);
   desc_knn_prepare_target(ctx, m->desc);
   (void)cloud_host(ctx, m->keypoints, false);       // (the keypoints' host copy rides on the wait below)
@@ -119,34 +120,9 @@ std::unique_ptr<mm3d_map> mm3d::pull_map_from_peer(mm3d_ctx *c, const mm3d_map *
   return make_map(std::move(pts), std::move(kp), std::move(desc));
 }
 
-// The normals point-to-plane ICP reads of a pair's target map: a map that mm3d_map_prepare did not give them (a map made
-// while the context was point-to-point, a cached one of such a call, one from parts) gets them on first use -- under its
-// points' lock, complete on the device before anybody else can see them, since other streams may share the map.
-static const mm3d_normals *map_normals(mm3d_ctx *ctx, const mm3d_map *m, const mm3d_params *p)
-{
-  std::lock_guard<std::recursive_mutex> lk(m->points->cache_mu);
-  if (!m->normals) {
-    std::unique_ptr<mm3d_normals> n(compute_normals(ctx, m->points, p->normal_radius));
-    ctx->sync();
-    const_cast<mm3d_map *>(m)->normals = std::move(n);
-  }
-  return m->normals.get();
-}
-
-// The estimation method as the rand() replay sees it: a prerejective alignment (mm3d_set_alignment) draws nothing from rand(),
-// which is MATCHING's case in pair_rand_replay; nor does the correlative alignment (mm3d_set_coarse_alignment).
-static int replay_method(const mm3d_ctx *ctx, const mm3d_params *p)
-{
-  if (ctx->coarse_method) return (int)MM3D_EST_MATCHING;
-  return ctx->align_method && p->estimation_method == MM3D_EST_SAC_IA ? (int)MM3D_EST_MATCHING : (int)p->estimation_method;
-}
-static bool prerejective(const mm3d_ctx *ctx, const mm3d_params *p)
-{
-  return !ctx->coarse_method && ctx->align_method && p->estimation_method == MM3D_EST_SAC_IA;
-}
 void mm3d::pair_replay_draws(GlibcRand &rnd, const mm3d_ctx *ctx, const mm3d_params *p, const std::vector<float4> &skp_host)
 {
-  pair_rand_replay(rnd, replay_method(ctx, p), skp_host, p->inlier_threshold, p->max_iterations);
+  pair_rand_replay(rnd, ctx->sel.replay_method(p), skp_host, p->inlier_threshold, p->max_iterations);
 }
 
 // what an estimate fills in, cleared; source_idx / target_idx are the caller's
@@ -167,15 +143,14 @@ void mm3d::pair_record_init(mm3d_pair_result *r, size_t source, size_t target)
 void mm3d::pair_estimate_impl(mm3d_ctx *ctx, const mm3d_map *s, const mm3d_map *t, const mm3d_params *p, bool execute,
                              mm3d_pair_result *out)
 {
-  if (execute && (ctx->icp_method || ctx->refine_method || ctx->coarse_method || ctx->confidence_method || prerejective(ctx, p))) {
-    // point-to-plane ICP (mm3d_set_icp_method), NDT (mm3d_set_refinement), the prerejective alignment (mm3d_set_alignment) and the
-    // overlap confidence (mm3d_set_confidence) live in the batch path: a batch of one, from (and advancing) the context's generator
+  if (execute && ctx->sel.batch_only(p)) {
+    // a batch of one, from (and advancing) the context's generator
     PairWork w{s, t, out, ctx->rnd};
     pairs_estimate_batch(ctx, &w, 1, p);
     return;
   }
   clear_estimate(out);
-  if (ctx->coarse_method || prerejective(ctx, p)) return;   // not executed, and nothing to replay (mm3d_set_alignment, mm3d_set_coarse_alignment)
+  if (ctx->sel.coarse || ctx->sel.prerejective(p)) return;   // not executed, and nothing to replay (mm3d_set_alignment, mm3d_set_coarse_alignment)
   // estimateTransform and transformScore of its result (R/src/map_merging.cpp:91-107) as one device
   // pipeline: the transform never visits the host in between
   double score = DBL_MAX;
@@ -239,17 +214,18 @@ void mm3d::pairs_estimate_batch(mm3d_ctx *ctx, PairWork *w, size_t n, const mm3d
   std::vector<PairFront> fronts(n);
   std::vector<IcpScoreJob> jobs(n);
   std::vector<SacPrepared> prepared;
+  const StageSelection &sel = ctx->sel;
   for (size_t i = 0; i < n; ++i) {
     mm3d_pair_result *out = w[i].out;
     clear_estimate(out);
     ctx->rnd = w[i].rnd;
-    if (ctx->coarse_method) {
+    if (sel.coarse) {
       // no keypoints, no descriptors, nothing of the generator: the two maps' signatures
-      ctx->coarse_method->front(ctx, w[i].s, w[i].t, p, fronts[i], &ctx->last_coarse_stats);
-    } else if (prerejective(ctx, p)) {
+      sel.coarse->front(ctx, w[i].s, w[i].t, p, fronts[i], &ctx->last_coarse_stats);
+    } else if (sel.prerejective(p)) {
       // the same inputs, max_correspondence_distance as the inlier distance; the generator's seed, none of its draws
-      ctx->align_method->front(ctx, ctx->align_options, w[i].rnd.seed0, w[i].s->keypoints, w[i].s->desc, w[i].t->keypoints, w[i].t->desc,
-                               p->max_correspondence_distance, fronts[i], &ctx->last_align_stats);
+      sel.align->front(ctx, sel.align_options, w[i].rnd.seed0, w[i].s->keypoints, w[i].s->desc, w[i].t->keypoints, w[i].t->desc,
+                       p->max_correspondence_distance, fronts[i], &ctx->last_align_stats);
     } else if (p->estimation_method == MM3D_EST_SAC_IA) {
       // argument mapping of matching.cpp:243-246: min_sample_distance := inlier_threshold
       sac_ia_replay(ctx, w[i].s->keypoints, w[i].s->desc, w[i].t->keypoints, w[i].t->desc, p->inlier_threshold, p->max_iterations, true,
@@ -284,17 +260,15 @@ void mm3d::pairs_estimate_batch(mm3d_ctx *ctx, PairWork *w, size_t n, const mm3d
   }
   // estimateTransform's ICP and transformScore of its result (R/src/map_merging.cpp:91-107), max_distance = max_correspondence_distance
   // (under mm3d_set_confidence nobody reads that score: it is not launched, and the ICP's states come back as they would have)
-  const bool want_score = !ctx->confidence_method;
-  if (ctx->refine_method) {                             // NDT in the ICP's place (mm3d_set_refinement): the targets' voxel tables
+  const bool want_score = !sel.confidence;
+  // NDT in the ICP's place (mm3d_set_refinement), else point-to-plane (mm3d_set_icp_method), else the reference's ICP; a method
+  // binds what it keeps on the targets (voxel tables, normals) to the jobs first
+  const IcpMethodBase *tail = sel.refine ? sel.refine : sel.icp;
+  if (tail) {
     if (p->refine_transform)
-      for (size_t i = 0; i < n; ++i) ctx->refine_method->prepare_target(ctx, w[i].t, p, &jobs[i]);
-    ctx->refine_method->score_batch(ctx, jobs.data(), (int)n, p->refine_transform != 0, p->max_correspondence_distance, p->max_iterations,
-                                    p->transform_epsilon, want_score, p->max_correspondence_distance);
-  } else if (ctx->icp_method) {                         // point-to-plane (mm3d_set_icp_method): the targets' normals
-    if (p->refine_transform)
-      for (size_t i = 0; i < n; ++i) jobs[i].tgt_normals = map_normals(ctx, w[i].t, p);
-    ctx->icp_method->score_batch(ctx, jobs.data(), (int)n, p->refine_transform != 0, p->max_correspondence_distance, p->max_iterations,
-                                 p->transform_epsilon, want_score, p->max_correspondence_distance);
+      for (size_t i = 0; i < n; ++i) tail->prepare_target(ctx, w[i].t, p, &jobs[i]);
+    tail->score_batch(ctx, jobs.data(), (int)n, p->refine_transform != 0, p->max_correspondence_distance, p->max_iterations,
+                      p->transform_epsilon, want_score, p->max_correspondence_distance);
   } else {
     icp_score_batch(ctx, jobs.data(), (int)n, p->refine_transform != 0, p->max_correspondence_distance, p->max_iterations, p->transform_epsilon,
                     want_score, p->max_correspondence_distance);
@@ -308,11 +282,11 @@ void mm3d::pairs_estimate_batch(mm3d_ctx *ctx, PairWork *w, size_t n, const mm3d
     out->icp_correspondences = jobs[i].out.n_corr;
     out->confidence = 1.0 / jobs[i].out.score;
   }
-  if (ctx->confidence_method) {
+  if (sel.confidence) {
     // the transforms are on the host: both maps' tables (made on first use), one launch and one wait for the whole batch
     std::vector<ConfidencePair> cp(n);
     for (size_t i = 0; i < n; ++i) cp[i] = ConfidencePair{w[i].s, w[i].t, w[i].out->transform, 0.0};
-    ctx->confidence_method->score(ctx, cp.data(), n, p, &ctx->last_confidence_stats);
+    sel.confidence->score(ctx, cp.data(), n, p, &ctx->last_confidence_stats);
     for (size_t i = 0; i < n; ++i) w[i].out->confidence = cp[i].confidence;
   }
 }

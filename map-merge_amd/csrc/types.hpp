@@ -20,19 +20,41 @@ struct KeypointSourceBase;
 struct CoarseMethodBase;
 struct ConfidenceMethodBase;
 
+// The opt-in stages of a context's pipeline (mm3d_set_icp_method, mm3d_set_alignment, mm3d_set_keypoints, mm3d_set_refinement,
+// mm3d_set_coarse_alignment, mm3d_set_confidence): a null method = the reference's stage.  The methods are process-wide
+// objects of their kernel files that hold no state and are not owned.  Every context has its own copy of the record; only
+// select_stages (drivers.hpp) changes one, and it and mm3d_set_streams hand the root's copy to the helpers.
+struct StageSelection {
+  const IcpMethodBase *icp = nullptr;                  // point-to-plane in the place of point-to-point
+  const AlignMethodBase *align = nullptr;              // the initial estimate under SAC_IA
+  const KeypointSourceBase *keypoints = nullptr;       // where a map's keypoints come from
+  const IcpMethodBase *refine = nullptr;               // what takes the ICP's place (NDT); `icp` keeps its own value beside it
+  const CoarseMethodBase *coarse = nullptr;            // what takes the initial estimate's place
+  const ConfidenceMethodBase *confidence = nullptr;    // what a pair record's confidence is
+  mm3d_alignment_options align_options;
+  mm3d_keypoint_options keypoint_options;
+  mm3d_refine_options refine_options;
+  mm3d_coarse_options coarse_options;
+  mm3d_confidence_options confidence_options;
+  StageSelection();                                    // capi.cpp: the options are the five mm3d_*_options_default's
+  int icp_method() const;                              // MM3D_ICP_*
+  // the pair's initial estimate is the prerejective alignment's
+  bool prerejective(const mm3d_params *p) const { return !coarse && align && p->estimation_method == MM3D_EST_SAC_IA; }
+  // The estimation method as the rand() replay sees it: neither the prerejective nor the correlative alignment draws from
+  // rand(), which is MATCHING's case in pair_rand_replay
+  int replay_method(const mm3d_params *p) const { return coarse || prerejective(p) ? (int)MM3D_EST_MATCHING : (int)p->estimation_method; }
+  // such a pair is estimated by pairs_estimate_batch alone (pair_estimate_impl hands it a batch of one)
+  bool batch_only(const mm3d_params *p) const { return icp || refine || coarse || confidence || prerejective(p); }
+};
+
 // The feature / pair cache of mm3d_estimate_maps_transforms (mm3d_set_map_cache; the concrete class is map_cache.cpp's).  The
 // drivers in capi.cpp only see this interface, so the host code links without it (tests/host_san).  One call at a time -- the
 // context's lock: begin, then lookups and inserts from any worker thread of the call, then commit (the call succeeded) or
 // abort (it did not: the cache is left exactly as it was before the call).
 struct MapCacheBase {
   virtual ~MapCacheBase() = default;
-  // icp_method: MM3D_ICP_* of the call (mm3d_set_icp_method); align: its alignment (mm3d_set_alignment); keypoints: where its
-  // maps' keypoints come from (mm3d_set_keypoints); refine: what refines its pairs (mm3d_set_refinement)
-  // coarse: what replaces its pairs' initial estimate (mm3d_set_coarse_alignment); confidence: what their records' confidence
-  // is (mm3d_set_confidence)
-  virtual void begin(size_t n_maps, const mm3d_params *p, int icp_method, const mm3d_alignment_options &align,
-                     const mm3d_keypoint_options &keypoints, const mm3d_refine_options &refine, const mm3d_coarse_options &coarse,
-                     const mm3d_confidence_options &confidence) = 0;
+  // sel: the call's stage selection (what keys a map's features and a pair's record besides the parameters)
+  virtual void begin(size_t n_maps, const mm3d_params *p, const StageSelection &sel) = 0;
   // map `slot`'s packed upload `raw` (non-empty, on c's stream): the cached bundle, borrowed for the call, or null.  One launch and
   // one wait on c (a second compare-only launch and wait when the digest names another candidate than the slot's last entry).
   virtual const mm3d_map *lookup(Context *c, size_t slot, const mm3d_cloud *raw) = 0;
@@ -52,35 +74,10 @@ struct MapCacheBase {
 struct mm3d_ctx : mm3d::Context {
   // mm3d_set_map_cache: null = off (the drivers take their plain path).  Owned by this context; never set on helpers or peers.
   mm3d::MapCacheBase *map_cache = nullptr;
-  // mm3d_set_icp_method: null = the reference's point-to-point ICP.  Not owned (a process-wide object of icp_plane.hip's that
-  // holds no state); set on the context and its helpers alike, and copied to helpers that mm3d_set_streams makes later.
-  const mm3d::IcpMethodBase *icp_method = nullptr;
-  // mm3d_set_alignment: null = the reference's SAC-IA.  Not owned (a process-wide object of align_prerej.hip's that holds no
-  // state); set, with the options, on the context and its helpers alike, and copied to helpers that mm3d_set_streams makes later.
-  const mm3d::AlignMethodBase *align_method = nullptr;
-  mm3d_alignment_options align_options{MM3D_ALIGN_SAC_IA, 1 << 16, 10, 0.9, 0.25};
+  mm3d::StageSelection sel;
+  // what the selected stages report of the most recent pair (mm3d_last_alignment_stats, mm3d_last_coarse_stats, mm3d_last_confidence_stats)
   mm3d_alignment_stats last_align_stats{0, 0, 0, -1, 0, 0};
-  // mm3d_set_keypoints: null = the reference's detectors (params.keypoint_type).  Not owned (a process-wide object of
-  // keypoints_uniform.hip's that holds no state); set, with the options, on the context, its helpers and its peers alike, and
-  // copied to helpers that mm3d_set_streams makes later.
-  const mm3d::KeypointSourceBase *keypoint_source = nullptr;
-  mm3d_keypoint_options keypoint_options{MM3D_KEYPOINTS_REFERENCE, 0.0};
-  // mm3d_set_refinement: null = the ICP that icp_method selects; otherwise it takes that ICP's place in the pair stage (NDT).
-  // Not owned (a process-wide object of ndt.hip's that holds no state); set, with the options, on the context and its helpers
-  // alike, and copied to helpers that mm3d_set_streams makes later.  icp_method keeps its own value beside it.
-  const mm3d::IcpMethodBase *refine_method = nullptr;
-  mm3d_refine_options refine_options{MM3D_REFINE_ICP, 0.0, 7, 6, 0.01};
-  // mm3d_set_coarse_alignment: null = the initial estimate that estimation_method and align_method select; otherwise it
-  // takes their place in the pair stage (align_correlative.hip).  Not owned (a process-wide object that holds no state); set,
-  // with the options, on the context and its helpers alike, and copied to helpers that mm3d_set_streams makes later.
-  const mm3d::CoarseMethodBase *coarse_method = nullptr;
-  mm3d_coarse_options coarse_options{MM3D_COARSE_NONE, 0.0, 4, 720, 6, 32, 0.5, 0.9, 3, 0.25};
   mm3d_coarse_stats last_coarse_stats{0, 0, 0, 0, 0, -1, 0, 0};
-  // mm3d_set_confidence: null = the reference's 1 / transformScore; otherwise it replaces a pair record's confidence after the
-  // pair stage (confidence_overlap.hip).  Not owned (a process-wide object that holds no state); set, with the options, on the
-  // context and its helpers alike, and copied to helpers that mm3d_set_streams makes later.
-  const mm3d::ConfidenceMethodBase *confidence_method = nullptr;
-  mm3d_confidence_options confidence_options{MM3D_CONFIDENCE_REFERENCE, 0.0, 8, 0.05, 0};
   mm3d_overlap_stats last_confidence_stats{0, 0, 0, 0, 0, 0, 0.0};
   // mm3d_set_streams: helper contexts (one HIP stream + one host thread each while a call is running)
   // that mm3d_estimate_maps_transforms deals maps and pairs to; owned by this context
@@ -246,17 +243,12 @@ struct mm3d_map {
   mm3d_cloud *points = nullptr;
   mm3d_cloud *keypoints = nullptr;
   mm3d_desc *desc = nullptr;
-  // the points' normals (normal_radius), kept for point-to-plane ICP only (mm3d_set_icp_method): null otherwise
-  std::unique_ptr<mm3d_normals> normals;
-  // the points' voxel Gaussians, kept for NDT only (mm3d_set_refinement): null otherwise.  Made and replaced under the
-  // points' cache_mu (mm3d_map_prepare, or a pair's first use of the map as a target).
-  std::unique_ptr<mm3d::NdtTable> ndt;
-  // the points' correlative signature, kept for mm3d_set_coarse_alignment only: null otherwise.  Made and replaced under the
-  // points' cache_mu (mm3d_map_prepare, or a pair's first use of the map); the normals above are kept for it too.
-  std::unique_ptr<mm3d::CoarseSignature> coarse;
-  // the points' overlap table, kept for mm3d_set_confidence only: null otherwise.  Made and replaced under the points'
-  // cache_mu (mm3d_map_prepare, or a pair's first use of the map, in either role).
-  std::unique_ptr<mm3d::OverlapTable> overlap;
+  // What the opt-in stages keep of the points, null until one asks: made and replaced through map_kept (map_kept.hpp) alone,
+  // by mm3d_map_prepare or a pair's first use of the map.
+  std::unique_ptr<mm3d_normals> normals;            // (normal_radius) point-to-plane ICP, the correlative signature
+  std::unique_ptr<mm3d::NdtTable> ndt;              // NDT's voxel Gaussians
+  std::unique_ptr<mm3d::CoarseSignature> coarse;    // the correlative alignment's signature
+  std::unique_ptr<mm3d::OverlapTable> overlap;      // the overlap confidence's table
   mm3d_map() = default;
   mm3d_map(const mm3d_map &) = delete;
   mm3d_map &operator=(const mm3d_map &) = delete;
@@ -391,10 +383,11 @@ struct IcpMethodBase {
   // icp_score_batch with this method's ICP
   virtual void score_batch(Context *c, IcpScoreJob *jobs, int n_jobs, bool run_icp, double max_corr_dist, int max_iterations, double eps,
                            bool want_score, double score_max_distance) const = 0;
-  // what the method keeps on a target map beyond its search structures (NDT's voxel table): made when missing or stale,
-  // complete on the device before anybody else can see it, and bound to `job` when there is one
-  virtual void prepare_target(mm3d_ctx *, const mm3d_map *, const mm3d_params *, IcpScoreJob *) const {}
+  // what the method keeps on a target map beyond its search structures (point-to-plane's normals, NDT's voxel table): made
+  // when missing or stale (map_kept.hpp; no wait when it is there), and bound to `job` when there is one
+  virtual void prepare_target(mm3d_ctx *, const mm3d_map *, const mm3d_params *, IcpScoreJob *) const = 0;
 };
+inline int StageSelection::icp_method() const { return icp ? icp->method() : MM3D_ICP_POINT_TO_POINT; }
 struct PairFront;
 // The initial alignment of a context's pair stage under SAC_IA (mm3d_set_alignment; the one concrete class is
 // align_prerej.hip's).  Like IcpMethodBase, the drivers in capi.cpp only see this interface, so the host code links without
@@ -422,8 +415,7 @@ struct KeypointSourceBase {
 // new kernels (tests/host_san); a null pointer on the context means the estimate that estimation_method selects.
 struct CoarseMethodBase {
   virtual ~CoarseMethodBase() = default;
-  // the map's signature at the context's options (and the normals it is made from): made when missing or stale, under the
-  // points' lock and complete on the device before anybody else can see it
+  // the map's signature at the context's options (and the normals it is made from), made when missing or stale (map_kept.hpp)
   virtual void prepare(mm3d_ctx *ctx, const mm3d_map *m, const mm3d_params *p) const = 0;
   // the pair's initial estimate: f.dT0 / f.on_device, or the identity in f.T0
   virtual void front(mm3d_ctx *ctx, const mm3d_map *s, const mm3d_map *t, const mm3d_params *p, PairFront &f, mm3d_coarse_stats *stats) const = 0;
@@ -434,8 +426,7 @@ struct CoarseMethodBase {
 struct ConfidencePair { const mm3d_map *s, *t; const float *T; double confidence; };   // T: the pair's transform on the host, 16 floats
 struct ConfidenceMethodBase {
   virtual ~ConfidenceMethodBase() = default;
-  // the map's table at the context's options: made when missing or stale, under the points' lock and complete on the device
-  // before anybody else can see it
+  // the map's table at the context's options, made when missing or stale (map_kept.hpp)
   virtual void prepare(mm3d_ctx *ctx, const mm3d_map *m, const mm3d_params *p) const = 0;
   // the confidences of a batch of pairs at their host transforms: one launch, one wait; stats (may be null) receives the
   // last pair's counts
