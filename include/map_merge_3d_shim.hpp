@@ -121,6 +121,61 @@ inline void check_confidence_devices(const mm3d_confidence_options &o, const cha
   if (o.method == MM3D_CONFIDENCE_OVERLAP && devices && *devices)
     throw std::runtime_error("mm3d: MM3D_CONFIDENCE=overlap is not available with MM3D_DEVICES (a device list carries no tables)");
 }
+// MM3D_ICP_REJECT=<term>[+<term>...]: the estimation context's ICP rejects correspondences (mm3d_set_icp_rejection).  Terms:
+// one_to_one, trimmed[:<overlap ratio in (0, 1]>], median[:<factor > 0>]; without a value, mm3d_icp_rejection_options_default's
+// (0.5, 1.0).  none or unset rejects nothing.  trimmed and median together, a term twice, an unknown term or a value out of
+// range throw, as a malformed MM3D_ICP does.
+inline mm3d_icp_rejection_options parse_icp_reject(const char *value)
+{
+  mm3d_icp_rejection_options o;
+  o.one_to_one = 0;
+  o.distance = MM3D_REJECT_NONE;
+  o.overlap_ratio = 0.5;
+  o.min_correspondences = 0;
+  o.median_factor = 1.0;
+  const std::string v = value ? value : "";
+  if (v.empty() || v == "none") return o;
+  bool ok = true;
+  for (size_t a = 0; ok && a <= v.size();) {
+    size_t b = v.find('+', a);
+    if (b == std::string::npos) b = v.size();
+    const std::string term = v.substr(a, b - a);
+    const size_t colon = term.find(':');
+    const std::string name = term.substr(0, colon);
+    double x = 0.0;
+    if (colon != std::string::npos) {
+      const char *s = term.c_str() + colon + 1;
+      char *end = nullptr;
+      x = std::strtod(s, &end);
+      ok = end != s && *end == '\0' && std::isfinite(x) && x > 0.0;
+    }
+    if (name == "one_to_one") {
+      ok = ok && colon == std::string::npos && !o.one_to_one;
+      o.one_to_one = 1;
+    } else if (name == "trimmed") {
+      ok = ok && o.distance == MM3D_REJECT_NONE && (colon == std::string::npos || x <= 1.0);
+      o.distance = MM3D_REJECT_TRIMMED;
+      if (colon != std::string::npos) o.overlap_ratio = x;
+    } else if (name == "median") {
+      ok = ok && o.distance == MM3D_REJECT_NONE;
+      o.distance = MM3D_REJECT_MEDIAN;
+      if (colon != std::string::npos) o.median_factor = x;
+    } else {
+      ok = false;
+    }
+    a = b + 1;
+  }
+  if (!ok)
+    throw std::runtime_error("mm3d: MM3D_ICP_REJECT must be none or terms joined by '+' out of one_to_one, trimmed[:<ratio>], "
+                             "median[:<factor>] (trimmed and median exclude each other), not '" + v + "'");
+  return o;
+}
+// Not available on a device list (its devices' pair loops run the ICP without rejection): an active value with MM3D_DEVICES throws.
+inline void check_icp_reject_devices(const mm3d_icp_rejection_options &o, const char *devices)
+{
+  if ((o.one_to_one || o.distance != MM3D_REJECT_NONE) && devices && *devices)
+    throw std::runtime_error("mm3d: MM3D_ICP_REJECT is not available with MM3D_DEVICES (a device list runs the ICP without rejection)");
+}
 }  // namespace mm3d_shim
 }  // namespace map_merge_3d
 
@@ -205,7 +260,10 @@ inline mm3d_ctx *ctx()
   // MM3D_REFINE=ndt[:<resolution>]: parse_refine above.  Not available on a device list: ndt with MM3D_DEVICES set as well throws.
   // MM3D_COARSE=correlative[:<cell>]: parse_coarse above.  Not available on a device list: correlative with MM3D_DEVICES set as well throws.
   // MM3D_CONFIDENCE=overlap[:<voxel>]: parse_confidence above.  Not available on a device list: overlap with MM3D_DEVICES set as well throws.
+  // MM3D_ICP_REJECT=one_to_one+trimmed:0.7 ...: parse_icp_reject above.  Not available on a device list: an active value with MM3D_DEVICES set as well throws.
   static mm3d_ctx *c = [] {
+    const mm3d_icp_rejection_options reject = parse_icp_reject(std::getenv("MM3D_ICP_REJECT"));
+    check_icp_reject_devices(reject, std::getenv("MM3D_DEVICES"));
     const mm3d_confidence_options confidence = parse_confidence(std::getenv("MM3D_CONFIDENCE"));
     check_confidence_devices(confidence, std::getenv("MM3D_DEVICES"));
     const mm3d_coarse_options coarse = parse_coarse(std::getenv("MM3D_COARSE"));
@@ -252,6 +310,8 @@ inline mm3d_ctx *ctx()
       throw std::runtime_error("mm3d: MM3D_COARSE was refused (the cell must be a positive float with a finite reciprocal)");
     if (confidence.method != MM3D_CONFIDENCE_REFERENCE && mm3d_set_confidence(e, &confidence) != MM3D_OK)
       throw std::runtime_error("mm3d: MM3D_CONFIDENCE was refused (the voxel must be a positive float with a finite reciprocal)");
+    if ((reject.one_to_one || reject.distance != MM3D_REJECT_NONE) && mm3d_set_icp_rejection(e, &reject) != MM3D_OK)
+      throw std::runtime_error(std::string("mm3d: MM3D_ICP_REJECT was refused: ") + mm3d_last_error(e));
     return e;
   }();
   return c;

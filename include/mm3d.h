@@ -843,6 +843,77 @@ int mm3d_transform_overlap(mm3d_ctx *ctx, const mm3d_cloud *source, const mm3d_c
 int mm3d_debug_overlap_table(mm3d_ctx *ctx, const mm3d_cloud *cloud, const mm3d_confidence_options *options, int box[12],
                              unsigned long long *words, size_t word_cap, unsigned char *view, size_t view_cap);
 
+/* ---------------------------------------------------------------- opt-in ICP correspondence rejection
+ * mm3d_set_icp_rejection lets the pair stage's ICP ignore correspondences: PCL's CorrespondenceRejectorOneToOne,
+ * CorrespondenceRejectorTrimmed and CorrespondenceRejectorMedianDistance, the three that need nothing but the correspondences.
+ * With the default options (nothing rejected) the selection is inactive and the pair stage runs the kernels it always ran.
+ * The rule, for ONE iteration of the loop that mm3d_set_icp_method states (everything else is that loop):
+ *   1. match     a finite source point is carried by the current float T; its exact float nearest target point is found (ties
+ *                to the lowest index); it is matched when d2 <= max_d2 (the float the ICP accepts at).
+ *   2. one_to_one  of all matched source points that share a target point, the one with the smallest 64-bit key
+ *                float_bits(d2) << 32 | original source index survives (an integer minimum: no arrival order shows).
+ *   3. distance  over the n survivors' d2 (non-negative, so its float bits order as the values do):
+ *       TRIMMED  k = max(min_correspondences, (long long)(overlap_ratio * (double)n)).  k >= n: nothing is cut.  k == 0:
+ *                everything is cut.  Otherwise tau is the k-th smallest d2 and every survivor with d2 <= tau is kept: ties at tau
+ *                are all kept, so kept >= k.  (PCL cuts its sorted list at k with an unspecified tie order: no parity is claimed.)
+ *       MEDIAN   m is the survivor d2 of 0-based rank n / 2 in ascending order; a survivor is kept when
+ *                (double)d2 <= (double)m * median_factor.
+ *                tau and m are exact order statistics (a radix select on the device, no host round trip in an iteration).
+ *   4. estimate  the sums of the selected estimate (point-to-point's 17 terms, point-to-plane's 30) run over the kept
+ *                correspondences only, in the order the default kernels add them, and the default finalize kernels run on
+ *                them: with nothing rejected the result is the default ICP's, bit for bit.  The "fewer than 3" stop, the MSE
+ *                of the convergence test and icp_correspondences all count kept correspondences.
+ * Results are bit-identical for every stream count, batch and cache setting.  Applies to the ICP of
+ * mm3d_estimate_maps_transforms and mm3d_pair_estimate, with either mm3d_set_icp_method; NDT (mm3d_set_refinement) does not
+ * read the setting, nor do mm3d_estimate_transform_icp, mm3d_estimate_transform_icp_plane, mm3d_estimate_transform,
+ * transformScore or the overlap confidence.  Working memory per pair of a batch: 8 B per source point, 8 B per target point
+ * under one_to_one, 4 KiB of histograms. */
+typedef enum { MM3D_REJECT_NONE = 0, MM3D_REJECT_TRIMMED = 1, MM3D_REJECT_MEDIAN = 2 } mm3d_reject_distance;
+typedef struct mm3d_icp_rejection_options {
+  int one_to_one;            /* 0 / 1 */
+  int distance;              /* MM3D_REJECT_* */
+  double overlap_ratio;      /* TRIMMED: 0 < rho <= 1 */
+  int min_correspondences;   /* TRIMMED: keep at least this many, >= 0 */
+  double median_factor;      /* MEDIAN: > 0, finite */
+} mm3d_icp_rejection_options;
+typedef struct mm3d_icp_rejection_stats {  /* of the LAST iteration that ran */
+  long long matched;         /* finite source points whose nearest target point has d2 <= max_d2 */
+  long long after_one_to_one;/* == matched when one_to_one is 0 */
+  long long kept;            /* == the pair record's icp_correspondences */
+  float threshold_d2;        /* tau (TRIMMED) or m (MEDIAN); +inf when distance is NONE, when nothing was cut or when there
+                              * was no survivor; -1 when TRIMMED cut everything (k == 0) */
+  int iterations, converged;
+} mm3d_icp_rejection_stats;
+void mm3d_icp_rejection_options_default(mm3d_icp_rejection_options *o);   /* 0, NONE, 0.5, 0, 1.0 (PCL's own defaults) */
+/* The selection is active when one_to_one || distance != MM3D_REJECT_NONE.  MM3D_EINVAL: ctx or options NULL, one_to_one not
+ * 0 / 1, an unknown distance, a value outside its range above (the values are checked whatever the selection).
+ * MM3D_EUNSUPPORTED: an active selection on a device-list context (mm3d_create_devices); mm3d_shard_begin returns
+ * MM3D_EUNSUPPORTED on a context with an active selection.  The setting reaches the context's mm3d_set_streams helpers, in
+ * either order, and is part of the map cache's pair key while active. */
+int mm3d_set_icp_rejection(mm3d_ctx *ctx, const mm3d_icp_rejection_options *options);
+int mm3d_get_icp_rejection(const mm3d_ctx *ctx, mm3d_icp_rejection_options *options);   /* MM3D_EINVAL for NULL */
+/* of the most recent pair whose ICP this context ran with rejection (the last pair of a whole-map call on one stream, or the
+ * call below); all zero, threshold_d2 +inf, before there was one */
+int mm3d_last_icp_rejection_stats(const mm3d_ctx *ctx, mm3d_icp_rejection_stats *stats);
+/* ICP with the rule above from initial_guess, whatever the context's setting: the correspondence stage of the rule runs even
+ * when `options` reject nothing.  target_normals NULL: the point-to-point estimate; else the point-to-plane one (normals in
+ * the target's order).  stats may be NULL.  MM3D_EINVAL: a NULL argument, options out of range, normals whose count differs
+ * from the target's. */
+int mm3d_estimate_transform_icp_rejecting(mm3d_ctx *ctx, const mm3d_cloud *source, const mm3d_cloud *target,
+                                          const mm3d_normals *target_normals, const float initial_guess[16],
+                                          double max_correspondence_distance, const mm3d_icp_rejection_options *options,
+                                          int max_iterations, double transformation_epsilon, float T[16],
+                                          mm3d_icp_rejection_stats *stats);
+/* test hook: ONE iteration's correspondence stage (steps 1 - 3) at T.  Per source point, in the caller's order: the matched
+ * target index (-1: none), the float d2 (+inf: none) and whether the correspondence was kept.  split: 1 or 4, as in
+ * mm3d_debug_nn_search.  stats (may be NULL): the counts and the threshold; iterations and converged are 0. */
+int mm3d_debug_icp_rejection(mm3d_ctx *ctx, const mm3d_cloud *source, const mm3d_cloud *target, const float T[16],
+                             double max_correspondence_distance, const mm3d_icp_rejection_options *options, int split, int *idx,
+                             float *d2, unsigned char *kept, mm3d_icp_rejection_stats *stats);
+/* test hook, process-wide like mm3d_debug_sacia_queries_per_thread: 0 = one or four work items per block chosen by size, as
+ * everywhere; 1 or 4 = forced in every rejecting launch from now on; negative = no change.  Returns the value in force. */
+int mm3d_debug_icp_rejection_split(int split);
+
 #ifdef __cplusplus
 }
 #endif

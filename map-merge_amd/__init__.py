@@ -175,6 +175,39 @@ class ConfidenceOptions(C.Structure):
         return tuple(int(getattr(self, k)) if t is C.c_int else float(getattr(self, k)) for k, t in self._fields_)
 
 
+class RejectDistance(enum.IntEnum):   # mm3d_reject_distance (not a reference enum)
+    NONE = 0
+    TRIMMED = 1
+    MEDIAN = 2
+
+
+class IcpRejectionOptions(C.Structure):
+    """mm3d_icp_rejection_options (mm3d_set_icp_rejection); the defaults are mm3d_icp_rejection_options_default's."""
+    _fields_ = [("one_to_one", C.c_int), ("distance", C.c_int), ("overlap_ratio", C.c_double), ("min_correspondences", C.c_int),
+                ("median_factor", C.c_double)]
+
+    def __init__(self, **kw):
+        super().__init__()
+        lib().mm3d_icp_rejection_options_default(C.byref(self))
+        kinds = dict(self._fields_)
+        for k, v in kw.items():
+            if k not in kinds:
+                raise TypeError("unknown ICP rejection option " + k)
+            setattr(self, k, int(v) if kinds[k] is C.c_int else float(v))
+
+    def as_tuple(self):
+        return tuple(int(getattr(self, k)) if t is C.c_int else float(getattr(self, k)) for k, t in self._fields_)
+
+
+class IcpRejectionStats(C.Structure):
+    """mm3d_icp_rejection_stats"""
+    _fields_ = [("matched", C.c_longlong), ("after_one_to_one", C.c_longlong), ("kept", C.c_longlong), ("threshold_d2", C.c_float),
+                ("iterations", C.c_int), ("converged", C.c_int)]
+
+    def as_dict(self):
+        return {k: (float if t is C.c_float else int)(getattr(self, k)) for k, t in self._fields_}
+
+
 class OverlapStats(C.Structure):
     """mm3d_overlap_stats"""
     _fields_ = [("points_st", C.c_longlong), ("in_st", C.c_longlong), ("hit_st", C.c_longlong), ("points_ts", C.c_longlong),
@@ -300,6 +333,12 @@ def sacia_queries_per_thread(k=-1):
     """mm3d_debug_sacia_queries_per_thread: force SAC-IA's error kernel to k source keypoints per thread (1, 2, 4, 8; 0: by
     the launch's size again; negative: leave as it is).  Returns the count large launches use."""
     return int(lib().mm3d_debug_sacia_queries_per_thread(int(k)))
+
+
+def icp_rejection_split(split=-1):
+    """mm3d_debug_icp_rejection_split: force every rejecting launch to one work item per wave (1) or per block (4); 0: chosen by
+    size again; negative: leave as it is.  Returns the value in force."""
+    return int(lib().mm3d_debug_icp_rejection_split(int(split)))
 
 
 class Context:
@@ -461,6 +500,25 @@ class Context:
         o = ConfidenceOptions()
         self._ck(lib().mm3d_get_confidence(self._h, C.byref(o)))
         return o
+
+    def setIcpRejection(self, options=None, **kw):
+        """mm3d_set_icp_rejection: which correspondences the pair stage's ICP ignores.  An IcpRejectionOptions, or its fields as
+        keywords (one_to_one=0 / 1, distance=RejectDistance.TRIMMED / MEDIAN, overlap_ratio=..., min_correspondences=...,
+        median_factor=...)."""
+        o = options if options is not None else IcpRejectionOptions(**kw)
+        self._ck(lib().mm3d_set_icp_rejection(self._h, C.byref(o)))
+
+    def getIcpRejection(self) -> "IcpRejectionOptions":
+        o = IcpRejectionOptions()
+        self._ck(lib().mm3d_get_icp_rejection(self._h, C.byref(o)))
+        return o
+
+    @property
+    def last_icp_rejection_stats(self) -> dict:
+        """mm3d_last_icp_rejection_stats: the last iteration of the most recent rejecting ICP this context ran."""
+        st = IcpRejectionStats()
+        self._ck(lib().mm3d_last_icp_rejection_stats(self._h, C.byref(st)))
+        return st.as_dict()
 
     def lastConfidenceStats(self) -> dict:
         st = OverlapStats()
@@ -639,6 +697,22 @@ class Context:
         self.last_icp_converged = lib().mm3d_last_icp_converged(self._h)
         return _Tout(T)
 
+    def estimateTransformICPRejecting(self, source_points, target_points, target_normals, initial_guess, max_correspondence_distance,
+                                      options=None, max_iterations=100, transformation_epsilon=0.0, **kw):
+        """mm3d_estimate_transform_icp_rejecting: ICP with correspondence rejection from initial_guess, whatever the context's
+        setting.  target_normals None: the point-to-point estimate, else the point-to-plane one."""
+        o = options if options is not None else IcpRejectionOptions(**kw)
+        g = _T(initial_guess)
+        T = np.zeros(16, dtype=np.float32)
+        st = IcpRejectionStats()
+        self._ck(lib().mm3d_estimate_transform_icp_rejecting(
+            self._h, source_points._h, target_points._h, target_normals._h if target_normals is not None else None,
+            g.ctypes.data_as(C.c_void_p), C.c_double(max_correspondence_distance), C.byref(o), int(max_iterations),
+            C.c_double(transformation_epsilon), T.ctypes.data_as(C.c_void_p), C.byref(st)))
+        self.last_icp_iterations = lib().mm3d_last_icp_iterations(self._h)
+        self.last_icp_converged = lib().mm3d_last_icp_converged(self._h)
+        return _Tout(T)
+
     def estimateTransformNDT(self, source_points, target_points, initial_guess, options=None, max_iterations=100,
                              transformation_epsilon=0.0, **kw):
         """mm3d_estimate_transform_ndt: NDT from initial_guess, whatever the context's setting (options.resolution > 0)."""
@@ -779,6 +853,22 @@ class Context:
                                             C.c_double(range), int(convention), int(split), idx.ctypes.data_as(C.c_void_p),
                                             d2.ctypes.data_as(C.c_void_p), C.byref(info)))
         return idx[:n], d2[:n], info.as_dict()
+
+    def debugIcpRejection(self, source_points, target_points, transform, max_correspondence_distance, options=None, split=1, **kw):
+        """mm3d_debug_icp_rejection: one iteration's correspondence stage at `transform`.  Returns (idx int32[n], d2 float32[n],
+        kept bool[n], stats dict) in the source's own order."""
+        o = options if options is not None else IcpRejectionOptions(**kw)
+        n = len(source_points)
+        idx = np.zeros(max(n, 1), dtype=np.int32)
+        d2 = np.zeros(max(n, 1), dtype=np.float32)
+        kept = np.zeros(max(n, 1), dtype=np.uint8)
+        t = _T(transform)
+        st = IcpRejectionStats()
+        self._ck(lib().mm3d_debug_icp_rejection(self._h, source_points._h, target_points._h, t.ctypes.data_as(C.c_void_p),
+                                                C.c_double(max_correspondence_distance), C.byref(o), int(split),
+                                                idx.ctypes.data_as(C.c_void_p), d2.ctypes.data_as(C.c_void_p),
+                                                kept.ctypes.data_as(C.c_void_p), C.byref(st)))
+        return idx[:n], d2[:n], kept[:n].astype(bool), st.as_dict()
 
     def transformScore(self, source_points, target_points, transform, max_distance) -> float:
         t = _T(transform)

@@ -35,6 +35,7 @@ mm3d::StageSelection::StageSelection()
   mm3d_refine_options_default(&refine_options);
   mm3d_coarse_options_default(&coarse_options);
   mm3d_confidence_options_default(&confidence_options);
+  mm3d_icp_rejection_options_default(&reject_options);
 }
 
 void mm3d::select_stages(mm3d_ctx *ctx, bool peers_follow, const std::function<void(StageSelection &)> &edit)
@@ -184,6 +185,10 @@ void mm3d_coarse_options_default(mm3d_coarse_options *o)
 void mm3d_confidence_options_default(mm3d_confidence_options *o)
 {
   if (o) *o = mm3d_confidence_options{MM3D_CONFIDENCE_REFERENCE, 0.0, 8, 0.05, 0};
+}
+void mm3d_icp_rejection_options_default(mm3d_icp_rejection_options *o)
+{
+  if (o) *o = mm3d_icp_rejection_options{0, MM3D_REJECT_NONE, 0.5, 0, 1.0};
 }
 
 // ---------------------------------------------------------------- context

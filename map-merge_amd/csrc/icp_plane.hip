@@ -183,6 +183,12 @@ void icp_plane_step(Context *c, const NnPlaneJob *jobs_dev, int count, unsigned 
     MM3D_LAUNCH(c, "icp_plane_corr_reduce", bytes, k_icp_plane_wave<4>, dim3(grid_x, count), dim3(256), 0, jobs_dev, max_d2, rmax);
   else
     MM3D_LAUNCH(c, "icp_plane_corr_reduce", bytes, k_icp_plane_wave<1>, dim3(grid_x, count), dim3(256), 0, jobs_dev, max_d2, rmax);
+  icp_plane_finalize(c, jobs_dev, count, finalize_bytes);
+}
+
+// (alone: the rejecting correspondence stage of icp_reject.hip writes the partials this reads)
+void icp_plane_finalize(Context *c, const NnPlaneJob *jobs_dev, int count, double finalize_bytes)
+{
   MM3D_LAUNCH(c, "icp_plane_finalize", finalize_bytes, k_icp_plane_finalize, dim3(count), dim3(256), 0, jobs_dev);
 }
 

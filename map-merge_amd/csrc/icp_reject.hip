@@ -1,0 +1,455 @@
+// icp_reject.hip -- correspondence rejection for the pair stage's ICP, opt-in (mm3d_set_icp_rejection): PCL's
+// CorrespondenceRejectorOneToOne, CorrespondenceRejectorTrimmed and CorrespondenceRejectorMedianDistance, the three rejectors
+// that need nothing but the correspondences.  include/mm3d.h states the rule.
+//
+// The default ICP fuses the search with its sums (k_nn_wave<0>, k_icp_plane_wave), so an order statistic over one iteration's
+// d2 has nowhere to happen.  Here the iteration is a correspondence STAGE of its own between the search and the sums, all of it
+// on the device, every launch over the pair batch (blockIdx.y = the pair) and returning at once for a pair that is done:
+//   k_rej_begin    one block per pair: the pair's record and its four histograms cleared
+//   k_rej_search   nn_search_body.hpp's wave-cooperative search (the same include as k_nn_wave, k_nn_probe and
+//                  k_icp_plane_wave); a lane stores {target index, d2 bits} at its point's place in the Hilbert-ordered source
+//                  (8 B per source point) and, under one_to_one, takes its target with an integer atomicMin of
+//                  d2 bits << 32 | original source index (8 B per target point): no arrival order shows
+//   k_rej_hist     pass 0 settles one_to_one in place (a loser keeps its index as -2 - index) and counts the survivors; passes
+//                  0 .. 3 are a most-significant-digit-first radix select over the survivors' 32 d2 bits, 8 bits a pass: LDS
+//                  histograms, integer atomics into the pair's 256 bins.  d2 >= 0, so the bits order like the values, and the
+//                  k-th smallest comes out EXACT.  The digit that holds the wanted rank is found at the head of the NEXT launch,
+//                  by every block for itself from the finished histogram (a 256-entry scan): all blocks compute the same
+//                  prefix and rank, and block-identical values are what they store.
+//   k_rej_reduce   the work item <-> wave <-> lane mapping of the search again: a lane decides "kept" from its 8 bytes and the
+//                  threshold, and the kept correspondences' terms (k_nn_wave<0>'s 17, or k_icp_plane_wave's 30 with normals) go
+//                  through wave_sum and the block step into the partials, in the default kernels' layout and order.
+// k_icp_finalize / k_icp_plane_finalize then run unchanged.  With nothing rejected the partials hold the default kernels' bits.
+#include <atomic>
+#include <cmath>
+
+#include "capi_guard.hpp"
+#include "drivers.hpp"
+#include "icp_solve6.hpp"
+#include "nn_core.hpp"
+
+namespace mm3d {
+
+// the options as the kernels take them
+struct RejOpts {
+  int one_to_one, distance, min_corr;
+  double ratio, factor;
+};
+constexpr int kRejPerBlock = 4096;     // source points per block of a histogram pass
+
+__global__ void __launch_bounds__(256) k_rej_begin(const NnRejectJob *__restrict__ rjobs)
+{
+  const NnRejectJob &rj = rjobs[blockIdx.x];
+  if (rj.nn.st->done) return;
+  for (int k = threadIdx.x; k < 4 * 256; k += 256) rj.hist[k] = 0u;
+  if (threadIdx.x == 0) {
+    RejRecord r;
+    r.matched = r.survivors = r.kept = 0u;
+    r.tau_bits = 0u;
+    r.cut = 1;
+    for (int q = 0; q < 4; ++q) { r.prefix[q] = 0u; r.rank[q] = 0u; }
+    *rj.rec = r;
+  }
+}
+
+template <int SPLIT>
+__global__ void __launch_bounds__(256) MM3D_NN_ATTR
+k_rej_search(const NnRejectJob *__restrict__ rjobs, float max_d2, float rmax)
+{
+  constexpr int MODE = 0;                                // (nn_search_body.hpp: the keyed search, with the winner's index)
+  const NnJob &job = rjobs[blockIdx.y].nn;
+  if ((int)blockIdx.x >= job.nblocks) return;            // the grid is as wide as the batch's largest job
+  const float4 *__restrict__ src = job.src;
+  const int2 *__restrict__ items = job.items;
+  const int n_items = job.n_items;
+  const GridView g = job.g;
+  const IcpState *__restrict__ st = job.st;
+  int2 *__restrict__ corr = rjobs[blockIdx.y].corr;
+  unsigned long long *__restrict__ owner = rjobs[blockIdx.y].owner;
+  RejRecord *__restrict__ rec = rjobs[blockIdx.y].rec;
+  const int max_ring = job.max_ring;
+  __shared__ float Ts[16];
+  __shared__ __attribute__((aligned(16))) float s_cx[4][kTile], s_cy[4][kTile], s_cz[4][kTile];
+  __shared__ __attribute__((aligned(16))) unsigned s_cw[4][kTile];
+  __shared__ int s_off[4][kRows];
+  __shared__ int s_beg[4][kRows];
+  __shared__ unsigned long long s_merge[SPLIT == 4 ? 4 : 1][64];
+  if (st->done) return;
+  if (threadIdx.x < 16) Ts[threadIdx.x] = st->T[threadIdx.x];
+  __syncthreads();
+#include "nn_search_body.hpp"
+  if (SPLIT == 4 && wave != 0) return;     // the four waves hold the same result
+  const bool matched = valid && best <= max_d2;   // false for INFINITY / NaN
+  if (valid) {
+    const unsigned w = (unsigned)(bkey & 0xffffffffull);
+    corr[i] = matched ? make_int2((int)w, __float_as_int(best)) : make_int2(-1, 0x7f800000);
+    if (matched && owner)
+      atomicMin(&owner[w], ((unsigned long long)__float_as_uint(best) << 32) | (unsigned long long)__float_as_uint(src[i].w));
+  }
+  const int n = __popcll(ballot(matched));
+  if (lane == 0 && n) atomicAdd(&rec->matched, (unsigned)n);
+}
+
+// The select's state before pass q + 1, from pass q's finished histogram and the state before pass q (q == 0: from the number
+// of survivors).  Called by all 256 threads of a block; every block of a launch arrives at the same values.
+struct RejSel { int cut; unsigned prefix, rank; };
+__device__ __forceinline__ RejSel rej_select_step(const NnRejectJob &rj, const RejOpts &o, int q, unsigned *s_scan, unsigned *s_res)
+{
+  const int t = threadIdx.x;
+  const RejRecord *rec = rj.rec;
+  int cut = 0;
+  unsigned prefix = 0u, rank = 0u;
+  if (q == 0) {
+    const long long n = (long long)rec->survivors;
+    if (o.distance == MM3D_REJECT_TRIMMED) {
+      const long long kr = (long long)(o.ratio * (double)n), k = kr > (long long)o.min_corr ? kr : (long long)o.min_corr;
+      if (k >= n) cut = 1;
+      else if (k == 0) cut = 2;
+      else rank = (unsigned)(k - 1);
+    } else {
+      if (n == 0) cut = 1;
+      else rank = (unsigned)(n / 2);
+    }
+  } else {
+    cut = rec->cut;
+    prefix = rec->prefix[q];
+    rank = rec->rank[q];
+  }
+  if (cut != 0) return RejSel{cut, 0u, 0u};      // (block-uniform)
+  const unsigned h = rj.hist[q * 256 + t];
+  s_scan[t] = h;
+  if (t < 2) s_res[t] = 0u;
+  __syncthreads();
+  for (int d = 1; d < 256; d <<= 1) {
+    const unsigned v = t >= d ? s_scan[t - d] : 0u;
+    __syncthreads();
+    s_scan[t] += v;
+    __syncthreads();
+  }
+  const unsigned incl = s_scan[t], excl = incl - h;
+  if (rank >= excl && rank < incl) { s_res[0] = (unsigned)t; s_res[1] = rank - excl; }
+  __syncthreads();
+  const RejSel r{0, (prefix << 8) | s_res[0], s_res[1]};
+  __syncthreads();
+  return r;
+}
+
+__global__ void __launch_bounds__(256) k_rej_hist(const NnRejectJob *__restrict__ rjobs, RejOpts o, int pass)
+{
+  const NnRejectJob &rj = rjobs[blockIdx.y];
+  if (rj.nn.st->done) return;
+  const int n_src = rj.n_src, base = (int)blockIdx.x * kRejPerBlock;
+  if (base >= n_src) return;
+  __shared__ unsigned s_h[256], s_scan[256], s_res[2];
+  const int t = threadIdx.x;
+  unsigned prefix = 0u;
+  if (pass > 0) {
+    const RejSel sel = rej_select_step(rj, o, pass - 1, s_scan, s_res);
+    if (t == 0) {      // (the same values from every block)
+      rj.rec->cut = sel.cut;
+      rj.rec->prefix[pass] = sel.prefix;
+      rj.rec->rank[pass] = sel.rank;
+    }
+    if (sel.cut != 0) return;
+    prefix = sel.prefix;
+  }
+  s_h[t] = 0u;
+  __syncthreads();
+  int mine = 0;
+  const int shift = 32 - 8 * pass;
+  const int end = min(base + kRejPerBlock, n_src);
+  for (int i = base + t; i < end; i += 256) {
+    const int2 cr = rj.corr[i];
+    if (cr.x < 0) continue;                   // no match, or lost its target
+    const unsigned bits = (unsigned)cr.y;
+    if (pass == 0) {
+      if (rj.owner) {
+        const unsigned long long key = ((unsigned long long)bits << 32) | (unsigned long long)__float_as_uint(rj.nn.src[i].w);
+        if (rj.owner[cr.x] != key) {
+          rj.corr[i] = make_int2(-2 - cr.x, cr.y);
+          continue;
+        }
+      }
+      ++mine;
+      if (o.distance != MM3D_REJECT_NONE) atomicAdd(&s_h[bits >> 24], 1u);
+    } else {
+      if ((bits >> shift) != prefix) continue;
+      atomicAdd(&s_h[(bits >> (shift - 8)) & 255u], 1u);
+    }
+  }
+  __syncthreads();
+  if (s_h[t]) atomicAdd(&rj.hist[pass * 256 + t], s_h[t]);
+  if (pass == 0) {
+    const int total = wave_sum(mine);
+    if ((t & 63) == 0 && total) atomicAdd(&rj.rec->survivors, (unsigned)total);
+  }
+}
+
+// the threshold of the iteration, after the select's last pass: by all 256 threads of a block
+struct RejCut { int cut; unsigned tau; };
+__device__ __forceinline__ RejCut rej_threshold(const NnRejectJob &rj, const RejOpts &o, unsigned *s_scan, unsigned *s_res)
+{
+  if (o.distance == MM3D_REJECT_NONE) return RejCut{1, 0u};
+  const RejSel sel = rej_select_step(rj, o, 3, s_scan, s_res);
+  if (threadIdx.x == 0 && sel.cut == 0) rj.rec->tau_bits = sel.prefix;      // (the same value from every block)
+  return RejCut{sel.cut, sel.prefix};
+}
+__device__ __forceinline__ bool rej_kept(int idx, unsigned bits, const RejCut &c, const RejOpts &o)
+{
+  if (idx < 0 || c.cut == 2) return false;
+  if (c.cut == 1) return true;
+  if (o.distance == MM3D_REJECT_TRIMMED) return bits <= c.tau;
+  return (double)__uint_as_float(bits) <= (double)__uint_as_float(c.tau) * o.factor;
+}
+
+// SPLIT 1: the partials per block of four work items, through k_nn_wave's block step; SPLIT 4: per work item.  Either way a
+// block holds four items, one per wave.
+template <int SPLIT, bool PLANE>
+__global__ void __launch_bounds__(256) k_rej_reduce(const NnRejectJob *__restrict__ rjobs, RejOpts o)
+{
+  constexpr int NACC = PLANE ? kPlaneAcc : kAcc;
+  const NnRejectJob &rj = rjobs[blockIdx.y];
+  const NnJob &job = rj.nn;
+  const int n_items = job.n_items;
+  if ((int)blockIdx.x * 4 >= n_items) return;
+  const IcpState *__restrict__ st = job.st;
+  if (st->done) return;
+  const float4 *__restrict__ src = job.src;
+  const float4 *__restrict__ tgt_ref = job.tgt_ref;
+  const float4 *__restrict__ nrm = rj.nrm;
+  double *__restrict__ partials = job.partials;
+  __shared__ float Ts[16];
+  __shared__ double red[4][NACC];
+  __shared__ unsigned s_scan[256], s_res[2];
+  if (threadIdx.x < 16) Ts[threadIdx.x] = st->T[threadIdx.x];
+  const RejCut cut = rej_threshold(rj, o, s_scan, s_res);
+  __syncthreads();
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int item = (int)blockIdx.x * 4 + wave;
+  const int2 it = item < n_items ? job.items[item] : make_int2(0, 0);
+  const int i = it.x + lane;
+  const bool valid = lane < it.y;
+  int2 cr = make_int2(-1, 0x7f800000);
+  if (valid) cr = rj.corr[i];
+  const bool corr = valid && rej_kept(cr.x, (unsigned)cr.y, cut, o);
+  const float best = __int_as_float(cr.y);
+  float3 p = make_float3(0.f, 0.f, 0.f);
+  if (corr) {
+    const float4 s = src[i];
+    p = xform(Ts, s.x, s.y, s.z);
+  }
+  const unsigned long long kept_mask = ballot(corr);
+  const bool any_corr = kept_mask != 0ull;       // wave-uniform
+  if (lane == 0 && any_corr) atomicAdd(&rj.rec->kept, (unsigned)__popcll(kept_mask));
+  if (!PLANE) {
+    // k_nn_wave<0>'s terms and order
+    double acc[kAcc];
+#pragma unroll
+    for (int k = 0; k < kAcc; ++k) acc[k] = 0.0;
+    if (corr) {
+      const float4 bq = tgt_ref[cr.x];
+      const float bqx = bq.x, bqy = bq.y, bqz = bq.z;
+      acc[0] = p.x; acc[1] = p.y; acc[2] = p.z;
+      acc[3] = bqx; acc[4] = bqy; acc[5] = bqz;
+      acc[6] = (double)bqx * p.x; acc[7] = (double)bqx * p.y; acc[8] = (double)bqx * p.z;
+      acc[9] = (double)bqy * p.x; acc[10] = (double)bqy * p.y; acc[11] = (double)bqy * p.z;
+      acc[12] = (double)bqz * p.x; acc[13] = (double)bqz * p.y; acc[14] = (double)bqz * p.z;
+      acc[15] = best;
+      acc[16] = 1.0;
+    }
+#pragma unroll
+    for (int k = 0; k < kAcc; ++k) {
+      const double v = any_corr ? wave_sum(acc[k]) : 0.0;
+      if (SPLIT == 4) {
+        if (lane == 0 && item < n_items) partials[(size_t)item * kAcc + k] = v;
+      } else if (lane == 0) {
+        red[wave][k] = v;
+      }
+    }
+  } else {
+    // k_icp_plane_wave's row, terms and order
+    double v[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    double r = 0.0, has_row = 0.0;
+    if (corr) {
+      const float4 n = nrm[cr.x];
+      if (isfinite(n.x) && isfinite(n.y) && isfinite(n.z)) {
+        const float4 d = tgt_ref[cr.x];
+        const double sx = p.x, sy = p.y, sz = p.z, nx = n.x, ny = n.y, nz = n.z;
+        v[0] = nz * sy - ny * sz;
+        v[1] = nx * sz - nz * sx;
+        v[2] = ny * sx - nx * sy;
+        v[3] = nx; v[4] = ny; v[5] = nz;
+        r = (nx * (double)d.x + ny * (double)d.y + nz * (double)d.z) - (nx * sx + ny * sy + nz * sz);
+        has_row = 1.0;
+      }
+    }
+    auto term = [&](int k) -> double {
+      if (k < 21) return v[kUi[k]] * v[kUj[k]];
+      if (k < 27) return v[k - 21] * r;
+      if (k == 27) return corr ? (double)best : 0.0;
+      if (k == 28) return corr ? 1.0 : 0.0;
+      return has_row;
+    };
+#pragma unroll
+    for (int k = 0; k < kPlaneAcc; ++k) {
+      const double s = any_corr ? wave_sum(term(k)) : 0.0;
+      if (SPLIT == 4) {
+        if (lane == 0 && item < n_items) partials[(size_t)item * kPlaneAcc + k] = s;
+      } else if (lane == 0) {
+        red[wave][k] = s;
+      }
+    }
+  }
+  if (SPLIT == 4) return;
+  __syncthreads();
+  if (threadIdx.x < NACC) {
+    const int k = threadIdx.x;
+    partials[(size_t)blockIdx.x * NACC + k] = red[0][k] + red[1][k] + red[2][k] + red[3][k];
+  }
+}
+
+// mm3d_debug_icp_rejection: the reduce kernel's decision per source point, stored at the point's ORIGINAL index
+__global__ void __launch_bounds__(256) k_rej_export(const NnRejectJob *__restrict__ rjobs, RejOpts o, int *__restrict__ out_idx,
+                                                    float *__restrict__ out_d2, unsigned char *__restrict__ out_kept)
+{
+  const NnRejectJob &rj = rjobs[0];
+  const NnJob &job = rj.nn;
+  const int n_items = job.n_items;
+  if ((int)blockIdx.x * 4 >= n_items) return;
+  __shared__ unsigned s_scan[256], s_res[2];
+  const RejCut cut = rej_threshold(rj, o, s_scan, s_res);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int item = (int)blockIdx.x * 4 + wave;
+  const int2 it = item < n_items ? job.items[item] : make_int2(0, 0);
+  const int i = it.x + lane;
+  const bool valid = lane < it.y;
+  bool kept = false;
+  if (valid) {
+    const int2 cr = rj.corr[i];
+    kept = rej_kept(cr.x, (unsigned)cr.y, cut, o);
+    const int orig = __float_as_int(job.src[i].w);
+    out_idx[orig] = cr.x == -1 ? -1 : (cr.x < 0 ? -2 - cr.x : cr.x);
+    out_d2[orig] = cr.x == -1 ? INFINITY : __int_as_float(cr.y);
+    out_kept[orig] = kept ? 1 : 0;
+  }
+  const unsigned long long m = ballot(kept);
+  if (lane == 0 && m) atomicAdd(&rj.rec->kept, (unsigned)__popcll(m));
+}
+
+static RejOpts rej_opts(const mm3d_icp_rejection_options &opt)
+{
+  return RejOpts{opt.one_to_one, opt.distance, opt.min_correspondences, opt.overlap_ratio, opt.median_factor};
+}
+
+// begin, search and the select's passes of one iteration
+static void reject_front(Context *c, const NnRejectJob *jobs_dev, int count, unsigned grid_x, unsigned max_src, bool split, float max_d2,
+                         float rmax, const mm3d_icp_rejection_options &opt, unsigned long long *owner_all, size_t owner_bytes, double bytes)
+{
+  const RejOpts o = rej_opts(opt);
+  MM3D_LAUNCH(c, "icp_reject_begin", count * 4096.0, k_rej_begin, dim3(count), dim3(256), 0, jobs_dev);
+  if (opt.one_to_one && owner_bytes) MM3D_HIP(hipMemsetAsync(owner_all, 0xff, owner_bytes, c->stream));
+  if (split)
+    MM3D_LAUNCH(c, "icp_reject_search", bytes, k_rej_search<4>, dim3(grid_x, count), dim3(256), 0, jobs_dev, max_d2, rmax);
+  else
+    MM3D_LAUNCH(c, "icp_reject_search", bytes, k_rej_search<1>, dim3(grid_x, count), dim3(256), 0, jobs_dev, max_d2, rmax);
+  const int passes = opt.distance != MM3D_REJECT_NONE ? 4 : opt.one_to_one ? 1 : 0;
+  for (int pass = 0; pass < passes; ++pass)
+    MM3D_LAUNCH(c, "icp_reject_select", (double)max_src * count * 8.0, k_rej_hist, dim3(div_up(max_src, kRejPerBlock), count), dim3(256), 0,
+                jobs_dev, o, pass);
+}
+
+void icp_reject_step(Context *c, const NnRejectJob *jobs_dev, int count, unsigned grid_x, unsigned max_src, bool split, bool plane,
+                     float max_d2, float rmax, const mm3d_icp_rejection_options &opt, unsigned long long *owner_all, size_t owner_bytes,
+                     double bytes)
+{
+  reject_front(c, jobs_dev, count, grid_x, max_src, split, max_d2, rmax, opt, owner_all, owner_bytes, bytes);
+  const RejOpts o = rej_opts(opt);
+  const dim3 grid(split ? div_up(grid_x, 4) : grid_x, count);      // four work items per block either way
+  const double rbytes = (double)max_src * count * 24.0;
+  if (split && plane) MM3D_LAUNCH(c, "icp_reject_reduce", rbytes, (k_rej_reduce<4, true>), grid, dim3(256), 0, jobs_dev, o);
+  else if (split) MM3D_LAUNCH(c, "icp_reject_reduce", rbytes, (k_rej_reduce<4, false>), grid, dim3(256), 0, jobs_dev, o);
+  else if (plane) MM3D_LAUNCH(c, "icp_reject_reduce", rbytes, (k_rej_reduce<1, true>), grid, dim3(256), 0, jobs_dev, o);
+  else MM3D_LAUNCH(c, "icp_reject_reduce", rbytes, (k_rej_reduce<1, false>), grid, dim3(256), 0, jobs_dev, o);
+}
+
+void icp_reject_debug(Context *c, const NnRejectJob *job_dev, unsigned grid_x, unsigned n_src, int n_items, bool split, float max_d2, float rmax,
+                      const mm3d_icp_rejection_options &opt, unsigned long long *owner, size_t owner_bytes, int *out_idx, float *out_d2,
+                      unsigned char *out_kept)
+{
+  reject_front(c, job_dev, 1, grid_x, n_src, split, max_d2, rmax, opt, owner, owner_bytes, n_src * 24.0);
+  MM3D_LAUNCH(c, "icp_reject_export", n_src * 17.0, k_rej_export, dim3(div_up(n_items, 4)), dim3(256), 0, job_dev, rej_opts(opt), out_idx, out_d2,
+              out_kept);
+}
+
+static std::atomic<int> g_forced_split{0};
+int icp_reject_forced_split() { return g_forced_split.load(); }
+
+bool icp_rejection_options_valid(const mm3d_icp_rejection_options *o)
+{
+  if (o->one_to_one != 0 && o->one_to_one != 1) return false;
+  if (o->distance != MM3D_REJECT_NONE && o->distance != MM3D_REJECT_TRIMMED && o->distance != MM3D_REJECT_MEDIAN) return false;
+  if (!(o->overlap_ratio > 0.0 && o->overlap_ratio <= 1.0)) return false;
+  if (o->min_correspondences < 0) return false;
+  return o->median_factor > 0.0 && std::isfinite(o->median_factor);
+}
+
+}  // namespace mm3d
+
+using namespace mm3d;
+
+extern "C" {
+
+int mm3d_set_icp_rejection(mm3d_ctx *ctx, const mm3d_icp_rejection_options *options)
+{
+  if (!ctx || !options || !icp_rejection_options_valid(options)) return MM3D_EINVAL;
+  std::lock_guard<std::mutex> lock(ctx->mu);        // (no call is running while the selection changes)
+  const bool active = options->one_to_one || options->distance != MM3D_REJECT_NONE;
+  if (active && refused_on_device_list(ctx, "mm3d_set_icp_rejection: not available on a device-list context")) return MM3D_EUNSUPPORTED;
+  select_stages(ctx, false, [&](StageSelection &s) { s.reject_options = *options; });
+  return MM3D_OK;
+}
+
+int mm3d_get_icp_rejection(const mm3d_ctx *ctx, mm3d_icp_rejection_options *options)
+{
+  if (!ctx || !options) return MM3D_EINVAL;
+  *options = ctx->sel.reject_options;
+  return MM3D_OK;
+}
+
+int mm3d_last_icp_rejection_stats(const mm3d_ctx *ctx, mm3d_icp_rejection_stats *stats)
+{
+  if (!ctx || !stats) return MM3D_EINVAL;
+  *stats = ctx->last_reject_stats;
+  return MM3D_OK;
+}
+
+int mm3d_estimate_transform_icp_rejecting(mm3d_ctx *ctx, const mm3d_cloud *source, const mm3d_cloud *target,
+                                          const mm3d_normals *target_normals, const float initial_guess[16], double max_corr_dist,
+                                          const mm3d_icp_rejection_options *options, int max_iterations, double eps, float T[16],
+                                          mm3d_icp_rejection_stats *stats)
+{
+  if (!source || !target || !initial_guess || !options || !T || !icp_rejection_options_valid(options)) return MM3D_EINVAL;
+  if (target_normals && target_normals->n != target->n) {
+    if (ctx) ctx->err = "mm3d_estimate_transform_icp_rejecting: the normals do not match the target's points";
+    return MM3D_EINVAL;
+  }
+  return guarded(ctx, [&] {
+    IcpScoreJob J;
+    J.src = source; J.tgt = target; J.tgt_normals = target_normals;
+    J.reject = options;
+    std::memcpy(J.guess_host, initial_guess, sizeof(J.guess_host));
+    if (target_normals) icp_plane_score_batch(ctx, &J, 1, true, max_corr_dist, max_iterations, eps, false, 0.0);
+    else icp_score_batch(ctx, &J, 1, true, max_corr_dist, max_iterations, eps, false, 0.0);
+    std::memcpy(T, J.out.T, sizeof(J.out.T));
+    ctx->last_reject_stats = J.reject_stats;
+    if (stats) *stats = J.reject_stats;
+  });
+}
+
+int mm3d_debug_icp_rejection_split(int split)
+{
+  if (split == 0 || split == 1 || split == 4) g_forced_split.store(split);
+  return g_forced_split.load();
+}
+
+}  // extern "C"

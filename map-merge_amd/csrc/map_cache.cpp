@@ -73,6 +73,12 @@ std::string pair_params_key(const mm3d_params *p, const StageSelection &sel)
   const bool ovl = conf.method == MM3D_CONFIDENCE_OVERLAP;
   k.i32(conf.method).f64(ovl ? conf.voxel : 0.0).i32(ovl ? conf.min_points : 0).f64(ovl ? conf.min_overlap : 0.0)
       .i32(ovl ? conf.view_margin : 0);
+  // the ICP's correspondence rejection (mm3d_set_icp_rejection): the five options while the selection is active, zeros
+  // otherwise (an inactive selection's other values are read by nothing: whatever they are, its records are shared)
+  const mm3d_icp_rejection_options &rej = sel.reject_options;
+  const bool rejecting = sel.rejecting();
+  k.i32(rejecting ? rej.one_to_one : 0).i32(rejecting ? rej.distance : 0).f64(rejecting ? rej.overlap_ratio : 0.0)
+      .i32(rejecting ? rej.min_correspondences : 0).f64(rejecting ? rej.median_factor : 0.0);
   return k.s;
 }
 

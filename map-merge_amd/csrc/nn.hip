@@ -324,7 +324,11 @@ static void launch_nn(Context *c, const char *name, double bytes, const NnJob *j
 // icp_corr_reduce + icp_finalize; everything else -- states, chunks, waits, the speculative point-to-point score -- is shared.
 // ndt: NDT (ndt.hip's ndt_step over NdtJobs that carry each target's voxel table) in the ICP's place: no grid of the target is
 // read by it, max_corr_dist is not read by it, and its partials are always per block of four work items.
+// Correspondence rejection (mm3d_set_icp_rejection): when the jobs carry options (IcpScoreJob::reject, the same for the whole batch),
+// the Point and Plane kinds take icp_reject.hip's icp_reject_step in the place of their search + reduction launch -- it leaves the
+// same partials for the kept correspondences -- and then their own finalize kernel.  NDT does not read the setting.
 enum class IcpKind { Point, Plane, Ndt };
+static float bits_to_float(unsigned u) { float f; memcpy(&f, &u, 4); return f; }
 static void icp_batch(Context *c, IcpScoreJob *jobs, int n_jobs, bool run_icp, double max_corr_dist, int max_iterations, double eps,
                       bool want_score, double score_max_distance, IcpKind kind)
 {
@@ -372,12 +376,14 @@ static void icp_batch(Context *c, IcpScoreJob *jobs, int n_jobs, bool run_icp, d
   }
   const int B = (int)live.size();
   if (B == 0) return;
+  const mm3d_icp_rejection_options *rej = (run_icp && !ndt) ? jobs[live[0].job].reject : nullptr;
 
   // one work item per block while the whole batch has too few items to fill the chip with one wave each
   // (the finalize kernels add the partials up in one fixed order, so the choice never shows in a result)
   int total_items = 0;
   for (const Live &L : live) total_items += L.n_items;
-  const bool split = nn_split_items(total_items);
+  const int forced_split = rej ? icp_reject_forced_split() : 0;       // (test hook: mm3d_debug_icp_rejection_split)
+  const bool split = forced_split ? forced_split == 4 : nn_split_items(total_items);
   size_t part_total = 0;
   unsigned grid_x = 0;
   double icp_bytes = 0.0, score_bytes = 0.0;
@@ -398,7 +404,22 @@ static void icp_batch(Context *c, IcpScoreJob *jobs, int n_jobs, bool run_icp, d
   }
   DevBuf<double> partials(c, icp_part_total), s_partials(c, want_score ? part_total : 1);
   DevBuf<double> out(c, (size_t)2 * B);
-  DevBuf<IcpState> st(c, B);
+  // (rejection: the pairs' records live behind the states, so that one copy brings both back)
+  const size_t rec_bytes = rej ? sizeof(RejRecord) * B : 0;
+  DevBuf<IcpState> st(c, B + div_up(rec_bytes, sizeof(IcpState)));
+  RejRecord *d_rec = (RejRecord *)(st.get() + B);
+  size_t rej_src = 0, rej_tgt = 0;
+  unsigned rej_max_src = 0;
+  if (rej)
+    for (const Live &L : live) {
+      rej_src += (size_t)L.ns;
+      rej_tgt += rej->one_to_one ? jobs[L.job].tgt->n : 0;
+      rej_max_src = std::max(rej_max_src, (unsigned)L.ns);
+    }
+  DevBuf<NnRejectJob> d_rjobs(c, rej ? (size_t)B : 1);
+  DevBuf<int2> rej_corr(c, rej ? rej_src : 1);
+  DevBuf<unsigned long long> rej_owner(c, rej_tgt ? rej_tgt : 1);
+  DevBuf<unsigned> rej_hist(c, rej ? (size_t)B * 1024 : 1);
   DevBuf<NnJob> d_jobs(c, (size_t)2 * B);                 // [0, B): ICP, [B, 2B): score
   DevBuf<NnPlaneJob> d_pjobs(c, plane ? (size_t)B : 1);   // point-to-plane: the ICP jobs with their normals
   DevBuf<NdtJob> d_njobs(c, ndt ? (size_t)B : 1);         // NDT: the ICP jobs with their voxel tables
@@ -406,13 +427,16 @@ static void icp_batch(Context *c, IcpScoreJob *jobs, int n_jobs, bool run_icp, d
   // host images, in the pinned arena: states | ICP jobs | score jobs | scores back | point-to-plane jobs | NDT jobs
   const size_t st_bytes = sizeof(IcpState) * B, job_bytes = sizeof(NnJob) * 2 * B, out_bytes = 16 * (size_t)B;
   const size_t pjob_bytes = plane ? sizeof(NnPlaneJob) * B : 0, njob_bytes = ndt ? sizeof(NdtJob) * B : 0;
-  char *pinned = (char *)c->pin(st_bytes + job_bytes + out_bytes + pjob_bytes + njob_bytes + 64);
+  const size_t rjob_bytes = rej ? sizeof(NnRejectJob) * B : 0, st_rec_bytes = st_bytes + rec_bytes;
+  char *pinned = (char *)c->pin(st_rec_bytes + job_bytes + out_bytes + pjob_bytes + njob_bytes + rjob_bytes + 64);
   IcpState *hp = (IcpState *)pinned;
-  NnJob *hj = (NnJob *)(pinned + ((st_bytes + 15) & ~(size_t)15));
+  RejRecord *hr = (RejRecord *)(pinned + st_bytes);
+  NnJob *hj = (NnJob *)(pinned + ((st_rec_bytes + 15) & ~(size_t)15));
   double *ho = (double *)((char *)hj + job_bytes);
   NnPlaneJob *hpj = (NnPlaneJob *)((char *)ho + out_bytes);
   NdtJob *hnj = (NdtJob *)((char *)hpj + pjob_bytes);
-  size_t off = 0, icp_off = 0;
+  NnRejectJob *hrj = (NnRejectJob *)((char *)hnj + njob_bytes);
+  size_t off = 0, icp_off = 0, rej_src_off = 0, rej_tgt_off = 0;
   for (int b = 0; b < B; ++b) {
     const Live &L = live[b];
     const IcpScoreJob &J = jobs[L.job];
@@ -443,6 +467,22 @@ static void icp_batch(Context *c, IcpScoreJob *jobs, int n_jobs, bool run_icp, d
       hpj[b].nn = q;
       hpj[b].nrm = L.tg ? (const float4 *)J.tgt_normals->nrm.get() : nullptr;
     }
+    if (rej) {
+      NnRejectJob rj;
+      memset(&rj, 0, sizeof(rj));
+      rj.nn = q;
+      rj.nrm = (plane && L.tg) ? (const float4 *)J.tgt_normals->nrm.get() : nullptr;
+      rj.corr = rej_corr.get() + rej_src_off;
+      rj.owner = rej->one_to_one ? rej_owner.get() + rej_tgt_off : nullptr;
+      rj.hist = rej_hist.get() + (size_t)b * 1024;
+      rj.rec = d_rec + b;
+      rj.n_src = L.ns;
+      hrj[b] = rj;
+      memset(&hr[b], 0, sizeof(RejRecord));
+      hr[b].cut = 1;
+      rej_src_off += (size_t)L.ns;
+      rej_tgt_off += rej->one_to_one ? J.tgt->n : 0;
+    }
     if (ndt) {
       NdtJob nj;
       memset(&nj, 0, sizeof(nj));
@@ -465,8 +505,13 @@ static void icp_batch(Context *c, IcpScoreJob *jobs, int n_jobs, bool run_icp, d
     off += (size_t)nb[b] * kAcc;
     icp_off += (size_t)(ndt ? div_up(L.n_items, 4) : nb[b]) * icp_acc;
   }
-  MM3D_HIP(hipMemcpyAsync(st.get(), hp, st_bytes, hipMemcpyHostToDevice, c->stream));
+  MM3D_HIP(hipMemcpyAsync(st.get(), hp, st_rec_bytes, hipMemcpyHostToDevice, c->stream));
   MM3D_HIP(hipMemcpyAsync(d_jobs.get(), hj, job_bytes, hipMemcpyHostToDevice, c->stream));
+  if (rej) {
+    MM3D_HIP(hipMemcpyAsync(d_rjobs.get(), hrj, rjob_bytes, hipMemcpyHostToDevice, c->stream));
+    // (a place of the Hilbert-ordered source that no work item covers holds "no match" for good)
+    MM3D_HIP(hipMemsetAsync(rej_corr.get(), 0xff, rej_src * sizeof(int2), c->stream));
+  }
   if (plane) MM3D_HIP(hipMemcpyAsync(d_pjobs.get(), hpj, pjob_bytes, hipMemcpyHostToDevice, c->stream));
   if (ndt) MM3D_HIP(hipMemcpyAsync(d_njobs.get(), hnj, njob_bytes, hipMemcpyHostToDevice, c->stream));
   for (int b = 0; b < B; ++b)
@@ -483,6 +528,13 @@ static void icp_batch(Context *c, IcpScoreJob *jobs, int n_jobs, bool run_icp, d
     const int chunk = round == 0 ? min_chunk : 2;
     if (run_icp) {
       for (int k = 0; k < chunk; ++k) {
+        if (rej) {
+          icp_reject_step(c, d_rjobs.get(), B, grid_x, rej_max_src, split, plane, max_d2, rmax, *rej, rej_owner.get(),
+                          rej_tgt * sizeof(unsigned long long), icp_bytes + rej_src * 8.0);
+          if (plane) icp_plane_finalize(c, d_pjobs.get(), B, icp_part_total * 8.0);
+          else MM3D_LAUNCH(c, "icp_finalize", part_total * 8.0, k_icp_finalize, dim3(B), dim3(256), 0, (const NnJob *)d_jobs.get());
+          continue;
+        }
         if (plane) {
           icp_plane_step(c, d_pjobs.get(), B, grid_x, split, max_d2, rmax, icp_bytes, icp_part_total * 8.0);
           continue;
@@ -500,7 +552,7 @@ static void icp_batch(Context *c, IcpScoreJob *jobs, int n_jobs, bool run_icp, d
       MM3D_LAUNCH(c, "score_finalize", 0, k_score_finalize, dim3(B), dim3(256), 0, (const NnJob *)(d_jobs.get() + B));
       MM3D_HIP(hipMemcpyAsync(ho, out.get(), out_bytes, hipMemcpyDeviceToHost, c->stream));
     }
-    MM3D_HIP(hipMemcpyAsync(hp, st.get(), st_bytes, hipMemcpyDeviceToHost, c->stream));
+    MM3D_HIP(hipMemcpyAsync(hp, st.get(), st_rec_bytes, hipMemcpyDeviceToHost, c->stream));
     c->sync();
     bool all_done = true;
     for (int b = 0; b < B; ++b) {
@@ -512,6 +564,15 @@ static void icp_batch(Context *c, IcpScoreJob *jobs, int n_jobs, bool run_icp, d
         J.out.converged = hp[b].converged;
         J.out.n_corr = hp[b].n_corr;
         if (want_score) J.out.score = ho[2 * b + 1] > 0.0 ? ho[2 * b] / ho[2 * b + 1] : DBL_MAX;
+        if (rej) {
+          const RejRecord &r = hr[b];
+          J.reject_stats.matched = r.matched;
+          J.reject_stats.after_one_to_one = rej->one_to_one ? r.survivors : r.matched;
+          J.reject_stats.kept = r.kept;
+          J.reject_stats.threshold_d2 = r.cut == 0 ? bits_to_float(r.tau_bits) : r.cut == 1 ? INFINITY : -1.0f;
+          J.reject_stats.iterations = hp[b].iters;
+          J.reject_stats.converged = hp[b].converged;
+        }
         J.closed = true;
       }
       if (!hp[b].done) all_done = false;
@@ -673,6 +734,85 @@ static void debug_nn_search(Context *c, const mm3d_cloud *src, const mm3d_cloud 
   if (info) *info = I;
 }
 
+// mm3d_debug_icp_rejection: range, cell, ring, distance transform, source order and work items as icp_batch derives them, one
+// iteration's correspondence stage (icp_reject.hip) at T with the split forced, and every source point's decision
+static void debug_icp_rejection(Context *c, const mm3d_cloud *src, const mm3d_cloud *tgt, const float T[16], double max_corr_dist,
+                                const mm3d_icp_rejection_options &opt, int split, int *idx, float *d2, unsigned char *kept,
+                                mm3d_icp_rejection_stats *stats)
+{
+  const NnRange r = nn_range_icp(max_corr_dist);
+  mm3d_icp_rejection_stats S{0, 0, 0, INFINITY, 0, 0};
+  std::vector<int> h_idx(src->n, -1);
+  std::vector<float> h_d2(src->n, INFINITY);
+  std::vector<unsigned char> h_kept(src->n, 0);
+  int ns = 0;
+  const float4 *sp = (src->n && tgt->n) ? morton_source(c, src, ns) : nullptr;
+  const Grid *tg = ns ? &cloud_grid(c, tgt, nn_cell_for(r.radius)) : nullptr;
+  if (tg && tg->n) {
+    const int max_ring = nn_max_ring(r.rmax, *tg);
+    grid_ensure_dt(c, *tg, max_ring);
+    const int n_items = src->n_wave_items;
+    const unsigned nblocks = split == 4 ? (unsigned)n_items : div_up(n_items, 4);
+    DevBuf<int> d_idx(c, src->n);
+    DevBuf<float> d_d2(c, src->n);
+    DevBuf<unsigned char> d_kept(c, src->n);
+    DevBuf<IcpState> st(c, 2);                       // the state, and the record behind it
+    RejRecord *d_rec = (RejRecord *)(st.get() + 1);
+    DevBuf<NnRejectJob> d_job(c, 1);
+    DevBuf<int2> corr(c, (size_t)ns);
+    DevBuf<unsigned long long> owner(c, opt.one_to_one ? tgt->n : 1);
+    DevBuf<unsigned> hist(c, 1024);
+    char *pinned = (char *)c->pin(2 * sizeof(IcpState) + sizeof(NnRejectJob) + 64);
+    IcpState *hs = (IcpState *)pinned;
+    RejRecord *hr = (RejRecord *)(hs + 1);
+    NnRejectJob *hj = (NnRejectJob *)(pinned + 2 * sizeof(IcpState));
+    memset(hs, 0, 2 * sizeof(IcpState));
+    memcpy(hs->T, T, 64);
+    hr->cut = 1;
+    NnRejectJob q;
+    memset(&q, 0, sizeof(q));
+    q.nn.src = sp;
+    q.nn.items = (const int2 *)src->wave_items.get();
+    q.nn.n_items = n_items;
+    q.nn.nblocks = (int)nblocks;
+    q.nn.split = split == 4 ? 1 : 0;
+    q.nn.g = tg->view();
+    q.nn.tgt_ref = (const float4 *)tgt->pts.get();
+    q.nn.st = st.get();
+    q.nn.max_ring = max_ring;
+    q.corr = corr.get();
+    q.owner = opt.one_to_one ? owner.get() : nullptr;
+    q.hist = hist.get();
+    q.rec = d_rec;
+    q.n_src = ns;
+    *hj = q;
+    // (non-finite source points are in no work item: they keep -1 / +inf / 0)
+    MM3D_HIP(hipMemcpyAsync(d_idx.get(), h_idx.data(), src->n * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    MM3D_HIP(hipMemcpyAsync(d_d2.get(), h_d2.data(), src->n * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    MM3D_HIP(hipMemsetAsync(d_kept.get(), 0, src->n, c->stream));
+    MM3D_HIP(hipMemsetAsync(corr.get(), 0xff, (size_t)ns * sizeof(int2), c->stream));
+    MM3D_HIP(hipMemcpyAsync(st.get(), hs, 2 * sizeof(IcpState), hipMemcpyHostToDevice, c->stream));
+    MM3D_HIP(hipMemcpyAsync(d_job.get(), hj, sizeof(NnRejectJob), hipMemcpyHostToDevice, c->stream));
+    icp_reject_debug(c, d_job.get(), nblocks, (unsigned)ns, n_items, split == 4, r.max_d2, r.rmax, opt, owner.get(),
+                     opt.one_to_one ? tgt->n * sizeof(unsigned long long) : 0, d_idx.get(), d_d2.get(), d_kept.get());
+    MM3D_HIP(hipMemcpyAsync(h_idx.data(), d_idx.get(), src->n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    MM3D_HIP(hipMemcpyAsync(h_d2.data(), d_d2.get(), src->n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    MM3D_HIP(hipMemcpyAsync(h_kept.data(), d_kept.get(), src->n, hipMemcpyDeviceToHost, c->stream));
+    MM3D_HIP(hipMemcpyAsync(hs, st.get(), 2 * sizeof(IcpState), hipMemcpyDeviceToHost, c->stream));
+    c->sync();
+    S.matched = hr->matched;
+    S.after_one_to_one = opt.one_to_one ? hr->survivors : hr->matched;
+    S.kept = hr->kept;
+    S.threshold_d2 = hr->cut == 0 ? bits_to_float(hr->tau_bits) : hr->cut == 1 ? INFINITY : -1.0f;
+  }
+  if (src->n) {
+    memcpy(idx, h_idx.data(), src->n * sizeof(int));
+    memcpy(d2, h_d2.data(), src->n * sizeof(float));
+    memcpy(kept, h_kept.data(), src->n);
+  }
+  if (stats) *stats = S;
+}
+
 #ifdef MM3D_NN_STATS
 extern "C" void mm3d_debug_nn_stats(unsigned long long *out, int reset)
 {
@@ -708,4 +848,16 @@ extern "C" int mm3d_debug_nn_search(mm3d_ctx *ctx, const mm3d_cloud *source, con
   if (!(range >= 0.0) || !std::isfinite(range)) return MM3D_EINVAL;
   if (source->n && (!idx || !d2)) return MM3D_EINVAL;
   return mm3d::guarded(ctx, [&] { mm3d::debug_nn_search(ctx, source, target, T, range, convention, split, idx, d2, info); });
+}
+
+extern "C" int mm3d_debug_icp_rejection(mm3d_ctx *ctx, const mm3d_cloud *source, const mm3d_cloud *target, const float T[16],
+                                        double max_correspondence_distance, const mm3d_icp_rejection_options *options, int split, int *idx,
+                                        float *d2, unsigned char *kept, mm3d_icp_rejection_stats *stats)
+{
+  if (!source || !target || !T || !options || !mm3d::icp_rejection_options_valid(options) || (split != 1 && split != 4)) return MM3D_EINVAL;
+  if (!(max_correspondence_distance >= 0.0) || !std::isfinite(max_correspondence_distance)) return MM3D_EINVAL;
+  if (source->n && (!idx || !d2 || !kept)) return MM3D_EINVAL;
+  return mm3d::guarded(ctx, [&] {
+    mm3d::debug_icp_rejection(ctx, source, target, T, max_correspondence_distance, *options, split, idx, d2, kept, stats);
+  });
 }

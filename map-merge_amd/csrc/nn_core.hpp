@@ -145,4 +145,40 @@ constexpr int kNdtAcc = 30;
 // IcpState protocol as icp_score_batch's
 void ndt_step(Context *c, const NdtJob *jobs_dev, int count, unsigned grid_x, double bytes, double finalize_bytes);
 
+// ICP with correspondence rejection (icp_reject.hip, mm3d_set_icp_rejection).  What one pair's selection leaves behind, on the
+// device beside the pair's IcpState and back on the host in the copy that brings the states: the counts of the last iteration
+// that ran and the state of the radix select (prefix / rank BEFORE pass q of four 8-bit passes over the d2 bits).
+struct RejRecord {
+  unsigned matched, survivors, kept;
+  unsigned tau_bits;          // TRIMMED: tau; MEDIAN: m (valid when cut == 0)
+  int cut;                    // 0: cut at tau_bits, 1: nothing is cut, 2: everything is cut
+  unsigned prefix[4], rank[4];
+};
+// the search job plus the rejecting stage's working memory; nn.partials: [nblocks][kAcc], or [nblocks][kPlaneAcc] with normals
+struct NnRejectJob {
+  NnJob nn;
+  const float4 *nrm;          // point-to-plane: the target's normals (tgt_ref's order); null: point-to-point
+  int2 *corr;                 // [n_src], at the point's place in the Hilbert-ordered source: {target index (-1: none;
+                              // -2 - index: lost its target under one_to_one), d2 bits}
+  unsigned long long *owner;  // one_to_one: [n_tgt] smallest key d2 bits << 32 | original source index per target point
+  unsigned *hist;             // [4][256]
+  RejRecord *rec;
+  int n_src;                  // finite source points
+};
+// One iteration's correspondence stage and sums for a batch: begin, search, the select's passes, the reduction into nn.partials
+// in the default kernels' layout and order.  The caller runs the default finalize kernel afterwards (k_icp_finalize over its
+// NnJobs, icp_plane_finalize over its NnPlaneJobs).  owner_all / owner_bytes: the batch's owner arrays as one region.
+void icp_reject_step(Context *c, const NnRejectJob *jobs_dev, int count, unsigned grid_x, unsigned max_src, bool split, bool plane,
+                     float max_d2, float rmax, const mm3d_icp_rejection_options &opt, unsigned long long *owner_all, size_t owner_bytes,
+                     double bytes);
+// icp_plane.hip: k_icp_plane_finalize alone
+void icp_plane_finalize(Context *c, const NnPlaneJob *jobs_dev, int count, double finalize_bytes);
+// mm3d_debug_icp_rejection_split: 0 (by size), 1 or 4
+int icp_reject_forced_split();
+// mm3d_debug_icp_rejection: begin, search and the select's passes for ONE job, then every source point's decision at its original index
+void icp_reject_debug(Context *c, const NnRejectJob *job_dev, unsigned grid_x, unsigned n_src, int n_items, bool split, float max_d2, float rmax,
+                      const mm3d_icp_rejection_options &opt, unsigned long long *owner, size_t owner_bytes, int *out_idx, float *out_d2,
+                      unsigned char *out_kept);
+bool icp_rejection_options_valid(const mm3d_icp_rejection_options *o);
+
 }  // namespace mm3d

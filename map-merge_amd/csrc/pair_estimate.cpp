@@ -257,6 +257,7 @@ void mm3d::pairs_estimate_batch(mm3d_ctx *ctx, PairWork *w, size_t n, const mm3d
     jobs[i].tgt = w[i].t->points;
     jobs[i].guess_dev = fronts[i].on_device ? fronts[i].dT0.get() : nullptr;
     std::memcpy(jobs[i].guess_host, fronts[i].T0, sizeof(fronts[i].T0));
+    if (sel.rejecting()) jobs[i].reject = &sel.reject_options;         // (mm3d_set_icp_rejection; NDT does not read it)
   }
   // estimateTransform's ICP and transformScore of its result (R/src/map_merging.cpp:91-107), max_distance = max_correspondence_distance
   // (under mm3d_set_confidence nobody reads that score: it is not launched, and the ICP's states come back as they would have)
@@ -282,6 +283,7 @@ void mm3d::pairs_estimate_batch(mm3d_ctx *ctx, PairWork *w, size_t n, const mm3d
     out->icp_correspondences = jobs[i].out.n_corr;
     out->confidence = 1.0 / jobs[i].out.score;
   }
+  if (sel.rejecting() && !sel.refine && p->refine_transform && n) ctx->last_reject_stats = jobs[n - 1].reject_stats;
   if (sel.confidence) {
     // the transforms are on the host: both maps' tables (made on first use), one launch and one wait for the whole batch
     std::vector<ConfidencePair> cp(n);

@@ -21,7 +21,7 @@ struct CoarseMethodBase;
 struct ConfidenceMethodBase;
 
 // The opt-in stages of a context's pipeline (mm3d_set_icp_method, mm3d_set_alignment, mm3d_set_keypoints, mm3d_set_refinement,
-// mm3d_set_coarse_alignment, mm3d_set_confidence): a null method = the reference's stage.  The methods are process-wide
+// mm3d_set_coarse_alignment, mm3d_set_confidence, mm3d_set_icp_rejection): a null method = the reference's stage.  The methods are process-wide
 // objects of their kernel files that hold no state and are not owned.  Every context has its own copy of the record; only
 // select_stages (drivers.hpp) changes one, and it and mm3d_set_streams hand the root's copy to the helpers.
 struct StageSelection {
@@ -36,7 +36,10 @@ struct StageSelection {
   mm3d_refine_options refine_options;
   mm3d_coarse_options coarse_options;
   mm3d_confidence_options confidence_options;
-  StageSelection();                                    // capi.cpp: the options are the five mm3d_*_options_default's
+  mm3d_icp_rejection_options reject_options;           // the ICP's correspondence rejection: no method object, icp_batch reads them
+  StageSelection();                                    // capi.cpp: the options are the six mm3d_*_options_default's
+  // the ICP of the pair stage rejects correspondences (mm3d_set_icp_rejection)
+  bool rejecting() const { return reject_options.one_to_one || reject_options.distance != MM3D_REJECT_NONE; }
   int icp_method() const;                              // MM3D_ICP_*
   // the pair's initial estimate is the prerejective alignment's
   bool prerejective(const mm3d_params *p) const { return !coarse && align && p->estimation_method == MM3D_EST_SAC_IA; }
@@ -44,7 +47,7 @@ struct StageSelection {
   // rand(), which is MATCHING's case in pair_rand_replay
   int replay_method(const mm3d_params *p) const { return coarse || prerejective(p) ? (int)MM3D_EST_MATCHING : (int)p->estimation_method; }
   // such a pair is estimated by pairs_estimate_batch alone (pair_estimate_impl hands it a batch of one)
-  bool batch_only(const mm3d_params *p) const { return icp || refine || coarse || confidence || prerejective(p); }
+  bool batch_only(const mm3d_params *p) const { return icp || refine || coarse || confidence || rejecting() || prerejective(p); }
 };
 
 // The feature / pair cache of mm3d_estimate_maps_transforms (mm3d_set_map_cache; the concrete class is map_cache.cpp's).  The
@@ -79,6 +82,7 @@ struct mm3d_ctx : mm3d::Context {
   mm3d_alignment_stats last_align_stats{0, 0, 0, -1, 0, 0};
   mm3d_coarse_stats last_coarse_stats{0, 0, 0, 0, 0, -1, 0, 0};
   mm3d_overlap_stats last_confidence_stats{0, 0, 0, 0, 0, 0, 0.0};
+  mm3d_icp_rejection_stats last_reject_stats{0, 0, 0, INFINITY, 0, 0};   // (mm3d_last_icp_rejection_stats)
   // mm3d_set_streams: helper contexts (one HIP stream + one host thread each while a call is running)
   // that mm3d_estimate_maps_transforms deals maps and pairs to; owned by this context
   std::vector<mm3d_ctx *> helpers;
@@ -364,6 +368,11 @@ struct IcpScoreJob {
   const mm3d_normals *tgt_normals = nullptr;   // point-to-plane ICP: the target's normals, in its order
   const NdtTable *tgt_ndt = nullptr;           // NDT: the target's voxel table, and how many voxels a point reads (1 or 7)
   int ndt_neighbours = 7;
+  // correspondence rejection (mm3d_set_icp_rejection; icp_reject.hip): non-null = the point-to-point and point-to-plane ICP run
+  // the rejecting correspondence stage with these options (the same for every job of a batch), even when they reject nothing;
+  // NDT does not read it.  reject_stats: the last iteration's counts.
+  const mm3d_icp_rejection_options *reject = nullptr;
+  mm3d_icp_rejection_stats reject_stats{0, 0, 0, INFINITY, 0, 0};
 };
 void icp_score_batch(Context *c, IcpScoreJob *jobs, int n_jobs, bool run_icp, double max_corr_dist, int max_iterations, double eps,
                      bool want_score, double score_max_distance);
