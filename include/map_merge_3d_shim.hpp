@@ -176,6 +176,45 @@ inline void check_icp_reject_devices(const mm3d_icp_rejection_options &o, const 
   if ((o.one_to_one || o.distance != MM3D_REJECT_NONE) && devices && *devices)
     throw std::runtime_error("mm3d: MM3D_ICP_REJECT is not available with MM3D_DEVICES (a device list runs the ICP without rejection)");
 }
+// MM3D_ICP_COLOR=1 or <lambda>[:<radius in metres>]: the estimation context's pair stage runs coloured ICP (mm3d_set_icp_color).
+// 1 alone: mm3d_icp_color_options_default's lambda (0.968) -- lambda 1 itself, point-to-plane's terms, is spelt 1.0 -- and, as
+// without a radius, params.normal_radius.  0, none or unset leaves it off.  A lambda outside (0, 1], a radius that is not
+// positive or anything else throws, as a malformed MM3D_ICP_REJECT does.
+inline mm3d_icp_color_options parse_icp_color(const char *value)
+{
+  mm3d_icp_color_options o;
+  o.enabled = 0;
+  o.lambda_geometric = 0.968;
+  o.gradient_radius = 0.0;
+  o.min_neighbours = 4;
+  const std::string v = value ? value : "";
+  if (v.empty() || v == "0" || v == "none") return o;
+  o.enabled = 1;
+  if (v == "1") return o;
+  const size_t colon = v.find(':');
+  const std::string head = v.substr(0, colon);
+  char *end = nullptr;
+  o.lambda_geometric = std::strtod(head.c_str(), &end);
+  bool ok = !head.empty() && *end == '\0' && o.lambda_geometric > 0.0 && o.lambda_geometric <= 1.0;
+  if (ok && colon != std::string::npos) {
+    const char *s = v.c_str() + colon + 1;
+    o.gradient_radius = std::strtod(s, &end);
+    ok = end != s && *end == '\0' && std::isfinite(o.gradient_radius) && o.gradient_radius > 0.0;
+  }
+  if (!ok)
+    throw std::runtime_error("mm3d: MM3D_ICP_COLOR must be 0, 1 or <lambda in (0, 1]>[:<radius in metres>], not '" + v + "'");
+  return o;
+}
+// Not available on a device list (its bundles carry no gradients) nor together with an active MM3D_ICP_REJECT (the rejecting
+// reduction has no colour variant): either combination throws.
+inline void check_icp_color_combinations(const mm3d_icp_color_options &o, const mm3d_icp_rejection_options &reject, const char *devices)
+{
+  if (!o.enabled) return;
+  if (devices && *devices)
+    throw std::runtime_error("mm3d: MM3D_ICP_COLOR is not available with MM3D_DEVICES (a device list carries no colour gradients)");
+  if (reject.one_to_one || reject.distance != MM3D_REJECT_NONE)
+    throw std::runtime_error("mm3d: MM3D_ICP_COLOR is not available with an active MM3D_ICP_REJECT (the rejecting ICP has no colour term)");
+}
 }  // namespace mm3d_shim
 }  // namespace map_merge_3d
 
@@ -261,9 +300,12 @@ inline mm3d_ctx *ctx()
   // MM3D_COARSE=correlative[:<cell>]: parse_coarse above.  Not available on a device list: correlative with MM3D_DEVICES set as well throws.
   // MM3D_CONFIDENCE=overlap[:<voxel>]: parse_confidence above.  Not available on a device list: overlap with MM3D_DEVICES set as well throws.
   // MM3D_ICP_REJECT=one_to_one+trimmed:0.7 ...: parse_icp_reject above.  Not available on a device list: an active value with MM3D_DEVICES set as well throws.
+  // MM3D_ICP_COLOR=1 or <lambda>[:<radius>]: parse_icp_color above.  Not available on a device list nor with an active MM3D_ICP_REJECT: either throws.
   static mm3d_ctx *c = [] {
     const mm3d_icp_rejection_options reject = parse_icp_reject(std::getenv("MM3D_ICP_REJECT"));
     check_icp_reject_devices(reject, std::getenv("MM3D_DEVICES"));
+    const mm3d_icp_color_options color = parse_icp_color(std::getenv("MM3D_ICP_COLOR"));
+    check_icp_color_combinations(color, reject, std::getenv("MM3D_DEVICES"));
     const mm3d_confidence_options confidence = parse_confidence(std::getenv("MM3D_CONFIDENCE"));
     check_confidence_devices(confidence, std::getenv("MM3D_DEVICES"));
     const mm3d_coarse_options coarse = parse_coarse(std::getenv("MM3D_COARSE"));
@@ -312,6 +354,8 @@ inline mm3d_ctx *ctx()
       throw std::runtime_error("mm3d: MM3D_CONFIDENCE was refused (the voxel must be a positive float with a finite reciprocal)");
     if ((reject.one_to_one || reject.distance != MM3D_REJECT_NONE) && mm3d_set_icp_rejection(e, &reject) != MM3D_OK)
       throw std::runtime_error(std::string("mm3d: MM3D_ICP_REJECT was refused: ") + mm3d_last_error(e));
+    if (color.enabled && mm3d_set_icp_color(e, &color) != MM3D_OK)
+      throw std::runtime_error(std::string("mm3d: MM3D_ICP_COLOR was refused: ") + mm3d_last_error(e));
     return e;
   }();
   return c;

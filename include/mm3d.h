@@ -914,6 +914,61 @@ int mm3d_debug_icp_rejection(mm3d_ctx *ctx, const mm3d_cloud *source, const mm3d
  * everywhere; 1 or 4 = forced in every rejecting launch from now on; negative = no change.  Returns the value in force. */
 int mm3d_debug_icp_rejection_split(int split);
 
+/* ---------------------------------------------------------------- opt-in coloured ICP
+ * mm3d_set_icp_color puts a photometric term beside point-to-plane's in the pair stage's ICP (Park, Zhou, Koltun, "Colored Point
+ * Cloud Registration Revisited", ICCV 2017; Open3D's registration_colored_icp is the known implementation, and no parity with it
+ * is claimed).  Planes leave a pose open along themselves -- a corridor one direction, a floor with a wall two -- and
+ * point-to-plane then stops at its degeneracy rule with T unchanged; the texture on such surfaces constrains exactly those
+ * directions.  Disabled (the default), the pair stage runs the kernels it always ran.
+ * Intensity: for rgba bits with bytes r, g, b, I = (float)((double)(299 r + 587 g + 114 b) / 255000.0), in [0, 1].
+ * The gradient record of a target point i, float4 (gx, gy, gz, I_i), made once per map and option set from the map's normals:
+ *   neighbours  the finite points j != i with float d2 = (dx dx + dy dy) + dz dz <= (float)(radius * radius), radius =
+ *               gradient_radius, or params.normal_radius when that is 0.  A non-finite point or normal, or fewer than
+ *               min_neighbours neighbours, gives g = 0.
+ *   otherwise, in double: e = p_j - p_i, u = e - (e.n) n, w = I_j - I_i; M = sum u u^T + k^2 n n^T (k the neighbour count: the
+ *               soft constraint g.n = 0), b = sum u w; M g = b by an unpivoted 3x3 LDLt; a pivot at or below 1e-12 trace(M) / 3
+ *               gives g = 0; g is rounded to float once.  The order of the sums is a function of the cloud and the radius alone.
+ * One iteration is mm3d_set_icp_method's in every respect but the terms.  Per matched source point, in double: s the
+ * float-transformed point, q the target point, n and (g, I_t) the target's normal and record, I_s from the source point's rgba;
+ *   vG = [s x n, n], rG = n.q - n.s                                       (point-to-plane's expressions)
+ *   e = s - q, h = e.n, m = g - (g.n) n, pred = I_t + g.(e - h n), rC = I_s - pred, vC = [s x m, m]
+ * and with mu = 1 - lambda_geometric the AtA term (i, j) is lambda (vG_i vG_j) + mu (vC_i vC_j), the Atr term i the same with
+ * rG and rC; the squared distances, the correspondence count and the row count are point-to-plane's.  A correspondence whose
+ * normal is not finite counts and adds no row; a zero gradient adds a zero colour row.  With lambda_geometric == 1 the terms are
+ * point-to-plane's own and the result is mm3d_estimate_transform_icp_plane's, bit for bit.
+ * Enabled, the pair stage's ICP is the coloured one whatever mm3d_set_icp_method says (mm3d_get_icp_method keeps answering its
+ * own value); NDT (mm3d_set_refinement) does not read the setting, transformScore stays point-to-point, the overlap confidence
+ * is untouched and nothing is drawn from rand().  mm3d_estimate_transform_icp and mm3d_estimate_transform_icp_plane do not see
+ * the setting.  Results are bit-identical for every stream count, batch and cache setting.  Memory: 16 B per filtered point of a
+ * map beside the 16 B of its normals. */
+typedef struct mm3d_icp_color_options {
+  int enabled;             /* 0 / 1 */
+  double lambda_geometric; /* weight of the geometric rows, 0 < lambda <= 1; the photometric rows get 1 - lambda */
+  double gradient_radius;  /* metres, > 0; 0 = params.normal_radius */
+  int min_neighbours;      /* a point with fewer neighbours in the radius has a zero gradient; >= 4 */
+} mm3d_icp_color_options;
+void mm3d_icp_color_options_default(mm3d_icp_color_options *o);   /* 0, 0.968, 0, 4 (lambda: Open3D's default) */
+/* MM3D_EINVAL: ctx or options NULL, enabled not 0 / 1, a value outside its range above (checked whatever `enabled` is).
+ * MM3D_EUNSUPPORTED: enabled on a device-list context (mm3d_create_devices), or while a correspondence rejection is active
+ * (mm3d_set_icp_rejection, which in turn refuses an active selection while colour is enabled); mm3d_shard_begin returns
+ * MM3D_EUNSUPPORTED on a context with colour enabled.  The setting reaches the context's mm3d_set_streams helpers, in either
+ * order, and is part of the map cache's pair key while enabled. */
+int mm3d_set_icp_color(mm3d_ctx *ctx, const mm3d_icp_color_options *options);
+int mm3d_get_icp_color(const mm3d_ctx *ctx, mm3d_icp_color_options *options);   /* MM3D_EINVAL for NULL */
+/* coloured ICP with the rule above from initial_guess, whatever options->enabled and the context's setting say; the target's
+ * records are made from target_normals (in the target's order) for this call.  MM3D_EINVAL: a NULL argument, options out of
+ * range, gradient_radius not > 0 (there are no parameters to take it from), normals whose count differs from the target's. */
+int mm3d_estimate_transform_icp_color(mm3d_ctx *ctx, const mm3d_cloud *source, const mm3d_cloud *target,
+                                      const mm3d_normals *target_normals, const float initial_guess[16],
+                                      double max_correspondence_distance, const mm3d_icp_color_options *options,
+                                      int max_iterations, double transformation_epsilon, float T[16]);
+/* test hook: the gradient records of `points` with `normals` (gradient_radius > 0), out = [n][4]: gx gy gz I, in the points' order */
+int mm3d_debug_color_gradients(mm3d_ctx *ctx, const mm3d_cloud *points, const mm3d_normals *normals,
+                               const mm3d_icp_color_options *options, float *out);
+/* test hook, process-wide like mm3d_debug_icp_rejection_split: 0 = one or four work items per block chosen by size, as
+ * everywhere; 1 or 4 = forced in every coloured launch from now on; negative = no change.  Returns the value in force. */
+int mm3d_debug_icp_color_split(int split);
+
 #ifdef __cplusplus
 }
 #endif

@@ -199,6 +199,23 @@ class IcpRejectionOptions(C.Structure):
         return tuple(int(getattr(self, k)) if t is C.c_int else float(getattr(self, k)) for k, t in self._fields_)
 
 
+class IcpColorOptions(C.Structure):
+    """mm3d_icp_color_options (mm3d_set_icp_color); the defaults are mm3d_icp_color_options_default's."""
+    _fields_ = [("enabled", C.c_int), ("lambda_geometric", C.c_double), ("gradient_radius", C.c_double), ("min_neighbours", C.c_int)]
+
+    def __init__(self, **kw):
+        super().__init__()
+        lib().mm3d_icp_color_options_default(C.byref(self))
+        kinds = dict(self._fields_)
+        for k, v in kw.items():
+            if k not in kinds:
+                raise TypeError("unknown coloured ICP option " + k)
+            setattr(self, k, int(v) if kinds[k] is C.c_int else float(v))
+
+    def as_tuple(self):
+        return tuple(int(getattr(self, k)) if t is C.c_int else float(getattr(self, k)) for k, t in self._fields_)
+
+
 class IcpRejectionStats(C.Structure):
     """mm3d_icp_rejection_stats"""
     _fields_ = [("matched", C.c_longlong), ("after_one_to_one", C.c_longlong), ("kept", C.c_longlong), ("threshold_d2", C.c_float),
@@ -339,6 +356,12 @@ def icp_rejection_split(split=-1):
     """mm3d_debug_icp_rejection_split: force every rejecting launch to one work item per wave (1) or per block (4); 0: chosen by
     size again; negative: leave as it is.  Returns the value in force."""
     return int(lib().mm3d_debug_icp_rejection_split(int(split)))
+
+
+def icp_color_split(split=-1):
+    """mm3d_debug_icp_color_split: force every coloured ICP launch to one work item per wave (1) or per block (4); 0: chosen by
+    size again; negative: leave as it is.  Returns the value in force."""
+    return int(lib().mm3d_debug_icp_color_split(int(split)))
 
 
 class Context:
@@ -511,6 +534,17 @@ class Context:
     def getIcpRejection(self) -> "IcpRejectionOptions":
         o = IcpRejectionOptions()
         self._ck(lib().mm3d_get_icp_rejection(self._h, C.byref(o)))
+        return o
+
+    def setIcpColor(self, options=None, **kw):
+        """mm3d_set_icp_color: coloured ICP in the pair stage.  An IcpColorOptions, or its fields as keywords (enabled=0 / 1,
+        lambda_geometric=..., gradient_radius=..., min_neighbours=...)."""
+        o = options if options is not None else IcpColorOptions(**kw)
+        self._ck(lib().mm3d_set_icp_color(self._h, C.byref(o)))
+
+    def getIcpColor(self) -> "IcpColorOptions":
+        o = IcpColorOptions()
+        self._ck(lib().mm3d_get_icp_color(self._h, C.byref(o)))
         return o
 
     @property
@@ -713,6 +747,21 @@ class Context:
         self.last_icp_converged = lib().mm3d_last_icp_converged(self._h)
         return _Tout(T)
 
+    def estimateTransformICPColor(self, source_points, target_points, target_normals, initial_guess, max_correspondence_distance,
+                                  options=None, max_iterations=100, transformation_epsilon=0.0, **kw):
+        """mm3d_estimate_transform_icp_color: coloured ICP from initial_guess, whatever the context's setting and options.enabled
+        (options.gradient_radius > 0; target_normals: one per target point)."""
+        o = options if options is not None else IcpColorOptions(**kw)
+        g = _T(initial_guess)
+        T = np.zeros(16, dtype=np.float32)
+        self._ck(lib().mm3d_estimate_transform_icp_color(
+            self._h, source_points._h, target_points._h, target_normals._h, g.ctypes.data_as(C.c_void_p),
+            C.c_double(max_correspondence_distance), C.byref(o), int(max_iterations), C.c_double(transformation_epsilon),
+            T.ctypes.data_as(C.c_void_p)))
+        self.last_icp_iterations = lib().mm3d_last_icp_iterations(self._h)
+        self.last_icp_converged = lib().mm3d_last_icp_converged(self._h)
+        return _Tout(T)
+
     def estimateTransformNDT(self, source_points, target_points, initial_guess, options=None, max_iterations=100,
                              transformation_epsilon=0.0, **kw):
         """mm3d_estimate_transform_ndt: NDT from initial_guess, whatever the context's setting (options.resolution > 0)."""
@@ -853,6 +902,14 @@ class Context:
                                             C.c_double(range), int(convention), int(split), idx.ctypes.data_as(C.c_void_p),
                                             d2.ctypes.data_as(C.c_void_p), C.byref(info)))
         return idx[:n], d2[:n], info.as_dict()
+
+    def debugColorGradients(self, points, normals, options=None, **kw):
+        """mm3d_debug_color_gradients: the gradient records of `points` with `normals`, float32[n][4]: gx gy gz I."""
+        o = options if options is not None else IcpColorOptions(**kw)
+        n = len(points)
+        out = np.zeros((max(n, 1), 4), dtype=np.float32)
+        self._ck(lib().mm3d_debug_color_gradients(self._h, points._h, normals._h, C.byref(o), out.ctypes.data_as(C.c_void_p)))
+        return out[:n]
 
     def debugIcpRejection(self, source_points, target_points, transform, max_correspondence_distance, options=None, split=1, **kw):
         """mm3d_debug_icp_rejection: one iteration's correspondence stage at `transform`.  Returns (idx int32[n], d2 float32[n],

@@ -36,6 +36,7 @@ mm3d::StageSelection::StageSelection()
   mm3d_coarse_options_default(&coarse_options);
   mm3d_confidence_options_default(&confidence_options);
   mm3d_icp_rejection_options_default(&reject_options);
+  mm3d_icp_color_options_default(&color_options);
 }
 
 void mm3d::select_stages(mm3d_ctx *ctx, bool peers_follow, const std::function<void(StageSelection &)> &edit)
@@ -189,6 +190,10 @@ void mm3d_confidence_options_default(mm3d_confidence_options *o)
 void mm3d_icp_rejection_options_default(mm3d_icp_rejection_options *o)
 {
   if (o) *o = mm3d_icp_rejection_options{0, MM3D_REJECT_NONE, 0.5, 0, 1.0};
+}
+void mm3d_icp_color_options_default(mm3d_icp_color_options *o)
+{
+  if (o) *o = mm3d_icp_color_options{0, 0.968, 0.0, 4};
 }
 
 // ---------------------------------------------------------------- context

@@ -405,6 +405,10 @@ int mm3d_set_icp_rejection(mm3d_ctx *ctx, const mm3d_icp_rejection_options *opti
   std::lock_guard<std::mutex> lock(ctx->mu);        // (no call is running while the selection changes)
   const bool active = options->one_to_one || options->distance != MM3D_REJECT_NONE;
   if (active && refused_on_device_list(ctx, "mm3d_set_icp_rejection: not available on a device-list context")) return MM3D_EUNSUPPORTED;
+  if (active && ctx->sel.color) {      // (k_rej_reduce has no colour variant)
+    ctx->err = "mm3d_set_icp_rejection: not available while coloured ICP is enabled (mm3d_set_icp_color)";
+    return MM3D_EUNSUPPORTED;
+  }
   select_stages(ctx, false, [&](StageSelection &s) { s.reject_options = *options; });
   return MM3D_OK;
 }

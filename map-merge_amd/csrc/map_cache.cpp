@@ -79,6 +79,12 @@ std::string pair_params_key(const mm3d_params *p, const StageSelection &sel)
   const bool rejecting = sel.rejecting();
   k.i32(rejecting ? rej.one_to_one : 0).i32(rejecting ? rej.distance : 0).f64(rejecting ? rej.overlap_ratio : 0.0)
       .i32(rejecting ? rej.min_correspondences : 0).f64(rejecting ? rej.median_factor : 0.0);
+  // coloured ICP (mm3d_set_icp_color): the four options while enabled, zeros otherwise (a disabled selection's other values
+  // are read by nothing: whatever they are, its records are shared)
+  const mm3d_icp_color_options &col = sel.color_options;
+  const bool colored = col.enabled != 0;
+  k.i32(colored ? col.enabled : 0).f64(colored ? col.lambda_geometric : 0.0).f64(colored ? col.gradient_radius : 0.0)
+      .i32(colored ? col.min_neighbours : 0);
   return k.s;
 }
 
@@ -116,7 +122,8 @@ struct Entry {
            (map->ndt ? map->ndt->rec.size() * 16 + map->ndt->index.size() * 4 : 0) +   // (voxel table: NDT only)
            (map->coarse ? (map->coarse->scells.size() + map->coarse->gcells.size()) * 16 + map->coarse->ccells.size() * 8 +
                               map->coarse->dil.size() + map->coarse->gh.size() * 4 : 0) +   // (signature: correlative alignment only)
-           (map->overlap ? map->overlap->near.size() * 8 + map->overlap->view.size() : 0);   // (table: overlap confidence only)
+           (map->overlap ? map->overlap->near.size() * 8 + map->overlap->view.size() : 0) +   // (table: overlap confidence only)
+           (map->color ? map->color->rec.size() * 16 : 0);   // (gradient records: coloured ICP only)
   }
 };
 

@@ -327,12 +327,15 @@ static void launch_nn(Context *c, const char *name, double bytes, const NnJob *j
 // Correspondence rejection (mm3d_set_icp_rejection): when the jobs carry options (IcpScoreJob::reject, the same for the whole batch),
 // the Point and Plane kinds take icp_reject.hip's icp_reject_step in the place of their search + reduction launch -- it leaves the
 // same partials for the kept correspondences -- and then their own finalize kernel.  NDT does not read the setting.
-enum class IcpKind { Point, Plane, Ndt };
+// color: coloured ICP (mm3d_set_icp_color): point-to-plane's jobs, partials and finalize kernel, with icp_color.hip's
+// icp_color_step over NnColorJobs (the target's gradient records, the source's reference points) as the search + reduction
+// launch.  The jobs carry no rejection options (the setters exclude each other).
+enum class IcpKind { Point, Plane, Ndt, Color };
 static float bits_to_float(unsigned u) { float f; memcpy(&f, &u, 4); return f; }
 static void icp_batch(Context *c, IcpScoreJob *jobs, int n_jobs, bool run_icp, double max_corr_dist, int max_iterations, double eps,
                       bool want_score, double score_max_distance, IcpKind kind)
 {
-  const bool plane = kind == IcpKind::Plane, ndt = kind == IcpKind::Ndt;
+  const bool color = kind == IcpKind::Color, plane = kind == IcpKind::Plane || color, ndt = kind == IcpKind::Ndt;
   static_assert(offsetof(IcpState, T) == 0, "the score kernel reads T at the head of the state");
   c->last_icp_iterations = 0;
   c->last_icp_converged = 0;
@@ -366,6 +369,7 @@ static void icp_batch(Context *c, IcpScoreJob *jobs, int n_jobs, bool run_icp, d
     }
     if (plane && tg && (!J.tgt_normals || J.tgt_normals->n != J.tgt->n))
       throw Error(MM3D_EINVAL, "point-to-plane ICP: the target's normals do not match its points");
+    if (color && tg && !J.tgt_color) throw Error(MM3D_EINVAL, "coloured ICP: the target has no gradient records");
     if (ndt_icp && !J.tgt_ndt) throw Error(MM3D_EINVAL, "NDT: the target has no voxel table");
     Live L{j, sp, ns, J.src->n_wave_items, tg, sg, 0, 0};
     L.max_ring = tg ? nn_max_ring(rmax, *tg) : 0;
@@ -376,13 +380,15 @@ static void icp_batch(Context *c, IcpScoreJob *jobs, int n_jobs, bool run_icp, d
   }
   const int B = (int)live.size();
   if (B == 0) return;
-  const mm3d_icp_rejection_options *rej = (run_icp && !ndt) ? jobs[live[0].job].reject : nullptr;
+  const mm3d_icp_rejection_options *rej = (run_icp && !ndt && !color) ? jobs[live[0].job].reject : nullptr;
+  const double color_lambda = jobs[live[0].job].color_lambda;
 
   // one work item per block while the whole batch has too few items to fill the chip with one wave each
   // (the finalize kernels add the partials up in one fixed order, so the choice never shows in a result)
   int total_items = 0;
   for (const Live &L : live) total_items += L.n_items;
-  const int forced_split = rej ? icp_reject_forced_split() : 0;       // (test hook: mm3d_debug_icp_rejection_split)
+  // (test hooks: mm3d_debug_icp_rejection_split, mm3d_debug_icp_color_split)
+  const int forced_split = rej ? icp_reject_forced_split() : (color && run_icp) ? icp_color_forced_split() : 0;
   const bool split = forced_split ? forced_split == 4 : nn_split_items(total_items);
   size_t part_total = 0;
   unsigned grid_x = 0;
@@ -399,7 +405,7 @@ static void icp_batch(Context *c, IcpScoreJob *jobs, int n_jobs, bool run_icp, d
     icp_part_total += (size_t)icp_nb * icp_acc;
     grid_x = std::max(grid_x, nb[b]);
     ndt_grid_x = std::max(ndt_grid_x, icp_nb);
-    icp_bytes += live[b].ns * (plane ? 28.0 : ndt ? 16.0 + 52.0 * jobs[live[b].job].ndt_neighbours : 12.0);   // (point-to-plane: + the winner's normal; NDT: the point, and an index word and a record per voxel)
+    icp_bytes += live[b].ns * (color ? 60.0 : plane ? 28.0 : ndt ? 16.0 + 52.0 * jobs[live[b].job].ndt_neighbours : 12.0);   // (point-to-plane: + the winner's normal; coloured: + its record and the source's reference point; NDT: the point, and an index word and a record per voxel)
     score_bytes += live[b].ns * 12.0 + (live[b].sg ? live[b].sg->n * 12.0 : 0.0);
   }
   DevBuf<double> partials(c, icp_part_total), s_partials(c, want_score ? part_total : 1);
@@ -423,12 +429,14 @@ static void icp_batch(Context *c, IcpScoreJob *jobs, int n_jobs, bool run_icp, d
   DevBuf<NnJob> d_jobs(c, (size_t)2 * B);                 // [0, B): ICP, [B, 2B): score
   DevBuf<NnPlaneJob> d_pjobs(c, plane ? (size_t)B : 1);   // point-to-plane: the ICP jobs with their normals
   DevBuf<NdtJob> d_njobs(c, ndt ? (size_t)B : 1);         // NDT: the ICP jobs with their voxel tables
+  DevBuf<NnColorJob> d_cjobs(c, color ? (size_t)B : 1);   // coloured: the point-to-plane jobs with the records and the source's reference points
 
-  // host images, in the pinned arena: states | ICP jobs | score jobs | scores back | point-to-plane jobs | NDT jobs
+  // host images, in the pinned arena: states | ICP jobs | score jobs | scores back | point-to-plane jobs | NDT jobs | rejecting jobs | coloured jobs
   const size_t st_bytes = sizeof(IcpState) * B, job_bytes = sizeof(NnJob) * 2 * B, out_bytes = 16 * (size_t)B;
   const size_t pjob_bytes = plane ? sizeof(NnPlaneJob) * B : 0, njob_bytes = ndt ? sizeof(NdtJob) * B : 0;
   const size_t rjob_bytes = rej ? sizeof(NnRejectJob) * B : 0, st_rec_bytes = st_bytes + rec_bytes;
-  char *pinned = (char *)c->pin(st_rec_bytes + job_bytes + out_bytes + pjob_bytes + njob_bytes + rjob_bytes + 64);
+  const size_t cjob_bytes = color ? sizeof(NnColorJob) * B : 0;
+  char *pinned = (char *)c->pin(st_rec_bytes + job_bytes + out_bytes + pjob_bytes + njob_bytes + rjob_bytes + cjob_bytes + 64);
   IcpState *hp = (IcpState *)pinned;
   RejRecord *hr = (RejRecord *)(pinned + st_bytes);
   NnJob *hj = (NnJob *)(pinned + ((st_rec_bytes + 15) & ~(size_t)15));
@@ -436,6 +444,7 @@ static void icp_batch(Context *c, IcpScoreJob *jobs, int n_jobs, bool run_icp, d
   NnPlaneJob *hpj = (NnPlaneJob *)((char *)ho + out_bytes);
   NdtJob *hnj = (NdtJob *)((char *)hpj + pjob_bytes);
   NnRejectJob *hrj = (NnRejectJob *)((char *)hnj + njob_bytes);
+  NnColorJob *hcj = (NnColorJob *)((char *)hrj + rjob_bytes);
   size_t off = 0, icp_off = 0, rej_src_off = 0, rej_tgt_off = 0;
   for (int b = 0; b < B; ++b) {
     const Live &L = live[b];
@@ -466,6 +475,11 @@ static void icp_batch(Context *c, IcpScoreJob *jobs, int n_jobs, bool run_icp, d
     if (plane) {
       hpj[b].nn = q;
       hpj[b].nrm = L.tg ? (const float4 *)J.tgt_normals->nrm.get() : nullptr;
+    }
+    if (color) {
+      hcj[b].pl = hpj[b];
+      hcj[b].rec = L.tg ? J.tgt_color : nullptr;
+      hcj[b].src_ref = (const float4 *)J.src->pts.get();
     }
     if (rej) {
       NnRejectJob rj;
@@ -514,6 +528,7 @@ static void icp_batch(Context *c, IcpScoreJob *jobs, int n_jobs, bool run_icp, d
   }
   if (plane) MM3D_HIP(hipMemcpyAsync(d_pjobs.get(), hpj, pjob_bytes, hipMemcpyHostToDevice, c->stream));
   if (ndt) MM3D_HIP(hipMemcpyAsync(d_njobs.get(), hnj, njob_bytes, hipMemcpyHostToDevice, c->stream));
+  if (color) MM3D_HIP(hipMemcpyAsync(d_cjobs.get(), hcj, cjob_bytes, hipMemcpyHostToDevice, c->stream));
   for (int b = 0; b < B; ++b)
     if (jobs[live[b].job].guess_dev)
       MM3D_HIP(hipMemcpyAsync(st.get() + b, jobs[live[b].job].guess_dev, 64, hipMemcpyDeviceToDevice, c->stream));
@@ -533,6 +548,11 @@ static void icp_batch(Context *c, IcpScoreJob *jobs, int n_jobs, bool run_icp, d
                           rej_tgt * sizeof(unsigned long long), icp_bytes + rej_src * 8.0);
           if (plane) icp_plane_finalize(c, d_pjobs.get(), B, icp_part_total * 8.0);
           else MM3D_LAUNCH(c, "icp_finalize", part_total * 8.0, k_icp_finalize, dim3(B), dim3(256), 0, (const NnJob *)d_jobs.get());
+          continue;
+        }
+        if (color) {
+          icp_color_step(c, d_cjobs.get(), B, grid_x, split, max_d2, rmax, color_lambda, icp_bytes);
+          icp_plane_finalize(c, d_pjobs.get(), B, icp_part_total * 8.0);
           continue;
         }
         if (plane) {
@@ -594,6 +614,12 @@ void icp_plane_score_batch(Context *c, IcpScoreJob *jobs, int n_jobs, bool run_i
                            bool want_score, double score_max_distance)
 {
   icp_batch(c, jobs, n_jobs, run_icp, max_corr_dist, max_iterations, eps, want_score, score_max_distance, IcpKind::Plane);
+}
+
+void icp_color_score_batch(Context *c, IcpScoreJob *jobs, int n_jobs, bool run_icp, double max_corr_dist, int max_iterations, double eps,
+                           bool want_score, double score_max_distance)
+{
+  icp_batch(c, jobs, n_jobs, run_icp, max_corr_dist, max_iterations, eps, want_score, score_max_distance, IcpKind::Color);
 }
 
 void ndt_score_batch(Context *c, IcpScoreJob *jobs, int n_jobs, bool run_icp, double max_corr_dist, int max_iterations, double eps,

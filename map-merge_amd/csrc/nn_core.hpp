@@ -181,4 +181,19 @@ void icp_reject_debug(Context *c, const NnRejectJob *job_dev, unsigned grid_x, u
                       unsigned char *out_kept);
 bool icp_rejection_options_valid(const mm3d_icp_rejection_options *o);
 
+// coloured ICP (icp_color.hip, mm3d_set_icp_color): the point-to-plane job plus the target's gradient records and the source's
+// reference points (their rgba).  pl.nn.partials: [nblocks][kPlaneAcc], read by k_icp_plane_finalize over the NnPlaneJobs.
+struct NnColorJob {
+  NnPlaneJob pl;
+  const float4 *rec;          // the target's records (gx, gy, gz, I), in tgt_ref's order
+  const float4 *src_ref;      // the source's points in reference order (nn.src's .w indexes them)
+};
+// one coloured iteration's search + reduction launch for a batch; the caller runs icp_plane_finalize afterwards.  lambda: the
+// weight of the geometric rows (the photometric ones get 1 - lambda; 1: point-to-plane's terms, bit for bit)
+void icp_color_step(Context *c, const NnColorJob *jobs_dev, int count, unsigned grid_x, bool split, float max_d2, float rmax, double lambda,
+                    double bytes);
+// mm3d_debug_icp_color_split: 0 (by size), 1 or 4
+int icp_color_forced_split();
+bool icp_color_options_valid(const mm3d_icp_color_options *o);
+
 }  // namespace mm3d

@@ -76,7 +76,7 @@ std::unique_ptr<mm3d_map> mm3d::map_features_impl(mm3d_ctx *ctx, const mm3d_clou
                                                                          : compute_fpfh(ctx, filt.get(), nrm.get(), kp.get(), p->descriptor_radius));
   if (wait) ctx->sync();
   std::unique_ptr<mm3d_map> m = make_map(std::move(filt), std::move(kp), std::move(desc));
-  if (ctx->sel.icp || ctx->sel.coarse) m->normals = std::move(nrm);    // point-to-plane ICP reads them (mm3d_set_icp_method), and the correlative signature
+  if (ctx->sel.icp || ctx->sel.coarse || ctx->sel.color) m->normals = std::move(nrm);    // point-to-plane and coloured ICP read them (mm3d_set_icp_method, mm3d_set_icp_color), and the correlative signature
   return m;
 }
 
@@ -85,6 +85,7 @@ void mm3d::map_prepare_impl(mm3d_ctx *ctx, mm3d_map *m, const mm3d_params *p)
   const StageSelection &sel = ctx->sel;
   if (sel.icp) sel.icp->prepare_target(ctx, m, p, nullptr);            // the normals (mm3d_set_icp_method): no wait when the map has them
   if (sel.refine) sel.refine->prepare_target(ctx, m, p, nullptr);      // NDT's voxel table (mm3d_set_refinement)
+  if (sel.color) sel.color->prepare_target(ctx, m, p, nullptr);        // the normals and the gradient records (mm3d_set_icp_color)
   if (sel.coarse) sel.coarse->prepare(ctx, m, p);                      // the correlative signature (mm3d_set_coarse_alignment)
   if (sel.confidence) sel.confidence->prepare(ctx, m, p);              // the overlap table (mm3d_set_confidence)
   prepare_pair_search(ctx, m->points, p->max_correspondence_distance, p->max_correspondence_distance);
@@ -262,9 +263,10 @@ void mm3d::pairs_estimate_batch(mm3d_ctx *ctx, PairWork *w, size_t n, const mm3d
   // estimateTransform's ICP and transformScore of its result (R/src/map_merging.cpp:91-107), max_distance = max_correspondence_distance
   // (under mm3d_set_confidence nobody reads that score: it is not launched, and the ICP's states come back as they would have)
   const bool want_score = !sel.confidence;
-  // NDT in the ICP's place (mm3d_set_refinement), else point-to-plane (mm3d_set_icp_method), else the reference's ICP; a method
-  // binds what it keeps on the targets (voxel tables, normals) to the jobs first
-  const IcpMethodBase *tail = sel.refine ? sel.refine : sel.icp;
+  // NDT in the ICP's place (mm3d_set_refinement), else coloured ICP (mm3d_set_icp_color), else point-to-plane
+  // (mm3d_set_icp_method), else the reference's ICP; a method binds what it keeps on the targets (voxel tables, normals,
+  // gradient records) to the jobs first
+  const IcpMethodBase *tail = sel.refine ? sel.refine : sel.color ? sel.color : sel.icp;
   if (tail) {
     if (p->refine_transform)
       for (size_t i = 0; i < n; ++i) tail->prepare_target(ctx, w[i].t, p, &jobs[i]);

@@ -21,7 +21,7 @@ struct CoarseMethodBase;
 struct ConfidenceMethodBase;
 
 // The opt-in stages of a context's pipeline (mm3d_set_icp_method, mm3d_set_alignment, mm3d_set_keypoints, mm3d_set_refinement,
-// mm3d_set_coarse_alignment, mm3d_set_confidence, mm3d_set_icp_rejection): a null method = the reference's stage.  The methods are process-wide
+// mm3d_set_coarse_alignment, mm3d_set_confidence, mm3d_set_icp_rejection, mm3d_set_icp_color): a null method = the reference's stage.  The methods are process-wide
 // objects of their kernel files that hold no state and are not owned.  Every context has its own copy of the record; only
 // select_stages (drivers.hpp) changes one, and it and mm3d_set_streams hand the root's copy to the helpers.
 struct StageSelection {
@@ -31,13 +31,15 @@ struct StageSelection {
   const IcpMethodBase *refine = nullptr;               // what takes the ICP's place (NDT); `icp` keeps its own value beside it
   const CoarseMethodBase *coarse = nullptr;            // what takes the initial estimate's place
   const ConfidenceMethodBase *confidence = nullptr;    // what a pair record's confidence is
+  const IcpMethodBase *color = nullptr;                // coloured ICP in the place of `icp`'s, which keeps its own value beside it
   mm3d_alignment_options align_options;
   mm3d_keypoint_options keypoint_options;
   mm3d_refine_options refine_options;
   mm3d_coarse_options coarse_options;
   mm3d_confidence_options confidence_options;
   mm3d_icp_rejection_options reject_options;           // the ICP's correspondence rejection: no method object, icp_batch reads them
-  StageSelection();                                    // capi.cpp: the options are the six mm3d_*_options_default's
+  mm3d_icp_color_options color_options;                // coloured ICP: `color` is non-null exactly while they are enabled
+  StageSelection();                                    // capi.cpp: the options are the seven mm3d_*_options_default's
   // the ICP of the pair stage rejects correspondences (mm3d_set_icp_rejection)
   bool rejecting() const { return reject_options.one_to_one || reject_options.distance != MM3D_REJECT_NONE; }
   int icp_method() const;                              // MM3D_ICP_*
@@ -47,7 +49,7 @@ struct StageSelection {
   // rand(), which is MATCHING's case in pair_rand_replay
   int replay_method(const mm3d_params *p) const { return coarse || prerejective(p) ? (int)MM3D_EST_MATCHING : (int)p->estimation_method; }
   // such a pair is estimated by pairs_estimate_batch alone (pair_estimate_impl hands it a batch of one)
-  bool batch_only(const mm3d_params *p) const { return icp || refine || coarse || confidence || rejecting() || prerejective(p); }
+  bool batch_only(const mm3d_params *p) const { return icp || refine || coarse || confidence || color || rejecting() || prerejective(p); }
 };
 
 // The feature / pair cache of mm3d_estimate_maps_transforms (mm3d_set_map_cache; the concrete class is map_cache.cpp's).  The
@@ -189,6 +191,15 @@ struct OverlapTable {
   DevBuf<unsigned char> view;                      // [nc[0] * nc[1] * nc[2]]
 };
 
+// What coloured ICP keeps of a map (icp_color.hip, mm3d_set_icp_color): per point the colour gradient on the tangent plane and
+// the intensity, in the points' order.  16 B per point beside the 16 B of the normals they are made from.
+struct ColorGradients {
+  double radius = 0.0;                             // what it was built with (a map's records are rebuilt when these change)
+  int min_neighbours = 0;
+  size_t n = 0;
+  DevBuf<float4> rec;                              // [n] (gx, gy, gz, I)
+};
+
 }  // namespace mm3d
 
 struct mm3d_cloud {
@@ -253,6 +264,7 @@ struct mm3d_map {
   std::unique_ptr<mm3d::NdtTable> ndt;              // NDT's voxel Gaussians
   std::unique_ptr<mm3d::CoarseSignature> coarse;    // the correlative alignment's signature
   std::unique_ptr<mm3d::OverlapTable> overlap;      // the overlap confidence's table
+  std::unique_ptr<mm3d::ColorGradients> color;      // coloured ICP's gradient records
   mm3d_map() = default;
   mm3d_map(const mm3d_map &) = delete;
   mm3d_map &operator=(const mm3d_map &) = delete;
@@ -373,11 +385,18 @@ struct IcpScoreJob {
   // NDT does not read it.  reject_stats: the last iteration's counts.
   const mm3d_icp_rejection_options *reject = nullptr;
   mm3d_icp_rejection_stats reject_stats{0, 0, 0, INFINITY, 0, 0};
+  // coloured ICP (mm3d_set_icp_color; icp_color.hip): the target's gradient records on the device, in its order, and the weight
+  // of the geometric rows (the same for every job of a batch)
+  const float4 *tgt_color = nullptr;
+  double color_lambda = 1.0;
 };
 void icp_score_batch(Context *c, IcpScoreJob *jobs, int n_jobs, bool run_icp, double max_corr_dist, int max_iterations, double eps,
                      bool want_score, double score_max_distance);
 // the same with point-to-plane ICP (icp_plane.hip's kernels; every job's tgt_normals set).  The score stays point-to-point.
 void icp_plane_score_batch(Context *c, IcpScoreJob *jobs, int n_jobs, bool run_icp, double max_corr_dist, int max_iterations, double eps,
+                           bool want_score, double score_max_distance);
+// the same with coloured ICP (icp_color.hip's kernels; every job's tgt_normals and tgt_color set).  The score stays point-to-point.
+void icp_color_score_batch(Context *c, IcpScoreJob *jobs, int n_jobs, bool run_icp, double max_corr_dist, int max_iterations, double eps,
                            bool want_score, double score_max_distance);
 // the same with NDT in the ICP's place (ndt.hip's kernels; every job's tgt_ndt set); max_corr_dist is read by the score only
 void ndt_score_batch(Context *c, IcpScoreJob *jobs, int n_jobs, bool run_icp, double max_corr_dist, int max_iterations, double eps,
