@@ -27,6 +27,14 @@
 
 namespace mm3d {
 
+// the point-to-plane job plus the target's gradient records and the source's reference points (their rgba).
+// pl.nn.partials: [nblocks][kPlaneAcc], read by k_icp_plane_finalize over the NnPlaneJobs.
+struct NnColorJob {
+  NnPlaneJob pl;
+  const float4 *rec;          // the target's records (gx, gy, gz, I), in tgt_ref's order
+  const float4 *src_ref;      // the source's points in reference order (nn.src's .w indexes them)
+};
+
 // I = (299 r + 587 g + 114 b) / 255000 in [0, 1]: SIFT's integer numerator (sift.hip's intensity_of), divided in double
 __device__ __forceinline__ float color_intensity(float w)
 {
@@ -254,20 +262,48 @@ k_icp_color_wave(const NnColorJob *__restrict__ cjobs, float max_d2, float rmax,
   }
 }
 
-void icp_color_step(Context *c, const NnColorJob *jobs_dev, int count, unsigned grid_x, bool split, float max_d2, float rmax, double lambda,
-                    double bytes)
-{
-  const double mu = 1.0 - lambda;
-  if (split)
-    MM3D_LAUNCH(c, "icp_color_corr_reduce", bytes, k_icp_color_wave<4>, dim3(grid_x, count), dim3(256), 0, jobs_dev, max_d2, rmax, lambda, mu);
-  else
-    MM3D_LAUNCH(c, "icp_color_corr_reduce", bytes, k_icp_color_wave<1>, dim3(grid_x, count), dim3(256), 0, jobs_dev, max_d2, rmax, lambda, mu);
-}
+static std::atomic<int> g_color_forced_split{0};      // mm3d_debug_icp_color_split: 0 (by size), 1 or 4
 
-static std::atomic<int> g_color_forced_split{0};
-int icp_color_forced_split() { return g_color_forced_split.load(); }
+namespace {
+// point-to-plane's jobs, partials and finalize kernel behind this file's search + reduction launch
+struct ColorStep final : IcpStep {
+  StepJobs<NnPlaneJob> plane;
+  StepJobs<NnColorJob> jobs;
+  double lambda = 1.0;       // the weight of the geometric rows (the photometric ones get 1 - lambda; 1: point-to-plane's terms, bit for bit)
+  ColorStep() { acc = kPlaneAcc; forced_split = g_color_forced_split.load(); }
+  double bytes_per_point(const IcpScoreJob &) const override { return 60.0; }      // (+ the winner's normal and record, the source's reference point)
+  void check(const IcpScoreJob &J) const override
+  {
+    icp_plane_check(J);
+    if (!J.tgt_color) throw Error(MM3D_EINVAL, "coloured ICP: the target has no gradient records");
+  }
+  size_t pinned_bytes(int B) const override { return plane.bytes(B) + jobs.bytes(B); }
+  void begin(Context *c, const IcpScoreJob *const *live, int B, char *pinned, void *, void *) override
+  {
+    jobs.begin(c, B, plane.begin(c, B, pinned));
+    lambda = live[0]->color_lambda;      // (the same for every job of a batch)
+  }
+  void bind(int b, const NnJob &q, const IcpScoreJob &J) override
+  {
+    plane.host[b] = icp_plane_job(q, J);
+    jobs.host[b] = NnColorJob{plane.host[b], J.tgt_color, (const float4 *)J.src->pts.get()};
+  }
+  void upload(Context *c) override { plane.upload(c); jobs.upload(c); }
+  void iterate(Context *c, const IcpLaunch &L) override
+  {
+    const double mu = 1.0 - lambda;
+    if (L.split)
+      MM3D_LAUNCH(c, "icp_color_corr_reduce", L.bytes, k_icp_color_wave<4>, dim3(L.grid_x, L.count), dim3(256), 0, (const NnColorJob *)jobs.dev.get(),
+                  L.max_d2, L.rmax, lambda, mu);
+    else
+      MM3D_LAUNCH(c, "icp_color_corr_reduce", L.bytes, k_icp_color_wave<1>, dim3(L.grid_x, L.count), dim3(256), 0, (const NnColorJob *)jobs.dev.get(),
+                  L.max_d2, L.rmax, lambda, mu);
+    icp_plane_finalize(c, plane.dev.get(), L.count, L.finalize_bytes);
+  }
+};
+}  // namespace
 
-bool icp_color_options_valid(const mm3d_icp_color_options *o)
+static bool icp_color_options_valid(const mm3d_icp_color_options *o)
 {
   if (o->enabled != 0 && o->enabled != 1) return false;
   if (!(o->lambda_geometric > 0.0 && o->lambda_geometric <= 1.0)) return false;
@@ -318,11 +354,7 @@ static const ColorGradients *map_color(mm3d_ctx *ctx, const mm3d_map *m, const m
 namespace {
 struct IcpColoured final : IcpMethodBase {
   int method() const override { return MM3D_ICP_POINT_TO_PLANE; }     // (not read: mm3d_get_icp_method answers StageSelection::icp's)
-  void score_batch(Context *c, IcpScoreJob *jobs, int n_jobs, bool run_icp, double max_corr_dist, int max_iterations, double eps,
-                   bool want_score, double score_max_distance) const override
-  {
-    icp_color_score_batch(c, jobs, n_jobs, run_icp, max_corr_dist, max_iterations, eps, want_score, score_max_distance);
-  }
+  std::unique_ptr<IcpStep> step(const mm3d_icp_rejection_options *) const override { return std::unique_ptr<IcpStep>(new ColorStep()); }
   void prepare_target(mm3d_ctx *ctx, const mm3d_map *m, const mm3d_params *p, IcpScoreJob *job) const override
   {
     const mm3d_normals *n = map_normals(ctx, m, p);
@@ -388,7 +420,7 @@ int mm3d_estimate_transform_icp_color(mm3d_ctx *ctx, const mm3d_cloud *source, c
     J.tgt_color = grad->rec.get();
     J.color_lambda = options->lambda_geometric;
     std::memcpy(J.guess_host, initial_guess, sizeof(J.guess_host));
-    icp_color_score_batch(ctx, &J, 1, true, max_corr_dist, max_iterations, eps, false, 0.0);
+    icp_score_batch(ctx, &g_coloured, &J, 1, true, max_corr_dist, max_iterations, eps, false, 0.0);
     std::memcpy(T, J.out.T, sizeof(J.out.T));
   });
 }

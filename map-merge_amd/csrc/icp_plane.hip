@@ -176,29 +176,41 @@ __global__ void __launch_bounds__(256) k_icp_plane_finalize(const NnPlaneJob *__
   st->prev_mse = mse;
 }
 
-void icp_plane_step(Context *c, const NnPlaneJob *jobs_dev, int count, unsigned grid_x, bool split, float max_d2, float rmax,
-                    double bytes, double finalize_bytes)
-{
-  if (split)
-    MM3D_LAUNCH(c, "icp_plane_corr_reduce", bytes, k_icp_plane_wave<4>, dim3(grid_x, count), dim3(256), 0, jobs_dev, max_d2, rmax);
-  else
-    MM3D_LAUNCH(c, "icp_plane_corr_reduce", bytes, k_icp_plane_wave<1>, dim3(grid_x, count), dim3(256), 0, jobs_dev, max_d2, rmax);
-  icp_plane_finalize(c, jobs_dev, count, finalize_bytes);
-}
-
-// (alone: the rejecting correspondence stage of icp_reject.hip writes the partials this reads)
+// (alone after the search of icp_color.hip and after the rejecting correspondence stage of icp_reject.hip, which write the
+// partials this reads)
 void icp_plane_finalize(Context *c, const NnPlaneJob *jobs_dev, int count, double finalize_bytes)
 {
   MM3D_LAUNCH(c, "icp_plane_finalize", finalize_bytes, k_icp_plane_finalize, dim3(count), dim3(256), 0, jobs_dev);
 }
 
 namespace {
+// icp_corr_reduce's and icp_finalize's counterparts over the ICP jobs with their normals
+struct PlaneStep final : IcpStep {
+  StepJobs<NnPlaneJob> jobs;
+  PlaneStep() { acc = kPlaneAcc; }
+  double bytes_per_point(const IcpScoreJob &) const override { return 28.0; }      // (+ the winner's normal)
+  void check(const IcpScoreJob &J) const override { icp_plane_check(J); }
+  size_t pinned_bytes(int B) const override { return jobs.bytes(B); }
+  void begin(Context *c, const IcpScoreJob *const *, int B, char *pinned, void *, void *) override { jobs.begin(c, B, pinned); }
+  void bind(int b, const NnJob &q, const IcpScoreJob &J) override { jobs.host[b] = icp_plane_job(q, J); }
+  void upload(Context *c) override { jobs.upload(c); }
+  void iterate(Context *c, const IcpLaunch &L) override
+  {
+    if (L.split)
+      MM3D_LAUNCH(c, "icp_plane_corr_reduce", L.bytes, k_icp_plane_wave<4>, dim3(L.grid_x, L.count), dim3(256), 0, (const NnPlaneJob *)jobs.dev.get(),
+                  L.max_d2, L.rmax);
+    else
+      MM3D_LAUNCH(c, "icp_plane_corr_reduce", L.bytes, k_icp_plane_wave<1>, dim3(L.grid_x, L.count), dim3(256), 0, (const NnPlaneJob *)jobs.dev.get(),
+                  L.max_d2, L.rmax);
+    icp_plane_finalize(c, jobs.dev.get(), L.count, L.finalize_bytes);
+  }
+};
+
 struct IcpPointToPlane final : IcpMethodBase {
   int method() const override { return MM3D_ICP_POINT_TO_PLANE; }
-  void score_batch(Context *c, IcpScoreJob *jobs, int n_jobs, bool run_icp, double max_corr_dist, int max_iterations, double eps,
-                   bool want_score, double score_max_distance) const override
+  std::unique_ptr<IcpStep> step(const mm3d_icp_rejection_options *reject) const override
   {
-    icp_plane_score_batch(c, jobs, n_jobs, run_icp, max_corr_dist, max_iterations, eps, want_score, score_max_distance);
+    return reject ? icp_reject_step(*reject, true) : std::unique_ptr<IcpStep>(new PlaneStep());
   }
   void prepare_target(mm3d_ctx *ctx, const mm3d_map *m, const mm3d_params *p, IcpScoreJob *job) const override
   {
@@ -208,6 +220,7 @@ struct IcpPointToPlane final : IcpMethodBase {
 };
 const IcpPointToPlane g_point_to_plane;
 }  // namespace
+const IcpMethodBase *icp_plane_method() { return &g_point_to_plane; }
 
 }  // namespace mm3d
 
@@ -242,7 +255,7 @@ int mm3d_estimate_transform_icp_plane(mm3d_ctx *ctx, const mm3d_cloud *source, c
     IcpScoreJob J;
     J.src = source; J.tgt = target; J.tgt_normals = target_normals;
     std::memcpy(J.guess_host, initial_guess, sizeof(J.guess_host));
-    icp_plane_score_batch(ctx, &J, 1, true, max_corr_dist, max_iterations, eps, false, 0.0);
+    icp_score_batch(ctx, &g_point_to_plane, &J, 1, true, max_corr_dist, max_iterations, eps, false, 0.0);
     std::memcpy(T, J.out.T, sizeof(J.out.T));
   });
 }

@@ -30,6 +30,27 @@
 
 namespace mm3d {
 
+// What one pair's selection leaves behind, on the device beside the pair's IcpState and back on the host in the copy that brings
+// the states: the counts of the last iteration that ran and the state of the radix select (prefix / rank BEFORE pass q of four
+// 8-bit passes over the d2 bits).
+struct RejRecord {
+  unsigned matched, survivors, kept;
+  unsigned tau_bits;          // TRIMMED: tau; MEDIAN: m (valid when cut == 0)
+  int cut;                    // 0: cut at tau_bits, 1: nothing is cut, 2: everything is cut
+  unsigned prefix[4], rank[4];
+};
+// the search job plus the rejecting stage's working memory; nn.partials: [nblocks][kAcc], or [nblocks][kPlaneAcc] with normals
+struct NnRejectJob {
+  NnJob nn;
+  const float4 *nrm;          // point-to-plane: the target's normals (tgt_ref's order); null: point-to-point
+  int2 *corr;                 // [n_src], at the point's place in the Hilbert-ordered source: {target index (-1: none;
+                              // -2 - index: lost its target under one_to_one), d2 bits}
+  unsigned long long *owner;  // one_to_one: [n_tgt] smallest key d2 bits << 32 | original source index per target point
+  unsigned *hist;             // [4][256]
+  RejRecord *rec;
+  int n_src;                  // finite source points
+};
+
 // the options as the kernels take them
 struct RejOpts {
   int one_to_one, distance, min_corr;
@@ -341,7 +362,7 @@ static RejOpts rej_opts(const mm3d_icp_rejection_options &opt)
   return RejOpts{opt.one_to_one, opt.distance, opt.min_correspondences, opt.overlap_ratio, opt.median_factor};
 }
 
-// begin, search and the select's passes of one iteration
+// begin, search and the select's passes of one iteration.  owner_all / owner_bytes: the batch's owner arrays as one region.
 static void reject_front(Context *c, const NnRejectJob *jobs_dev, int count, unsigned grid_x, unsigned max_src, bool split, float max_d2,
                          float rmax, const mm3d_icp_rejection_options &opt, unsigned long long *owner_all, size_t owner_bytes, double bytes)
 {
@@ -358,39 +379,167 @@ static void reject_front(Context *c, const NnRejectJob *jobs_dev, int count, uns
                 jobs_dev, o, pass);
 }
 
-void icp_reject_step(Context *c, const NnRejectJob *jobs_dev, int count, unsigned grid_x, unsigned max_src, bool split, bool plane,
-                     float max_d2, float rmax, const mm3d_icp_rejection_options &opt, unsigned long long *owner_all, size_t owner_bytes,
-                     double bytes)
+// a pair's record as the caller sees it (iterations and converged are the state's)
+static mm3d_icp_rejection_stats rej_stats(const RejRecord &r, const mm3d_icp_rejection_options &opt, int iterations, int converged)
 {
-  reject_front(c, jobs_dev, count, grid_x, max_src, split, max_d2, rmax, opt, owner_all, owner_bytes, bytes);
-  const RejOpts o = rej_opts(opt);
-  const dim3 grid(split ? div_up(grid_x, 4) : grid_x, count);      // four work items per block either way
-  const double rbytes = (double)max_src * count * 24.0;
-  if (split && plane) MM3D_LAUNCH(c, "icp_reject_reduce", rbytes, (k_rej_reduce<4, true>), grid, dim3(256), 0, jobs_dev, o);
-  else if (split) MM3D_LAUNCH(c, "icp_reject_reduce", rbytes, (k_rej_reduce<4, false>), grid, dim3(256), 0, jobs_dev, o);
-  else if (plane) MM3D_LAUNCH(c, "icp_reject_reduce", rbytes, (k_rej_reduce<1, true>), grid, dim3(256), 0, jobs_dev, o);
-  else MM3D_LAUNCH(c, "icp_reject_reduce", rbytes, (k_rej_reduce<1, false>), grid, dim3(256), 0, jobs_dev, o);
+  float tau;
+  std::memcpy(&tau, &r.tau_bits, 4);
+  return mm3d_icp_rejection_stats{(long long)r.matched, (long long)(opt.one_to_one ? r.survivors : r.matched), (long long)r.kept,
+                                  r.cut == 0 ? tau : r.cut == 1 ? INFINITY : -1.0f, iterations, converged};
+}
+static RejRecord rej_record_init()
+{
+  RejRecord r;
+  std::memset(&r, 0, sizeof(r));
+  r.cut = 1;
+  return r;
 }
 
-void icp_reject_debug(Context *c, const NnRejectJob *job_dev, unsigned grid_x, unsigned n_src, int n_items, bool split, float max_d2, float rmax,
-                      const mm3d_icp_rejection_options &opt, unsigned long long *owner, size_t owner_bytes, int *out_idx, float *out_d2,
-                      unsigned char *out_kept)
+static std::atomic<int> g_forced_split{0};      // mm3d_debug_icp_rejection_split: 0 (by size), 1 or 4
+
+namespace {
+// One iteration: the correspondence stage and the reduction into the ICP jobs' partials in the default kernels' layout and order,
+// then the default finalize kernel -- k_icp_finalize over the batch's NnJobs or, with normals, k_icp_plane_finalize over
+// NnPlaneJobs kept here.  The pairs' records ride behind the states.
+struct RejectStep final : IcpStep {
+  const mm3d_icp_rejection_options opt;
+  const bool plane;
+  StepJobs<NnRejectJob> jobs;
+  StepJobs<NnPlaneJob> pjobs;
+  DevBuf<int2> corr;                      // the batch's sources, one after the other
+  DevBuf<unsigned long long> owner;       // one_to_one: the batch's targets
+  DevBuf<unsigned> hist;
+  RejRecord *rec_host = nullptr, *rec_dev = nullptr;
+  size_t n_src = 0, n_tgt = 0, src_off = 0, tgt_off = 0;
+  unsigned max_src = 0;
+  RejectStep(const mm3d_icp_rejection_options &o, bool normals) : opt(o), plane(normals)
+  {
+    acc = plane ? kPlaneAcc : kAcc;
+    forced_split = g_forced_split.load();
+  }
+  double bytes_per_point(const IcpScoreJob &) const override { return plane ? 28.0 : 12.0; }
+  void check(const IcpScoreJob &J) const override { if (plane) icp_plane_check(J); }
+  size_t pinned_bytes(int B) const override { return jobs.bytes(B) + (plane ? pjobs.bytes(B) : 0); }
+  size_t record_bytes(int B) const override { return sizeof(RejRecord) * B; }
+  void begin(Context *c, const IcpScoreJob *const *live, int B, char *pinned, void *rh, void *rd) override
+  {
+    for (int b = 0; b < B; ++b) {
+      n_src += live[b]->src->n_finite;
+      n_tgt += opt.one_to_one ? live[b]->tgt->n : 0;
+      max_src = std::max(max_src, (unsigned)live[b]->src->n_finite);
+    }
+    pinned = jobs.begin(c, B, pinned);
+    if (plane) pjobs.begin(c, B, pinned);
+    corr = DevBuf<int2>(c, n_src);
+    owner = DevBuf<unsigned long long>(c, n_tgt ? n_tgt : 1);
+    hist = DevBuf<unsigned>(c, (size_t)B * 1024);
+    rec_host = (RejRecord *)rh;
+    rec_dev = (RejRecord *)rd;
+  }
+  void bind(int b, const NnJob &q, const IcpScoreJob &J) override
+  {
+    if (plane) pjobs.host[b] = icp_plane_job(q, J);
+    jobs.host[b] = NnRejectJob{q, plane ? pjobs.host[b].nrm : nullptr, corr.get() + src_off, opt.one_to_one ? owner.get() + tgt_off : nullptr,
+                               hist.get() + (size_t)b * 1024, rec_dev + b, (int)J.src->n_finite};
+    rec_host[b] = rej_record_init();
+    src_off += J.src->n_finite;
+    tgt_off += opt.one_to_one ? J.tgt->n : 0;
+  }
+  void upload(Context *c) override
+  {
+    jobs.upload(c);
+    // (a place of the Hilbert-ordered source that no work item covers holds "no match" for good)
+    MM3D_HIP(hipMemsetAsync(corr.get(), 0xff, n_src * sizeof(int2), c->stream));
+    if (plane) pjobs.upload(c);
+  }
+  void iterate(Context *c, const IcpLaunch &L) override
+  {
+    const NnRejectJob *jobs_dev = jobs.dev.get();
+    reject_front(c, jobs_dev, L.count, L.grid_x, max_src, L.split, L.max_d2, L.rmax, opt, owner.get(), n_tgt * sizeof(unsigned long long),
+                 L.bytes + n_src * 8.0);
+    const RejOpts o = rej_opts(opt);
+    const dim3 grid(L.split ? div_up(L.grid_x, 4) : L.grid_x, L.count);      // four work items per block either way
+    const double rbytes = (double)max_src * L.count * 24.0;
+    if (L.split && plane) MM3D_LAUNCH(c, "icp_reject_reduce", rbytes, (k_rej_reduce<4, true>), grid, dim3(256), 0, jobs_dev, o);
+    else if (L.split) MM3D_LAUNCH(c, "icp_reject_reduce", rbytes, (k_rej_reduce<4, false>), grid, dim3(256), 0, jobs_dev, o);
+    else if (plane) MM3D_LAUNCH(c, "icp_reject_reduce", rbytes, (k_rej_reduce<1, true>), grid, dim3(256), 0, jobs_dev, o);
+    else MM3D_LAUNCH(c, "icp_reject_reduce", rbytes, (k_rej_reduce<1, false>), grid, dim3(256), 0, jobs_dev, o);
+    if (plane) icp_plane_finalize(c, pjobs.dev.get(), L.count, L.finalize_bytes);
+    else icp_point_finalize(c, L.jobs_dev, L.count, L.finalize_bytes);
+  }
+  void close(int b, const IcpState &h, IcpScoreJob &J) override { J.reject_stats = rej_stats(rec_host[b], opt, h.iters, h.converged); }
+};
+}  // namespace
+
+std::unique_ptr<IcpStep> icp_reject_step(const mm3d_icp_rejection_options &opt, bool normals)
 {
-  reject_front(c, job_dev, 1, grid_x, n_src, split, max_d2, rmax, opt, owner, owner_bytes, n_src * 24.0);
-  MM3D_LAUNCH(c, "icp_reject_export", n_src * 17.0, k_rej_export, dim3(div_up(n_items, 4)), dim3(256), 0, job_dev, rej_opts(opt), out_idx, out_d2,
-              out_kept);
+  return std::unique_ptr<IcpStep>(new RejectStep(opt, normals));
 }
 
-static std::atomic<int> g_forced_split{0};
-int icp_reject_forced_split() { return g_forced_split.load(); }
-
-bool icp_rejection_options_valid(const mm3d_icp_rejection_options *o)
+static bool icp_rejection_options_valid(const mm3d_icp_rejection_options *o)
 {
   if (o->one_to_one != 0 && o->one_to_one != 1) return false;
   if (o->distance != MM3D_REJECT_NONE && o->distance != MM3D_REJECT_TRIMMED && o->distance != MM3D_REJECT_MEDIAN) return false;
   if (!(o->overlap_ratio > 0.0 && o->overlap_ratio <= 1.0)) return false;
   if (o->min_correspondences < 0) return false;
   return o->median_factor > 0.0 && std::isfinite(o->median_factor);
+}
+
+// mm3d_debug_icp_rejection: the search set-up as icp_batch derives it, one iteration's begin, search and select passes at T with
+// the split forced, and every source point's decision at its original index
+static void debug_icp_rejection(Context *c, const mm3d_cloud *src, const mm3d_cloud *tgt, const float T[16], double max_corr_dist,
+                                const mm3d_icp_rejection_options &opt, int split, int *idx, float *d2, unsigned char *kept,
+                                mm3d_icp_rejection_stats *stats)
+{
+  const NnRange r = nn_range_icp(max_corr_dist);
+  mm3d_icp_rejection_stats S{0, 0, 0, INFINITY, 0, 0};
+  std::vector<int> h_idx(src->n, -1);
+  std::vector<float> h_d2(src->n, INFINITY);
+  std::vector<unsigned char> h_kept(src->n, 0);
+  const NnSearch s = nn_search(c, src, tgt, &r);
+  if (s.grid) {
+    const unsigned nblocks = nn_blocks(s.n_items, split == 4);
+    DevBuf<int> d_idx(c, src->n);
+    DevBuf<float> d_d2(c, src->n);
+    DevBuf<unsigned char> d_kept(c, src->n);
+    DevBuf<IcpState> st(c, 2);                       // the state, and the record behind it
+    DevBuf<NnRejectJob> d_job(c, 1);
+    DevBuf<int2> corr(c, (size_t)s.ns);
+    DevBuf<unsigned long long> owner(c, opt.one_to_one ? tgt->n : 1);
+    DevBuf<unsigned> hist(c, 1024);
+    char *pinned = (char *)c->pin(2 * sizeof(IcpState) + sizeof(NnRejectJob) + 64);
+    IcpState *hs = (IcpState *)pinned;
+    RejRecord *hr = (RejRecord *)(hs + 1);
+    NnRejectJob *hj = (NnRejectJob *)(pinned + 2 * sizeof(IcpState));
+    std::memset(hs, 0, 2 * sizeof(IcpState));
+    std::memcpy(hs->T, T, 64);
+    *hr = rej_record_init();
+    *hj = NnRejectJob{nn_job(s, split == 4, nblocks, st.get(), nullptr, nullptr, nullptr), nullptr, corr.get(),
+                      opt.one_to_one ? owner.get() : nullptr, hist.get(), (RejRecord *)(st.get() + 1), s.ns};
+    // (non-finite source points are in no work item: they keep -1 / +inf / 0)
+    MM3D_HIP(hipMemcpyAsync(d_idx.get(), h_idx.data(), src->n * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    MM3D_HIP(hipMemcpyAsync(d_d2.get(), h_d2.data(), src->n * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    MM3D_HIP(hipMemsetAsync(d_kept.get(), 0, src->n, c->stream));
+    MM3D_HIP(hipMemsetAsync(corr.get(), 0xff, (size_t)s.ns * sizeof(int2), c->stream));
+    MM3D_HIP(hipMemcpyAsync(st.get(), hs, 2 * sizeof(IcpState), hipMemcpyHostToDevice, c->stream));
+    MM3D_HIP(hipMemcpyAsync(d_job.get(), hj, sizeof(NnRejectJob), hipMemcpyHostToDevice, c->stream));
+    reject_front(c, d_job.get(), 1, nblocks, (unsigned)s.ns, split == 4, r.max_d2, r.rmax, opt, owner.get(),
+                 opt.one_to_one ? tgt->n * sizeof(unsigned long long) : 0, s.ns * 24.0);
+    MM3D_LAUNCH(c, "icp_reject_export", s.ns * 17.0, k_rej_export, dim3(div_up(s.n_items, 4)), dim3(256), 0, (const NnRejectJob *)d_job.get(),
+                rej_opts(opt), d_idx.get(), d_d2.get(), d_kept.get());
+    MM3D_HIP(hipMemcpyAsync(h_idx.data(), d_idx.get(), src->n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    MM3D_HIP(hipMemcpyAsync(h_d2.data(), d_d2.get(), src->n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    MM3D_HIP(hipMemcpyAsync(h_kept.data(), d_kept.get(), src->n, hipMemcpyDeviceToHost, c->stream));
+    MM3D_HIP(hipMemcpyAsync(hs, st.get(), 2 * sizeof(IcpState), hipMemcpyDeviceToHost, c->stream));
+    c->sync();
+    S = rej_stats(*hr, opt, 0, 0);
+  }
+  if (src->n) {
+    std::memcpy(idx, h_idx.data(), src->n * sizeof(int));
+    std::memcpy(d2, h_d2.data(), src->n * sizeof(float));
+    std::memcpy(kept, h_kept.data(), src->n);
+  }
+  if (stats) *stats = S;
 }
 
 }  // namespace mm3d
@@ -442,8 +591,7 @@ int mm3d_estimate_transform_icp_rejecting(mm3d_ctx *ctx, const mm3d_cloud *sourc
     J.src = source; J.tgt = target; J.tgt_normals = target_normals;
     J.reject = options;
     std::memcpy(J.guess_host, initial_guess, sizeof(J.guess_host));
-    if (target_normals) icp_plane_score_batch(ctx, &J, 1, true, max_corr_dist, max_iterations, eps, false, 0.0);
-    else icp_score_batch(ctx, &J, 1, true, max_corr_dist, max_iterations, eps, false, 0.0);
+    icp_score_batch(ctx, target_normals ? icp_plane_method() : nullptr, &J, 1, true, max_corr_dist, max_iterations, eps, false, 0.0);
     std::memcpy(T, J.out.T, sizeof(J.out.T));
     ctx->last_reject_stats = J.reject_stats;
     if (stats) *stats = J.reject_stats;
@@ -454,6 +602,16 @@ int mm3d_debug_icp_rejection_split(int split)
 {
   if (split == 0 || split == 1 || split == 4) g_forced_split.store(split);
   return g_forced_split.load();
+}
+
+int mm3d_debug_icp_rejection(mm3d_ctx *ctx, const mm3d_cloud *source, const mm3d_cloud *target, const float T[16],
+                             double max_correspondence_distance, const mm3d_icp_rejection_options *options, int split, int *idx, float *d2,
+                             unsigned char *kept, mm3d_icp_rejection_stats *stats)
+{
+  if (!source || !target || !T || !options || !icp_rejection_options_valid(options) || (split != 1 && split != 4)) return MM3D_EINVAL;
+  if (!(max_correspondence_distance >= 0.0) || !std::isfinite(max_correspondence_distance)) return MM3D_EINVAL;
+  if (source->n && (!idx || !d2 || !kept)) return MM3D_EINVAL;
+  return guarded(ctx, [&] { debug_icp_rejection(ctx, source, target, T, max_correspondence_distance, *options, split, idx, d2, kept, stats); });
 }
 
 }  // extern "C"

@@ -15,7 +15,7 @@
 //                  Lane l takes the run's positions l, l + 64, ... in ascending order and the 64 lane sums meet in wave_sum's
 //                  fixed butterfly: one order, whatever the launch.  Lane 0 rounds to float once, stores the 48-byte record
 //                  and the voxel's word of the dense index.
-// One iteration of a batch (ndt_step), two launches like icp_corr_reduce / icp_finalize:
+// One iteration of a batch (NdtStep), two launches like icp_corr_reduce / icp_finalize:
 //   k_ndt_wave      a lane per source point over the source's Hilbert order and work items (k_nn_wave's: neighbouring lanes
 //                   hit neighbouring voxels), blockIdx.y = the pair.  1 or 7 index loads, three 16-byte loads per valid
 //                   voxel, the terms in double; per lane sum_w P (6), sum_w P q (3), sum w and the term count, from which the
@@ -34,6 +34,20 @@
 #include "scan_fused.hpp"
 
 namespace mm3d {
+
+// The job's source side and state (nn.g, nn.tgt_ref and nn.max_ring are not read; nn.split is 0: always four work items per
+// block, so nn.partials is [ceil(n_items / 4)][kNdtAcc] whatever the batch), and the target's voxel table
+struct NdtJob {
+  NnJob nn;
+  const float4 *rec;          // NdtTable::rec
+  const int *index;           // NdtTable::index
+  float inv, mn[3];
+  int dims[3];
+  int neighbours;             // 1 or 7
+  int n_src;                  // finite source points: the divisor of the convergence test's mean weight
+};
+// H upper triangle (21) | g (6) | sum w | terms | points with at least one term
+constexpr int kNdtAcc = 30;
 
 namespace {
 
@@ -407,13 +421,44 @@ std::unique_ptr<NdtTable> ndt_build_table(Context *c, const mm3d_cloud *tgt, dou
   return t;
 }
 
+// the lookup + reduction launch, then the solve / accumulate / convergence launch, on the IcpState protocol of the ICP's.  No
+// grid of the target is read and max_corr_dist is not read.
+struct NdtStep final : IcpStep {
+  StepJobs<NdtJob> jobs;
+  NdtStep() { acc = kNdtAcc; searches = false; }
+  double bytes_per_point(const IcpScoreJob &J) const override { return 16.0 + 52.0 * J.ndt_neighbours; }      // (the point, and an index word and a record per voxel)
+  void check(const IcpScoreJob &J) const override
+  {
+    if (!J.tgt_ndt) throw Error(MM3D_EINVAL, "NDT: the target has no voxel table");
+  }
+  size_t pinned_bytes(int B) const override { return jobs.bytes(B); }
+  void begin(Context *c, const IcpScoreJob *const *, int B, char *pinned, void *, void *) override { jobs.begin(c, B, pinned); }
+  void bind(int b, const NnJob &q, const IcpScoreJob &J) override
+  {
+    NdtJob nj;
+    std::memset(&nj, 0, sizeof(nj));
+    nj.nn = q;
+    if (const NdtTable *t = J.tgt_ndt) {
+      nj.rec = (const float4 *)t->rec.get();
+      nj.index = (const int *)t->index.get();
+      nj.inv = t->inv;
+      for (int a = 0; a < 3; ++a) { nj.mn[a] = t->mn[a]; nj.dims[a] = t->dims[a]; }
+    }
+    nj.neighbours = J.ndt_neighbours;
+    nj.n_src = (int)J.src->n_finite;
+    jobs.host[b] = nj;
+  }
+  void upload(Context *c) override { jobs.upload(c); }
+  void iterate(Context *c, const IcpLaunch &L) override
+  {
+    MM3D_LAUNCH(c, "ndt_wave", L.bytes, k_ndt_wave, dim3(L.grid_x, L.count), dim3(256), 0, (const NdtJob *)jobs.dev.get());
+    MM3D_LAUNCH(c, "ndt_finalize", L.finalize_bytes, k_ndt_finalize, dim3(L.count), dim3(256), 0, (const NdtJob *)jobs.dev.get());
+  }
+};
+
 struct RefineNdt final : IcpMethodBase {
   int method() const override { return MM3D_REFINE_NDT; }
-  void score_batch(Context *c, IcpScoreJob *jobs, int n_jobs, bool run_icp, double max_corr_dist, int max_iterations, double eps,
-                   bool want_score, double score_max_distance) const override
-  {
-    ndt_score_batch(c, jobs, n_jobs, run_icp, max_corr_dist, max_iterations, eps, want_score, score_max_distance);
-  }
+  std::unique_ptr<IcpStep> step(const mm3d_icp_rejection_options *) const override { return std::unique_ptr<IcpStep>(new NdtStep()); }
   // the map's table at the context's options (map_kept.hpp)
   void prepare_target(mm3d_ctx *ctx, const mm3d_map *m, const mm3d_params *p, IcpScoreJob *job) const override
   {
@@ -429,12 +474,6 @@ struct RefineNdt final : IcpMethodBase {
 const RefineNdt g_ndt;
 
 }  // namespace
-
-void ndt_step(Context *c, const NdtJob *jobs_dev, int count, unsigned grid_x, double bytes, double finalize_bytes)
-{
-  MM3D_LAUNCH(c, "ndt_wave", bytes, k_ndt_wave, dim3(grid_x, count), dim3(256), 0, jobs_dev);
-  MM3D_LAUNCH(c, "ndt_finalize", finalize_bytes, k_ndt_finalize, dim3(count), dim3(256), 0, jobs_dev);
-}
 
 }  // namespace mm3d
 
@@ -470,7 +509,7 @@ int mm3d_estimate_transform_ndt(mm3d_ctx *ctx, const mm3d_cloud *source, const m
     IcpScoreJob J;
     J.src = source; J.tgt = target; J.tgt_ndt = t.get(); J.ndt_neighbours = options->neighbours;
     std::memcpy(J.guess_host, initial_guess, sizeof(J.guess_host));
-    ndt_score_batch(ctx, &J, 1, true, 0.0, max_iterations, eps, false, 0.0);
+    icp_score_batch(ctx, &g_ndt, &J, 1, true, 0.0, max_iterations, eps, false, 0.0);
     std::memcpy(T, J.out.T, sizeof(J.out.T));
   });
 }

@@ -141,20 +141,6 @@ k_nn_probe(const NnJob *__restrict__ jobs, float max_d2, float rmax, int *__rest
 }
 
 // one block: reduce partials, Umeyama, accumulate, convergence (DefaultConvergenceCriteria)
-// Partial sums of "block" b as the four-items-per-block kernel writes them.  The one-item-per-block kernel leaves
-// one partial per item; adding four neighbours here, in the order that kernel's last step does, gives the same
-// bits -- so which variant ran (a choice that depends on what else was ready at the time) never shows in a result.
-__device__ __forceinline__ double nn_block_partial(const double *__restrict__ p, int b, int k, int split, int n_items)
-{
-  if (!split) return p[(size_t)b * kAcc + k];
-  const int i = b * 4;
-  double v = p[(size_t)i * kAcc + k];
-  v += (i + 1 < n_items) ? p[(size_t)(i + 1) * kAcc + k] : 0.0;
-  v += (i + 2 < n_items) ? p[(size_t)(i + 2) * kAcc + k] : 0.0;
-  v += (i + 3 < n_items) ? p[(size_t)(i + 3) * kAcc + k] : 0.0;
-  return v;
-}
-
 __global__ void __launch_bounds__(256) k_icp_finalize(const NnJob *__restrict__ jobs)
 {
   __shared__ double red[4][kAcc];
@@ -169,7 +155,7 @@ __global__ void __launch_bounds__(256) k_icp_finalize(const NnJob *__restrict__ 
   for (int k = 0; k < kAcc; ++k) acc[k] = 0.0;
   for (int b = threadIdx.x; b < nblocks; b += blockDim.x)
 #pragma unroll
-    for (int k = 0; k < kAcc; ++k) acc[k] += nn_block_partial(partials, b, k, split, n_items);
+    for (int k = 0; k < kAcc; ++k) acc[k] += nn_block_partial_n<kAcc>(partials, b, k, split, n_items);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
   for (int k = 0; k < kAcc; ++k) {
@@ -246,8 +232,8 @@ __global__ void __launch_bounds__(256) k_score_finalize(const NnJob *__restrict_
   if (st && (!st->done || st->scored)) return;
   double s = 0.0, n = 0.0;
   for (int b = threadIdx.x; b < nblocks; b += blockDim.x) {
-    s += nn_block_partial(partials, b, 15, split, n_items);
-    n += nn_block_partial(partials, b, 16, split, n_items);
+    s += nn_block_partial_n<kAcc>(partials, b, 15, split, n_items);
+    n += nn_block_partial_n<kAcc>(partials, b, 16, split, n_items);
   }
   s = wave_sum(s); n = wave_sum(n);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -260,14 +246,6 @@ __global__ void __launch_bounds__(256) k_score_finalize(const NnJob *__restrict_
   }
 }
 
-// the source runs in the cloud's Hilbert order, one compact work item (<= 64 points) per wave (grid.hip)
-static const float4 *morton_source(Context *c, const mm3d_cloud *src, int &n)
-{
-  cloud_hilbert(c, src);
-  n = (int)src->n_finite;
-  return src->hil_pts.get();
-}
-
 static float nn_cell_for(double radius)
 {
   float cell = (float)(radius * 0.25);
@@ -275,11 +253,8 @@ static float nn_cell_for(double radius)
   return cell;
 }
 
-// What a search derives from its range: the largest squared distance that is still a correspondence, the radius the
-// search has to prove (with the slack that covers its own rounding) and the radius the target's grid is built for.
-struct NnRange { float max_d2, rmax; double radius; };
 // ICP: max_corr_dist is a distance.  (double)d2 > max_dist_sqr rejects: accept d2 <= largest float not above max_dist_sqr
-static NnRange nn_range_icp(double max_corr_dist)
+NnRange nn_range_icp(double max_corr_dist)
 {
   const double max_dist_sqr = max_corr_dist * max_corr_dist;
   float max_d2 = (float)max_dist_sqr;
@@ -287,7 +262,7 @@ static NnRange nn_range_icp(double max_corr_dist)
   return {max_d2, (float)(max_corr_dist * 1.0001 + 1e-5), max_corr_dist};
 }
 // score: max_range_ is compared with the SQUARED distance (PCL quirk), so the search radius is sqrt(max_distance)
-static NnRange nn_range_score(double max_distance)
+NnRange nn_range_score(double max_distance)
 {
   const double radius = std::sqrt(max_distance > 0 ? max_distance : 0.0);
   float max_d2 = (float)max_distance;
@@ -301,7 +276,47 @@ static int nn_max_ring(float rmax, const Grid &g) { return (int)std::ceil(rmax /
 // wave each: 256 CUs x 4 SIMDs take 1024 waves before any two share a SIMD.  Measured on MI355X, pairs/s with
 // the split off / on: 16 x 100 k points (1.3 k items) 1765 / 1823, 4 x 200 k (2.5 k items) 245 / 257,
 // 64 x 50 k (0.6 k items) 4135 / 4925, 16 x 500 k (7.8 k items) 706 / 669.
-static bool nn_split_items(int n_items) { return n_items <= 4096; }
+bool nn_split_items(int n_items) { return n_items <= 4096; }
+
+// the source runs in the cloud's Hilbert order, one compact work item (<= 64 points) per wave (grid.hip); the target's grid has
+// cells of a quarter of the radius and a distance transform out to the ring the radius needs
+NnSearch nn_search(Context *c, const mm3d_cloud *src, const mm3d_cloud *tgt, const NnRange *range)
+{
+  NnSearch s;
+  if (src->n == 0 || tgt->n == 0) return s;
+  cloud_hilbert(c, src);
+  if (src->n_finite == 0) return s;
+  s.src = src->hil_pts.get();
+  s.items = (const int2 *)src->wave_items.get();
+  s.ns = (int)src->n_finite;
+  s.n_items = src->n_wave_items;
+  s.tgt_ref = (const float4 *)tgt->pts.get();
+  if (!range) return s;
+  const Grid &g = cloud_grid(c, tgt, nn_cell_for(range->radius));
+  if (g.n == 0) return s;
+  s.grid = &g;
+  s.max_ring = nn_max_ring(range->rmax, g);
+  grid_ensure_dt(c, g, s.max_ring);
+  return s;
+}
+
+NnJob nn_job(const NnSearch &s, bool split, unsigned nblocks, IcpState *st, const float *Tc, double *partials, double *out)
+{
+  NnJob q;
+  memset(&q, 0, sizeof(q));
+  q.src = s.src;
+  q.items = s.items;
+  q.n_items = s.n_items;
+  q.nblocks = (int)nblocks;
+  q.split = split ? 1 : 0;
+  if (s.grid) { q.g = s.grid->view(); q.max_ring = s.max_ring; }
+  q.tgt_ref = s.tgt_ref;
+  q.st = st;
+  q.Tc = Tc;
+  q.partials = partials;
+  q.out = out;
+  return q;
+}
 
 // launches k_nn_wave<MODE> over `count` jobs (device array), picking the one-item-per-block variant for small sources
 template <int MODE>
@@ -314,48 +329,50 @@ static void launch_nn(Context *c, const char *name, double bytes, const NnJob *j
     MM3D_LAUNCH(c, name, bytes, (k_nn_wave<MODE, 1>), dim3(grid_x, count), dim3(256), 0, jobs_dev, max_d2, rmax);
 }
 
+void icp_point_finalize(Context *c, const NnJob *jobs_dev, int count, double bytes)
+{
+  MM3D_LAUNCH(c, "icp_finalize", bytes, k_icp_finalize, dim3(count), dim3(256), 0, jobs_dev);
+}
+
+namespace {
+// the reference's point-to-point ICP: the batch's own NnJobs are all it needs
+struct PointStep final : IcpStep {
+  double bytes_per_point(const IcpScoreJob &) const override { return 12.0; }
+  void iterate(Context *c, const IcpLaunch &L) override
+  {
+    launch_nn<0>(c, "icp_corr_reduce", L.bytes, L.jobs_dev, L.count, L.grid_x, L.split, L.max_d2, L.rmax);
+    icp_point_finalize(c, L.jobs_dev, L.count, L.finalize_bytes);
+  }
+};
+}  // namespace
+
 // ICP from a guess and, if wanted, transformScore of the result -- the tail of every pair estimate -- for a BATCH
 // of pairs in lockstep: one launch per step serves every pair of the batch (blockIdx.y = the pair), and the batch
 // shares ONE host synchronisation per chunk of iterations.  A guess may already live on the device (SAC-IA's
 // winning hypothesis), the score kernel reads the transform straight out of the ICP state, and the states and
 // scores come back in one copy.  The score is launched speculatively after each chunk of iterations; a pair's
 // score is only kept once its ICP has finished (it nearly always has: the reference's epsilon is loose).
-// plane: point-to-plane ICP (icp_plane.hip's icp_plane_step over NnPlaneJobs that carry each target's normals) instead of
-// icp_corr_reduce + icp_finalize; everything else -- states, chunks, waits, the speculative point-to-point score -- is shared.
-// ndt: NDT (ndt.hip's ndt_step over NdtJobs that carry each target's voxel table) in the ICP's place: no grid of the target is
-// read by it, max_corr_dist is not read by it, and its partials are always per block of four work items.
-// Correspondence rejection (mm3d_set_icp_rejection): when the jobs carry options (IcpScoreJob::reject, the same for the whole batch),
-// the Point and Plane kinds take icp_reject.hip's icp_reject_step in the place of their search + reduction launch -- it leaves the
-// same partials for the kept correspondences -- and then their own finalize kernel.  NDT does not read the setting.
-// color: coloured ICP (mm3d_set_icp_color): point-to-plane's jobs, partials and finalize kernel, with icp_color.hip's
-// icp_color_step over NnColorJobs (the target's gradient records, the source's reference points) as the search + reduction
-// launch.  The jobs carry no rejection options (the setters exclude each other).
-enum class IcpKind { Point, Plane, Ndt, Color };
-static float bits_to_float(unsigned u) { float f; memcpy(&f, &u, 4); return f; }
-static void icp_batch(Context *c, IcpScoreJob *jobs, int n_jobs, bool run_icp, double max_corr_dist, int max_iterations, double eps,
-                      bool want_score, double score_max_distance, IcpKind kind)
+// Which ICP runs is the step's business (IcpStep, nn_core.hpp): everything here -- states, chunks, waits, the speculative
+// point-to-point score -- is shared by all of them.
+static void icp_batch(Context *c, IcpStep &step, IcpScoreJob *jobs, int n_jobs, bool run_icp, double max_corr_dist, int max_iterations,
+                      double eps, bool want_score, double score_max_distance)
 {
-  const bool color = kind == IcpKind::Color, plane = kind == IcpKind::Plane || color, ndt = kind == IcpKind::Ndt;
   static_assert(offsetof(IcpState, T) == 0, "the score kernel reads T at the head of the state");
   c->last_icp_iterations = 0;
   c->last_icp_converged = 0;
   // the ICP's and the score's search parameters
   const NnRange icp_range = nn_range_icp(max_corr_dist), score_range = nn_range_score(score_max_distance);
-  const double score_radius = score_range.radius;
-  const float max_d2 = icp_range.max_d2, rmax = icp_range.rmax;
-  const float s_max_d2 = score_range.max_d2, s_rmax = score_range.rmax;
+  const bool icp_grid = run_icp && step.searches;
 
-  struct Live { int job; const float4 *sp; int ns, n_items; const Grid *tg, *sg; int max_ring, s_ring; };
+  struct Live { NnSearch icp, score; };
   std::vector<Live> live;
+  std::vector<IcpScoreJob *> live_jobs;
   for (int j = 0; j < n_jobs; ++j) {
     IcpScoreJob &J = jobs[j];
     J.out.iterations = 0; J.out.converged = 0; J.out.n_corr = 0; J.out.score = DBL_MAX;
-    int ns = 0;
-    const float4 *sp = (J.src->n && J.tgt->n) ? morton_source(c, J.src, ns) : nullptr;
-    const Grid *tg = (ns && run_icp && !ndt) ? &cloud_grid(c, J.tgt, nn_cell_for(max_corr_dist)) : nullptr;
-    const bool ndt_icp = ns && run_icp && ndt;
-    const Grid *sg = (ns && want_score) ? &cloud_grid(c, J.tgt, nn_cell_for(score_radius)) : nullptr;
-    if (ns == 0 || (tg && tg->n == 0) || (sg && sg->n == 0) || (!tg && !sg && !ndt_icp)) {
+    const NnSearch si = nn_search(c, J.src, J.tgt, icp_grid ? &icp_range : nullptr);
+    const NnSearch ss = want_score ? nn_search(c, J.src, J.tgt, &score_range) : NnSearch();
+    if (!si.src || (icp_grid && !si.grid) || (want_score && !ss.grid) || (!run_icp && !want_score)) {
       // nothing to search: Identity * guess, and the score of an empty search
       if (J.guess_dev) {
         float *hT = (float *)c->pin(256);
@@ -367,88 +384,54 @@ static void icp_batch(Context *c, IcpScoreJob *jobs, int n_jobs, bool run_icp, d
       }
       continue;
     }
-    if (plane && tg && (!J.tgt_normals || J.tgt_normals->n != J.tgt->n))
-      throw Error(MM3D_EINVAL, "point-to-plane ICP: the target's normals do not match its points");
-    if (color && tg && !J.tgt_color) throw Error(MM3D_EINVAL, "coloured ICP: the target has no gradient records");
-    if (ndt_icp && !J.tgt_ndt) throw Error(MM3D_EINVAL, "NDT: the target has no voxel table");
-    Live L{j, sp, ns, J.src->n_wave_items, tg, sg, 0, 0};
-    L.max_ring = tg ? nn_max_ring(rmax, *tg) : 0;
-    if (tg) grid_ensure_dt(c, *tg, L.max_ring);
-    L.s_ring = sg ? nn_max_ring(s_rmax, *sg) : 0;
-    if (sg) grid_ensure_dt(c, *sg, L.s_ring);
-    live.push_back(L);
+    if (run_icp) step.check(J);
+    live.push_back(Live{si, ss});
+    live_jobs.push_back(&J);
   }
   const int B = (int)live.size();
   if (B == 0) return;
-  const mm3d_icp_rejection_options *rej = (run_icp && !ndt && !color) ? jobs[live[0].job].reject : nullptr;
-  const double color_lambda = jobs[live[0].job].color_lambda;
 
   // one work item per block while the whole batch has too few items to fill the chip with one wave each
   // (the finalize kernels add the partials up in one fixed order, so the choice never shows in a result)
   int total_items = 0;
-  for (const Live &L : live) total_items += L.n_items;
-  // (test hooks: mm3d_debug_icp_rejection_split, mm3d_debug_icp_color_split)
-  const int forced_split = rej ? icp_reject_forced_split() : (color && run_icp) ? icp_color_forced_split() : 0;
+  for (const Live &L : live) total_items += L.icp.n_items;
+  const int forced_split = run_icp ? step.forced_split : 0;
   const bool split = forced_split ? forced_split == 4 : nn_split_items(total_items);
-  size_t part_total = 0;
-  unsigned grid_x = 0;
+  // (a step that does not search keeps four items per block whatever the batch does)
+  const bool icp_split = split && step.searches;
+  size_t part_total = 0, icp_part_total = 0;
+  unsigned grid_x = 0, icp_grid_x = 0;
   double icp_bytes = 0.0, score_bytes = 0.0;
-  std::vector<unsigned> nb(B);
-  // (the ICP partials: kAcc per block, kPlaneAcc for point-to-plane; the score's stay kAcc)
-  const int icp_acc = plane ? kPlaneAcc : ndt ? kNdtAcc : kAcc;
-  size_t icp_part_total = 0;
-  unsigned ndt_grid_x = 0;
+  std::vector<unsigned> nb(B), icp_nb(B);
   for (int b = 0; b < B; ++b) {
-    nb[b] = split ? (unsigned)live[b].n_items : div_up(live[b].n_items, 4);
+    nb[b] = nn_blocks(live[b].icp.n_items, split);
+    icp_nb[b] = nn_blocks(live[b].icp.n_items, icp_split);
     part_total += (size_t)nb[b] * kAcc;
-    const unsigned icp_nb = ndt ? div_up(live[b].n_items, 4) : nb[b];
-    icp_part_total += (size_t)icp_nb * icp_acc;
+    icp_part_total += (size_t)icp_nb[b] * step.acc;
     grid_x = std::max(grid_x, nb[b]);
-    ndt_grid_x = std::max(ndt_grid_x, icp_nb);
-    icp_bytes += live[b].ns * (color ? 60.0 : plane ? 28.0 : ndt ? 16.0 + 52.0 * jobs[live[b].job].ndt_neighbours : 12.0);   // (point-to-plane: + the winner's normal; coloured: + its record and the source's reference point; NDT: the point, and an index word and a record per voxel)
-    score_bytes += live[b].ns * 12.0 + (live[b].sg ? live[b].sg->n * 12.0 : 0.0);
+    icp_grid_x = std::max(icp_grid_x, icp_nb[b]);
+    icp_bytes += live[b].icp.ns * step.bytes_per_point(*live_jobs[b]);
+    score_bytes += live[b].icp.ns * 12.0 + (live[b].score.grid ? live[b].score.grid->n * 12.0 : 0.0);
   }
   DevBuf<double> partials(c, icp_part_total), s_partials(c, want_score ? part_total : 1);
   DevBuf<double> out(c, (size_t)2 * B);
-  // (rejection: the pairs' records live behind the states, so that one copy brings both back)
-  const size_t rec_bytes = rej ? sizeof(RejRecord) * B : 0;
+  // (what a step keeps per pair beside the state lives behind the states, so that one copy brings both back)
+  const size_t rec_bytes = step.record_bytes(B);
   DevBuf<IcpState> st(c, B + div_up(rec_bytes, sizeof(IcpState)));
-  RejRecord *d_rec = (RejRecord *)(st.get() + B);
-  size_t rej_src = 0, rej_tgt = 0;
-  unsigned rej_max_src = 0;
-  if (rej)
-    for (const Live &L : live) {
-      rej_src += (size_t)L.ns;
-      rej_tgt += rej->one_to_one ? jobs[L.job].tgt->n : 0;
-      rej_max_src = std::max(rej_max_src, (unsigned)L.ns);
-    }
-  DevBuf<NnRejectJob> d_rjobs(c, rej ? (size_t)B : 1);
-  DevBuf<int2> rej_corr(c, rej ? rej_src : 1);
-  DevBuf<unsigned long long> rej_owner(c, rej_tgt ? rej_tgt : 1);
-  DevBuf<unsigned> rej_hist(c, rej ? (size_t)B * 1024 : 1);
   DevBuf<NnJob> d_jobs(c, (size_t)2 * B);                 // [0, B): ICP, [B, 2B): score
-  DevBuf<NnPlaneJob> d_pjobs(c, plane ? (size_t)B : 1);   // point-to-plane: the ICP jobs with their normals
-  DevBuf<NdtJob> d_njobs(c, ndt ? (size_t)B : 1);         // NDT: the ICP jobs with their voxel tables
-  DevBuf<NnColorJob> d_cjobs(c, color ? (size_t)B : 1);   // coloured: the point-to-plane jobs with the records and the source's reference points
 
-  // host images, in the pinned arena: states | ICP jobs | score jobs | scores back | point-to-plane jobs | NDT jobs | rejecting jobs | coloured jobs
+  // host images, in the pinned arena: states | the step's records | ICP jobs | score jobs | scores back | the step's jobs.
+  // ONE request: a later pin() may replace the arena under the pointers of an earlier one.
   const size_t st_bytes = sizeof(IcpState) * B, job_bytes = sizeof(NnJob) * 2 * B, out_bytes = 16 * (size_t)B;
-  const size_t pjob_bytes = plane ? sizeof(NnPlaneJob) * B : 0, njob_bytes = ndt ? sizeof(NdtJob) * B : 0;
-  const size_t rjob_bytes = rej ? sizeof(NnRejectJob) * B : 0, st_rec_bytes = st_bytes + rec_bytes;
-  const size_t cjob_bytes = color ? sizeof(NnColorJob) * B : 0;
-  char *pinned = (char *)c->pin(st_rec_bytes + job_bytes + out_bytes + pjob_bytes + njob_bytes + rjob_bytes + cjob_bytes + 64);
+  const size_t st_rec_bytes = st_bytes + rec_bytes;
+  char *pinned = (char *)c->pin(st_rec_bytes + job_bytes + out_bytes + step.pinned_bytes(B) + 64);
   IcpState *hp = (IcpState *)pinned;
-  RejRecord *hr = (RejRecord *)(pinned + st_bytes);
   NnJob *hj = (NnJob *)(pinned + ((st_rec_bytes + 15) & ~(size_t)15));
   double *ho = (double *)((char *)hj + job_bytes);
-  NnPlaneJob *hpj = (NnPlaneJob *)((char *)ho + out_bytes);
-  NdtJob *hnj = (NdtJob *)((char *)hpj + pjob_bytes);
-  NnRejectJob *hrj = (NnRejectJob *)((char *)hnj + njob_bytes);
-  NnColorJob *hcj = (NnColorJob *)((char *)hrj + rjob_bytes);
-  size_t off = 0, icp_off = 0, rej_src_off = 0, rej_tgt_off = 0;
+  step.begin(c, live_jobs.data(), B, (char *)ho + out_bytes, pinned + st_bytes, st.get() + B);
+  size_t off = 0, icp_off = 0;
   for (int b = 0; b < B; ++b) {
-    const Live &L = live[b];
-    const IcpScoreJob &J = jobs[L.job];
+    const IcpScoreJob &J = *live_jobs[b];
     IcpState h;
     memset(&h, 0, sizeof(h));
     if (!J.guess_dev) memcpy(h.T, J.guess_host, sizeof(h.T));
@@ -458,80 +441,18 @@ static void icp_batch(Context *c, IcpScoreJob *jobs, int n_jobs, bool run_icp, d
     h.max_iter = max_iterations;
     h.done = run_icp ? 0 : 1;
     hp[b] = h;
-    NnJob q;
-    memset(&q, 0, sizeof(q));
-    q.src = L.sp;
-    q.items = (const int2 *)J.src->wave_items.get();
-    q.n_items = L.n_items;
-    q.nblocks = (int)nb[b];
-    q.split = split ? 1 : 0;
-    q.tgt_ref = (const float4 *)J.tgt->pts.get();
-    q.st = st.get() + b;
-    q.Tc = nullptr;
-    q.out = out.get() + 2 * b;
-    if (L.tg) { q.g = L.tg->view(); q.max_ring = L.max_ring; }
-    q.partials = partials.get() + icp_off;
-    hj[b] = q;
-    if (plane) {
-      hpj[b].nn = q;
-      hpj[b].nrm = L.tg ? (const float4 *)J.tgt_normals->nrm.get() : nullptr;
-    }
-    if (color) {
-      hcj[b].pl = hpj[b];
-      hcj[b].rec = L.tg ? J.tgt_color : nullptr;
-      hcj[b].src_ref = (const float4 *)J.src->pts.get();
-    }
-    if (rej) {
-      NnRejectJob rj;
-      memset(&rj, 0, sizeof(rj));
-      rj.nn = q;
-      rj.nrm = (plane && L.tg) ? (const float4 *)J.tgt_normals->nrm.get() : nullptr;
-      rj.corr = rej_corr.get() + rej_src_off;
-      rj.owner = rej->one_to_one ? rej_owner.get() + rej_tgt_off : nullptr;
-      rj.hist = rej_hist.get() + (size_t)b * 1024;
-      rj.rec = d_rec + b;
-      rj.n_src = L.ns;
-      hrj[b] = rj;
-      memset(&hr[b], 0, sizeof(RejRecord));
-      hr[b].cut = 1;
-      rej_src_off += (size_t)L.ns;
-      rej_tgt_off += rej->one_to_one ? J.tgt->n : 0;
-    }
-    if (ndt) {
-      NdtJob nj;
-      memset(&nj, 0, sizeof(nj));
-      nj.nn = q;
-      nj.nn.split = 0;
-      nj.nn.nblocks = (int)div_up(L.n_items, 4);
-      if (const NdtTable *t = run_icp ? J.tgt_ndt : nullptr) {
-        nj.rec = (const float4 *)t->rec.get();
-        nj.index = (const int *)t->index.get();
-        nj.inv = t->inv;
-        for (int a = 0; a < 3; ++a) { nj.mn[a] = t->mn[a]; nj.dims[a] = t->dims[a]; }
-      }
-      nj.neighbours = J.ndt_neighbours;
-      nj.n_src = L.ns;
-      hnj[b] = nj;
-    }
-    if (L.sg) { q.g = L.sg->view(); q.max_ring = L.s_ring; }
-    q.partials = s_partials.get() + (want_score ? off : 0);
-    hj[B + b] = q;
+    hj[b] = nn_job(live[b].icp, icp_split, icp_nb[b], st.get() + b, nullptr, partials.get() + icp_off, out.get() + 2 * b);
+    step.bind(b, hj[b], J);
+    hj[B + b] = nn_job(live[b].score, split, nb[b], st.get() + b, nullptr, s_partials.get() + (want_score ? off : 0), out.get() + 2 * b);
     off += (size_t)nb[b] * kAcc;
-    icp_off += (size_t)(ndt ? div_up(L.n_items, 4) : nb[b]) * icp_acc;
+    icp_off += (size_t)icp_nb[b] * step.acc;
   }
   MM3D_HIP(hipMemcpyAsync(st.get(), hp, st_rec_bytes, hipMemcpyHostToDevice, c->stream));
   MM3D_HIP(hipMemcpyAsync(d_jobs.get(), hj, job_bytes, hipMemcpyHostToDevice, c->stream));
-  if (rej) {
-    MM3D_HIP(hipMemcpyAsync(d_rjobs.get(), hrj, rjob_bytes, hipMemcpyHostToDevice, c->stream));
-    // (a place of the Hilbert-ordered source that no work item covers holds "no match" for good)
-    MM3D_HIP(hipMemsetAsync(rej_corr.get(), 0xff, rej_src * sizeof(int2), c->stream));
-  }
-  if (plane) MM3D_HIP(hipMemcpyAsync(d_pjobs.get(), hpj, pjob_bytes, hipMemcpyHostToDevice, c->stream));
-  if (ndt) MM3D_HIP(hipMemcpyAsync(d_njobs.get(), hnj, njob_bytes, hipMemcpyHostToDevice, c->stream));
-  if (color) MM3D_HIP(hipMemcpyAsync(d_cjobs.get(), hcj, cjob_bytes, hipMemcpyHostToDevice, c->stream));
+  step.upload(c);
   for (int b = 0; b < B; ++b)
-    if (jobs[live[b].job].guess_dev)
-      MM3D_HIP(hipMemcpyAsync(st.get() + b, jobs[live[b].job].guess_dev, 64, hipMemcpyDeviceToDevice, c->stream));
+    if (live_jobs[b]->guess_dev)
+      MM3D_HIP(hipMemcpyAsync(st.get() + b, live_jobs[b]->guess_dev, 64, hipMemcpyDeviceToDevice, c->stream));
   // iterations launched between two looks at the `done` flags: with the reference's loose epsilon 86 % of the pairs
   // converge in one iteration and 95 % in two.  A launch after `done` does nothing, but it is not free on a GPU
   // that runs sixteen streams: its blocks still queue for 20 KB of LDS and 128 registers behind the other streams'
@@ -539,36 +460,13 @@ static void icp_batch(Context *c, IcpScoreJob *jobs, int n_jobs, bool run_icp, d
   // pairs is then usually finished), later ones after two.
   static const int first_chunk_knob = [] { const char *e = getenv("MM3D_ICP_FIRST_CHUNK"); return e ? atoi(e) : 0; }();   // A/B knob (1 or 2; 0: by batch size)
   const int min_chunk = first_chunk_knob > 0 ? std::min(first_chunk_knob, 2) : (B <= 2 ? 1 : 2);
+  const IcpLaunch launch{d_jobs.get(), B, icp_grid_x, icp_split, icp_range.max_d2, icp_range.rmax, icp_bytes, icp_part_total * 8.0};
   for (int round = 0;; ++round) {
     const int chunk = round == 0 ? min_chunk : 2;
-    if (run_icp) {
-      for (int k = 0; k < chunk; ++k) {
-        if (rej) {
-          icp_reject_step(c, d_rjobs.get(), B, grid_x, rej_max_src, split, plane, max_d2, rmax, *rej, rej_owner.get(),
-                          rej_tgt * sizeof(unsigned long long), icp_bytes + rej_src * 8.0);
-          if (plane) icp_plane_finalize(c, d_pjobs.get(), B, icp_part_total * 8.0);
-          else MM3D_LAUNCH(c, "icp_finalize", part_total * 8.0, k_icp_finalize, dim3(B), dim3(256), 0, (const NnJob *)d_jobs.get());
-          continue;
-        }
-        if (color) {
-          icp_color_step(c, d_cjobs.get(), B, grid_x, split, max_d2, rmax, color_lambda, icp_bytes);
-          icp_plane_finalize(c, d_pjobs.get(), B, icp_part_total * 8.0);
-          continue;
-        }
-        if (plane) {
-          icp_plane_step(c, d_pjobs.get(), B, grid_x, split, max_d2, rmax, icp_bytes, icp_part_total * 8.0);
-          continue;
-        }
-        if (ndt) {
-          ndt_step(c, d_njobs.get(), B, ndt_grid_x, icp_bytes, icp_part_total * 8.0);
-          continue;
-        }
-        launch_nn<0>(c, "icp_corr_reduce", icp_bytes, d_jobs.get(), B, grid_x, split, max_d2, rmax);
-        MM3D_LAUNCH(c, "icp_finalize", part_total * 8.0, k_icp_finalize, dim3(B), dim3(256), 0, (const NnJob *)d_jobs.get());
-      }
-    }
+    if (run_icp)
+      for (int k = 0; k < chunk; ++k) step.iterate(c, launch);
     if (want_score) {
-      launch_nn<1>(c, "score_nn_reduce", score_bytes, d_jobs.get() + B, B, grid_x, split, s_max_d2, s_rmax);
+      launch_nn<1>(c, "score_nn_reduce", score_bytes, d_jobs.get() + B, B, grid_x, split, score_range.max_d2, score_range.rmax);
       MM3D_LAUNCH(c, "score_finalize", 0, k_score_finalize, dim3(B), dim3(256), 0, (const NnJob *)(d_jobs.get() + B));
       MM3D_HIP(hipMemcpyAsync(ho, out.get(), out_bytes, hipMemcpyDeviceToHost, c->stream));
     }
@@ -576,7 +474,7 @@ static void icp_batch(Context *c, IcpScoreJob *jobs, int n_jobs, bool run_icp, d
     c->sync();
     bool all_done = true;
     for (int b = 0; b < B; ++b) {
-      IcpScoreJob &J = jobs[live[b].job];
+      IcpScoreJob &J = *live_jobs[b];
       if (hp[b].done && !J.closed) {
         // first chunk after which this pair is finished: its state and score are final
         memcpy(J.out.T, hp[b].T, sizeof(J.out.T));
@@ -584,48 +482,28 @@ static void icp_batch(Context *c, IcpScoreJob *jobs, int n_jobs, bool run_icp, d
         J.out.converged = hp[b].converged;
         J.out.n_corr = hp[b].n_corr;
         if (want_score) J.out.score = ho[2 * b + 1] > 0.0 ? ho[2 * b] / ho[2 * b + 1] : DBL_MAX;
-        if (rej) {
-          const RejRecord &r = hr[b];
-          J.reject_stats.matched = r.matched;
-          J.reject_stats.after_one_to_one = rej->one_to_one ? r.survivors : r.matched;
-          J.reject_stats.kept = r.kept;
-          J.reject_stats.threshold_d2 = r.cut == 0 ? bits_to_float(r.tau_bits) : r.cut == 1 ? INFINITY : -1.0f;
-          J.reject_stats.iterations = hp[b].iters;
-          J.reject_stats.converged = hp[b].converged;
-        }
+        step.close(b, hp[b], J);
         J.closed = true;
       }
       if (!hp[b].done) all_done = false;
     }
     if (all_done) break;
   }
-  const IcpScoreJob &last = jobs[live[B - 1].job];
+  const IcpScoreJob &last = *live_jobs[B - 1];
   c->last_icp_iterations = last.out.iterations;
   c->last_icp_converged = last.out.converged;
 }
 
-void icp_score_batch(Context *c, IcpScoreJob *jobs, int n_jobs, bool run_icp, double max_corr_dist, int max_iterations, double eps,
-                     bool want_score, double score_max_distance)
+// Where the step is chosen: the method's (null: the reference's point-to-point ICP), and a method that can reject correspondences
+// makes the rejecting step when the jobs carry options (IcpScoreJob::reject, the same for the whole batch) and the ICP runs.
+void icp_score_batch(Context *c, const IcpMethodBase *method, IcpScoreJob *jobs, int n_jobs, bool run_icp, double max_corr_dist,
+                     int max_iterations, double eps, bool want_score, double score_max_distance)
 {
-  icp_batch(c, jobs, n_jobs, run_icp, max_corr_dist, max_iterations, eps, want_score, score_max_distance, IcpKind::Point);
-}
-
-void icp_plane_score_batch(Context *c, IcpScoreJob *jobs, int n_jobs, bool run_icp, double max_corr_dist, int max_iterations, double eps,
-                           bool want_score, double score_max_distance)
-{
-  icp_batch(c, jobs, n_jobs, run_icp, max_corr_dist, max_iterations, eps, want_score, score_max_distance, IcpKind::Plane);
-}
-
-void icp_color_score_batch(Context *c, IcpScoreJob *jobs, int n_jobs, bool run_icp, double max_corr_dist, int max_iterations, double eps,
-                           bool want_score, double score_max_distance)
-{
-  icp_batch(c, jobs, n_jobs, run_icp, max_corr_dist, max_iterations, eps, want_score, score_max_distance, IcpKind::Color);
-}
-
-void ndt_score_batch(Context *c, IcpScoreJob *jobs, int n_jobs, bool run_icp, double max_corr_dist, int max_iterations, double eps,
-                     bool want_score, double score_max_distance)
-{
-  icp_batch(c, jobs, n_jobs, run_icp, max_corr_dist, max_iterations, eps, want_score, score_max_distance, IcpKind::Ndt);
+  const mm3d_icp_rejection_options *reject = (run_icp && n_jobs) ? jobs[0].reject : nullptr;
+  const std::unique_ptr<IcpStep> step = method ? method->step(reject)
+                                        : reject ? icp_reject_step(*reject, false)
+                                                 : std::unique_ptr<IcpStep>(new PointStep());
+  icp_batch(c, *step, jobs, n_jobs, run_icp, max_corr_dist, max_iterations, eps, want_score, score_max_distance);
 }
 
 PairTail icp_score(Context *c, const mm3d_cloud *src, const mm3d_cloud *tgt, const float *guess_dev, const float guess_host[16],
@@ -634,7 +512,7 @@ PairTail icp_score(Context *c, const mm3d_cloud *src, const mm3d_cloud *tgt, con
   IcpScoreJob J;
   J.src = src; J.tgt = tgt; J.guess_dev = guess_dev;
   if (guess_host) memcpy(J.guess_host, guess_host, sizeof(J.guess_host));
-  icp_score_batch(c, &J, 1, run_icp, max_corr_dist, max_iterations, eps, want_score, score_max_distance);
+  icp_score_batch(c, nullptr, &J, 1, run_icp, max_corr_dist, max_iterations, eps, want_score, score_max_distance);
   return J.out;
 }
 
@@ -651,18 +529,11 @@ IcpResult icp(Context *c, const mm3d_cloud *src, const mm3d_cloud *tgt, const fl
 
 double transform_score(Context *c, const mm3d_cloud *src, const mm3d_cloud *tgt, const float T[16], double max_distance)
 {
-  if (src->n == 0 || tgt->n == 0) return DBL_MAX;
   const NnRange range = nn_range_score(max_distance);
-  const Grid &tg = cloud_grid(c, tgt, nn_cell_for(range.radius));
-  int ns = 0;
-  const float4 *sp = morton_source(c, src, ns);
-  if (ns == 0 || tg.n == 0) return DBL_MAX;
-  const float max_d2 = range.max_d2, rmax = range.rmax;
-  const int max_ring = nn_max_ring(rmax, tg);
-  grid_ensure_dt(c, tg, max_ring);
-  const int n_items = src->n_wave_items;
-  const bool split = nn_split_items(n_items);
-  const unsigned nblocks = split ? (unsigned)n_items : div_up(n_items, 4);
+  const NnSearch s = nn_search(c, src, tgt, &range);
+  if (!s.grid) return DBL_MAX;
+  const bool split = nn_split_items(s.n_items);
+  const unsigned nblocks = nn_blocks(s.n_items, split);
   DevBuf<double> partials(c, (size_t)nblocks * kAcc);
   DevBuf<float> dT(c, 16);
   DevBuf<double> out(c, 2);
@@ -672,31 +543,18 @@ double transform_score(Context *c, const mm3d_cloud *src, const mm3d_cloud *tgt,
   double *ho = (double *)(pinned + 128);
   NnJob *hj = (NnJob *)(pinned + 256);
   memcpy(hT, T, 64);
-  NnJob q;
-  memset(&q, 0, sizeof(q));
-  q.src = sp;
-  q.items = (const int2 *)src->wave_items.get();
-  q.n_items = n_items;
-  q.nblocks = (int)nblocks;
-  q.split = split ? 1 : 0;
-  q.g = tg.view();
-  q.tgt_ref = (const float4 *)tgt->pts.get();
-  q.Tc = dT.get();
-  q.partials = partials.get();
-  q.out = out.get();
-  q.max_ring = max_ring;
-  *hj = q;
+  *hj = nn_job(s, split, nblocks, nullptr, dT.get(), partials.get(), out.get());
   MM3D_HIP(hipMemcpyAsync(dT.get(), hT, 64, hipMemcpyHostToDevice, c->stream));
   MM3D_HIP(hipMemcpyAsync(d_job.get(), hj, sizeof(NnJob), hipMemcpyHostToDevice, c->stream));
-  launch_nn<1>(c, "score_nn_reduce", ns * 12.0 + tg.n * 12.0, d_job.get(), 1, nblocks, split, max_d2, rmax);
+  launch_nn<1>(c, "score_nn_reduce", s.ns * 12.0 + s.grid->n * 12.0, d_job.get(), 1, nblocks, split, range.max_d2, range.rmax);
   MM3D_LAUNCH(c, "score_finalize", 0, k_score_finalize, dim3(1), dim3(256), 0, (const NnJob *)d_job.get());
   MM3D_HIP(hipMemcpyAsync(ho, out.get(), 16, hipMemcpyDeviceToHost, c->stream));
   c->sync();
   return ho[1] > 0.0 ? ho[0] / ho[1] : DBL_MAX;
 }
 
-// mm3d_debug_nn_search: range, cell, ring and distance transform as icp_batch (convention 0) or transform_score (1) derive
-// them, the source in its Hilbert order and work items as every search takes it, one launch of k_nn_probe with the split forced
+// mm3d_debug_nn_search: the search set-up as icp_batch (convention 0) or transform_score (1) derive it, one launch of
+// k_nn_probe with the split forced
 static void debug_nn_search(Context *c, const mm3d_cloud *src, const mm3d_cloud *tgt, const float T[16], double range, int convention,
                             int split, int *idx, float *d2, mm3d_nn_search_info *info)
 {
@@ -707,18 +565,13 @@ static void debug_nn_search(Context *c, const mm3d_cloud *src, const mm3d_cloud 
   I.rmax = r.rmax;
   std::vector<int> h_idx(src->n, -1);
   std::vector<float> h_d2(src->n, INFINITY);
-  int ns = 0;
-  const float4 *sp = (src->n && tgt->n) ? morton_source(c, src, ns) : nullptr;
-  const Grid *tg = ns ? &cloud_grid(c, tgt, nn_cell_for(r.radius)) : nullptr;
-  if (tg && tg->n) {
-    const int max_ring = nn_max_ring(r.rmax, *tg);
-    grid_ensure_dt(c, *tg, max_ring);
-    const int n_items = src->n_wave_items;
-    const unsigned nblocks = split == 4 ? (unsigned)n_items : div_up(n_items, 4);
-    I.cell = tg->cell;
-    I.max_ring = max_ring;
-    for (int a = 0; a < 3; ++a) { I.dims[a] = tg->dims[a]; I.origin[a] = tg->mn[a]; }
-    I.n_items = n_items;
+  const NnSearch s = nn_search(c, src, tgt, &r);
+  if (s.grid) {
+    const unsigned nblocks = nn_blocks(s.n_items, split == 4);
+    I.cell = s.grid->cell;
+    I.max_ring = s.max_ring;
+    for (int a = 0; a < 3; ++a) { I.dims[a] = s.grid->dims[a]; I.origin[a] = s.grid->mn[a]; }
+    I.n_items = s.n_items;
     DevBuf<int> d_idx(c, src->n);
     DevBuf<float> d_d2(c, src->n), dT(c, 16);
     DevBuf<NnJob> d_job(c, 1);
@@ -726,28 +579,17 @@ static void debug_nn_search(Context *c, const mm3d_cloud *src, const mm3d_cloud 
     float *hT = (float *)pinned;
     NnJob *hj = (NnJob *)(pinned + 256);
     memcpy(hT, T, 64);
-    NnJob q;
-    memset(&q, 0, sizeof(q));
-    q.src = sp;
-    q.items = (const int2 *)src->wave_items.get();
-    q.n_items = n_items;
-    q.nblocks = (int)nblocks;
-    q.split = split == 4 ? 1 : 0;
-    q.g = tg->view();
-    q.tgt_ref = (const float4 *)tgt->pts.get();
-    q.Tc = dT.get();
-    q.max_ring = max_ring;
-    *hj = q;
+    *hj = nn_job(s, split == 4, nblocks, nullptr, dT.get(), nullptr, nullptr);
     // (non-finite source points are in no work item: they keep -1 / +inf)
     MM3D_HIP(hipMemcpyAsync(d_idx.get(), h_idx.data(), src->n * sizeof(int), hipMemcpyHostToDevice, c->stream));
     MM3D_HIP(hipMemcpyAsync(d_d2.get(), h_d2.data(), src->n * sizeof(float), hipMemcpyHostToDevice, c->stream));
     MM3D_HIP(hipMemcpyAsync(dT.get(), hT, 64, hipMemcpyHostToDevice, c->stream));
     MM3D_HIP(hipMemcpyAsync(d_job.get(), hj, sizeof(NnJob), hipMemcpyHostToDevice, c->stream));
     if (split == 4)
-      MM3D_LAUNCH(c, "debug_nn_search", ns * 24.0, (k_nn_probe<4>), dim3(nblocks), dim3(256), 0, (const NnJob *)d_job.get(), r.max_d2, r.rmax,
+      MM3D_LAUNCH(c, "debug_nn_search", s.ns * 24.0, (k_nn_probe<4>), dim3(nblocks), dim3(256), 0, (const NnJob *)d_job.get(), r.max_d2, r.rmax,
                   d_idx.get(), d_d2.get());
     else
-      MM3D_LAUNCH(c, "debug_nn_search", ns * 24.0, (k_nn_probe<1>), dim3(nblocks), dim3(256), 0, (const NnJob *)d_job.get(), r.max_d2, r.rmax,
+      MM3D_LAUNCH(c, "debug_nn_search", s.ns * 24.0, (k_nn_probe<1>), dim3(nblocks), dim3(256), 0, (const NnJob *)d_job.get(), r.max_d2, r.rmax,
                   d_idx.get(), d_d2.get());
     MM3D_HIP(hipMemcpyAsync(h_idx.data(), d_idx.get(), src->n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
     MM3D_HIP(hipMemcpyAsync(h_d2.data(), d_d2.get(), src->n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
@@ -758,85 +600,6 @@ static void debug_nn_search(Context *c, const mm3d_cloud *src, const mm3d_cloud 
     memcpy(d2, h_d2.data(), src->n * sizeof(float));
   }
   if (info) *info = I;
-}
-
-// mm3d_debug_icp_rejection: range, cell, ring, distance transform, source order and work items as icp_batch derives them, one
-// iteration's correspondence stage (icp_reject.hip) at T with the split forced, and every source point's decision
-static void debug_icp_rejection(Context *c, const mm3d_cloud *src, const mm3d_cloud *tgt, const float T[16], double max_corr_dist,
-                                const mm3d_icp_rejection_options &opt, int split, int *idx, float *d2, unsigned char *kept,
-                                mm3d_icp_rejection_stats *stats)
-{
-  const NnRange r = nn_range_icp(max_corr_dist);
-  mm3d_icp_rejection_stats S{0, 0, 0, INFINITY, 0, 0};
-  std::vector<int> h_idx(src->n, -1);
-  std::vector<float> h_d2(src->n, INFINITY);
-  std::vector<unsigned char> h_kept(src->n, 0);
-  int ns = 0;
-  const float4 *sp = (src->n && tgt->n) ? morton_source(c, src, ns) : nullptr;
-  const Grid *tg = ns ? &cloud_grid(c, tgt, nn_cell_for(r.radius)) : nullptr;
-  if (tg && tg->n) {
-    const int max_ring = nn_max_ring(r.rmax, *tg);
-    grid_ensure_dt(c, *tg, max_ring);
-    const int n_items = src->n_wave_items;
-    const unsigned nblocks = split == 4 ? (unsigned)n_items : div_up(n_items, 4);
-    DevBuf<int> d_idx(c, src->n);
-    DevBuf<float> d_d2(c, src->n);
-    DevBuf<unsigned char> d_kept(c, src->n);
-    DevBuf<IcpState> st(c, 2);                       // the state, and the record behind it
-    RejRecord *d_rec = (RejRecord *)(st.get() + 1);
-    DevBuf<NnRejectJob> d_job(c, 1);
-    DevBuf<int2> corr(c, (size_t)ns);
-    DevBuf<unsigned long long> owner(c, opt.one_to_one ? tgt->n : 1);
-    DevBuf<unsigned> hist(c, 1024);
-    char *pinned = (char *)c->pin(2 * sizeof(IcpState) + sizeof(NnRejectJob) + 64);
-    IcpState *hs = (IcpState *)pinned;
-    RejRecord *hr = (RejRecord *)(hs + 1);
-    NnRejectJob *hj = (NnRejectJob *)(pinned + 2 * sizeof(IcpState));
-    memset(hs, 0, 2 * sizeof(IcpState));
-    memcpy(hs->T, T, 64);
-    hr->cut = 1;
-    NnRejectJob q;
-    memset(&q, 0, sizeof(q));
-    q.nn.src = sp;
-    q.nn.items = (const int2 *)src->wave_items.get();
-    q.nn.n_items = n_items;
-    q.nn.nblocks = (int)nblocks;
-    q.nn.split = split == 4 ? 1 : 0;
-    q.nn.g = tg->view();
-    q.nn.tgt_ref = (const float4 *)tgt->pts.get();
-    q.nn.st = st.get();
-    q.nn.max_ring = max_ring;
-    q.corr = corr.get();
-    q.owner = opt.one_to_one ? owner.get() : nullptr;
-    q.hist = hist.get();
-    q.rec = d_rec;
-    q.n_src = ns;
-    *hj = q;
-    // (non-finite source points are in no work item: they keep -1 / +inf / 0)
-    MM3D_HIP(hipMemcpyAsync(d_idx.get(), h_idx.data(), src->n * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    MM3D_HIP(hipMemcpyAsync(d_d2.get(), h_d2.data(), src->n * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    MM3D_HIP(hipMemsetAsync(d_kept.get(), 0, src->n, c->stream));
-    MM3D_HIP(hipMemsetAsync(corr.get(), 0xff, (size_t)ns * sizeof(int2), c->stream));
-    MM3D_HIP(hipMemcpyAsync(st.get(), hs, 2 * sizeof(IcpState), hipMemcpyHostToDevice, c->stream));
-    MM3D_HIP(hipMemcpyAsync(d_job.get(), hj, sizeof(NnRejectJob), hipMemcpyHostToDevice, c->stream));
-    icp_reject_debug(c, d_job.get(), nblocks, (unsigned)ns, n_items, split == 4, r.max_d2, r.rmax, opt, owner.get(),
-                     opt.one_to_one ? tgt->n * sizeof(unsigned long long) : 0, d_idx.get(), d_d2.get(), d_kept.get());
-    MM3D_HIP(hipMemcpyAsync(h_idx.data(), d_idx.get(), src->n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    MM3D_HIP(hipMemcpyAsync(h_d2.data(), d_d2.get(), src->n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    MM3D_HIP(hipMemcpyAsync(h_kept.data(), d_kept.get(), src->n, hipMemcpyDeviceToHost, c->stream));
-    MM3D_HIP(hipMemcpyAsync(hs, st.get(), 2 * sizeof(IcpState), hipMemcpyDeviceToHost, c->stream));
-    c->sync();
-    S.matched = hr->matched;
-    S.after_one_to_one = opt.one_to_one ? hr->survivors : hr->matched;
-    S.kept = hr->kept;
-    S.threshold_d2 = hr->cut == 0 ? bits_to_float(hr->tau_bits) : hr->cut == 1 ? INFINITY : -1.0f;
-  }
-  if (src->n) {
-    memcpy(idx, h_idx.data(), src->n * sizeof(int));
-    memcpy(d2, h_d2.data(), src->n * sizeof(float));
-    memcpy(kept, h_kept.data(), src->n);
-  }
-  if (stats) *stats = S;
 }
 
 #ifdef MM3D_NN_STATS
@@ -852,15 +615,8 @@ extern "C" void mm3d_debug_nn_stats(unsigned long long *out, int reset)
 // estimates only READ the clouds' caches, so one map can serve pairs on several contexts at once.
 void prepare_pair_search(Context *c, const mm3d_cloud *points, double max_corr_dist, double score_max_distance)
 {
-  if (points->n == 0) return;
-  int ns = 0;
-  (void)morton_source(c, points, ns);
   const NnRange ranges[2] = {nn_range_icp(max_corr_dist), nn_range_score(score_max_distance)};
-  for (const NnRange &range : ranges) {
-    const Grid &g = cloud_grid(c, points, nn_cell_for(range.radius));
-    if (g.n == 0) continue;
-    grid_ensure_dt(c, g, nn_max_ring(range.rmax, g));
-  }
+  for (const NnRange &range : ranges) (void)nn_search(c, points, points, &range);
 }
 
 }  // namespace mm3d
@@ -874,16 +630,4 @@ extern "C" int mm3d_debug_nn_search(mm3d_ctx *ctx, const mm3d_cloud *source, con
   if (!(range >= 0.0) || !std::isfinite(range)) return MM3D_EINVAL;
   if (source->n && (!idx || !d2)) return MM3D_EINVAL;
   return mm3d::guarded(ctx, [&] { mm3d::debug_nn_search(ctx, source, target, T, range, convention, split, idx, d2, info); });
-}
-
-extern "C" int mm3d_debug_icp_rejection(mm3d_ctx *ctx, const mm3d_cloud *source, const mm3d_cloud *target, const float T[16],
-                                        double max_correspondence_distance, const mm3d_icp_rejection_options *options, int split, int *idx,
-                                        float *d2, unsigned char *kept, mm3d_icp_rejection_stats *stats)
-{
-  if (!source || !target || !T || !options || !mm3d::icp_rejection_options_valid(options) || (split != 1 && split != 4)) return MM3D_EINVAL;
-  if (!(max_correspondence_distance >= 0.0) || !std::isfinite(max_correspondence_distance)) return MM3D_EINVAL;
-  if (source->n && (!idx || !d2 || !kept)) return MM3D_EINVAL;
-  return mm3d::guarded(ctx, [&] {
-    mm3d::debug_icp_rejection(ctx, source, target, T, max_correspondence_distance, *options, split, idx, d2, kept, stats);
-  });
 }

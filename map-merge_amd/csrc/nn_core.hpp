@@ -1,5 +1,7 @@
-// nn_core.hpp -- what the ICP / score kernels of nn.hip (k_nn_wave) and the point-to-plane ICP kernel of icp_plane.hip
-// (k_icp_plane_wave) share: the search knobs, the ICP state, the job layout and the wave helpers.  The search itself is
+// nn_core.hpp -- what the ICP / score tail of a pair estimate is made of, shared by nn.hip (the batch driver, the point-to-point
+// ICP and the score) and the files that put another ICP in its place (icp_plane.hip, icp_color.hip, icp_reject.hip, ndt.hip):
+// the search knobs, the ICP state, the job layout and the wave helpers of the kernels; and, for the host, the set-up of one
+// search (NnSearch) and the interface through which a variant takes part in a batch (IcpStep).  The search itself is
 // nn_search_body.hpp (see there).
 #pragma once
 #include <cfloat>
@@ -115,85 +117,100 @@ __device__ __forceinline__ double nn_block_partial_n(const double *__restrict__ 
   return v;
 }
 
-// point-to-plane ICP (icp_plane.hip): the search job plus the target's normals, in the target's reference order (tgt_ref's)
+// What a search derives from its range: the largest squared distance that is still a correspondence, the radius the
+// search has to prove (with the slack that covers its own rounding) and the radius the target's grid is built for.
+struct NnRange { float max_d2, rmax; double radius; };
+NnRange nn_range_icp(double max_corr_dist);
+NnRange nn_range_score(double max_distance);
+// one work item per block (the kernels' SPLIT 4) for a source of so few items, and the blocks a job then takes
+bool nn_split_items(int n_items);
+inline unsigned nn_blocks(int n_items, bool split) { return split ? (unsigned)n_items : div_up(n_items, 4); }
+
+// What a search of `src` in `tgt` needs on the host.  src is null when there is nothing to search (an empty cloud, no finite
+// source point); grid is null then, when the target has no finite point, and when no range was given (NDT reads no grid).
+struct NnSearch {
+  const float4 *src = nullptr;      // the source in Hilbert order,
+  const int2 *items = nullptr;      // its work items,
+  int ns = 0, n_items = 0;          // its finite points and how many items they make
+  const float4 *tgt_ref = nullptr;  // the target in reference order
+  const Grid *grid = nullptr;       // the target's grid at the range's cell, its distance transform built out to
+  int max_ring = 0;                 // this ring
+};
+// builds what is missing of it on the clouds' caches (cloud_hilbert, cloud_grid, grid_ensure_dt)
+NnSearch nn_search(Context *c, const mm3d_cloud *src, const mm3d_cloud *tgt, const NnRange *range);
+NnJob nn_job(const NnSearch &s, bool split, unsigned nblocks, IcpState *st, const float *Tc, double *partials, double *out);
+
+// One ICP variant's side of a batch of pairs (nn.hip's icp_batch).  The batch owns what is common: the live pairs, the split,
+// the states, the ICP and score NnJobs, the one pinned block, the chunked iterations with their speculative score, the one
+// copy back and wait per round.  It asks the step for the rest, in this order: check per pair, the sizes, begin, bind per pair,
+// upload, iterate per iteration, close per pair.
+struct IcpLaunch {
+  const NnJob *jobs_dev;            // the batch's ICP jobs
+  int count;
+  unsigned grid_x;                  // the largest job's blocks
+  bool split;
+  float max_d2, rmax;
+  double bytes, finalize_bytes;     // profile table: bytes_per_point over the batch; the partials
+};
+struct IcpStep {
+  virtual ~IcpStep() = default;
+  int acc = kAcc;                   // doubles per block of partials
+  bool searches = true;             // reads the target's grid and follows the batch's split (NDT: neither; four items per block)
+  int forced_split = 0;             // test hook: 0 (by size), 1 or 4
+  virtual double bytes_per_point(const IcpScoreJob &J) const = 0;   // profile table
+  virtual void check(const IcpScoreJob &) const {}                  // throws when the pair lacks the variant's operand
+  // Asked before the batch's one pin() (a second request could replace the arena): host bytes for B pairs, a multiple of 16,
+  // and bytes that ride behind the IcpStates in the state copies, up and back
+  virtual size_t pinned_bytes(int B) const { return 0; }
+  virtual size_t record_bytes(int B) const { return 0; }
+  // the step's device arrays for the B live pairs; its part of the pinned block; the bytes behind the states on both sides
+  virtual void begin(Context *c, const IcpScoreJob *const *live, int B, char *pinned, void *rec_host, void *rec_dev) {}
+  virtual void bind(int b, const NnJob &q, const IcpScoreJob &J) {}  // pair b, from its filled ICP job
+  virtual void upload(Context *c) {}
+  virtual void iterate(Context *c, const IcpLaunch &L) = 0;         // the search / reduction launches and the finalize launch
+  virtual void close(int b, const IcpState &h, IcpScoreJob &J) {}   // pair b has finished: h and the records are final
+};
+// a step's job array: the host image in the batch's pinned block and the device copy
+template <class Job>
+struct StepJobs {
+  DevBuf<Job> dev;
+  Job *host = nullptr;
+  static size_t bytes(int B) { return (sizeof(Job) * B + 15) & ~(size_t)15; }
+  char *begin(Context *c, int B, char *pinned)
+  {
+    dev = DevBuf<Job>(c, (size_t)B);
+    host = (Job *)pinned;
+    return pinned + bytes(B);
+  }
+  void upload(Context *c) { MM3D_HIP(hipMemcpyAsync(dev.get(), host, sizeof(Job) * dev.size(), hipMemcpyHostToDevice, c->stream)); }
+};
+
+// nn.hip: k_icp_finalize over NnJobs (the rejecting step without normals ends an iteration with it)
+void icp_point_finalize(Context *c, const NnJob *jobs_dev, int count, double bytes);
+
+// point-to-plane ICP (icp_plane.hip): the search job plus the target's normals, in the target's reference order (tgt_ref's).
+// Coloured ICP and the rejecting step with normals keep such an array too: k_icp_plane_finalize reads it.
 struct NnPlaneJob {
   NnJob nn;                   // nn.partials: [nblocks][kPlaneAcc]
   const float4 *nrm;
 };
 // AtA upper triangle (21) | Atr (6) | sum d2 | correspondences | rows with a finite normal
 constexpr int kPlaneAcc = 30;
-// one point-to-plane ICP iteration of a batch (icp_corr_reduce's and icp_finalize's counterparts): the search + reduction
-// launch, then the solve / accumulate / convergence launch, on the same IcpState protocol as icp_score_batch's
-void icp_plane_step(Context *c, const NnPlaneJob *jobs_dev, int count, unsigned grid_x, bool split, float max_d2, float rmax,
-                    double bytes, double finalize_bytes);
-
-
-// NDT (ndt.hip): the job's source side and state (nn.g, nn.tgt_ref and nn.max_ring are not read; nn.split is 0: always four work
-// items per block, so nn.partials is [ceil(n_items / 4)][kNdtAcc] whatever the batch), and the target's voxel table
-struct NdtJob {
-  NnJob nn;
-  const float4 *rec;          // NdtTable::rec
-  const int *index;           // NdtTable::index
-  float inv, mn[3];
-  int dims[3];
-  int neighbours;             // 1 or 7
-  int n_src;                  // finite source points: the divisor of the convergence test's mean weight
-};
-// H upper triangle (21) | g (6) | sum w | terms | points with at least one term
-constexpr int kNdtAcc = 30;
-// one NDT iteration of a batch: the lookup + reduction launch, then the solve / accumulate / convergence launch, on the same
-// IcpState protocol as icp_score_batch's
-void ndt_step(Context *c, const NdtJob *jobs_dev, int count, unsigned grid_x, double bytes, double finalize_bytes);
-
-// ICP with correspondence rejection (icp_reject.hip, mm3d_set_icp_rejection).  What one pair's selection leaves behind, on the
-// device beside the pair's IcpState and back on the host in the copy that brings the states: the counts of the last iteration
-// that ran and the state of the radix select (prefix / rank BEFORE pass q of four 8-bit passes over the d2 bits).
-struct RejRecord {
-  unsigned matched, survivors, kept;
-  unsigned tau_bits;          // TRIMMED: tau; MEDIAN: m (valid when cut == 0)
-  int cut;                    // 0: cut at tau_bits, 1: nothing is cut, 2: everything is cut
-  unsigned prefix[4], rank[4];
-};
-// the search job plus the rejecting stage's working memory; nn.partials: [nblocks][kAcc], or [nblocks][kPlaneAcc] with normals
-struct NnRejectJob {
-  NnJob nn;
-  const float4 *nrm;          // point-to-plane: the target's normals (tgt_ref's order); null: point-to-point
-  int2 *corr;                 // [n_src], at the point's place in the Hilbert-ordered source: {target index (-1: none;
-                              // -2 - index: lost its target under one_to_one), d2 bits}
-  unsigned long long *owner;  // one_to_one: [n_tgt] smallest key d2 bits << 32 | original source index per target point
-  unsigned *hist;             // [4][256]
-  RejRecord *rec;
-  int n_src;                  // finite source points
-};
-// One iteration's correspondence stage and sums for a batch: begin, search, the select's passes, the reduction into nn.partials
-// in the default kernels' layout and order.  The caller runs the default finalize kernel afterwards (k_icp_finalize over its
-// NnJobs, icp_plane_finalize over its NnPlaneJobs).  owner_all / owner_bytes: the batch's owner arrays as one region.
-void icp_reject_step(Context *c, const NnRejectJob *jobs_dev, int count, unsigned grid_x, unsigned max_src, bool split, bool plane,
-                     float max_d2, float rmax, const mm3d_icp_rejection_options &opt, unsigned long long *owner_all, size_t owner_bytes,
-                     double bytes);
-// icp_plane.hip: k_icp_plane_finalize alone
+inline void icp_plane_check(const IcpScoreJob &J)
+{
+  if (!J.tgt_normals || J.tgt_normals->n != J.tgt->n)
+    throw Error(MM3D_EINVAL, "point-to-plane ICP: the target's normals do not match its points");
+}
+inline NnPlaneJob icp_plane_job(const NnJob &q, const IcpScoreJob &J)
+{
+  return NnPlaneJob{q, J.tgt_normals ? (const float4 *)J.tgt_normals->nrm.get() : nullptr};
+}
+// icp_plane.hip: k_icp_plane_finalize over NnPlaneJobs; the method, for a stage-level call that has normals
 void icp_plane_finalize(Context *c, const NnPlaneJob *jobs_dev, int count, double finalize_bytes);
-// mm3d_debug_icp_rejection_split: 0 (by size), 1 or 4
-int icp_reject_forced_split();
-// mm3d_debug_icp_rejection: begin, search and the select's passes for ONE job, then every source point's decision at its original index
-void icp_reject_debug(Context *c, const NnRejectJob *job_dev, unsigned grid_x, unsigned n_src, int n_items, bool split, float max_d2, float rmax,
-                      const mm3d_icp_rejection_options &opt, unsigned long long *owner, size_t owner_bytes, int *out_idx, float *out_d2,
-                      unsigned char *out_kept);
-bool icp_rejection_options_valid(const mm3d_icp_rejection_options *o);
+const IcpMethodBase *icp_plane_method();
 
-// coloured ICP (icp_color.hip, mm3d_set_icp_color): the point-to-plane job plus the target's gradient records and the source's
-// reference points (their rgba).  pl.nn.partials: [nblocks][kPlaneAcc], read by k_icp_plane_finalize over the NnPlaneJobs.
-struct NnColorJob {
-  NnPlaneJob pl;
-  const float4 *rec;          // the target's records (gx, gy, gz, I), in tgt_ref's order
-  const float4 *src_ref;      // the source's points in reference order (nn.src's .w indexes them)
-};
-// one coloured iteration's search + reduction launch for a batch; the caller runs icp_plane_finalize afterwards.  lambda: the
-// weight of the geometric rows (the photometric ones get 1 - lambda; 1: point-to-plane's terms, bit for bit)
-void icp_color_step(Context *c, const NnColorJob *jobs_dev, int count, unsigned grid_x, bool split, float max_d2, float rmax, double lambda,
-                    double bytes);
-// mm3d_debug_icp_color_split: 0 (by size), 1 or 4
-int icp_color_forced_split();
-bool icp_color_options_valid(const mm3d_icp_color_options *o);
+// icp_reject.hip (mm3d_set_icp_rejection): the step that puts a correspondence stage between the search and the sums of the
+// point-to-point ICP or, with normals, of point-to-plane
+std::unique_ptr<IcpStep> icp_reject_step(const mm3d_icp_rejection_options &opt, bool normals);
 
 }  // namespace mm3d

@@ -267,15 +267,10 @@ void mm3d::pairs_estimate_batch(mm3d_ctx *ctx, PairWork *w, size_t n, const mm3d
   // (mm3d_set_icp_method), else the reference's ICP; a method binds what it keeps on the targets (voxel tables, normals,
   // gradient records) to the jobs first
   const IcpMethodBase *tail = sel.refine ? sel.refine : sel.color ? sel.color : sel.icp;
-  if (tail) {
-    if (p->refine_transform)
-      for (size_t i = 0; i < n; ++i) tail->prepare_target(ctx, w[i].t, p, &jobs[i]);
-    tail->score_batch(ctx, jobs.data(), (int)n, p->refine_transform != 0, p->max_correspondence_distance, p->max_iterations,
-                      p->transform_epsilon, want_score, p->max_correspondence_distance);
-  } else {
-    icp_score_batch(ctx, jobs.data(), (int)n, p->refine_transform != 0, p->max_correspondence_distance, p->max_iterations, p->transform_epsilon,
-                    want_score, p->max_correspondence_distance);
-  }
+  if (tail && p->refine_transform)
+    for (size_t i = 0; i < n; ++i) tail->prepare_target(ctx, w[i].t, p, &jobs[i]);
+  icp_score_batch(ctx, tail, jobs.data(), (int)n, p->refine_transform != 0, p->max_correspondence_distance, p->max_iterations,
+                  p->transform_epsilon, want_score, p->max_correspondence_distance);
   for (size_t i = 0; i < n; ++i) {
     mm3d_pair_result *out = w[i].out;
     std::memcpy(out->transform, jobs[i].out.T, sizeof(out->transform));

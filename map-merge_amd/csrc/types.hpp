@@ -37,7 +37,7 @@ struct StageSelection {
   mm3d_refine_options refine_options;
   mm3d_coarse_options coarse_options;
   mm3d_confidence_options confidence_options;
-  mm3d_icp_rejection_options reject_options;           // the ICP's correspondence rejection: no method object, icp_batch reads them
+  mm3d_icp_rejection_options reject_options;           // the ICP's correspondence rejection: no method object, the jobs carry them
   mm3d_icp_color_options color_options;                // coloured ICP: `color` is non-null exactly while they are enabled
   StageSelection();                                    // capi.cpp: the options are the seven mm3d_*_options_default's
   // the ICP of the pair stage rejects correspondences (mm3d_set_icp_rejection)
@@ -370,7 +370,8 @@ void desc_knn_rows(Context *c, const mm3d_desc *A, const int *rows_dev, int n_ro
 // registration.hip
 struct IcpResult { float T[16]; int iterations; int converged; };
 struct PairTail { float T[16]; int iterations; int converged; int n_corr; double score; };
-// one pair of a batch of ICP + score tails (icp_score_batch): inputs, then the result
+// one pair of a batch of ICP + score tails (icp_score_batch): inputs (the common ones, then what each method's
+// prepare_target or a stage-level call binds for its step), then the result
 struct IcpScoreJob {
   const mm3d_cloud *src = nullptr, *tgt = nullptr;
   const float *guess_dev = nullptr;     // the guess on the device, or
@@ -390,29 +391,23 @@ struct IcpScoreJob {
   const float4 *tgt_color = nullptr;
   double color_lambda = 1.0;
 };
-void icp_score_batch(Context *c, IcpScoreJob *jobs, int n_jobs, bool run_icp, double max_corr_dist, int max_iterations, double eps,
-                     bool want_score, double score_max_distance);
-// the same with point-to-plane ICP (icp_plane.hip's kernels; every job's tgt_normals set).  The score stays point-to-point.
-void icp_plane_score_batch(Context *c, IcpScoreJob *jobs, int n_jobs, bool run_icp, double max_corr_dist, int max_iterations, double eps,
-                           bool want_score, double score_max_distance);
-// the same with coloured ICP (icp_color.hip's kernels; every job's tgt_normals and tgt_color set).  The score stays point-to-point.
-void icp_color_score_batch(Context *c, IcpScoreJob *jobs, int n_jobs, bool run_icp, double max_corr_dist, int max_iterations, double eps,
-                           bool want_score, double score_max_distance);
-// the same with NDT in the ICP's place (ndt.hip's kernels; every job's tgt_ndt set); max_corr_dist is read by the score only
-void ndt_score_batch(Context *c, IcpScoreJob *jobs, int n_jobs, bool run_icp, double max_corr_dist, int max_iterations, double eps,
-                     bool want_score, double score_max_distance);
-// The ICP method of a context's pair stage (mm3d_set_icp_method: icp_plane.hip's class) or what takes its place
-// (mm3d_set_refinement: ndt.hip's).  Like MapCacheBase,
-// the drivers in capi.cpp only see this interface, so the host code links without the new kernels (tests/host_san); a null
-// pointer on the context means the reference's point-to-point ICP (icp_score_batch).
+struct IcpStep;      // nn_core.hpp
+// The ICP + score tail of a batch of pairs (nn.hip) with `method`'s ICP; null: the reference's point-to-point ICP.  When the ICP
+// runs and the jobs carry rejection options, a method that can reject correspondences does.  The score stays point-to-point.
+void icp_score_batch(Context *c, const IcpMethodBase *method, IcpScoreJob *jobs, int n_jobs, bool run_icp, double max_corr_dist,
+                     int max_iterations, double eps, bool want_score, double score_max_distance);
+// What stands in the place of the pair stage's point-to-point ICP on a context: point-to-plane (mm3d_set_icp_method,
+// icp_plane.hip), coloured ICP (mm3d_set_icp_color, icp_color.hip) or NDT (mm3d_set_refinement, ndt.hip).  Like MapCacheBase,
+// the drivers in capi.cpp only see this interface, so the host code links without the kernels (tests/host_san); a null
+// pointer on the context means the reference's point-to-point ICP.
 struct IcpMethodBase {
   virtual ~IcpMethodBase() = default;
   virtual int method() const = 0;                        // MM3D_ICP_*
-  // icp_score_batch with this method's ICP
-  virtual void score_batch(Context *c, IcpScoreJob *jobs, int n_jobs, bool run_icp, double max_corr_dist, int max_iterations, double eps,
-                           bool want_score, double score_max_distance) const = 0;
-  // what the method keeps on a target map beyond its search structures (point-to-plane's normals, NDT's voxel table): made
-  // when missing or stale (map_kept.hpp; no wait when it is there), and bound to `job` when there is one
+  // this method's side of one icp_score_batch; reject: the batch's rejection options, or null.  Point-to-plane makes the
+  // rejecting step with normals then; NDT and coloured ICP do not read it.
+  virtual std::unique_ptr<IcpStep> step(const mm3d_icp_rejection_options *reject) const = 0;
+  // what the method keeps on a target map beyond its search structures (point-to-plane's normals, NDT's voxel table, the
+  // gradient records): made when missing or stale (map_kept.hpp; no wait when it is there), and bound to `job` when there is one
   virtual void prepare_target(mm3d_ctx *, const mm3d_map *, const mm3d_params *, IcpScoreJob *) const = 0;
 };
 inline int StageSelection::icp_method() const { return icp ? icp->method() : MM3D_ICP_POINT_TO_POINT; }

@@ -242,7 +242,7 @@ static PairTail fake_tail(const mm3d_cloud *src, const mm3d_cloud *tgt, const fl
   r.score = want_score ? 0.25 + 1e-6 * (double)((src->n * 31 + tgt->n) % 1000) : 0.0;
   return r;
 }
-void icp_score_batch(Context *, IcpScoreJob *jobs, int n_jobs, bool run_icp, double, int, double, bool want_score, double)
+void icp_score_batch(Context *, const IcpMethodBase *, IcpScoreJob *jobs, int n_jobs, bool run_icp, double, int, double, bool want_score, double)
 {
   for (int i = 0; i < n_jobs; ++i) {
     jobs[i].out = fake_tail(jobs[i].src, jobs[i].tgt, jobs[i].guess_dev ? jobs[i].guess_dev : jobs[i].guess_host, run_icp, want_score);

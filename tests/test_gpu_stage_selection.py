@@ -2,7 +2,9 @@
 mm3d_set_coarse_alignment, mm3d_set_confidence).  Each stage's own file (test_gpu_icp_plane.py ... test_gpu_confidence.py)
 checks it alone; here a context holds several selections at once, and whatever the order of the setters and mm3d_set_streams
 -- helpers made before, after, or destroyed and remade -- every context must hold the same selection and compute the same
-bits.  Every comparison is exact: the library promises bit-identical records for every stream count."""
+bits.  Then what every ICP selection shares, the pair batch: pairs of unequal size in one batch against the stage-level entry
+points, and the entry points with nothing to search.  Every comparison is exact: the library promises bit-identical records
+for every stream count."""
 import numpy as np
 import pytest
 
@@ -125,6 +127,103 @@ def test_selections_together_in_every_order_of_the_calls(mm, clouds, untouched, 
     _same(_run(back, clouds, p), untouched[method])
     for c in cs:
         c.close()
+
+
+# ---------------------------------------------------------------- the ICP variants' side of a pair batch
+# what a context selects, and the stage-level entry point that runs the same ICP on one pair (nt: the target's normals)
+TRIM_ONE_TO_ONE = dict(one_to_one=1, distance=1, overlap_ratio=0.7)
+NDT_RESOLUTION = 2.0
+ICP_VARIANTS = {
+    "default": ({}, lambda c, s, t, nt, g, p: c.estimateTransformICP(s, t, g, p.max_correspondence_distance, 0.0, p.max_iterations,
+                                                                        p.transform_epsilon)),
+    "plane": (dict(IcpMethod=1), lambda c, s, t, nt, g, p: c.estimateTransformICPPlane(s, t, nt, g, p.max_correspondence_distance,
+                                                                                        p.max_iterations, p.transform_epsilon)),
+    "ndt": (dict(Refinement=dict(method=1, resolution=NDT_RESOLUTION)),
+            lambda c, s, t, nt, g, p: c.estimateTransformNDT(s, t, g, method=1, resolution=NDT_RESOLUTION, max_iterations=p.max_iterations,
+                                                             transformation_epsilon=p.transform_epsilon)),
+    "rejecting": (dict(IcpRejection=TRIM_ONE_TO_ONE),
+                  lambda c, s, t, nt, g, p: c.estimateTransformICPRejecting(s, t, None, g, p.max_correspondence_distance,
+                                                                            max_iterations=p.max_iterations,
+                                                                            transformation_epsilon=p.transform_epsilon, **TRIM_ONE_TO_ONE)),
+    "rejecting-plane": (dict(IcpRejection=TRIM_ONE_TO_ONE, IcpMethod=1),
+                        lambda c, s, t, nt, g, p: c.estimateTransformICPRejecting(s, t, nt, g, p.max_correspondence_distance,
+                                                                                  max_iterations=p.max_iterations,
+                                                                                  transformation_epsilon=p.transform_epsilon, **TRIM_ONE_TO_ONE)),
+    "coloured": (dict(IcpColor=dict(enabled=1)),      # (gradient_radius 0: the normal radius)
+                 lambda c, s, t, nt, g, p: c.estimateTransformICPColor(s, t, nt, g, p.max_correspondence_distance,
+                                                                       max_iterations=p.max_iterations,
+                                                                       transformation_epsilon=p.transform_epsilon, gradient_radius=p.normal_radius)),
+}
+NEEDS_NORMALS = ("plane", "rejecting-plane", "coloured")
+THINNING = (1, 2, 3, 4)      # every k-th point of the fixture's maps: four maps of clearly different size
+
+
+@pytest.fixture(scope="module")
+def unequal_clouds(synth):
+    _, maps = synth.synth_maps(4, 30000, overlap_step=0.4)
+    return [synth.pack_points(x, col)[::k].copy() for (x, col, _), k in zip(maps, THINNING)]
+
+
+@pytest.mark.parametrize("variant", list(ICP_VARIANTS))
+def test_unequal_sources_in_one_batch(mm, unequal_clouds, variant):
+    """Pairs of different source and target sizes in one batch (every per-pair offset into the batch's arrays differs from its
+    neighbours'): one and four streams give the same bytes, and every pair is the stage-level entry point's result from the
+    pair's pre-ICP guess, bit for bit."""
+    selection, stage = ICP_VARIANTS[variant]
+    p = _params(mm, SAC_IA)
+    c = mm.Context(0)
+    _select(mm, c, selection)
+    four = mm.Context(0)
+    _select(mm, four, selection)
+    four.setStreams(4)
+    one = _run(c, unequal_clouds, p)
+    _same(one, _run(four, unequal_clouds, p))
+    hook = dict(rejecting=mm.icp_rejection_split, coloured=mm.icp_color_split).get(variant.split("-")[0])
+    if hook:          # the launches with four work items per block, over the same unequal jobs: the same bytes
+        hook(1)
+        try:
+            _same(one, _run(c, unequal_clouds, p))
+        finally:
+            hook(0)
+    p_off = _params(mm, SAC_IA)
+    p_off.refine_transform = 0
+    guesses = _run(c, unequal_clouds, p_off)[1]
+    maps = [c.mapFeatures(c.cloud(x), p) for x in unequal_clouds]
+    normals = [c.computeSurfaceNormals(m.points, p.normal_radius) if variant in NEEDS_NORMALS else None for m in maps]
+    iterated = set()
+    for g, r in zip(guesses, one[1]):
+        s, t = int(r["source_idx"]), int(r["target_idx"])
+        assert (int(g["source_idx"]), int(g["target_idx"])) == (s, t)
+        T = stage(c, maps[s].points, maps[t].points, normals[t], g["transform"].reshape(4, 4).T, p)
+        assert np.array_equal(T.T.reshape(16).view(np.uint32), r["transform"].view(np.uint32))
+        assert c.last_icp_iterations == int(r["icp_iterations"])
+        if int(r["icp_iterations"]) > 0:
+            iterated.add(len(maps[s].points))
+    assert len(iterated) >= 3          # at least three pairs that iterate, their sources of pairwise different size
+    c.close()
+    four.close()
+
+
+@pytest.mark.parametrize("empty", ["source", "target"])
+@pytest.mark.parametrize("variant", list(ICP_VARIANTS))
+def test_nothing_to_search(mm, variant, empty):
+    """An empty source, or an empty target: every stage-level entry point answers MM3D_OK, the guess bit for bit and no iteration."""
+    _, stage = ICP_VARIANTS[variant]
+    rng = np.random.default_rng(5)
+    xyz = rng.uniform(-2.0, 2.0, (300, 3)).astype(np.float32)
+    full = np.zeros(300, dtype=mm.POINT)
+    full["x"], full["y"], full["z"] = xyz[:, 0], xyz[:, 1], xyz[:, 2]
+    c = mm.Context(0)
+    clouds = dict(source=c.cloud(full), target=c.cloud(full))
+    clouds[empty] = c.cloud(full[:0])
+    nt = c.computeSurfaceNormals(clouds["target"], 0.5) if variant in NEEDS_NORMALS else None
+    guess = np.eye(4, dtype=np.float32)
+    guess[:3, :3] = [[0.8, -0.6, 0.0], [0.6, 0.8, 0.0], [0.0, 0.0, 1.0]]
+    guess[:3, 3] = [0.1, -0.2, 0.3]
+    T = stage(c, clouds["source"], clouds["target"], nt, guess, _params(mm, SAC_IA))
+    assert np.array_equal(np.asarray(T, dtype=np.float32).view(np.uint32), guess.view(np.uint32))
+    assert c.last_icp_iterations == 0
+    c.close()
 
 
 def test_defaults_exist_once(mm):
