@@ -215,6 +215,37 @@ inline void check_icp_color_combinations(const mm3d_icp_color_options &o, const 
   if (reject.one_to_one || reject.distance != MM3D_REJECT_NONE)
     throw std::runtime_error("mm3d: MM3D_ICP_COLOR is not available with an active MM3D_ICP_REJECT (the rejecting ICP has no colour term)");
 }
+// MM3D_ICP_GENERALIZED=1 or <epsilon>: the estimation context's pair stage runs generalized ICP (mm3d_set_icp_generalized).
+// 1 alone: mm3d_icp_generalized_options_default's epsilon (1e-3) -- epsilon 1 itself is spelt 1.0.  0, none or unset leaves it
+// off.  An epsilon outside (0, 1] or anything else throws, as a malformed MM3D_ICP_COLOR does.
+inline mm3d_icp_generalized_options parse_icp_generalized(const char *value)
+{
+  mm3d_icp_generalized_options o;
+  o.enabled = 0;
+  o.epsilon = 1e-3;
+  const std::string v = value ? value : "";
+  if (v.empty() || v == "0" || v == "none") return o;
+  o.enabled = 1;
+  if (v == "1") return o;
+  char *end = nullptr;
+  o.epsilon = std::strtod(v.c_str(), &end);
+  if (!(end != v.c_str() && *end == '\0' && o.epsilon > 0.0 && o.epsilon <= 1.0))
+    throw std::runtime_error("mm3d: MM3D_ICP_GENERALIZED must be 0, 1 or <epsilon in (0, 1]>, not '" + v + "'");
+  return o;
+}
+// Not available on a device list (its bundles carry no normals), nor together with an active MM3D_ICP_REJECT or an active
+// MM3D_ICP_COLOR (neither has a plane-to-plane variant): each combination throws.
+inline void check_icp_generalized_combinations(const mm3d_icp_generalized_options &o, const mm3d_icp_rejection_options &reject,
+                                               const mm3d_icp_color_options &color, const char *devices)
+{
+  if (!o.enabled) return;
+  if (devices && *devices)
+    throw std::runtime_error("mm3d: MM3D_ICP_GENERALIZED is not available with MM3D_DEVICES (a device list carries no normals)");
+  if (reject.one_to_one || reject.distance != MM3D_REJECT_NONE)
+    throw std::runtime_error("mm3d: MM3D_ICP_GENERALIZED is not available with an active MM3D_ICP_REJECT (the rejecting ICP has no plane-to-plane term)");
+  if (color.enabled)
+    throw std::runtime_error("mm3d: MM3D_ICP_GENERALIZED is not available with an active MM3D_ICP_COLOR (coloured ICP has no plane-to-plane term)");
+}
 }  // namespace mm3d_shim
 }  // namespace map_merge_3d
 
@@ -301,11 +332,14 @@ inline mm3d_ctx *ctx()
   // MM3D_CONFIDENCE=overlap[:<voxel>]: parse_confidence above.  Not available on a device list: overlap with MM3D_DEVICES set as well throws.
   // MM3D_ICP_REJECT=one_to_one+trimmed:0.7 ...: parse_icp_reject above.  Not available on a device list: an active value with MM3D_DEVICES set as well throws.
   // MM3D_ICP_COLOR=1 or <lambda>[:<radius>]: parse_icp_color above.  Not available on a device list nor with an active MM3D_ICP_REJECT: either throws.
+  // MM3D_ICP_GENERALIZED=1 or <epsilon>: parse_icp_generalized above.  Not available on a device list nor with an active MM3D_ICP_REJECT or MM3D_ICP_COLOR: each throws.
   static mm3d_ctx *c = [] {
     const mm3d_icp_rejection_options reject = parse_icp_reject(std::getenv("MM3D_ICP_REJECT"));
     check_icp_reject_devices(reject, std::getenv("MM3D_DEVICES"));
     const mm3d_icp_color_options color = parse_icp_color(std::getenv("MM3D_ICP_COLOR"));
     check_icp_color_combinations(color, reject, std::getenv("MM3D_DEVICES"));
+    const mm3d_icp_generalized_options generalized = parse_icp_generalized(std::getenv("MM3D_ICP_GENERALIZED"));
+    check_icp_generalized_combinations(generalized, reject, color, std::getenv("MM3D_DEVICES"));
     const mm3d_confidence_options confidence = parse_confidence(std::getenv("MM3D_CONFIDENCE"));
     check_confidence_devices(confidence, std::getenv("MM3D_DEVICES"));
     const mm3d_coarse_options coarse = parse_coarse(std::getenv("MM3D_COARSE"));
@@ -356,6 +390,8 @@ inline mm3d_ctx *ctx()
       throw std::runtime_error(std::string("mm3d: MM3D_ICP_REJECT was refused: ") + mm3d_last_error(e));
     if (color.enabled && mm3d_set_icp_color(e, &color) != MM3D_OK)
       throw std::runtime_error(std::string("mm3d: MM3D_ICP_COLOR was refused: ") + mm3d_last_error(e));
+    if (generalized.enabled && mm3d_set_icp_generalized(e, &generalized) != MM3D_OK)
+      throw std::runtime_error(std::string("mm3d: MM3D_ICP_GENERALIZED was refused: ") + mm3d_last_error(e));
     return e;
   }();
   return c;

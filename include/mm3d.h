@@ -887,7 +887,8 @@ typedef struct mm3d_icp_rejection_stats {  /* of the LAST iteration that ran */
 void mm3d_icp_rejection_options_default(mm3d_icp_rejection_options *o);   /* 0, NONE, 0.5, 0, 1.0 (PCL's own defaults) */
 /* The selection is active when one_to_one || distance != MM3D_REJECT_NONE.  MM3D_EINVAL: ctx or options NULL, one_to_one not
  * 0 / 1, an unknown distance, a value outside its range above (the values are checked whatever the selection).
- * MM3D_EUNSUPPORTED: an active selection on a device-list context (mm3d_create_devices); mm3d_shard_begin returns
+ * MM3D_EUNSUPPORTED: an active selection on a device-list context (mm3d_create_devices), or while coloured ICP
+ * (mm3d_set_icp_color) or generalized ICP (mm3d_set_icp_generalized) is enabled; mm3d_shard_begin returns
  * MM3D_EUNSUPPORTED on a context with an active selection.  The setting reaches the context's mm3d_set_streams helpers, in
  * either order, and is part of the map cache's pair key while active. */
 int mm3d_set_icp_rejection(mm3d_ctx *ctx, const mm3d_icp_rejection_options *options);
@@ -950,7 +951,8 @@ typedef struct mm3d_icp_color_options {
 void mm3d_icp_color_options_default(mm3d_icp_color_options *o);   /* 0, 0.968, 0, 4 (lambda: Open3D's default) */
 /* MM3D_EINVAL: ctx or options NULL, enabled not 0 / 1, a value outside its range above (checked whatever `enabled` is).
  * MM3D_EUNSUPPORTED: enabled on a device-list context (mm3d_create_devices), or while a correspondence rejection is active
- * (mm3d_set_icp_rejection, which in turn refuses an active selection while colour is enabled); mm3d_shard_begin returns
+ * (mm3d_set_icp_rejection, which in turn refuses an active selection while colour is enabled) or generalized ICP is enabled
+ * (mm3d_set_icp_generalized, likewise); mm3d_shard_begin returns
  * MM3D_EUNSUPPORTED on a context with colour enabled.  The setting reaches the context's mm3d_set_streams helpers, in either
  * order, and is part of the map cache's pair key while enabled. */
 int mm3d_set_icp_color(mm3d_ctx *ctx, const mm3d_icp_color_options *options);
@@ -968,6 +970,58 @@ int mm3d_debug_color_gradients(mm3d_ctx *ctx, const mm3d_cloud *points, const mm
 /* test hook, process-wide like mm3d_debug_icp_rejection_split: 0 = one or four work items per block chosen by size, as
  * everywhere; 1 or 4 = forced in every coloured launch from now on; negative = no change.  Returns the value in force. */
 int mm3d_debug_icp_color_split(int split);
+
+/* ---------------------------------------------------------------- opt-in generalized ICP
+ * mm3d_set_icp_generalized makes the pair stage's ICP plane-to-plane (Segal, Haehnel, Thrun, "Generalized-ICP", RSS 2009; PCL's
+ * GeneralizedIterativeClosestPoint and Open3D's registration_generalized_icp are the known implementations, and no parity with
+ * either is claimed).  Two maps sample the same surfaces differently, so a nearest neighbour is rarely the same surface point:
+ * point-to-point is pulled along the surface by the sampling, and a source point near an edge that matches the neighbouring face
+ * pulls point-to-plane.  Here a correspondence is weighted by the inverse of the sum of both surfaces' covariances, each the
+ * disc I - (1 - epsilon) n n^T of its normal (PCL's R diag(1, 1, epsilon) R^T): an in-plane slide costs nothing, and a match
+ * across two faces counts only along their common edge.  The covariances follow from the normals a map keeps already: nothing
+ * new is made or stored per map.  Disabled (the default), the pair stage runs the kernels it always ran.
+ * One iteration is mm3d_set_icp_method's in every respect but the 6x6 system: the float transform of the source by T, the exact
+ * float nearest neighbour accepted at d2 <= max_d2, fewer than 3 correspondences -> stop, not converged, T <- Tinc * T in float
+ * with Tinc = [Rz(gamma) Ry(beta) Rx(alpha) | t], and DefaultConvergenceCriteria's three tests.  Per matched source point i (its
+ * index in the source's own order), in double: s the float-transformed point, q the target point, n_s and n_t the two normals.
+ * A normal is usable when its three components are finite and n.n = (nx nx + ny ny) + nz nz > 0; its unit vector is
+ * n / sqrt(n.n); the sign does not matter.  With both usable:
+ *   m     = R n_s, R the 3x3 of T promoted to double, m_r = (R_r0 n_0 + R_r1 n_1) + R_r2 n_2 (not renormalised)
+ *   Sigma = 2 I - (1 - epsilon) (n_t n_t^T + m m^T)                   (eigenvalues in [2 epsilon, 2])
+ *   W     = Sigma^-1, the adjugate over the determinant
+ *   e     = q - s,  J = [-[s]x | I3],  x = (alpha, beta, gamma, tx, ty, tz)
+ * and the correspondence adds J^T W J to AtA, J^T W e to Atr, d2 to the squared distances, 1 to the correspondences and 3 to
+ * the rows.  With either normal unusable it adds d2 and the 1 only (point-to-plane's rule for a non-finite normal).  The
+ * solve, its degeneracy rule (fewer than 6 rows, or an LDLt pivot at or below 1e-12 trace / 6: stop, not converged, T as it
+ * was) and the tail are point-to-plane's own.
+ * Enabled, the pair stage's ICP is the generalized one whatever mm3d_set_icp_method says (mm3d_get_icp_method keeps answering
+ * its own value), with both maps' normals at params.normal_radius; NDT (mm3d_set_refinement) does not read the setting,
+ * transformScore stays point-to-point, the overlap confidence is untouched and nothing is drawn from rand().  The other stage
+ * entry points do not see the setting.  Results are bit-identical for every stream count, batch and cache setting.  Memory:
+ * the 16 B per filtered point of a map's normals. */
+typedef struct mm3d_icp_generalized_options {
+  int enabled;             /* 0 / 1 */
+  double epsilon;          /* a surface's covariance along its normal, 0 < epsilon <= 1 (1: both covariances I, point-to-point's weights) */
+} mm3d_icp_generalized_options;
+void mm3d_icp_generalized_options_default(mm3d_icp_generalized_options *o);   /* 0, 1e-3 (PCL's gicp_epsilon) */
+/* MM3D_EINVAL: ctx or options NULL, enabled not 0 / 1, epsilon outside (0, 1] or not finite (checked whatever `enabled` is).
+ * MM3D_EUNSUPPORTED: enabled on a device-list context (mm3d_create_devices), or while a correspondence rejection is active
+ * (mm3d_set_icp_rejection) or coloured ICP is enabled (mm3d_set_icp_color), each of which in turn refuses an active selection
+ * while this is enabled; mm3d_shard_begin returns MM3D_EUNSUPPORTED on a context with it enabled.  The setting reaches the
+ * context's mm3d_set_streams helpers, in either order, and is part of the map cache's pair key while enabled. */
+int mm3d_set_icp_generalized(mm3d_ctx *ctx, const mm3d_icp_generalized_options *options);
+int mm3d_get_icp_generalized(const mm3d_ctx *ctx, mm3d_icp_generalized_options *options);   /* MM3D_EINVAL for NULL */
+/* generalized ICP with the rule above from initial_guess, whatever options->enabled and the context's setting say; each cloud's
+ * normals in that cloud's order.  MM3D_EINVAL: a NULL argument, epsilon out of range, normals whose count differs from their
+ * cloud's. */
+int mm3d_estimate_transform_icp_generalized(mm3d_ctx *ctx, const mm3d_cloud *source, const mm3d_normals *source_normals,
+                                            const mm3d_cloud *target, const mm3d_normals *target_normals,
+                                            const float initial_guess[16], double max_correspondence_distance,
+                                            const mm3d_icp_generalized_options *options, int max_iterations,
+                                            double transformation_epsilon, float T[16]);
+/* test hook, process-wide like mm3d_debug_icp_color_split: 0 = one or four work items per block chosen by size, as everywhere;
+ * 1 or 4 = forced in every generalized launch from now on; negative = no change.  Returns the value in force. */
+int mm3d_debug_icp_generalized_split(int split);
 
 #ifdef __cplusplus
 }

@@ -216,6 +216,23 @@ class IcpColorOptions(C.Structure):
         return tuple(int(getattr(self, k)) if t is C.c_int else float(getattr(self, k)) for k, t in self._fields_)
 
 
+class IcpGeneralizedOptions(C.Structure):
+    """mm3d_icp_generalized_options (mm3d_set_icp_generalized); the defaults are mm3d_icp_generalized_options_default's."""
+    _fields_ = [("enabled", C.c_int), ("epsilon", C.c_double)]
+
+    def __init__(self, **kw):
+        super().__init__()
+        lib().mm3d_icp_generalized_options_default(C.byref(self))
+        kinds = dict(self._fields_)
+        for k, v in kw.items():
+            if k not in kinds:
+                raise TypeError("unknown generalized ICP option " + k)
+            setattr(self, k, int(v) if kinds[k] is C.c_int else float(v))
+
+    def as_tuple(self):
+        return tuple(int(getattr(self, k)) if t is C.c_int else float(getattr(self, k)) for k, t in self._fields_)
+
+
 class IcpRejectionStats(C.Structure):
     """mm3d_icp_rejection_stats"""
     _fields_ = [("matched", C.c_longlong), ("after_one_to_one", C.c_longlong), ("kept", C.c_longlong), ("threshold_d2", C.c_float),
@@ -362,6 +379,12 @@ def icp_color_split(split=-1):
     """mm3d_debug_icp_color_split: force every coloured ICP launch to one work item per wave (1) or per block (4); 0: chosen by
     size again; negative: leave as it is.  Returns the value in force."""
     return int(lib().mm3d_debug_icp_color_split(int(split)))
+
+
+def icp_generalized_split(split=-1):
+    """mm3d_debug_icp_generalized_split: force every generalized ICP launch to one work item per wave (1) or per block (4); 0:
+    chosen by size again; negative: leave as it is.  Returns the value in force."""
+    return int(lib().mm3d_debug_icp_generalized_split(int(split)))
 
 
 class Context:
@@ -545,6 +568,17 @@ class Context:
     def getIcpColor(self) -> "IcpColorOptions":
         o = IcpColorOptions()
         self._ck(lib().mm3d_get_icp_color(self._h, C.byref(o)))
+        return o
+
+    def setIcpGeneralized(self, options=None, **kw):
+        """mm3d_set_icp_generalized: generalized (plane-to-plane) ICP in the pair stage.  An IcpGeneralizedOptions, or its fields
+        as keywords (enabled=0 / 1, epsilon=...)."""
+        o = options if options is not None else IcpGeneralizedOptions(**kw)
+        self._ck(lib().mm3d_set_icp_generalized(self._h, C.byref(o)))
+
+    def getIcpGeneralized(self) -> "IcpGeneralizedOptions":
+        o = IcpGeneralizedOptions()
+        self._ck(lib().mm3d_get_icp_generalized(self._h, C.byref(o)))
         return o
 
     @property
@@ -756,6 +790,21 @@ class Context:
         T = np.zeros(16, dtype=np.float32)
         self._ck(lib().mm3d_estimate_transform_icp_color(
             self._h, source_points._h, target_points._h, target_normals._h, g.ctypes.data_as(C.c_void_p),
+            C.c_double(max_correspondence_distance), C.byref(o), int(max_iterations), C.c_double(transformation_epsilon),
+            T.ctypes.data_as(C.c_void_p)))
+        self.last_icp_iterations = lib().mm3d_last_icp_iterations(self._h)
+        self.last_icp_converged = lib().mm3d_last_icp_converged(self._h)
+        return _Tout(T)
+
+    def estimateTransformICPGeneralized(self, source_points, source_normals, target_points, target_normals, initial_guess,
+                                        max_correspondence_distance, max_iterations=100, transformation_epsilon=0.0, epsilon=None):
+        """mm3d_estimate_transform_icp_generalized: generalized ICP from initial_guess, whatever the context's setting (each
+        cloud's normals: one per point; epsilon: mm3d_icp_generalized_options_default's when None)."""
+        o = IcpGeneralizedOptions() if epsilon is None else IcpGeneralizedOptions(epsilon=epsilon)
+        g = _T(initial_guess)
+        T = np.zeros(16, dtype=np.float32)
+        self._ck(lib().mm3d_estimate_transform_icp_generalized(
+            self._h, source_points._h, source_normals._h, target_points._h, target_normals._h, g.ctypes.data_as(C.c_void_p),
             C.c_double(max_correspondence_distance), C.byref(o), int(max_iterations), C.c_double(transformation_epsilon),
             T.ctypes.data_as(C.c_void_p)))
         self.last_icp_iterations = lib().mm3d_last_icp_iterations(self._h)

@@ -37,6 +37,7 @@ mm3d::StageSelection::StageSelection()
   mm3d_confidence_options_default(&confidence_options);
   mm3d_icp_rejection_options_default(&reject_options);
   mm3d_icp_color_options_default(&color_options);
+  mm3d_icp_generalized_options_default(&generalized_options);
 }
 
 void mm3d::select_stages(mm3d_ctx *ctx, bool peers_follow, const std::function<void(StageSelection &)> &edit)
@@ -194,6 +195,10 @@ void mm3d_icp_rejection_options_default(mm3d_icp_rejection_options *o)
 void mm3d_icp_color_options_default(mm3d_icp_color_options *o)
 {
   if (o) *o = mm3d_icp_color_options{0, 0.968, 0.0, 4};
+}
+void mm3d_icp_generalized_options_default(mm3d_icp_generalized_options *o)
+{
+  if (o) *o = mm3d_icp_generalized_options{0, 1e-3};
 }
 
 // ---------------------------------------------------------------- context

@@ -85,6 +85,10 @@ std::string pair_params_key(const mm3d_params *p, const StageSelection &sel)
   const bool colored = col.enabled != 0;
   k.i32(colored ? col.enabled : 0).f64(colored ? col.lambda_geometric : 0.0).f64(colored ? col.gradient_radius : 0.0)
       .i32(colored ? col.min_neighbours : 0);
+  // generalized ICP (mm3d_set_icp_generalized): (enabled, epsilon) while enabled, zeros otherwise
+  const mm3d_icp_generalized_options &gen = sel.generalized_options;
+  const bool generalized = gen.enabled != 0;
+  k.i32(generalized ? gen.enabled : 0).f64(generalized ? gen.epsilon : 0.0);
   return k.s;
 }
 

@@ -1,5 +1,5 @@
 // nn_core.hpp -- what the ICP / score tail of a pair estimate is made of, shared by nn.hip (the batch driver, the point-to-point
-// ICP and the score) and the files that put another ICP in its place (icp_plane.hip, icp_color.hip, icp_reject.hip, ndt.hip):
+// ICP and the score) and the files that put another ICP in its place (icp_plane.hip, icp_color.hip, icp_generalized.hip, icp_reject.hip, ndt.hip):
 // the search knobs, the ICP state, the job layout and the wave helpers of the kernels; and, for the host, the set-up of one
 // search (NnSearch) and the interface through which a variant takes part in a batch (IcpStep).  The search itself is
 // nn_search_body.hpp (see there).
@@ -189,7 +189,7 @@ struct StepJobs {
 void icp_point_finalize(Context *c, const NnJob *jobs_dev, int count, double bytes);
 
 // point-to-plane ICP (icp_plane.hip): the search job plus the target's normals, in the target's reference order (tgt_ref's).
-// Coloured ICP and the rejecting step with normals keep such an array too: k_icp_plane_finalize reads it.
+// Coloured ICP, generalized ICP and the rejecting step with normals keep such an array too: k_icp_plane_finalize reads it.
 struct NnPlaneJob {
   NnJob nn;                   // nn.partials: [nblocks][kPlaneAcc]
   const float4 *nrm;

@@ -76,7 +76,9 @@ std::unique_ptr<mm3d_map> mm3d::map_features_impl(mm3d_ctx *ctx, const mm3d_clou
                                                                          : compute_fpfh(ctx, filt.get(), nrm.get(), kp.get(), p->descriptor_radius));
   if (wait) ctx->sync();
   std::unique_ptr<mm3d_map> m = make_map(std::move(filt), std::move(kp), std::move(desc));
-  if (ctx->sel.icp || ctx->sel.coarse || ctx->sel.color) m->normals = std::move(nrm);    // point-to-plane and coloured ICP read them (mm3d_set_icp_method, mm3d_set_icp_color), and the correlative signature
+  // point-to-plane, coloured and generalized ICP read them (mm3d_set_icp_method, mm3d_set_icp_color, mm3d_set_icp_generalized),
+  // and the correlative signature
+  if (ctx->sel.icp || ctx->sel.coarse || ctx->sel.color || ctx->sel.generalized) m->normals = std::move(nrm);
   return m;
 }
 
@@ -86,6 +88,7 @@ void mm3d::map_prepare_impl(mm3d_ctx *ctx, mm3d_map *m, const mm3d_params *p)
   if (sel.icp) sel.icp->prepare_target(ctx, m, p, nullptr);            // the normals (mm3d_set_icp_method): no wait when the map has them
   if (sel.refine) sel.refine->prepare_target(ctx, m, p, nullptr);      // NDT's voxel table (mm3d_set_refinement)
   if (sel.color) sel.color->prepare_target(ctx, m, p, nullptr);        // the normals and the gradient records (mm3d_set_icp_color)
+  if (sel.generalized) sel.generalized->prepare_target(ctx, m, p, nullptr);   // the normals, for either role (mm3d_set_icp_generalized)
   if (sel.coarse) sel.coarse->prepare(ctx, m, p);                      // the correlative signature (mm3d_set_coarse_alignment)
   if (sel.confidence) sel.confidence->prepare(ctx, m, p);              // the overlap table (mm3d_set_confidence)
   prepare_pair_search(ctx, m->points, p->max_correspondence_distance, p->max_correspondence_distance);
@@ -263,12 +266,15 @@ void mm3d::pairs_estimate_batch(mm3d_ctx *ctx, PairWork *w, size_t n, const mm3d
   // estimateTransform's ICP and transformScore of its result (R/src/map_merging.cpp:91-107), max_distance = max_correspondence_distance
   // (under mm3d_set_confidence nobody reads that score: it is not launched, and the ICP's states come back as they would have)
   const bool want_score = !sel.confidence;
-  // NDT in the ICP's place (mm3d_set_refinement), else coloured ICP (mm3d_set_icp_color), else point-to-plane
-  // (mm3d_set_icp_method), else the reference's ICP; a method binds what it keeps on the targets (voxel tables, normals,
-  // gradient records) to the jobs first
-  const IcpMethodBase *tail = sel.refine ? sel.refine : sel.color ? sel.color : sel.icp;
+  // NDT in the ICP's place (mm3d_set_refinement), else coloured ICP (mm3d_set_icp_color), else generalized ICP
+  // (mm3d_set_icp_generalized), else point-to-plane (mm3d_set_icp_method), else the reference's ICP; a method binds what it keeps
+  // on the targets (voxel tables, normals, gradient records) and on the sources (generalized ICP's normals) to the jobs first
+  const IcpMethodBase *tail = sel.refine ? sel.refine : sel.color ? sel.color : sel.generalized ? sel.generalized : sel.icp;
   if (tail && p->refine_transform)
-    for (size_t i = 0; i < n; ++i) tail->prepare_target(ctx, w[i].t, p, &jobs[i]);
+    for (size_t i = 0; i < n; ++i) {
+      tail->prepare_target(ctx, w[i].t, p, &jobs[i]);
+      tail->prepare_source(ctx, w[i].s, p, &jobs[i]);
+    }
   icp_score_batch(ctx, tail, jobs.data(), (int)n, p->refine_transform != 0, p->max_correspondence_distance, p->max_iterations,
                   p->transform_epsilon, want_score, p->max_correspondence_distance);
   for (size_t i = 0; i < n; ++i) {

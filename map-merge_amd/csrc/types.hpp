@@ -21,7 +21,7 @@ struct CoarseMethodBase;
 struct ConfidenceMethodBase;
 
 // The opt-in stages of a context's pipeline (mm3d_set_icp_method, mm3d_set_alignment, mm3d_set_keypoints, mm3d_set_refinement,
-// mm3d_set_coarse_alignment, mm3d_set_confidence, mm3d_set_icp_rejection, mm3d_set_icp_color): a null method = the reference's stage.  The methods are process-wide
+// mm3d_set_coarse_alignment, mm3d_set_confidence, mm3d_set_icp_rejection, mm3d_set_icp_color, mm3d_set_icp_generalized): a null method = the reference's stage.  The methods are process-wide
 // objects of their kernel files that hold no state and are not owned.  Every context has its own copy of the record; only
 // select_stages (drivers.hpp) changes one, and it and mm3d_set_streams hand the root's copy to the helpers.
 struct StageSelection {
@@ -32,6 +32,7 @@ struct StageSelection {
   const CoarseMethodBase *coarse = nullptr;            // what takes the initial estimate's place
   const ConfidenceMethodBase *confidence = nullptr;    // what a pair record's confidence is
   const IcpMethodBase *color = nullptr;                // coloured ICP in the place of `icp`'s, which keeps its own value beside it
+  const IcpMethodBase *generalized = nullptr;          // generalized ICP in the place of `icp`'s, which keeps its own value beside it
   mm3d_alignment_options align_options;
   mm3d_keypoint_options keypoint_options;
   mm3d_refine_options refine_options;
@@ -39,7 +40,8 @@ struct StageSelection {
   mm3d_confidence_options confidence_options;
   mm3d_icp_rejection_options reject_options;           // the ICP's correspondence rejection: no method object, the jobs carry them
   mm3d_icp_color_options color_options;                // coloured ICP: `color` is non-null exactly while they are enabled
-  StageSelection();                                    // capi.cpp: the options are the seven mm3d_*_options_default's
+  mm3d_icp_generalized_options generalized_options;    // generalized ICP: `generalized` is non-null exactly while they are enabled
+  StageSelection();                                    // capi.cpp: the options are the eight mm3d_*_options_default's
   // the ICP of the pair stage rejects correspondences (mm3d_set_icp_rejection)
   bool rejecting() const { return reject_options.one_to_one || reject_options.distance != MM3D_REJECT_NONE; }
   int icp_method() const;                              // MM3D_ICP_*
@@ -49,7 +51,7 @@ struct StageSelection {
   // rand(), which is MATCHING's case in pair_rand_replay
   int replay_method(const mm3d_params *p) const { return coarse || prerejective(p) ? (int)MM3D_EST_MATCHING : (int)p->estimation_method; }
   // such a pair is estimated by pairs_estimate_batch alone (pair_estimate_impl hands it a batch of one)
-  bool batch_only(const mm3d_params *p) const { return icp || refine || coarse || confidence || color || rejecting() || prerejective(p); }
+  bool batch_only(const mm3d_params *p) const { return icp || refine || coarse || confidence || color || generalized || rejecting() || prerejective(p); }
 };
 
 // The feature / pair cache of mm3d_estimate_maps_transforms (mm3d_set_map_cache; the concrete class is map_cache.cpp's).  The
@@ -260,7 +262,7 @@ struct mm3d_map {
   mm3d_desc *desc = nullptr;
   // What the opt-in stages keep of the points, null until one asks: made and replaced through map_kept (map_kept.hpp) alone,
   // by mm3d_map_prepare or a pair's first use of the map.
-  std::unique_ptr<mm3d_normals> normals;            // (normal_radius) point-to-plane ICP, the correlative signature
+  std::unique_ptr<mm3d_normals> normals;            // (normal_radius) point-to-plane, coloured and generalized ICP, the correlative signature
   std::unique_ptr<mm3d::NdtTable> ndt;              // NDT's voxel Gaussians
   std::unique_ptr<mm3d::CoarseSignature> coarse;    // the correlative alignment's signature
   std::unique_ptr<mm3d::OverlapTable> overlap;      // the overlap confidence's table
@@ -390,6 +392,10 @@ struct IcpScoreJob {
   // of the geometric rows (the same for every job of a batch)
   const float4 *tgt_color = nullptr;
   double color_lambda = 1.0;
+  // generalized ICP (mm3d_set_icp_generalized; icp_generalized.hip): the source's normals, in its order, and epsilon (the same
+  // for every job of a batch)
+  const mm3d_normals *src_normals = nullptr;
+  double generalized_epsilon = 1e-3;
 };
 struct IcpStep;      // nn_core.hpp
 // The ICP + score tail of a batch of pairs (nn.hip) with `method`'s ICP; null: the reference's point-to-point ICP.  When the ICP
@@ -397,7 +403,8 @@ struct IcpStep;      // nn_core.hpp
 void icp_score_batch(Context *c, const IcpMethodBase *method, IcpScoreJob *jobs, int n_jobs, bool run_icp, double max_corr_dist,
                      int max_iterations, double eps, bool want_score, double score_max_distance);
 // What stands in the place of the pair stage's point-to-point ICP on a context: point-to-plane (mm3d_set_icp_method,
-// icp_plane.hip), coloured ICP (mm3d_set_icp_color, icp_color.hip) or NDT (mm3d_set_refinement, ndt.hip).  Like MapCacheBase,
+// icp_plane.hip), coloured ICP (mm3d_set_icp_color, icp_color.hip), generalized ICP (mm3d_set_icp_generalized,
+// icp_generalized.hip) or NDT (mm3d_set_refinement, ndt.hip).  Like MapCacheBase,
 // the drivers in capi.cpp only see this interface, so the host code links without the kernels (tests/host_san); a null
 // pointer on the context means the reference's point-to-point ICP.
 struct IcpMethodBase {
@@ -409,6 +416,8 @@ struct IcpMethodBase {
   // what the method keeps on a target map beyond its search structures (point-to-plane's normals, NDT's voxel table, the
   // gradient records): made when missing or stale (map_kept.hpp; no wait when it is there), and bound to `job` when there is one
   virtual void prepare_target(mm3d_ctx *, const mm3d_map *, const mm3d_params *, IcpScoreJob *) const = 0;
+  // the same for a pair's source map (generalized ICP's normals); the others keep nothing on a source
+  virtual void prepare_source(mm3d_ctx *, const mm3d_map *, const mm3d_params *, IcpScoreJob *) const {}
 };
 inline int StageSelection::icp_method() const { return icp ? icp->method() : MM3D_ICP_POINT_TO_POINT; }
 struct PairFront;
