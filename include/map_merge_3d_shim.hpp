@@ -246,6 +246,37 @@ inline void check_icp_generalized_combinations(const mm3d_icp_generalized_option
   if (color.enabled)
     throw std::runtime_error("mm3d: MM3D_ICP_GENERALIZED is not available with an active MM3D_ICP_COLOR (coloured ICP has no plane-to-plane term)");
 }
+// MM3D_ESTIMATOR=consistency or consistency:<seeds>: under MATCHING the estimation context's pairs take their initial estimate
+// from the consistency graph of the correspondences (mm3d_set_estimator; without a number, mm3d_estimator_options_default's 64
+// seeds; tolerance and consensus keep its values, 0 = inlier_threshold and 20).  ransac or unset keeps the reference's RANSAC.
+// A seed count outside 1 .. 4096 or anything else throws, as a malformed MM3D_COARSE does.
+inline mm3d_estimator_options parse_estimator(const char *value)
+{
+  mm3d_estimator_options o;
+  o.method = MM3D_ESTIMATOR_RANSAC;
+  o.tolerance = 0.0;
+  o.seeds = 64;
+  o.consensus = 20;
+  const std::string v = value ? value : "";
+  if (v.empty() || v == "ransac") return o;
+  bool ok = v.compare(0, 11, "consistency") == 0 && (v.size() == 11 || v[11] == ':');
+  if (ok && v.size() > 11) {
+    const char *s = v.c_str() + 12;
+    char *end = nullptr;
+    const long n = std::strtol(s, &end, 10);
+    ok = end != s && *end == '\0' && *s >= '0' && *s <= '9' && n >= 1 && n <= 4096;
+    if (ok) o.seeds = (int)n;
+  }
+  if (!ok) throw std::runtime_error("mm3d: MM3D_ESTIMATOR must be ransac, consistency or consistency:<seeds in 1 .. 4096>, not '" + v + "'");
+  o.method = MM3D_ESTIMATOR_CONSISTENCY;
+  return o;
+}
+// Not available on a device list (its devices' pair loops run RANSAC): consistency with MM3D_DEVICES set as well throws.
+inline void check_estimator_devices(const mm3d_estimator_options &o, const char *devices)
+{
+  if (o.method == MM3D_ESTIMATOR_CONSISTENCY && devices && *devices)
+    throw std::runtime_error("mm3d: MM3D_ESTIMATOR=consistency is not available with MM3D_DEVICES (a device list's pair loops run RANSAC)");
+}
 }  // namespace mm3d_shim
 }  // namespace map_merge_3d
 
@@ -333,7 +364,10 @@ inline mm3d_ctx *ctx()
   // MM3D_ICP_REJECT=one_to_one+trimmed:0.7 ...: parse_icp_reject above.  Not available on a device list: an active value with MM3D_DEVICES set as well throws.
   // MM3D_ICP_COLOR=1 or <lambda>[:<radius>]: parse_icp_color above.  Not available on a device list nor with an active MM3D_ICP_REJECT: either throws.
   // MM3D_ICP_GENERALIZED=1 or <epsilon>: parse_icp_generalized above.  Not available on a device list nor with an active MM3D_ICP_REJECT or MM3D_ICP_COLOR: each throws.
+  // MM3D_ESTIMATOR=consistency[:<seeds>]: parse_estimator above.  Not available on a device list: consistency with MM3D_DEVICES set as well throws.
   static mm3d_ctx *c = [] {
+    const mm3d_estimator_options estimator = parse_estimator(std::getenv("MM3D_ESTIMATOR"));
+    check_estimator_devices(estimator, std::getenv("MM3D_DEVICES"));
     const mm3d_icp_rejection_options reject = parse_icp_reject(std::getenv("MM3D_ICP_REJECT"));
     check_icp_reject_devices(reject, std::getenv("MM3D_DEVICES"));
     const mm3d_icp_color_options color = parse_icp_color(std::getenv("MM3D_ICP_COLOR"));
@@ -392,6 +426,8 @@ inline mm3d_ctx *ctx()
       throw std::runtime_error(std::string("mm3d: MM3D_ICP_COLOR was refused: ") + mm3d_last_error(e));
     if (generalized.enabled && mm3d_set_icp_generalized(e, &generalized) != MM3D_OK)
       throw std::runtime_error(std::string("mm3d: MM3D_ICP_GENERALIZED was refused: ") + mm3d_last_error(e));
+    if (estimator.method != MM3D_ESTIMATOR_RANSAC && mm3d_set_estimator(e, &estimator) != MM3D_OK)
+      throw std::runtime_error(std::string("mm3d: MM3D_ESTIMATOR was refused: ") + mm3d_last_error(e));
     return e;
   }();
   return c;

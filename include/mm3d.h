@@ -1023,6 +1023,83 @@ int mm3d_estimate_transform_icp_generalized(mm3d_ctx *ctx, const mm3d_cloud *sou
  * 1 or 4 = forced in every generalized launch from now on; negative = no change.  Returns the value in force. */
 int mm3d_debug_icp_generalized_split(int split);
 
+/* ---------------------------------------------------------------- opt-in consistency-graph estimation under MATCHING
+ * mm3d_set_estimator replaces the RANSAC behind estimation_method = MATCHING (pcl's CorrespondenceRejectorSampleConsensus:
+ * 1 000 three-point samples, clean with probability w^3 at an inlier share w, so blind below about 10 %) by a deterministic
+ * estimator over the rigidity of the correspondence set: two correct correspondences preserve the distance between their
+ * points, a wrong one does so only by chance, so the graph of pairwise length-compatible correspondences holds the inliers as a
+ * clique (Leordeanu and Hebert, "A spectral technique for correspondence problems using pairwise constraints", ICCV 2005; Chen
+ * et al., "SC2-PCR", CVPR 2022).  It draws nothing from rand() nor from the RANSAC's mt19937.
+ * The rule.  Inputs: C correspondences (s_i, t_i, .) in the order of findFeatureCorrespondences, the two keypoint clouds,
+ * inlier_threshold and the options; p_i / q_i = the float coordinates of source keypoint s_i / target keypoint t_i, widened to
+ * double.  All arithmetic is one IEEE operation per written operation (the library is built with -ffp-contract=off).
+ *  1. Compatibility.  tau = options.tolerance, or inlier_threshold when it is 0; t2 = tau tau.  For i != j:
+ *     da = (dx dx + dy dy) + dz dz on p_i - p_j, db likewise on q_i - q_j, and A_ij = 1 exactly when s_i != s_j, t_i != t_j,
+ *     da > t2, db > t2 and e e <= 4.0 (da db) with e = (da + db) - t2 -- which is | |p_i-p_j| - |q_i-q_j| | <= tau without a
+ *     square root.  Anything non-finite fails, because every comparison is false.  A is symmetric with a zero diagonal, kept as
+ *     bit rows of ceil(C / 64) 64-bit words: bit j of row i is in word j / 64, bit j % 64; bits at and beyond C are zero.
+ *  2. Degree.  deg_i = sum_j A_ij.
+ *  3. Seeds.  The correspondences with deg_i >= 2, ordered by (deg descending, i ascending); the first
+ *     min(options.seeds, their number) are kept, and the position in that list is the seed's rank.
+ *  4. Second order, per seed s.  S_sj = A_sj ? popcount(row_s & row_j) : 0, the number of correspondences compatible with both.
+ *     The consensus set K_s is s together with the options.consensus - 1 indices j of largest S_sj >= 1, ties to the lower j;
+ *     it is read in ascending index order.  A seed with |K_s| < 3 has no hypothesis.
+ *  5. Hypothesis.  Umeyama without scale over the pairs of K_s: the sums in double, in ascending index order, the SVD core of
+ *     the library at precision 1e-12 (as the prerejective refit), the result rounded once to a float 4x4.
+ *  6. Score.  The number of the C correspondences within the threshold under the hypothesis, as RANSAC counts them: the float
+ *     transform, d2 < inlier_threshold^2.
+ *  7. Pick.  The hypothesis with the most inliers, ties to the lower rank.  Its transform goes through what RANSAC's best model
+ *     goes through: the inliers in correspondence order, failure below three inliers or on an identity model, the float
+ *     Umeyama over the inliers.  No seed or no hypothesis: the all-zero matrix with no inliers, the reference's "could not be
+ *     estimated".
+ *  8. Limits.  C < 3 gives the zero matrix; C > 32 768 gives MM3D_EUNSUPPORTED (the bit rows would pass 128 MB per pair in
+ *     flight).
+ * Results are bit-identical whatever else runs: every decision is an integer or a comparison of fixed-order doubles, so they
+ * do not depend on the stream count, the batch, the driver, the map cache or mm3d_srand.
+ * The stage applies where params.estimation_method == MATCHING and no coarse alignment is selected, in
+ * mm3d_estimate_maps_transforms and mm3d_pair_estimate; a pair record's n_correspondences and n_inliers mean what they mean
+ * under RANSAC.  mm3d_estimate_transform and mm3d_estimate_transform_from_correspondences stay the reference's. */
+typedef enum { MM3D_ESTIMATOR_RANSAC = 0, MM3D_ESTIMATOR_CONSISTENCY = 1 } mm3d_estimator_method;
+typedef struct mm3d_estimator_options {
+  int method;              /* mm3d_estimator_method */
+  double tolerance;        /* tau of step 1, >= 0; 0 = inlier_threshold */
+  int seeds;               /* 1..4096 */
+  int consensus;           /* 3..64: |K_s| at most */
+} mm3d_estimator_options;
+void mm3d_estimator_options_default(mm3d_estimator_options *o);   /* RANSAC, 0, 64, 20 */
+/* MM3D_EINVAL: ctx or options NULL, an unknown method, or a value out of range (checked whatever the method).
+ * MM3D_EUNSUPPORTED: CONSISTENCY on a device-list context (mm3d_create_devices); mm3d_shard_begin returns MM3D_EUNSUPPORTED on
+ * a context with it selected.  The setting reaches the context's mm3d_set_streams helpers, in either order, and is part of the
+ * map cache's pair key while selected. */
+int mm3d_set_estimator(mm3d_ctx *ctx, const mm3d_estimator_options *options);
+int mm3d_get_estimator(const mm3d_ctx *ctx, mm3d_estimator_options *options);   /* MM3D_EINVAL for NULL */
+typedef struct mm3d_estimator_stats {
+  long long correspondences;   /* C */
+  long long edges;             /* sum of deg / 2 */
+  long long seeds;             /* seeds kept (step 3) */
+  long long hypotheses;        /* seeds with a hypothesis (step 4) */
+  int winner_index;            /* the winning seed's correspondence, -1: none */
+  int winner_rank;             /* its rank, -1: none */
+  int winner_inliers;          /* its count of step 6 */
+} mm3d_estimator_stats;
+/* of the context's most recent pair estimated with the stage selected */
+int mm3d_last_estimator_stats(const mm3d_ctx *ctx, mm3d_estimator_stats *stats);
+/* the rule above on a caller's correspondences, whatever options->method and the context's setting say; the arguments of
+ * mm3d_estimate_transform_from_correspondences, the options and the statistics (may be NULL).  MM3D_EINVAL: a NULL argument,
+ * options out of range, a correspondence index out of range; MM3D_EUNSUPPORTED: n_corr > 32 768. */
+int mm3d_estimate_transform_consistency(mm3d_ctx *ctx, const mm3d_cloud *source_keypoints, const mm3d_cloud *target_keypoints,
+                                        const mm3d_corr *corr, size_t n_corr, double inlier_threshold,
+                                        const mm3d_estimator_options *options, float T[16], mm3d_corr *inliers, size_t cap,
+                                        size_t *n_inliers, mm3d_estimator_stats *stats);
+/* test hook: the intermediate results of the same call (any output may be NULL).  With W = ceil(n_corr / 64) and
+ * H = min(options->seeds, n_corr): rows [n_corr][W] the bit rows, deg [n_corr], seeds [H] by rank (-1 padded) and their number,
+ * consensus [H][options->consensus] ascending (-1 padded), hypotheses [H][16] column-major floats (zero without one),
+ * counts [H] (-1 without a hypothesis).  n_corr < 3 leaves everything untouched but *n_seeds = 0. */
+int mm3d_debug_consistency(mm3d_ctx *ctx, const mm3d_cloud *source_keypoints, const mm3d_cloud *target_keypoints,
+                           const mm3d_corr *corr, size_t n_corr, double inlier_threshold, const mm3d_estimator_options *options,
+                           unsigned long long *rows, int *deg, int *seeds, size_t *n_seeds, int *consensus, float *hypotheses,
+                           int *counts);
+
 #ifdef __cplusplus
 }
 #endif

@@ -233,6 +233,37 @@ class IcpGeneralizedOptions(C.Structure):
         return tuple(int(getattr(self, k)) if t is C.c_int else float(getattr(self, k)) for k, t in self._fields_)
 
 
+class EstimatorMethod(enum.IntEnum):   # mm3d_estimator_method (not a reference enum)
+    RANSAC = 0
+    CONSISTENCY = 1
+
+
+class EstimatorOptions(C.Structure):
+    """mm3d_estimator_options (mm3d_set_estimator); the defaults are mm3d_estimator_options_default's."""
+    _fields_ = [("method", C.c_int), ("tolerance", C.c_double), ("seeds", C.c_int), ("consensus", C.c_int)]
+
+    def __init__(self, **kw):
+        super().__init__()
+        lib().mm3d_estimator_options_default(C.byref(self))
+        kinds = dict(self._fields_)
+        for k, v in kw.items():
+            if k not in kinds:
+                raise TypeError("unknown estimator option " + k)
+            setattr(self, k, int(v) if kinds[k] is C.c_int else float(v))
+
+    def as_tuple(self):
+        return tuple(int(getattr(self, k)) if t is C.c_int else float(getattr(self, k)) for k, t in self._fields_)
+
+
+class EstimatorStats(C.Structure):
+    """mm3d_estimator_stats"""
+    _fields_ = [("correspondences", C.c_longlong), ("edges", C.c_longlong), ("seeds", C.c_longlong), ("hypotheses", C.c_longlong),
+                ("winner_index", C.c_int), ("winner_rank", C.c_int), ("winner_inliers", C.c_int)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 class IcpRejectionStats(C.Structure):
     """mm3d_icp_rejection_stats"""
     _fields_ = [("matched", C.c_longlong), ("after_one_to_one", C.c_longlong), ("kept", C.c_longlong), ("threshold_d2", C.c_float),
@@ -496,6 +527,22 @@ class Context:
         self._ck(lib().mm3d_last_alignment_stats(self._h, C.byref(st)))
         return st.as_dict()
 
+    def setEstimator(self, options=None, **kw):
+        """mm3d_set_estimator: what estimates a pair from its correspondences under MATCHING.  An EstimatorOptions, or its fields
+        as keywords (method=EstimatorMethod.CONSISTENCY, tolerance=..., seeds=..., consensus=...)."""
+        o = options if options is not None else EstimatorOptions(**kw)
+        self._ck(lib().mm3d_set_estimator(self._h, C.byref(o)))
+
+    def getEstimator(self) -> "EstimatorOptions":
+        o = EstimatorOptions()
+        self._ck(lib().mm3d_get_estimator(self._h, C.byref(o)))
+        return o
+
+    def lastEstimatorStats(self) -> dict:
+        st = EstimatorStats()
+        self._ck(lib().mm3d_last_estimator_stats(self._h, C.byref(st)))
+        return st.as_dict()
+
     def setKeypoints(self, options=None, **kw):
         """mm3d_set_keypoints: where the whole-map calls take a map's keypoints from.  A KeypointOptions, or its fields as
         keywords (source=KeypointSource.UNIFORM, leaf=... in metres; 0 = the default fraction of descriptor_radius)."""
@@ -704,6 +751,45 @@ class Context:
             C.c_double(inlier_threshold), T.ctypes.data_as(C.c_void_p), inl.ctypes.data_as(C.c_void_p),
             C.c_size_t(len(inl)), C.byref(n)))
         return _Tout(T), inl[:n.value].copy()
+
+    def estimateTransformConsistency(self, source_keypoints, target_keypoints, correspondences, inlier_threshold: float,
+                                     options=None, **kw):
+        """mm3d_estimate_transform_consistency: (T, inliers, stats dict), whatever the context's setting."""
+        o = options if options is not None else EstimatorOptions(**kw)
+        corr = np.ascontiguousarray(correspondences, dtype=CORR)
+        T = np.zeros(16, dtype=np.float32)
+        inl = np.empty(max(len(corr), 1), dtype=CORR)
+        n = C.c_size_t()
+        st = EstimatorStats()
+        self._ck(lib().mm3d_estimate_transform_consistency(
+            self._h, source_keypoints._h, target_keypoints._h, corr.ctypes.data_as(C.c_void_p), C.c_size_t(len(corr)),
+            C.c_double(inlier_threshold), C.byref(o), T.ctypes.data_as(C.c_void_p), inl.ctypes.data_as(C.c_void_p),
+            C.c_size_t(len(inl)), C.byref(n), C.byref(st)))
+        return _Tout(T), inl[:n.value].copy(), st.as_dict()
+
+    def consistencyGraph(self, source_keypoints, target_keypoints, correspondences, inlier_threshold: float, options=None, **kw):
+        """mm3d_debug_consistency: a dict of rows [C][ceil(C / 64)] uint64, deg [C], seeds [n_seeds] by rank, consensus
+        [n_seeds][consensus] ascending and -1 padded, hypotheses [n_seeds][4][4] (row-major, as every transform here) and
+        counts [n_seeds] (-1 without a hypothesis)."""
+        o = options if options is not None else EstimatorOptions(**kw)
+        corr = np.ascontiguousarray(correspondences, dtype=CORR)
+        n_c = len(corr)
+        W, H, K = (n_c + 63) // 64, min(int(o.seeds), n_c), int(o.consensus)
+        rows = np.zeros((n_c, W), dtype=np.uint64)
+        deg = np.zeros(n_c, dtype=np.int32)
+        seeds = np.full(max(H, 1), -1, dtype=np.int32)
+        cons = np.full((max(H, 1), K), -1, dtype=np.int32)
+        hyp = np.zeros((max(H, 1), 16), dtype=np.float32)
+        counts = np.full(max(H, 1), -1, dtype=np.int32)
+        n = C.c_size_t()
+        self._ck(lib().mm3d_debug_consistency(
+            self._h, source_keypoints._h, target_keypoints._h, corr.ctypes.data_as(C.c_void_p), C.c_size_t(n_c),
+            C.c_double(inlier_threshold), C.byref(o), rows.ctypes.data_as(C.c_void_p), deg.ctypes.data_as(C.c_void_p),
+            seeds.ctypes.data_as(C.c_void_p), C.byref(n), cons.ctypes.data_as(C.c_void_p), hyp.ctypes.data_as(C.c_void_p),
+            counts.ctypes.data_as(C.c_void_p)))
+        m = int(n.value)
+        return dict(rows=rows, deg=deg, seeds=seeds[:m].copy(), consensus=cons[:m].copy(),
+                    hypotheses=hyp[:m].reshape(m, 4, 4).transpose(0, 2, 1).copy(), counts=counts[:m].copy())
 
     def estimateTransformFromDescriptorsSets(self, source_keypoints, source_descriptors, target_keypoints,
                                              target_descriptors, min_sample_distance, max_correspondence_distance,

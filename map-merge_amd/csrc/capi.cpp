@@ -38,6 +38,7 @@ mm3d::StageSelection::StageSelection()
   mm3d_icp_rejection_options_default(&reject_options);
   mm3d_icp_color_options_default(&color_options);
   mm3d_icp_generalized_options_default(&generalized_options);
+  mm3d_estimator_options_default(&estimator_options);
 }
 
 void mm3d::select_stages(mm3d_ctx *ctx, bool peers_follow, const std::function<void(StageSelection &)> &edit)
@@ -199,6 +200,10 @@ void mm3d_icp_color_options_default(mm3d_icp_color_options *o)
 void mm3d_icp_generalized_options_default(mm3d_icp_generalized_options *o)
 {
   if (o) *o = mm3d_icp_generalized_options{0, 1e-3};
+}
+void mm3d_estimator_options_default(mm3d_estimator_options *o)
+{
+  if (o) *o = mm3d_estimator_options{MM3D_ESTIMATOR_RANSAC, 0.0, 64, 20};
 }
 
 // ---------------------------------------------------------------- context

@@ -65,6 +65,7 @@ int mm3d_shard_begin(mm3d_ctx *ctx, const mm3d_cloud_view *clouds, size_t n, con
     if (sel.rejecting()) throw Error(MM3D_EUNSUPPORTED, "mm3d_shard_begin: the ranks' pair loops run the ICP without correspondence rejection");
     if (sel.color) throw Error(MM3D_EUNSUPPORTED, "mm3d_shard_begin: shard bundles carry no colour gradients for coloured ICP");
     if (sel.generalized) throw Error(MM3D_EUNSUPPORTED, "mm3d_shard_begin: shard bundles carry no normals for generalized ICP");
+    if (sel.estimator) throw Error(MM3D_EUNSUPPORTED, "mm3d_shard_begin: the ranks' pair loops run RANSAC, not the consistency estimation");
     *out = shard_begin_impl(ctx, clouds, n, params, rank, world);
   });
 }

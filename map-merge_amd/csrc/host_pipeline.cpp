@@ -84,6 +84,48 @@ size_t find_correspondences(Context *c, const mm3d_desc *s, const mm3d_desc *t, 
   return out.size();
 }
 
+// ---------------------------------------------------------------- what the best model goes through
+// R/src/matching.cpp:127-140
+size_t ransac_model_tail(const std::vector<float4> &skp, const std::vector<float4> &tkp, const mm3d_corr *corr, const std::vector<int> &indices,
+                         const std::vector<int> &indices_tgt, const float bT[16], double thr2, float T[16], std::vector<mm3d_corr> &inliers)
+{
+  const int n_corr = (int)indices.size();
+  int max_src = 0;
+  for (int i = 0; i < n_corr; ++i) max_src = std::max(max_src, indices[i]);
+  std::vector<int> pos_of_src(max_src + 1, -1);
+  for (int i = 0; i < n_corr; ++i) pos_of_src[indices[i]] = i;
+  // selectWithinDistance -> remaining correspondences in index order
+  for (int i = 0; i < n_corr; ++i) {
+    float p[3];
+    const float4 &s = skp[indices[i]], &t = tkp[indices_tgt[i]];
+    xform_host(bT, s.x, s.y, s.z, p);
+    const float dx = p[0] - t.x, dy = p[1] - t.y, dz = p[2] - t.z;
+    const float d = dx * dx + dy * dy + dz * dz;
+    if ((double)d < thr2) inliers.push_back(corr[pos_of_src[indices[i]]]);
+  }
+  bool fail = inliers.size() < 3;
+  if (!fail) {
+    // ransac.getBestTransformation().isIdentity()  (Eigen isIdentity, float precision 1e-5)
+    bool is_id = true;
+    for (int cc = 0; cc < 4 && is_id; ++cc)
+      for (int r = 0; r < 4; ++r) {
+        const float v = bT[cc * 4 + r];
+        if (r == cc) { if (!(std::fabs(v - 1.0f) <= 1e-5f * std::fmin(std::fabs(v), 1.0f))) { is_id = false; break; } }
+        else { if (!(std::fabs(v) <= 1e-5f)) { is_id = false; break; } }
+      }
+    fail = is_id;
+  }
+  if (fail) { inliers.clear(); return 0; }
+  std::vector<float> s(inliers.size() * 3), d(inliers.size() * 3);
+  for (size_t i = 0; i < inliers.size(); ++i) {
+    const float4 &p = skp[inliers[i].index_query], &q = tkp[inliers[i].index_match];
+    s[i * 3] = p.x; s[i * 3 + 1] = p.y; s[i * 3 + 2] = p.z;
+    d[i * 3] = q.x; d[i * 3 + 1] = q.y; d[i * 3 + 2] = q.z;
+  }
+  umeyama_f32(s.data(), d.data(), (int)inliers.size(), T);
+  return inliers.size();
+}
+
 // ---------------------------------------------------------------- RANSAC + SVD on inliers
 // R/src/matching.cpp:110-140
 size_t ransac_transform(Context *c, const mm3d_cloud *skp_, const mm3d_cloud *tkp_, const mm3d_corr *corr,
@@ -106,8 +148,8 @@ size_t ransac_transform(Context *c, const mm3d_cloud *skp_, const mm3d_cloud *tk
     indices[i] = corr[i].index_query; indices_tgt[i] = corr[i].index_match; shuffled[i] = indices[i];
     max_src = std::max(max_src, indices[i]);
   }
-  std::vector<int> tgt_of_src(max_src + 1, -1), pos_of_src(max_src + 1, -1);
-  for (int i = 0; i < n_corr; ++i) { tgt_of_src[indices[i]] = indices_tgt[i]; pos_of_src[indices[i]] = i; }
+  std::vector<int> tgt_of_src(max_src + 1, -1);
+  for (int i = 0; i < n_corr; ++i) tgt_of_src[indices[i]] = indices_tgt[i];
 
   // computeSampleDistanceThreshold(cloud, indices): float raw-moment covariance -> eigen33
   double sample_dist_thresh;
@@ -200,37 +242,7 @@ size_t ransac_transform(Context *c, const mm3d_cloud *skp_, const mm3d_cloud *tk
     if (iterations > max_iterations) break;
   }
   if (best_h < 0) return 0;
-  const float *bT = &T_all[(size_t)best_h * 16];
-  // selectWithinDistance -> remaining correspondences in index order
-  for (int i = 0; i < n_corr; ++i) {
-    float p[3];
-    const float4 &s = skp[indices[i]], &t = tkp[indices_tgt[i]];
-    xform_host(bT, s.x, s.y, s.z, p);
-    const float dx = p[0] - t.x, dy = p[1] - t.y, dz = p[2] - t.z;
-    const float d = dx * dx + dy * dy + dz * dz;
-    if ((double)d < thr2) inliers.push_back(corr[pos_of_src[indices[i]]]);
-  }
-  bool fail = inliers.size() < 3;
-  if (!fail) {
-    // ransac.getBestTransformation().isIdentity()  (Eigen isIdentity, float precision 1e-5)
-    bool is_id = true;
-    for (int cc = 0; cc < 4 && is_id; ++cc)
-      for (int r = 0; r < 4; ++r) {
-        const float v = bT[cc * 4 + r];
-        if (r == cc) { if (!(std::fabs(v - 1.0f) <= 1e-5f * std::fmin(std::fabs(v), 1.0f))) { is_id = false; break; } }
-        else { if (!(std::fabs(v) <= 1e-5f)) { is_id = false; break; } }
-      }
-    fail = is_id;
-  }
-  if (fail) { inliers.clear(); return 0; }
-  std::vector<float> s(inliers.size() * 3), d(inliers.size() * 3);
-  for (size_t i = 0; i < inliers.size(); ++i) {
-    const float4 &p = skp[inliers[i].index_query], &q = tkp[inliers[i].index_match];
-    s[i * 3] = p.x; s[i * 3 + 1] = p.y; s[i * 3 + 2] = p.z;
-    d[i * 3] = q.x; d[i * 3 + 1] = q.y; d[i * 3 + 2] = q.z;
-  }
-  umeyama_f32(s.data(), d.data(), (int)inliers.size(), T);
-  return inliers.size();
+  return ransac_model_tail(skp, tkp, corr, indices, indices_tgt, &T_all[(size_t)best_h * 16], thr2, T, inliers);
 }
 
 // The rand() stream of one SampleConsensusInitialAlignment::computeTransformation: H iterations of

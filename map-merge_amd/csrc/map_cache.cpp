@@ -89,6 +89,11 @@ std::string pair_params_key(const mm3d_params *p, const StageSelection &sel)
   const mm3d_icp_generalized_options &gen = sel.generalized_options;
   const bool generalized = gen.enabled != 0;
   k.i32(generalized ? gen.enabled : 0).f64(generalized ? gen.epsilon : 0.0);
+  // the estimator under MATCHING (mm3d_set_estimator): a RANSAC record is never a consistency one's, nor a consistency one
+  // that of other options (which RANSAC does not read: whatever they are, its records are shared)
+  const mm3d_estimator_options &est = sel.estimator_options;
+  const bool cons = est.method == MM3D_ESTIMATOR_CONSISTENCY;
+  k.i32(cons ? est.method : 0).f64(cons ? est.tolerance : 0.0).i32(cons ? est.seeds : 0).i32(cons ? est.consensus : 0);
   return k.s;
 }
 

@@ -230,6 +230,10 @@ void mm3d::pairs_estimate_batch(mm3d_ctx *ctx, PairWork *w, size_t n, const mm3d
       // the same inputs, max_correspondence_distance as the inlier distance; the generator's seed, none of its draws
       sel.align->front(ctx, sel.align_options, w[i].rnd.seed0, w[i].s->keypoints, w[i].s->desc, w[i].t->keypoints, w[i].t->desc,
                        p->max_correspondence_distance, fronts[i], &ctx->last_align_stats);
+    } else if (sel.consistency(p)) {
+      // the same correspondences, the consistency graph in RANSAC's place (mm3d_set_estimator); nothing of the generator
+      sel.estimator->front(ctx, sel.estimator_options, w[i].s->keypoints, w[i].s->desc, w[i].t->keypoints, w[i].t->desc,
+                           p->inlier_threshold, (size_t)p->matching_k, fronts[i], &ctx->last_estimator_stats);
     } else if (p->estimation_method == MM3D_EST_SAC_IA) {
       // argument mapping of matching.cpp:243-246: min_sample_distance := inlier_threshold
       sac_ia_replay(ctx, w[i].s->keypoints, w[i].s->desc, w[i].t->keypoints, w[i].t->desc, p->inlier_threshold, p->max_iterations, true,

@@ -19,9 +19,11 @@ struct AlignMethodBase;
 struct KeypointSourceBase;
 struct CoarseMethodBase;
 struct ConfidenceMethodBase;
+struct EstimatorMethodBase;
 
 // The opt-in stages of a context's pipeline (mm3d_set_icp_method, mm3d_set_alignment, mm3d_set_keypoints, mm3d_set_refinement,
-// mm3d_set_coarse_alignment, mm3d_set_confidence, mm3d_set_icp_rejection, mm3d_set_icp_color, mm3d_set_icp_generalized): a null method = the reference's stage.  The methods are process-wide
+// mm3d_set_coarse_alignment, mm3d_set_confidence, mm3d_set_icp_rejection, mm3d_set_icp_color, mm3d_set_icp_generalized,
+// mm3d_set_estimator): a null method = the reference's stage.  The methods are process-wide
 // objects of their kernel files that hold no state and are not owned.  Every context has its own copy of the record; only
 // select_stages (drivers.hpp) changes one, and it and mm3d_set_streams hand the root's copy to the helpers.
 struct StageSelection {
@@ -33,6 +35,7 @@ struct StageSelection {
   const ConfidenceMethodBase *confidence = nullptr;    // what a pair record's confidence is
   const IcpMethodBase *color = nullptr;                // coloured ICP in the place of `icp`'s, which keeps its own value beside it
   const IcpMethodBase *generalized = nullptr;          // generalized ICP in the place of `icp`'s, which keeps its own value beside it
+  const EstimatorMethodBase *estimator = nullptr;      // the initial estimate under MATCHING: the consistency graph in RANSAC's place
   mm3d_alignment_options align_options;
   mm3d_keypoint_options keypoint_options;
   mm3d_refine_options refine_options;
@@ -41,17 +44,20 @@ struct StageSelection {
   mm3d_icp_rejection_options reject_options;           // the ICP's correspondence rejection: no method object, the jobs carry them
   mm3d_icp_color_options color_options;                // coloured ICP: `color` is non-null exactly while they are enabled
   mm3d_icp_generalized_options generalized_options;    // generalized ICP: `generalized` is non-null exactly while they are enabled
-  StageSelection();                                    // capi.cpp: the options are the eight mm3d_*_options_default's
+  mm3d_estimator_options estimator_options;            // `estimator` is non-null exactly while their method is CONSISTENCY
+  StageSelection();                                    // capi.cpp: the options are the nine mm3d_*_options_default's
   // the ICP of the pair stage rejects correspondences (mm3d_set_icp_rejection)
   bool rejecting() const { return reject_options.one_to_one || reject_options.distance != MM3D_REJECT_NONE; }
   int icp_method() const;                              // MM3D_ICP_*
   // the pair's initial estimate is the prerejective alignment's
   bool prerejective(const mm3d_params *p) const { return !coarse && align && p->estimation_method == MM3D_EST_SAC_IA; }
+  // the pair's initial estimate is the consistency graph's (MATCHING draws nothing from rand(): replay_method is as it was)
+  bool consistency(const mm3d_params *p) const { return !coarse && estimator && p->estimation_method == MM3D_EST_MATCHING; }
   // The estimation method as the rand() replay sees it: neither the prerejective nor the correlative alignment draws from
   // rand(), which is MATCHING's case in pair_rand_replay
   int replay_method(const mm3d_params *p) const { return coarse || prerejective(p) ? (int)MM3D_EST_MATCHING : (int)p->estimation_method; }
   // such a pair is estimated by pairs_estimate_batch alone (pair_estimate_impl hands it a batch of one)
-  bool batch_only(const mm3d_params *p) const { return icp || refine || coarse || confidence || color || generalized || rejecting() || prerejective(p); }
+  bool batch_only(const mm3d_params *p) const { return icp || refine || coarse || confidence || color || generalized || rejecting() || prerejective(p) || consistency(p); }
 };
 
 // The feature / pair cache of mm3d_estimate_maps_transforms (mm3d_set_map_cache; the concrete class is map_cache.cpp's).  The
@@ -87,6 +93,7 @@ struct mm3d_ctx : mm3d::Context {
   mm3d_coarse_stats last_coarse_stats{0, 0, 0, 0, 0, -1, 0, 0};
   mm3d_overlap_stats last_confidence_stats{0, 0, 0, 0, 0, 0, 0.0};
   mm3d_icp_rejection_stats last_reject_stats{0, 0, 0, INFINITY, 0, 0};   // (mm3d_last_icp_rejection_stats)
+  mm3d_estimator_stats last_estimator_stats{0, 0, 0, 0, -1, -1, 0};      // (mm3d_last_estimator_stats)
   // mm3d_set_streams: helper contexts (one HIP stream + one host thread each while a call is running)
   // that mm3d_estimate_maps_transforms deals maps and pairs to; owned by this context
   std::vector<mm3d_ctx *> helpers;
@@ -464,6 +471,15 @@ struct ConfidenceMethodBase {
   // last pair's counts
   virtual void score(mm3d_ctx *ctx, ConfidencePair *pairs, size_t n, const mm3d_params *p, mm3d_overlap_stats *stats) const = 0;
 };
+// What takes RANSAC's place behind estimation_method = MATCHING (mm3d_set_estimator; the one concrete class is
+// estimate_consistency.hip's).  Like AlignMethodBase, the drivers and pair_estimate.cpp only see this interface, so the host
+// code links without the new kernels (tests/host_san); a null pointer on the context means the reference's RANSAC.
+struct EstimatorMethodBase {
+  virtual ~EstimatorMethodBase() = default;
+  // estimate_pair_front's MATCHING branch with this method: findFeatureCorrespondences, then the estimate in f.T0 and f.counts
+  virtual void front(Context *c, const mm3d_estimator_options &o, const mm3d_cloud *skp, const mm3d_desc *sd, const mm3d_cloud *tkp,
+                     const mm3d_desc *td, double inlier_threshold, size_t matching_k, PairFront &f, mm3d_estimator_stats *stats) const = 0;
+};
 struct PairCounts { int n_correspondences = 0, n_inliers = 0, icp_correspondences = 0; };
 // ICP (optional) from a guess on the device (guess_dev != null) or on the host, then transformScore
 // (optional) of the result, with one host synchronisation
@@ -497,6 +513,11 @@ void prepare_sacia_target(Context *c, const mm3d_cloud *kp, float corr_thresh);
 size_t find_correspondences(Context *c, const mm3d_desc *s, const mm3d_desc *t, size_t k, std::vector<mm3d_corr> &out);
 size_t ransac_transform(Context *c, const mm3d_cloud *skp, const mm3d_cloud *tkp, const mm3d_corr *corr,
                         size_t n_corr, double inlier_threshold, float T[16], std::vector<mm3d_corr> &inliers);
+// What RANSAC's best model bT goes through (matching.cpp:127-140), shared with the consistency estimator: the correspondences
+// within thr2 under bT in index order, failure (0, T and inliers as they were) below three of them or on an identity model,
+// else umeyama_f32 over them into T.  is / it: the correspondences' keypoint indices, checked by the caller.
+size_t ransac_model_tail(const std::vector<float4> &skp, const std::vector<float4> &tkp, const mm3d_corr *corr, const std::vector<int> &is,
+                         const std::vector<int> &it, const float bT[16], double thr2, float T[16], std::vector<mm3d_corr> &inliers);
 // T_dev == nullptr: the winning transform is returned in T (host).  Otherwise, when the device path
 // ran, *T_dev receives it (16 floats on the device), T is left at identity and true is returned.
 bool sac_ia(Context *c, const mm3d_cloud *skp, const mm3d_desc *sd, const mm3d_cloud *tkp, const mm3d_desc *td,
