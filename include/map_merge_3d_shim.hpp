@@ -277,6 +277,55 @@ inline void check_estimator_devices(const mm3d_estimator_options &o, const char 
   if (o.method == MM3D_ESTIMATOR_CONSISTENCY && devices && *devices)
     throw std::runtime_error("mm3d: MM3D_ESTIMATOR=consistency is not available with MM3D_DEVICES (a device list's pair loops run RANSAC)");
 }
+// MM3D_ICP_SAMPLE=normal_space:<fraction>[:<bins>] or stride:<fraction>: the estimation context's ICP searches with a sample of
+// the source map (mm3d_set_icp_sampling): that fraction of its valid points, in (0, 1]; bins 1, 2, 4 or 8 cells per axis of a
+// face of the normal cube (without one: mm3d_icp_sampling_options_default's 4).  A method without a fraction takes the default
+// 0.25.  none or unset keeps every point.  Anything else throws, as a malformed MM3D_ICP_COLOR does.
+inline mm3d_icp_sampling_options parse_icp_sample(const char *value)
+{
+  mm3d_icp_sampling_options o;
+  o.method = MM3D_ICP_SAMPLE_NONE;
+  o.fraction = 0.25;
+  o.max_points = 0;
+  o.bins = 4;
+  const std::string v = value ? value : "";
+  if (v.empty() || v == "none") return o;
+  const std::string::size_type c1 = v.find(':');
+  const std::string name = v.substr(0, c1);
+  bool ok = name == "normal_space" || name == "stride";
+  o.method = name == "stride" ? MM3D_ICP_SAMPLE_STRIDE : MM3D_ICP_SAMPLE_NORMAL_SPACE;
+  if (ok && c1 != std::string::npos) {
+    const std::string::size_type c2 = v.find(':', c1 + 1);
+    const std::string frac = v.substr(c1 + 1, c2 == std::string::npos ? std::string::npos : c2 - c1 - 1);
+    char *end = nullptr;
+    o.fraction = std::strtod(frac.c_str(), &end);
+    ok = !frac.empty() && end == frac.c_str() + frac.size() && o.fraction > 0.0 && o.fraction <= 1.0;
+    if (ok && c2 != std::string::npos) {
+      const std::string b = v.substr(c2 + 1);
+      ok = o.method == MM3D_ICP_SAMPLE_NORMAL_SPACE && (b == "1" || b == "2" || b == "4" || b == "8");
+      if (ok) o.bins = b[0] - '0';
+    }
+  }
+  if (!ok)
+    throw std::runtime_error("mm3d: MM3D_ICP_SAMPLE must be none, normal_space[:<fraction in (0, 1]>[:<bins 1|2|4|8>]] or stride[:<fraction>], not '" + v + "'");
+  return o;
+}
+// Not available on a device list (its devices' pair loops search with the whole source), nor together with MM3D_REFINE=ndt, an
+// active MM3D_ICP_COLOR or MM3D_ICP_GENERALIZED (none of them reads a sample): each combination throws.
+inline void check_icp_sample_combinations(const mm3d_icp_sampling_options &o, const mm3d_refine_options &refine,
+                                          const mm3d_icp_color_options &color, const mm3d_icp_generalized_options &generalized,
+                                          const char *devices)
+{
+  if (o.method == MM3D_ICP_SAMPLE_NONE) return;
+  if (devices && *devices)
+    throw std::runtime_error("mm3d: MM3D_ICP_SAMPLE is not available with MM3D_DEVICES (a device list's pair loops search with the whole source)");
+  if (refine.method == MM3D_REFINE_NDT)
+    throw std::runtime_error("mm3d: MM3D_ICP_SAMPLE is not available with MM3D_REFINE=ndt (NDT searches nothing)");
+  if (color.enabled)
+    throw std::runtime_error("mm3d: MM3D_ICP_SAMPLE is not available with an active MM3D_ICP_COLOR (coloured ICP reads the whole source)");
+  if (generalized.enabled)
+    throw std::runtime_error("mm3d: MM3D_ICP_SAMPLE is not available with an active MM3D_ICP_GENERALIZED (generalized ICP reads the whole source)");
+}
 }  // namespace mm3d_shim
 }  // namespace map_merge_3d
 
@@ -365,6 +414,7 @@ inline mm3d_ctx *ctx()
   // MM3D_ICP_COLOR=1 or <lambda>[:<radius>]: parse_icp_color above.  Not available on a device list nor with an active MM3D_ICP_REJECT: either throws.
   // MM3D_ICP_GENERALIZED=1 or <epsilon>: parse_icp_generalized above.  Not available on a device list nor with an active MM3D_ICP_REJECT or MM3D_ICP_COLOR: each throws.
   // MM3D_ESTIMATOR=consistency[:<seeds>]: parse_estimator above.  Not available on a device list: consistency with MM3D_DEVICES set as well throws.
+  // MM3D_ICP_SAMPLE=normal_space:0.25[:<bins>] or stride:0.1: parse_icp_sample above.  Not available on a device list nor with MM3D_REFINE=ndt, MM3D_ICP_COLOR or MM3D_ICP_GENERALIZED: each throws.
   static mm3d_ctx *c = [] {
     const mm3d_estimator_options estimator = parse_estimator(std::getenv("MM3D_ESTIMATOR"));
     check_estimator_devices(estimator, std::getenv("MM3D_DEVICES"));
@@ -383,6 +433,8 @@ inline mm3d_ctx *ctx()
     mm3d_refine_options refine = parse_refine(std::getenv("MM3D_REFINE"));
     if (refine.method == MM3D_REFINE_NDT && std::getenv("MM3D_DEVICES") && *std::getenv("MM3D_DEVICES"))
       throw std::runtime_error("mm3d: MM3D_REFINE=ndt is not available with MM3D_DEVICES (a device list carries no voxel tables)");
+    const mm3d_icp_sampling_options sampling = parse_icp_sample(std::getenv("MM3D_ICP_SAMPLE"));
+    check_icp_sample_combinations(sampling, refine, color, generalized, std::getenv("MM3D_DEVICES"));
     const char *al = std::getenv("MM3D_ALIGN");
     const std::string align = al ? al : "";
     if (!align.empty() && align != "sac_ia" && align != "prerejective")
@@ -428,6 +480,8 @@ inline mm3d_ctx *ctx()
       throw std::runtime_error(std::string("mm3d: MM3D_ICP_GENERALIZED was refused: ") + mm3d_last_error(e));
     if (estimator.method != MM3D_ESTIMATOR_RANSAC && mm3d_set_estimator(e, &estimator) != MM3D_OK)
       throw std::runtime_error(std::string("mm3d: MM3D_ESTIMATOR was refused: ") + mm3d_last_error(e));
+    if (sampling.method != MM3D_ICP_SAMPLE_NONE && mm3d_set_icp_sampling(e, &sampling) != MM3D_OK)
+      throw std::runtime_error(std::string("mm3d: MM3D_ICP_SAMPLE was refused: ") + mm3d_last_error(e));
     return e;
   }();
   return c;

@@ -1100,6 +1100,81 @@ int mm3d_debug_consistency(mm3d_ctx *ctx, const mm3d_cloud *source_keypoints, co
                            unsigned long long *rows, int *deg, int *seeds, size_t *n_seeds, int *consensus, float *hypotheses,
                            int *counts);
 
+/* ---------------------------------------------------------------- opt-in ICP source sampling
+ * mm3d_set_icp_sampling makes the pair stage's ICP search a SAMPLE of the source map instead of every point of it: the step that
+ * PCL offers as NormalSpaceSampling and Open3D as a down-sampling before registration_icp.  Every other opt-in widens what
+ * registers; this one reduces what the ICP has to look at.  MM3D_ICP_SAMPLE_NORMAL_SPACE (Rusinkiewicz and Levoy, "Efficient
+ * variants of the ICP algorithm", 3DIM 2001; no parity with PCL's class is claimed) keeps the same number of points from every
+ * direction a surface faces, so the few points of a door frame or a kerb have their say beside the many of the floor;
+ * MM3D_ICP_SAMPLE_STRIDE keeps evenly spaced valid points in the cloud's order.  MM3D_ICP_SAMPLE_NONE, the default: the pair
+ * stage runs what it always ran.
+ * The rule.  Everything is integer arithmetic, or an IEEE f32 multiply and a compare: no division of floats, no libm.
+ *  1. Valid points.  Under STRIDE a point is valid when its three coordinates are finite; under NORMAL_SPACE its normal's three
+ *     components must be finite too, and not all zero (-0 is zero).  Invalid points are never sampled; n_valid counts the valid.
+ *  2. Buckets.  STRIDE has the one bucket 0.  NORMAL_SPACE has 3 bins^2 of them, bins in {1, 2, 4, 8}: the face a is the index of
+ *     the normal's largest |component|, ties to the lowest index; s = n_a, b = (a + 1) % 3, c = (a + 2) % 3.  Antipodes fold -- n
+ *     and -n share a bucket, both constrain the same plane: q = n_b when s > 0 and -n_b when s < 0, r = |s|.  The cell is
+ *     cu = #{k in 1 .. bins - 1 : q >= e_k r}, the edge e_k = -1 + 2 k / bins being exact in f32 and e_k r ONE rounded f32
+ *     multiply; cv is the same from n_c.  The bucket is (a bins + cu) bins + cv.
+ *  3. Budget.  m = min(n_valid, floor(fraction n_valid)), the product in double; m = min(m, max_points) when max_points > 0;
+ *     m is at least 1 when n_valid > 0.
+ *  4. Water-fill.  With c_b the buckets' counts, L is the largest integer in [0, max c_b] with sum min(c_b, L) <= m, and
+ *     take_b = min(c_b, L); the m - sum take_b that remain (fewer than there are buckets with c_b > L) go one each to the buckets
+ *     with c_b > L, in ascending bucket index.  sum take_b = m exactly, and a bucket with c_b <= L is taken whole.
+ *  5. Selection.  A valid point has the rank r among its bucket's points, from 0, in the cloud's order.  It is kept exactly when
+ *     floor((r + 1) take_b / c_b) > floor(r take_b / c_b), in 64-bit integers: take_b points of the bucket, evenly spaced.
+ *  6. The sample is the kept points in the cloud's order (the 16-byte records, colour included), a cloud of its own.
+ * Selected, a pair's ICP searches the target with the SOURCE map's sample -- made with the map's normals at params.normal_radius
+ * under NORMAL_SPACE, kept on the map, remade when the options change, built by mm3d_map_prepare or on the map's first use as a
+ * source -- and is in every other respect the ICP it was: mm3d_set_icp_method's point-to-point or point-to-plane, with or without
+ * mm3d_set_icp_rejection.  By construction the result is mm3d_sample_icp_source followed by the stage call on the sample.  A
+ * pair record's icp_correspondences (and the rejection's statistics) then count SAMPLED points.  transformScore -- the pair's
+ * confidence -- and the overlap confidence stay over the full source.  params.refine_transform 0 runs no ICP and no sampling.
+ * A pair whose source has no valid point takes the ICP's empty-search path: the guess, no iterations, confidence 1 / DBL_MAX.
+ * Nothing is drawn from rand(); results are bit-identical for every stream count, batch and cache setting.  Memory: 16 B per
+ * sampled point plus its query copy, per map. */
+typedef enum { MM3D_ICP_SAMPLE_NONE = 0, MM3D_ICP_SAMPLE_STRIDE = 1, MM3D_ICP_SAMPLE_NORMAL_SPACE = 2 } mm3d_icp_sample_method;
+typedef struct mm3d_icp_sampling_options {
+  int method;              /* mm3d_icp_sample_method */
+  double fraction;         /* of the valid points, 0 < fraction <= 1 */
+  int max_points;          /* >= 0; 0 = no cap */
+  int bins;                /* 1, 2, 4 or 8 cells per axis of a face (NORMAL_SPACE) */
+} mm3d_icp_sampling_options;
+void mm3d_icp_sampling_options_default(mm3d_icp_sampling_options *o);   /* NONE, 0.25, 0, 4 */
+/* MM3D_EINVAL: ctx or options NULL, an unknown method, fraction outside (0, 1], bins not 1 / 2 / 4 / 8, max_points < 0 (checked
+ * whatever the method).  MM3D_EUNSUPPORTED: a method other than NONE on a device-list context (mm3d_create_devices), or while
+ * NDT (mm3d_set_refinement), coloured ICP (mm3d_set_icp_color) or generalized ICP (mm3d_set_icp_generalized) is selected, each of
+ * which in turn refuses its selection while a sampling method is set; mm3d_shard_begin returns MM3D_EUNSUPPORTED on a context
+ * with one.  The setting reaches the context's mm3d_set_streams helpers, in either order, and is part of the map cache's pair
+ * key while a method is set. */
+int mm3d_set_icp_sampling(mm3d_ctx *ctx, const mm3d_icp_sampling_options *options);
+int mm3d_get_icp_sampling(const mm3d_ctx *ctx, mm3d_icp_sampling_options *options);   /* MM3D_EINVAL for NULL */
+typedef struct mm3d_icp_sampling_stats {
+  long long points;            /* of the cloud */
+  long long valid;             /* n_valid */
+  long long sampled;           /* m */
+  int buckets;                 /* buckets with c_b > 0 */
+  int level;                   /* L */
+} mm3d_icp_sampling_stats;
+/* of the most recent sample this context made or fetched from a map (a stage call below, or a pair's source) */
+int mm3d_last_icp_sampling_stats(const mm3d_ctx *ctx, mm3d_icp_sampling_stats *stats);
+/* The rule above on a caller's cloud, whatever the context's setting: *out receives the sample (free it with mm3d_cloud_free; its
+ * size is m), indices (may be NULL) the kept points' indices in `points`, ascending, at most `capacity` of them.  normals: one
+ * per point under NORMAL_SPACE; not read, and may be NULL, under STRIDE.  MM3D_EINVAL: a NULL argument, options out of range or
+ * of method NONE, normals whose count differs from the points'. */
+int mm3d_sample_icp_source(mm3d_ctx *ctx, const mm3d_cloud *points, const mm3d_normals *normals,
+                           const mm3d_icp_sampling_options *options, mm3d_cloud **out, int *indices, size_t capacity);
+/* mm3d_sample_icp_source of the source followed by mm3d_estimate_transform_icp (target_normals NULL) or
+ * mm3d_estimate_transform_icp_plane on the sample, from initial_guess, whatever the context's setting; options of method NONE
+ * run the ICP on the source as it is.  mm3d_last_icp_iterations / mm3d_last_icp_converged report on it.  A source without a valid
+ * point: MM3D_OK, T = initial_guess, no iterations.  MM3D_EINVAL: a NULL argument other than the two normals where they are not
+ * read, options out of range, normals whose count differs from their cloud's. */
+int mm3d_estimate_transform_icp_sampled(mm3d_ctx *ctx, const mm3d_cloud *source, const mm3d_normals *source_normals,
+                                        const mm3d_cloud *target, const mm3d_normals *target_normals,
+                                        const mm3d_icp_sampling_options *options, const float initial_guess[16],
+                                        double max_correspondence_distance, int max_iterations, double transformation_epsilon,
+                                        float T[16]);
+
 #ifdef __cplusplus
 }
 #endif

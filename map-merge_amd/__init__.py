@@ -255,6 +255,37 @@ class EstimatorOptions(C.Structure):
         return tuple(int(getattr(self, k)) if t is C.c_int else float(getattr(self, k)) for k, t in self._fields_)
 
 
+class IcpSampleMethod(enum.IntEnum):   # mm3d_icp_sample_method (not a reference enum)
+    NONE = 0
+    STRIDE = 1
+    NORMAL_SPACE = 2
+
+
+class IcpSamplingOptions(C.Structure):
+    """mm3d_icp_sampling_options (mm3d_set_icp_sampling); the defaults are mm3d_icp_sampling_options_default's."""
+    _fields_ = [("method", C.c_int), ("fraction", C.c_double), ("max_points", C.c_int), ("bins", C.c_int)]
+
+    def __init__(self, **kw):
+        super().__init__()
+        lib().mm3d_icp_sampling_options_default(C.byref(self))
+        kinds = dict(self._fields_)
+        for k, v in kw.items():
+            if k not in kinds:
+                raise TypeError("unknown ICP sampling option " + k)
+            setattr(self, k, int(v) if kinds[k] is C.c_int else float(v))
+
+    def as_tuple(self):
+        return tuple(int(getattr(self, k)) if t is C.c_int else float(getattr(self, k)) for k, t in self._fields_)
+
+
+class IcpSamplingStats(C.Structure):
+    """mm3d_icp_sampling_stats"""
+    _fields_ = [("points", C.c_longlong), ("valid", C.c_longlong), ("sampled", C.c_longlong), ("buckets", C.c_int), ("level", C.c_int)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 class EstimatorStats(C.Structure):
     """mm3d_estimator_stats"""
     _fields_ = [("correspondences", C.c_longlong), ("edges", C.c_longlong), ("seeds", C.c_longlong), ("hypotheses", C.c_longlong),
@@ -628,6 +659,23 @@ class Context:
         self._ck(lib().mm3d_get_icp_generalized(self._h, C.byref(o)))
         return o
 
+    def setIcpSampling(self, options=None, **kw):
+        """mm3d_set_icp_sampling: the pair stage's ICP searches with a sample of the source map.  An IcpSamplingOptions, or its
+        fields as keywords (method=IcpSampleMethod.STRIDE / NORMAL_SPACE, fraction=..., max_points=..., bins=...)."""
+        o = options if options is not None else IcpSamplingOptions(**kw)
+        self._ck(lib().mm3d_set_icp_sampling(self._h, C.byref(o)))
+
+    def getIcpSampling(self) -> "IcpSamplingOptions":
+        o = IcpSamplingOptions()
+        self._ck(lib().mm3d_get_icp_sampling(self._h, C.byref(o)))
+        return o
+
+    def lastIcpSamplingStats(self) -> dict:
+        """mm3d_last_icp_sampling_stats: the most recent sample this context made or fetched from a map."""
+        st = IcpSamplingStats()
+        self._ck(lib().mm3d_last_icp_sampling_stats(self._h, C.byref(st)))
+        return st.as_dict()
+
     @property
     def last_icp_rejection_stats(self) -> dict:
         """mm3d_last_icp_rejection_stats: the last iteration of the most recent rejecting ICP this context ran."""
@@ -892,6 +940,33 @@ class Context:
         self._ck(lib().mm3d_estimate_transform_icp_generalized(
             self._h, source_points._h, source_normals._h, target_points._h, target_normals._h, g.ctypes.data_as(C.c_void_p),
             C.c_double(max_correspondence_distance), C.byref(o), int(max_iterations), C.c_double(transformation_epsilon),
+            T.ctypes.data_as(C.c_void_p)))
+        self.last_icp_iterations = lib().mm3d_last_icp_iterations(self._h)
+        self.last_icp_converged = lib().mm3d_last_icp_converged(self._h)
+        return _Tout(T)
+
+    def sampleIcpSource(self, points, normals, options=None, indices=True, **kw):
+        """mm3d_sample_icp_source: (the sample as a Cloud, the kept points' indices in `points` -- None with indices=False) under
+        the options, whatever the context's setting.  normals: one per point under NORMAL_SPACE, None under STRIDE."""
+        o = options if options is not None else IcpSamplingOptions(**kw)
+        h = C.c_void_p()
+        idx = np.full(max(len(points), 1), -1, dtype=np.int32) if indices else None
+        self._ck(lib().mm3d_sample_icp_source(self._h, points._h, normals._h if normals is not None else None, C.byref(o), C.byref(h),
+                                              idx.ctypes.data_as(C.c_void_p) if indices else None, C.c_size_t(len(points) if indices else 0)))
+        cloud = Cloud(self, h)
+        return cloud, (idx[:len(cloud)].copy() if indices else None)
+
+    def estimateTransformICPSampled(self, source_points, source_normals, target_points, target_normals, initial_guess,
+                                    max_correspondence_distance, options=None, max_iterations=100, transformation_epsilon=0.0, **kw):
+        """mm3d_estimate_transform_icp_sampled: mm3d_sample_icp_source of the source, then the point-to-point ICP (target_normals
+        None) or the point-to-plane ICP on the sample, whatever the context's setting."""
+        o = options if options is not None else IcpSamplingOptions(**kw)
+        g = _T(initial_guess)
+        T = np.zeros(16, dtype=np.float32)
+        self._ck(lib().mm3d_estimate_transform_icp_sampled(
+            self._h, source_points._h, source_normals._h if source_normals is not None else None, target_points._h,
+            target_normals._h if target_normals is not None else None, C.byref(o), g.ctypes.data_as(C.c_void_p),
+            C.c_double(max_correspondence_distance), int(max_iterations), C.c_double(transformation_epsilon),
             T.ctypes.data_as(C.c_void_p)))
         self.last_icp_iterations = lib().mm3d_last_icp_iterations(self._h)
         self.last_icp_converged = lib().mm3d_last_icp_converged(self._h)

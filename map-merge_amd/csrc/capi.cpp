@@ -39,6 +39,7 @@ mm3d::StageSelection::StageSelection()
   mm3d_icp_color_options_default(&color_options);
   mm3d_icp_generalized_options_default(&generalized_options);
   mm3d_estimator_options_default(&estimator_options);
+  mm3d_icp_sampling_options_default(&sampling_options);
 }
 
 void mm3d::select_stages(mm3d_ctx *ctx, bool peers_follow, const std::function<void(StageSelection &)> &edit)
@@ -204,6 +205,10 @@ void mm3d_icp_generalized_options_default(mm3d_icp_generalized_options *o)
 void mm3d_estimator_options_default(mm3d_estimator_options *o)
 {
   if (o) *o = mm3d_estimator_options{MM3D_ESTIMATOR_RANSAC, 0.0, 64, 20};
+}
+void mm3d_icp_sampling_options_default(mm3d_icp_sampling_options *o)
+{
+  if (o) *o = mm3d_icp_sampling_options{MM3D_ICP_SAMPLE_NONE, 0.25, 0, 4};
 }
 
 // ---------------------------------------------------------------- context

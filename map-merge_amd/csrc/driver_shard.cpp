@@ -66,6 +66,7 @@ int mm3d_shard_begin(mm3d_ctx *ctx, const mm3d_cloud_view *clouds, size_t n, con
     if (sel.color) throw Error(MM3D_EUNSUPPORTED, "mm3d_shard_begin: shard bundles carry no colour gradients for coloured ICP");
     if (sel.generalized) throw Error(MM3D_EUNSUPPORTED, "mm3d_shard_begin: shard bundles carry no normals for generalized ICP");
     if (sel.estimator) throw Error(MM3D_EUNSUPPORTED, "mm3d_shard_begin: the ranks' pair loops run RANSAC, not the consistency estimation");
+    if (sel.sampler) throw Error(MM3D_EUNSUPPORTED, "mm3d_shard_begin: the ranks' pair loops run the ICP on the whole source, not on a sample");
     *out = shard_begin_impl(ctx, clouds, n, params, rank, world);
   });
 }

@@ -424,9 +424,9 @@ struct RejectStep final : IcpStep {
   void begin(Context *c, const IcpScoreJob *const *live, int B, char *pinned, void *rh, void *rd) override
   {
     for (int b = 0; b < B; ++b) {
-      n_src += live[b]->src->n_finite;
+      n_src += live[b]->icp_source()->n_finite;              // (the ICP's source: a sample under mm3d_set_icp_sampling)
       n_tgt += opt.one_to_one ? live[b]->tgt->n : 0;
-      max_src = std::max(max_src, (unsigned)live[b]->src->n_finite);
+      max_src = std::max(max_src, (unsigned)live[b]->icp_source()->n_finite);
     }
     pinned = jobs.begin(c, B, pinned);
     if (plane) pjobs.begin(c, B, pinned);
@@ -440,9 +440,9 @@ struct RejectStep final : IcpStep {
   {
     if (plane) pjobs.host[b] = icp_plane_job(q, J);
     jobs.host[b] = NnRejectJob{q, plane ? pjobs.host[b].nrm : nullptr, corr.get() + src_off, opt.one_to_one ? owner.get() + tgt_off : nullptr,
-                               hist.get() + (size_t)b * 1024, rec_dev + b, (int)J.src->n_finite};
+                               hist.get() + (size_t)b * 1024, rec_dev + b, (int)J.icp_source()->n_finite};
     rec_host[b] = rej_record_init();
-    src_off += J.src->n_finite;
+    src_off += J.icp_source()->n_finite;
     tgt_off += opt.one_to_one ? J.tgt->n : 0;
   }
   void upload(Context *c) override

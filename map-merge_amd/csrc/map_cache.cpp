@@ -94,6 +94,11 @@ std::string pair_params_key(const mm3d_params *p, const StageSelection &sel)
   const mm3d_estimator_options &est = sel.estimator_options;
   const bool cons = est.method == MM3D_ESTIMATOR_CONSISTENCY;
   k.i32(cons ? est.method : 0).f64(cons ? est.tolerance : 0.0).i32(cons ? est.seeds : 0).i32(cons ? est.consensus : 0);
+  // the ICP's source sampling (mm3d_set_icp_sampling): the four options while a method is set, zeros otherwise (nothing reads
+  // the other values under NONE: whatever they are, its records are shared)
+  const mm3d_icp_sampling_options &smp = sel.sampling_options;
+  const bool sampling = smp.method != MM3D_ICP_SAMPLE_NONE;
+  k.i32(sampling ? smp.method : 0).f64(sampling ? smp.fraction : 0.0).i32(sampling ? smp.max_points : 0).i32(sampling ? smp.bins : 0);
   return k.s;
 }
 
@@ -132,7 +137,8 @@ struct Entry {
            (map->coarse ? (map->coarse->scells.size() + map->coarse->gcells.size()) * 16 + map->coarse->ccells.size() * 8 +
                               map->coarse->dil.size() + map->coarse->gh.size() * 4 : 0) +   // (signature: correlative alignment only)
            (map->overlap ? map->overlap->near.size() * 8 + map->overlap->view.size() : 0) +   // (table: overlap confidence only)
-           (map->color ? map->color->rec.size() * 16 : 0);   // (gradient records: coloured ICP only)
+           (map->color ? map->color->rec.size() * 16 : 0) +   // (gradient records: coloured ICP only)
+           (map->icp_sample ? cloud_bytes(map->icp_sample->cloud.get()) : 0);   // (the source sample: ICP sampling only)
   }
 };
 

@@ -370,7 +370,8 @@ static void icp_batch(Context *c, IcpStep &step, IcpScoreJob *jobs, int n_jobs, 
   for (int j = 0; j < n_jobs; ++j) {
     IcpScoreJob &J = jobs[j];
     J.out.iterations = 0; J.out.converged = 0; J.out.n_corr = 0; J.out.score = DBL_MAX;
-    const NnSearch si = nn_search(c, J.src, J.tgt, icp_grid ? &icp_range : nullptr);
+    // (the ICP searches with its own source -- a sample under mm3d_set_icp_sampling --, the score with the pair's)
+    const NnSearch si = nn_search(c, J.icp_source(), J.tgt, icp_grid ? &icp_range : nullptr);
     const NnSearch ss = want_score ? nn_search(c, J.src, J.tgt, &score_range) : NnSearch();
     if (!si.src || (icp_grid && !si.grid) || (want_score && !ss.grid) || (!run_icp && !want_score)) {
       // nothing to search: Identity * guess, and the score of an empty search
@@ -393,25 +394,26 @@ static void icp_batch(Context *c, IcpStep &step, IcpScoreJob *jobs, int n_jobs, 
 
   // one work item per block while the whole batch has too few items to fill the chip with one wave each
   // (the finalize kernels add the partials up in one fixed order, so the choice never shows in a result)
-  int total_items = 0;
-  for (const Live &L : live) total_items += L.icp.n_items;
+  // Each of the two searches from its own items: they are the same items unless the ICP's source is a sample.
+  int total_items = 0, score_items = 0;
+  for (const Live &L : live) { total_items += L.icp.n_items; score_items += want_score ? L.score.n_items : L.icp.n_items; }
   const int forced_split = run_icp ? step.forced_split : 0;
-  const bool split = forced_split ? forced_split == 4 : nn_split_items(total_items);
+  const bool split = forced_split ? forced_split == 4 : nn_split_items(score_items);
   // (a step that does not search keeps four items per block whatever the batch does)
-  const bool icp_split = split && step.searches;
+  const bool icp_split = (forced_split ? forced_split == 4 : nn_split_items(total_items)) && step.searches;
   size_t part_total = 0, icp_part_total = 0;
   unsigned grid_x = 0, icp_grid_x = 0;
   double icp_bytes = 0.0, score_bytes = 0.0;
   std::vector<unsigned> nb(B), icp_nb(B);
   for (int b = 0; b < B; ++b) {
-    nb[b] = nn_blocks(live[b].icp.n_items, split);
+    nb[b] = nn_blocks(want_score ? live[b].score.n_items : live[b].icp.n_items, split);
     icp_nb[b] = nn_blocks(live[b].icp.n_items, icp_split);
     part_total += (size_t)nb[b] * kAcc;
     icp_part_total += (size_t)icp_nb[b] * step.acc;
     grid_x = std::max(grid_x, nb[b]);
     icp_grid_x = std::max(icp_grid_x, icp_nb[b]);
     icp_bytes += live[b].icp.ns * step.bytes_per_point(*live_jobs[b]);
-    score_bytes += live[b].icp.ns * 12.0 + (live[b].score.grid ? live[b].score.grid->n * 12.0 : 0.0);
+    score_bytes += (want_score ? live[b].score.ns : live[b].icp.ns) * 12.0 + (live[b].score.grid ? live[b].score.grid->n * 12.0 : 0.0);
   }
   DevBuf<double> partials(c, icp_part_total), s_partials(c, want_score ? part_total : 1);
   DevBuf<double> out(c, (size_t)2 * B);

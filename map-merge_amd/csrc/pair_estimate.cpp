@@ -77,8 +77,9 @@ std::unique_ptr<mm3d_map> mm3d::map_features_impl(mm3d_ctx *ctx, const mm3d_clou
   if (wait) ctx->sync();
   std::unique_ptr<mm3d_map> m = make_map(std::move(filt), std::move(kp), std::move(desc));
   // point-to-plane, coloured and generalized ICP read them (mm3d_set_icp_method, mm3d_set_icp_color, mm3d_set_icp_generalized),
-  // and the correlative signature
-  if (ctx->sel.icp || ctx->sel.coarse || ctx->sel.color || ctx->sel.generalized) m->normals = std::move(nrm);
+  // the correlative signature, and normal-space sampling (mm3d_set_icp_sampling)
+  const bool normal_space = ctx->sel.sampler && ctx->sel.sampling_options.method == MM3D_ICP_SAMPLE_NORMAL_SPACE;
+  if (ctx->sel.icp || ctx->sel.coarse || ctx->sel.color || ctx->sel.generalized || normal_space) m->normals = std::move(nrm);
   return m;
 }
 
@@ -91,6 +92,7 @@ void mm3d::map_prepare_impl(mm3d_ctx *ctx, mm3d_map *m, const mm3d_params *p)
   if (sel.generalized) sel.generalized->prepare_target(ctx, m, p, nullptr);   // the normals, for either role (mm3d_set_icp_generalized)
   if (sel.coarse) sel.coarse->prepare(ctx, m, p);                      // the correlative signature (mm3d_set_coarse_alignment)
   if (sel.confidence) sel.confidence->prepare(ctx, m, p);              // the overlap table (mm3d_set_confidence)
+  if (sel.sampler && p->refine_transform) (void)sel.sampler->sample(ctx, m, p, nullptr);   // the ICP's source sample (mm3d_set_icp_sampling)
   prepare_pair_search(ctx, m->points, p->max_correspondence_distance, p->max_correspondence_distance);
   if (p->estimation_method == MM3D_EST_SAC_IA && sel.align) sel.align->prepare(ctx, m->keypoints, p->max_correspondence_distance);
   else if (p->estimation_method == MM3D_EST_SAC_IA) prepare_sacia_target(ctx, m->keypoints, (float)p->max_correspondence_distance);
@@ -266,6 +268,8 @@ void mm3d::pairs_estimate_batch(mm3d_ctx *ctx, PairWork *w, size_t n, const mm3d
     jobs[i].guess_dev = fronts[i].on_device ? fronts[i].dT0.get() : nullptr;
     std::memcpy(jobs[i].guess_host, fronts[i].T0, sizeof(fronts[i].T0));
     if (sel.rejecting()) jobs[i].reject = &sel.reject_options;         // (mm3d_set_icp_rejection; NDT does not read it)
+    // (mm3d_set_icp_sampling: the ICP searches with the source map's sample, the score stays over the map)
+    if (sel.sampler && p->refine_transform) jobs[i].icp_src = sel.sampler->sample(ctx, w[i].s, p, &ctx->last_sampling_stats);
   }
   // estimateTransform's ICP and transformScore of its result (R/src/map_merging.cpp:91-107), max_distance = max_correspondence_distance
   // (under mm3d_set_confidence nobody reads that score: it is not launched, and the ICP's states come back as they would have)

@@ -20,10 +20,11 @@ struct KeypointSourceBase;
 struct CoarseMethodBase;
 struct ConfidenceMethodBase;
 struct EstimatorMethodBase;
+struct IcpSamplerBase;
 
 // The opt-in stages of a context's pipeline (mm3d_set_icp_method, mm3d_set_alignment, mm3d_set_keypoints, mm3d_set_refinement,
 // mm3d_set_coarse_alignment, mm3d_set_confidence, mm3d_set_icp_rejection, mm3d_set_icp_color, mm3d_set_icp_generalized,
-// mm3d_set_estimator): a null method = the reference's stage.  The methods are process-wide
+// mm3d_set_estimator, mm3d_set_icp_sampling): a null method = the reference's stage.  The methods are process-wide
 // objects of their kernel files that hold no state and are not owned.  Every context has its own copy of the record; only
 // select_stages (drivers.hpp) changes one, and it and mm3d_set_streams hand the root's copy to the helpers.
 struct StageSelection {
@@ -36,6 +37,7 @@ struct StageSelection {
   const IcpMethodBase *color = nullptr;                // coloured ICP in the place of `icp`'s, which keeps its own value beside it
   const IcpMethodBase *generalized = nullptr;          // generalized ICP in the place of `icp`'s, which keeps its own value beside it
   const EstimatorMethodBase *estimator = nullptr;      // the initial estimate under MATCHING: the consistency graph in RANSAC's place
+  const IcpSamplerBase *sampler = nullptr;             // what the ICP searches with: a sample of the source map in the place of all of it
   mm3d_alignment_options align_options;
   mm3d_keypoint_options keypoint_options;
   mm3d_refine_options refine_options;
@@ -45,7 +47,8 @@ struct StageSelection {
   mm3d_icp_color_options color_options;                // coloured ICP: `color` is non-null exactly while they are enabled
   mm3d_icp_generalized_options generalized_options;    // generalized ICP: `generalized` is non-null exactly while they are enabled
   mm3d_estimator_options estimator_options;            // `estimator` is non-null exactly while their method is CONSISTENCY
-  StageSelection();                                    // capi.cpp: the options are the nine mm3d_*_options_default's
+  mm3d_icp_sampling_options sampling_options;          // `sampler` is non-null exactly while their method is not NONE
+  StageSelection();                                    // capi.cpp: the options are the ten mm3d_*_options_default's
   // the ICP of the pair stage rejects correspondences (mm3d_set_icp_rejection)
   bool rejecting() const { return reject_options.one_to_one || reject_options.distance != MM3D_REJECT_NONE; }
   int icp_method() const;                              // MM3D_ICP_*
@@ -57,7 +60,7 @@ struct StageSelection {
   // rand(), which is MATCHING's case in pair_rand_replay
   int replay_method(const mm3d_params *p) const { return coarse || prerejective(p) ? (int)MM3D_EST_MATCHING : (int)p->estimation_method; }
   // such a pair is estimated by pairs_estimate_batch alone (pair_estimate_impl hands it a batch of one)
-  bool batch_only(const mm3d_params *p) const { return icp || refine || coarse || confidence || color || generalized || rejecting() || prerejective(p) || consistency(p); }
+  bool batch_only(const mm3d_params *p) const { return icp || refine || coarse || confidence || color || generalized || rejecting() || prerejective(p) || consistency(p) || sampler; }
 };
 
 // The feature / pair cache of mm3d_estimate_maps_transforms (mm3d_set_map_cache; the concrete class is map_cache.cpp's).  The
@@ -94,6 +97,7 @@ struct mm3d_ctx : mm3d::Context {
   mm3d_overlap_stats last_confidence_stats{0, 0, 0, 0, 0, 0, 0.0};
   mm3d_icp_rejection_stats last_reject_stats{0, 0, 0, INFINITY, 0, 0};   // (mm3d_last_icp_rejection_stats)
   mm3d_estimator_stats last_estimator_stats{0, 0, 0, 0, -1, -1, 0};      // (mm3d_last_estimator_stats)
+  mm3d_icp_sampling_stats last_sampling_stats{0, 0, 0, 0, 0};            // (mm3d_last_icp_sampling_stats)
   // mm3d_set_streams: helper contexts (one HIP stream + one host thread each while a call is running)
   // that mm3d_estimate_maps_transforms deals maps and pairs to; owned by this context
   std::vector<mm3d_ctx *> helpers;
@@ -262,6 +266,16 @@ struct mm3d_desc {
   mm3d::DevBuf<float> rf;
 };
 
+namespace mm3d {
+// What ICP source sampling keeps of a map (icp_sample.hip, mm3d_set_icp_sampling): the sample as a cloud of its own, which carries
+// the query order the ICP searches with like any other cloud.  16 B per sampled point plus that copy.
+struct IcpSample {
+  mm3d_icp_sampling_options opt{};                 // what it was made with (a map's sample is remade when these change)
+  std::unique_ptr<mm3d_cloud> cloud;
+  mm3d_icp_sampling_stats stats{0, 0, 0, 0, 0};
+};
+}  // namespace mm3d
+
 // A map owns its parts: whoever holds the map frees all of them with `delete m` (mm3d_map_from_parts adopts the caller's).
 struct mm3d_map {
   mm3d_cloud *points = nullptr;
@@ -274,6 +288,7 @@ struct mm3d_map {
   std::unique_ptr<mm3d::CoarseSignature> coarse;    // the correlative alignment's signature
   std::unique_ptr<mm3d::OverlapTable> overlap;      // the overlap confidence's table
   std::unique_ptr<mm3d::ColorGradients> color;      // coloured ICP's gradient records
+  std::unique_ptr<mm3d::IcpSample> icp_sample;      // the source sample of the ICP
   mm3d_map() = default;
   mm3d_map(const mm3d_map &) = delete;
   mm3d_map &operator=(const mm3d_map &) = delete;
@@ -403,6 +418,10 @@ struct IcpScoreJob {
   // for every job of a batch)
   const mm3d_normals *src_normals = nullptr;
   double generalized_epsilon = 1e-3;
+  // source sampling (mm3d_set_icp_sampling; icp_sample.hip): what the ICP searches with in src's place, null = src itself.  The
+  // score stays over src.
+  const mm3d_cloud *icp_src = nullptr;
+  const mm3d_cloud *icp_source() const { return icp_src ? icp_src : src; }
 };
 struct IcpStep;      // nn_core.hpp
 // The ICP + score tail of a batch of pairs (nn.hip) with `method`'s ICP; null: the reference's point-to-point ICP.  When the ICP
@@ -479,6 +498,15 @@ struct EstimatorMethodBase {
   // estimate_pair_front's MATCHING branch with this method: findFeatureCorrespondences, then the estimate in f.T0 and f.counts
   virtual void front(Context *c, const mm3d_estimator_options &o, const mm3d_cloud *skp, const mm3d_desc *sd, const mm3d_cloud *tkp,
                      const mm3d_desc *td, double inlier_threshold, size_t matching_k, PairFront &f, mm3d_estimator_stats *stats) const = 0;
+};
+// What the pair stage's ICP searches with when it is not the whole source map (mm3d_set_icp_sampling; the one concrete class is
+// icp_sample.hip's).  Like IcpMethodBase, the drivers and pair_estimate.cpp only see this interface, so the host code links
+// without the new kernels (tests/host_san); a null pointer on the context means every point of the source.
+struct IcpSamplerBase {
+  virtual ~IcpSamplerBase() = default;
+  // the map's sample at the context's options (and, under NORMAL_SPACE, the normals it is made from), made when missing or stale
+  // (map_kept.hpp; no wait when it is there); stats (may be null) receives what it was made with
+  virtual const mm3d_cloud *sample(mm3d_ctx *ctx, const mm3d_map *m, const mm3d_params *p, mm3d_icp_sampling_stats *stats) const = 0;
 };
 struct PairCounts { int n_correspondences = 0, n_inliers = 0, icp_correspondences = 0; };
 // ICP (optional) from a guess on the device (guess_dev != null) or on the host, then transformScore
