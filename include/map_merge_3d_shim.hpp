@@ -45,6 +45,36 @@ inline mm3d_keypoint_options parse_keypoints(const char *value)
   o.source = MM3D_KEYPOINTS_UNIFORM;
   return o;
 }
+// MM3D_OUTLIERS=statistical, statistical:<mean_k> or statistical:<mean_k>:<stddev_mult>: the estimation context's maps are filtered
+// by the statistical rule instead of the reference's radius filter (mm3d_set_outlier_filter; what is not given keeps
+// mm3d_outlier_options_default's value, 16 and 2.0); reference or unset keeps removeOutliers.  Anything else throws.
+inline mm3d_outlier_options parse_outliers(const char *value)
+{
+  mm3d_outlier_options o;
+  o.method = MM3D_OUTLIERS_RADIUS;
+  o.mean_k = 16;
+  o.stddev_mult = 2.0;
+  const std::string v = value ? value : "";
+  if (v.empty() || v == "reference") return o;
+  bool ok = v.compare(0, 11, "statistical") == 0 && (v.size() == 11 || v[11] == ':');
+  if (ok && v.size() > 11) {
+    const char *s = v.c_str() + 12;
+    char *end = nullptr;
+    const long k = std::strtol(s, &end, 10);
+    ok = end != s && (*end == '\0' || *end == ':') && k >= 1 && k <= 64 && *s >= '0' && *s <= '9';
+    o.mean_k = (int)k;
+    if (ok && *end == ':') {
+      s = end + 1;
+      o.stddev_mult = std::strtod(s, &end);
+      ok = end != s && *end == '\0' && std::isfinite(o.stddev_mult) && o.stddev_mult >= 0.0 && ((*s >= '0' && *s <= '9') || *s == '.');
+    }
+  }
+  if (!ok)
+    throw std::runtime_error("mm3d: MM3D_OUTLIERS must be reference, statistical, statistical:<mean_k 1 .. 64> or "
+                             "statistical:<mean_k>:<stddev_mult >= 0>, not '" + v + "'");
+  o.method = MM3D_OUTLIERS_STATISTICAL;
+  return o;
+}
 // MM3D_REFINE=ndt or ndt:<resolution in metres>: the estimation context's pair stage refines with NDT in the ICP's place
 // (mm3d_set_refinement; without a resolution, the library's default multiple of params.resolution; the other options keep
 // mm3d_refine_options_default's values); icp or unset keeps the ICP that MM3D_ICP selects.  Anything else throws.
@@ -407,6 +437,7 @@ inline mm3d_ctx *ctx()
   // MM3D_ALIGN=prerejective: under SAC_IA the pair stage's initial alignment is the prerejective one (mm3d_set_alignment), with
   // MM3D_ALIGN_SAMPLES=<draws> if given; sac_ia or unset keeps the reference's.  Not available on a device list either.
   // MM3D_KEYPOINTS=uniform[:<leaf>]: parse_keypoints above; it works on a device list too.
+  // MM3D_OUTLIERS=statistical[:<mean_k>[:<stddev_mult>]]: parse_outliers above; it works on a device list too.
   // MM3D_REFINE=ndt[:<resolution>]: parse_refine above.  Not available on a device list: ndt with MM3D_DEVICES set as well throws.
   // MM3D_COARSE=correlative[:<cell>]: parse_coarse above.  Not available on a device list: correlative with MM3D_DEVICES set as well throws.
   // MM3D_CONFIDENCE=overlap[:<voxel>]: parse_confidence above.  Not available on a device list: overlap with MM3D_DEVICES set as well throws.
@@ -430,6 +461,7 @@ inline mm3d_ctx *ctx()
     if (coarse.method == MM3D_COARSE_CORRELATIVE && std::getenv("MM3D_DEVICES") && *std::getenv("MM3D_DEVICES"))
       throw std::runtime_error("mm3d: MM3D_COARSE=correlative is not available with MM3D_DEVICES (a device list carries no signatures)");
     const mm3d_keypoint_options keypoints = parse_keypoints(std::getenv("MM3D_KEYPOINTS"));
+    const mm3d_outlier_options outliers = parse_outliers(std::getenv("MM3D_OUTLIERS"));
     mm3d_refine_options refine = parse_refine(std::getenv("MM3D_REFINE"));
     if (refine.method == MM3D_REFINE_NDT && std::getenv("MM3D_DEVICES") && *std::getenv("MM3D_DEVICES"))
       throw std::runtime_error("mm3d: MM3D_REFINE=ndt is not available with MM3D_DEVICES (a device list carries no voxel tables)");
@@ -466,6 +498,8 @@ inline mm3d_ctx *ctx()
     }
     if (keypoints.source != MM3D_KEYPOINTS_REFERENCE && mm3d_set_keypoints(e, &keypoints) != MM3D_OK)
       throw std::runtime_error("mm3d: MM3D_KEYPOINTS was refused (the leaf must be a positive float with a finite reciprocal)");
+    if (outliers.method != MM3D_OUTLIERS_RADIUS && mm3d_set_outlier_filter(e, &outliers) != MM3D_OK)
+      throw std::runtime_error("mm3d: MM3D_OUTLIERS was refused (mean_k must be 1 .. 64, stddev_mult finite and not negative)");
     if (refine.method != MM3D_REFINE_ICP && mm3d_set_refinement(e, &refine) != MM3D_OK)
       throw std::runtime_error("mm3d: MM3D_REFINE was refused (the resolution must be a positive float with a finite reciprocal)");
     if (coarse.method != MM3D_COARSE_NONE && mm3d_set_coarse_alignment(e, &coarse) != MM3D_OK)

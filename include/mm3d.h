@@ -364,6 +364,57 @@ void mm3d_keypoint_options_default(mm3d_keypoint_options *o);     /* source MM3D
  * value is checked whatever the source). */
 int mm3d_set_keypoints(mm3d_ctx *ctx, const mm3d_keypoint_options *options);
 int mm3d_get_keypoints(const mm3d_ctx *ctx, mm3d_keypoint_options *options);        /* MM3D_EINVAL for NULL */
+/* What filters a down-sampled map before anything else looks at it (off the reference's path; MM3D_OUTLIERS_RADIUS, the
+ * reference's removeOutliers(descriptor_radius, outliers_min_neighbours), by default).  The radius filter is a fixed density
+ * threshold: a map somewhat sparser than its two numbers assume is deleted whole.  With MM3D_OUTLIERS_STATISTICAL every place
+ * that runs removeOutliers behind a whole-map call -- mm3d_map_features, mm3d_estimate_maps_transforms on one stream or many, on
+ * a device list (mm3d_create_devices) and mm3d_shard_begin -- takes mm3d_remove_outliers_statistical(the down-sampled points,
+ * mean_k, stddev_mult) instead: the density-adaptive filter that users of pcl::StatisticalOutlierRemoval and Open3D's
+ * remove_statistical_outlier expect.  params.outliers_min_neighbours is then not read by the filter; descriptor_radius keeps
+ * every other role; mm3d_params does not change.  The stand-alone mm3d_remove_outliers is untouched.
+ *   The rule, for a cloud of n records, mean_k in 1 .. 64 and stddev_mult finite and >= 0 (no parity with PCL's class is
+ *   claimed):
+ *   1. A point is valid when its three coordinates are finite.  Invalid points are never kept, never counted and never anybody's
+ *      neighbour.  n_valid counts the valid points.
+ *   2. k' = min(mean_k, n_valid - 1).  If n_valid <= 1, every valid point is kept and the statistics are zero.
+ *   3. For a valid point i, take the k' smallest values of the multiset { d2(i, j) : j valid, j != i }, where
+ *      d2 = (dx * dx + dy * dy) + dz * dz in float, every operation rounded to nearest, nothing contracted.  A duplicate point
+ *      has d2 = 0 and is a neighbour.  d_i = (sum of sqrt((double)d2)) / k', summed in double in ascending order of d2.  Which
+ *      of several equal distances is taken cannot change d_i, so the rule names no tie-break.
+ *   4. S = sum d_i and Q = sum d_i^2 over the valid points, in double, in a fixed order that depends on the cloud alone (blocks
+ *      of 4096 consecutive records: lane l of 256 adds records l, l + 256, ... in that order, the lanes by a fixed tree, the
+ *      blocks in ascending order), never on stream count, batch, cache, driver or device.  mu = S / n_valid;
+ *      var = max(0, (Q - S * S / n_valid) / (n_valid - 1)), PCL's formula; sigma = sqrt(var); t = mu + stddev_mult * sigma.
+ *   5. Point i is kept iff it is valid and d_i <= t.  The result is the kept 16-byte records in the cloud's order, colour
+ *      included.
+ *   - mean_k is capped at 64: one wave's width on this hardware, and above PCL's tutorial value (50) and Open3D's (20).
+ *   - The defaults (16, 2.0) removed 97 - 100 % of 150 points planted in the free space of a 4 000-point room and kept at least
+ *     99.9 % of the room (DESIGN.md section 7n has the table).
+ *   - The setting reaches the context's mm3d_set_streams helpers in either order of the two calls, and every device of a
+ *     device-list context; only a map's features change, and those travel in the bundles, so device lists and shards carry it.
+ *     Every rank of a sharded call must use the same setting.  Nothing is drawn from rand().  Results are bit-identical for
+ *     every stream count, driver, batch and cache setting.
+ *   - The map cache's map key holds (method, mean_k, stddev_mult), zeros under MM3D_OUTLIERS_RADIUS: a radius-filtered bundle
+ *     is never served for a statistical one, nor one of other options. */
+typedef enum { MM3D_OUTLIERS_RADIUS = 0, MM3D_OUTLIERS_STATISTICAL = 1 } mm3d_outlier_method;
+typedef struct mm3d_outlier_options {
+  int method;                 /* MM3D_OUTLIERS_* */
+  int mean_k;                 /* 1 .. 64 */
+  double stddev_mult;         /* finite, >= 0 */
+} mm3d_outlier_options;
+void mm3d_outlier_options_default(mm3d_outlier_options *o);       /* MM3D_OUTLIERS_RADIUS, 16, 2.0 */
+/* MM3D_EINVAL: ctx or options NULL, an unknown method, mean_k outside 1 .. 64, stddev_mult negative or not finite (the values
+ * are checked whatever the method). */
+int mm3d_set_outlier_filter(mm3d_ctx *ctx, const mm3d_outlier_options *options);
+int mm3d_get_outlier_filter(const mm3d_ctx *ctx, mm3d_outlier_options *options);   /* MM3D_EINVAL for NULL */
+typedef struct mm3d_outlier_stats {
+  long long points, valid, kept;      /* n, n_valid, the size of the result */
+  int k;                              /* k' */
+  double mean, stddev, threshold;     /* mu, sigma, t */
+} mm3d_outlier_stats;
+/* The statistical filter's last run on this context: mm3d_remove_outliers_statistical, or mm3d_map_features under
+ * MM3D_OUTLIERS_STATISTICAL (all zero before the first).  MM3D_EINVAL for NULL. */
+int mm3d_last_outlier_stats(const mm3d_ctx *ctx, mm3d_outlier_stats *stats);
 /* What refines a pair's initial estimate where params.refine_transform is set (off the reference's path; MM3D_REFINE_ICP by
  * default: the ICP that mm3d_set_icp_method selects, which mm3d_get_icp_method keeps answering whatever the refinement is).
  * MM3D_REFINE_NDT runs the Normal Distributions Transform in the ICP's place: a Gauss-Newton form of point-to-distribution
@@ -475,6 +526,22 @@ int mm3d_detect_keypoints(mm3d_ctx *ctx, const mm3d_cloud *points, const mm3d_no
  * sensible one (audit row 16a).  The result does not depend on launch geometry or on the order in which
  * anything arrives: all minima are integer minima.  One host wait, for the keypoint count. */
 int mm3d_uniform_keypoints(mm3d_ctx *ctx, const mm3d_cloud *points, double leaf, mm3d_cloud **out);
+/* Statistical outlier removal (not a reference function; mm3d_set_outlier_filter states the rule and puts it behind the
+ * whole-map calls).  mm3d_knn_mean_distances is step 3 alone: out[i] = d_i in the cloud's order, NaN for an invalid point (and
+ * for every point when n_valid <= 1).  mm3d_remove_outliers_statistical is the whole rule on a caller's cloud, whatever the
+ * context's setting; the result keeps the input's voxel lattice and carries the kept points' bounding box, as
+ * mm3d_remove_outliers' does.  One host wait each beyond what the cloud's bounding box and its grid cost (none for a
+ * down-sampled cloud at a small mean_k; a caller's raw cloud waits for its box, and a grid cell of more than ten voxel leaves,
+ * mean_k of about 40 and above, for the grid's own check).
+ *   - MM3D_EINVAL: a NULL argument; mean_k outside 1 .. 64; stddev_mult negative or not finite; a cloud of 2^31 points or more.
+ *     MM3D_ECAPACITY: capacity below mm3d_cloud_size(points).  An empty cloud gives MM3D_OK and an empty result.
+ *   - An exact k'-nearest search over the library's cell-sorted grid; the result does not depend on the grid's cell, on launch
+ *     geometry or on the order in which anything arrives. */
+int mm3d_knn_mean_distances(mm3d_ctx *ctx, const mm3d_cloud *points, int mean_k, double *out, size_t capacity);
+int mm3d_remove_outliers_statistical(mm3d_ctx *ctx, const mm3d_cloud *in, int mean_k, double stddev_mult, mm3d_cloud **out);
+/* Diagnostics of the k'-nearest search, process-wide, collected on contexts with mm3d_set_debug on (a host wait per call):
+ * out[0] queries, out[1] those that looked past their first 3 x 3 x 3 box of cells, out[2] those a second launch served. */
+void mm3d_debug_outlier_search(long long out[3], int reset);
 /* The Harris response of every point (HarrisKeypoint3D::responseHarris, what detectKeypoints(HARRIS)
  * thresholds and suppresses); dst receives mm3d_cloud_size(points) floats. */
 int mm3d_harris_response(mm3d_ctx *ctx, const mm3d_cloud *points, const mm3d_normals *normals, double radius,

@@ -97,6 +97,37 @@ class KeypointOptions(C.Structure):
             setattr(self, k, int(v) if k == "source" else float(v))
 
 
+class OutlierMethod(enum.IntEnum):  # mm3d_outlier_method (not a reference enum)
+    RADIUS = 0
+    STATISTICAL = 1
+
+
+class OutlierOptions(C.Structure):
+    """mm3d_outlier_options (mm3d_set_outlier_filter); the defaults are mm3d_outlier_options_default's."""
+    _fields_ = [("method", C.c_int), ("mean_k", C.c_int), ("stddev_mult", C.c_double)]
+
+    def __init__(self, **kw):
+        super().__init__()
+        lib().mm3d_outlier_options_default(C.byref(self))
+        kinds = dict(self._fields_)
+        for k, v in kw.items():
+            if k not in kinds:
+                raise TypeError("unknown outlier option " + k)
+            setattr(self, k, int(v) if kinds[k] is C.c_int else float(v))
+
+    def as_tuple(self):
+        return (int(self.method), int(self.mean_k), float(self.stddev_mult))
+
+
+class OutlierStats(C.Structure):
+    """mm3d_outlier_stats"""
+    _fields_ = [("points", C.c_longlong), ("valid", C.c_longlong), ("kept", C.c_longlong), ("k", C.c_int), ("mean", C.c_double),
+                ("stddev", C.c_double), ("threshold", C.c_double)]
+
+    def as_dict(self):
+        return {k: (float if t is C.c_double else int)(getattr(self, k)) for k, t in self._fields_}
+
+
 class RefineMethod(enum.IntEnum):   # mm3d_refine_method (not a reference enum)
     ICP = 0
     NDT = 1
@@ -585,6 +616,24 @@ class Context:
         self._ck(lib().mm3d_get_keypoints(self._h, C.byref(o)))
         return o
 
+    def setOutlierFilter(self, options=None, **kw):
+        """mm3d_set_outlier_filter: what filters a down-sampled map behind the whole-map calls.  An OutlierOptions, or its fields
+        as keywords (method=OutlierMethod.STATISTICAL, mean_k=1 .. 64, stddev_mult=...)."""
+        o = options if options is not None else OutlierOptions(**kw)
+        self._ck(lib().mm3d_set_outlier_filter(self._h, C.byref(o)))
+
+    def getOutlierFilter(self) -> "OutlierOptions":
+        o = OutlierOptions()
+        self._ck(lib().mm3d_get_outlier_filter(self._h, C.byref(o)))
+        return o
+
+    @property
+    def last_outlier_stats(self) -> dict:
+        """mm3d_last_outlier_stats: the statistical filter's last run on this context."""
+        st = OutlierStats()
+        self._ck(lib().mm3d_last_outlier_stats(self._h, C.byref(st)))
+        return st.as_dict()
+
     def setRefinement(self, options=None, **kw):
         """mm3d_set_refinement: what refines a pair's initial estimate.  A RefineOptions, or its fields as keywords
         (method=RefineMethod.NDT, resolution=... in metres; 0 = the default multiple of params.resolution, neighbours=1 or 7,
@@ -749,6 +798,20 @@ class Context:
         """mm3d_uniform_keypoints: of every occupied voxel of the global lattice of side leaf, the point nearest its centre."""
         h = C.c_void_p()
         self._ck(lib().mm3d_uniform_keypoints(self._h, points._h, C.c_double(leaf), C.byref(h)))
+        return Cloud(self, h)
+
+    def knnMeanDistances(self, points: "Cloud", mean_k: int) -> np.ndarray:
+        """mm3d_knn_mean_distances: every point's mean distance to its min(mean_k, valid points - 1) nearest neighbours, float64 in
+        the cloud's order; NaN for a non-finite point."""
+        out = np.empty(len(points), dtype=np.float64)
+        self._ck(lib().mm3d_knn_mean_distances(self._h, points._h, int(mean_k), out.ctypes.data_as(C.c_void_p), C.c_size_t(len(out))))
+        return out
+
+    def removeOutliersStatistical(self, cloud: "Cloud", mean_k: int = 16, stddev_mult: float = 2.0) -> "Cloud":
+        """mm3d_remove_outliers_statistical: the points whose mean distance to their mean_k nearest neighbours is at most the
+        cloud's mean of it plus stddev_mult standard deviations."""
+        h = C.c_void_p()
+        self._ck(lib().mm3d_remove_outliers_statistical(self._h, cloud._h, int(mean_k), C.c_double(stddev_mult), C.byref(h)))
         return Cloud(self, h)
 
     def siftCertOctave(self, points: "Cloud", min_scale: float, octave: int):

@@ -40,6 +40,7 @@ mm3d::StageSelection::StageSelection()
   mm3d_icp_generalized_options_default(&generalized_options);
   mm3d_estimator_options_default(&estimator_options);
   mm3d_icp_sampling_options_default(&sampling_options);
+  mm3d_outlier_options_default(&outlier_options);
 }
 
 void mm3d::select_stages(mm3d_ctx *ctx, bool peers_follow, const std::function<void(StageSelection &)> &edit)
@@ -206,6 +207,11 @@ void mm3d_estimator_options_default(mm3d_estimator_options *o)
 {
   if (o) *o = mm3d_estimator_options{MM3D_ESTIMATOR_RANSAC, 0.0, 64, 20};
 }
+void mm3d_outlier_options_default(mm3d_outlier_options *o)
+{
+  if (o) *o = mm3d_outlier_options{MM3D_OUTLIERS_RADIUS, 16, 2.0};
+}
+
 void mm3d_icp_sampling_options_default(mm3d_icp_sampling_options *o)
 {
   if (o) *o = mm3d_icp_sampling_options{MM3D_ICP_SAMPLE_NONE, 0.25, 0, 4};

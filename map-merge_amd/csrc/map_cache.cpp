@@ -40,6 +40,11 @@ std::string feature_key(const mm3d_params *p, const StageSelection &sel)
   // where the keypoints come from (mm3d_set_keypoints): a bundle of the reference's detectors is never a uniform one's, nor
   // one of another leaf (0 = the default, a function of descriptor_radius above; not read under the reference's detectors)
   k.i32(kp.source).f64(kp.source == MM3D_KEYPOINTS_UNIFORM ? kp.leaf : 0.0);
+  // what filters the down-sampled cloud (mm3d_set_outlier_filter): a radius-filtered bundle is never a statistical one's, nor
+  // one of other options (which the radius filter does not read: whatever they are, its bundles are shared)
+  const mm3d_outlier_options &ol = sel.outlier_options;
+  const bool stat = ol.method == MM3D_OUTLIERS_STATISTICAL;
+  k.i32(stat ? ol.method : 0).i32(stat ? ol.mean_k : 0).f64(stat ? ol.stddev_mult : 0.0);
   return k.s;
 }
 

@@ -44,7 +44,9 @@ std::unique_ptr<mm3d_map> mm3d::map_features_impl(mm3d_ctx *ctx, const mm3d_clou
   if (p->descriptor_type < 0 || p->descriptor_type >= 6) throw Error(MM3D_EINVAL, "unknown descriptor type");   // dispatch_descriptors.h:63
   std::unique_ptr<mm3d_cloud> down(downsample(ctx, raw, p->resolution));
   // NB: the outlier radius is the DESCRIPTOR radius (map_merging.cpp:219-220)
-  std::unique_ptr<mm3d_cloud> filt(remove_outliers(ctx, down.get(), p->descriptor_radius, p->outliers_min_neighbours));
+  // (mm3d_set_outlier_filter: the statistical rule in its place; outliers_min_neighbours is then not read)
+  std::unique_ptr<mm3d_cloud> filt(ctx->sel.outliers ? ctx->sel.outliers->filter(ctx, down.get(), ctx->sel.outlier_options, &ctx->last_outlier_stats)
+                                                     : remove_outliers(ctx, down.get(), p->descriptor_radius, p->outliers_min_neighbours));
   down.reset();
   // computeSurfaceNormals, then detectKeypoints(points, normals, type, keypoint_threshold, normal_radius, resolution)
   // (map_merging.cpp:225-233).  SIFT does not read the normals, and its first octave builds every point's sorted
