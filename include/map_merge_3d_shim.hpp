@@ -75,6 +75,43 @@ inline mm3d_outlier_options parse_outliers(const char *value)
   o.method = MM3D_OUTLIERS_STATISTICAL;
   return o;
 }
+// MM3D_CLUSTERS=min_size:<n>, min_size:<n>:<tolerance> or largest[:<tolerance>]: the small connected components of the estimation
+// context's filtered maps are dropped (mm3d_set_cluster_filter; min_size alone keeps mm3d_cluster_options_default's 100, no
+// tolerance means twice params.resolution); off or unset runs nothing.  Anything else throws.
+inline mm3d_cluster_options parse_clusters(const char *value)
+{
+  mm3d_cluster_options o;
+  o.method = MM3D_CLUSTERS_OFF;
+  o.min_size = 100;
+  o.tolerance = 0.0;
+  const std::string v = value ? value : "";
+  if (v.empty() || v == "off") return o;
+  const bool largest = v.compare(0, 7, "largest") == 0 && (v.size() == 7 || v[7] == ':');
+  const bool min_size = v.compare(0, 8, "min_size") == 0 && (v.size() == 8 || v[8] == ':');
+  bool ok = largest || min_size;
+  const size_t head = largest ? 7 : 8;
+  if (ok && v.size() > head) {
+    const char *s = v.c_str() + head + 1;
+    char *end = nullptr;
+    bool more = largest;                     // (largest: the tolerance is the only field)
+    if (min_size) {
+      const long k = std::strtol(s, &end, 10);
+      ok = end != s && (*end == '\0' || *end == ':') && k >= 1 && k <= 2147483647L && *s >= '0' && *s <= '9';
+      o.min_size = (int)k;
+      more = ok && *end == ':';
+      if (more) s = end + 1;
+    }
+    if (ok && more) {
+      o.tolerance = std::strtod(s, &end);
+      ok = end != s && *end == '\0' && std::isfinite(o.tolerance) && o.tolerance > 0.0 && ((*s >= '0' && *s <= '9') || *s == '.');
+    }
+  }
+  if (!ok)
+    throw std::runtime_error("mm3d: MM3D_CLUSTERS must be off, min_size:<n >= 1>, min_size:<n>:<tolerance > 0>, largest or "
+                             "largest:<tolerance>, not '" + v + "'");
+  o.method = largest ? MM3D_CLUSTERS_LARGEST : MM3D_CLUSTERS_MIN_SIZE;
+  return o;
+}
 // MM3D_REFINE=ndt or ndt:<resolution in metres>: the estimation context's pair stage refines with NDT in the ICP's place
 // (mm3d_set_refinement; without a resolution, the library's default multiple of params.resolution; the other options keep
 // mm3d_refine_options_default's values); icp or unset keeps the ICP that MM3D_ICP selects.  Anything else throws.
@@ -438,6 +475,7 @@ inline mm3d_ctx *ctx()
   // MM3D_ALIGN_SAMPLES=<draws> if given; sac_ia or unset keeps the reference's.  Not available on a device list either.
   // MM3D_KEYPOINTS=uniform[:<leaf>]: parse_keypoints above; it works on a device list too.
   // MM3D_OUTLIERS=statistical[:<mean_k>[:<stddev_mult>]]: parse_outliers above; it works on a device list too.
+  // MM3D_CLUSTERS=min_size:<n>[:<tolerance>] or largest[:<tolerance>]: parse_clusters above; it works on a device list too.
   // MM3D_REFINE=ndt[:<resolution>]: parse_refine above.  Not available on a device list: ndt with MM3D_DEVICES set as well throws.
   // MM3D_COARSE=correlative[:<cell>]: parse_coarse above.  Not available on a device list: correlative with MM3D_DEVICES set as well throws.
   // MM3D_CONFIDENCE=overlap[:<voxel>]: parse_confidence above.  Not available on a device list: overlap with MM3D_DEVICES set as well throws.
@@ -462,6 +500,7 @@ inline mm3d_ctx *ctx()
       throw std::runtime_error("mm3d: MM3D_COARSE=correlative is not available with MM3D_DEVICES (a device list carries no signatures)");
     const mm3d_keypoint_options keypoints = parse_keypoints(std::getenv("MM3D_KEYPOINTS"));
     const mm3d_outlier_options outliers = parse_outliers(std::getenv("MM3D_OUTLIERS"));
+    const mm3d_cluster_options clusters = parse_clusters(std::getenv("MM3D_CLUSTERS"));
     mm3d_refine_options refine = parse_refine(std::getenv("MM3D_REFINE"));
     if (refine.method == MM3D_REFINE_NDT && std::getenv("MM3D_DEVICES") && *std::getenv("MM3D_DEVICES"))
       throw std::runtime_error("mm3d: MM3D_REFINE=ndt is not available with MM3D_DEVICES (a device list carries no voxel tables)");
@@ -500,6 +539,8 @@ inline mm3d_ctx *ctx()
       throw std::runtime_error("mm3d: MM3D_KEYPOINTS was refused (the leaf must be a positive float with a finite reciprocal)");
     if (outliers.method != MM3D_OUTLIERS_RADIUS && mm3d_set_outlier_filter(e, &outliers) != MM3D_OK)
       throw std::runtime_error("mm3d: MM3D_OUTLIERS was refused (mean_k must be 1 .. 64, stddev_mult finite and not negative)");
+    if (clusters.method != MM3D_CLUSTERS_OFF && mm3d_set_cluster_filter(e, &clusters) != MM3D_OK)
+      throw std::runtime_error("mm3d: MM3D_CLUSTERS was refused (min_size must be at least 1, the tolerance finite and not negative)");
     if (refine.method != MM3D_REFINE_ICP && mm3d_set_refinement(e, &refine) != MM3D_OK)
       throw std::runtime_error("mm3d: MM3D_REFINE was refused (the resolution must be a positive float with a finite reciprocal)");
     if (coarse.method != MM3D_COARSE_NONE && mm3d_set_coarse_alignment(e, &coarse) != MM3D_OK)

@@ -415,6 +415,55 @@ typedef struct mm3d_outlier_stats {
 /* The statistical filter's last run on this context: mm3d_remove_outliers_statistical, or mm3d_map_features under
  * MM3D_OUTLIERS_STATISTICAL (all zero before the first).  MM3D_EINVAL for NULL. */
 int mm3d_last_outlier_stats(const mm3d_ctx *ctx, mm3d_outlier_stats *stats);
+/* What removes the small connected components of a filtered map (off the reference's path; MM3D_CLUSTERS_OFF by default: nothing
+ * runs).  Both outlier filters are density tests: a person, another robot or a floating fragment of a bad scan is a compact,
+ * dense blob in free space and passes them.  With a method selected, every place that filters a map behind a whole-map call --
+ * mm3d_map_features, mm3d_estimate_maps_transforms on one stream or many, on a device list (mm3d_create_devices) and
+ * mm3d_shard_begin -- runs mm3d_remove_small_clusters(the cloud that left the outlier filter, radius or statistical, tolerance,
+ * method, min_size) before the normals: Euclidean clustering as users of pcl::EuclideanClusterExtraction and Open3D's
+ * cluster_dbscan expect it.  A map that the cluster filter empties is handled like one the outlier filter emptied.  mm3d_params
+ * does not change; the stand-alone mm3d_remove_outliers* are untouched.
+ *   The rule, for a cloud of n 16-byte records and a tolerance finite and > 0 (no parity with PCL's class is claimed: PCL takes
+ *   a kd-tree radius search in float, and its cluster order is an artefact of it):
+ *   1. A point is valid when its three coordinates are finite.  Invalid points are never kept, never counted in a cluster and
+ *      never anybody's neighbour; their label is -1.
+ *   2. Two valid points i != j are adjacent iff (double)d2 <= tolerance * tolerance, the product formed in double, where
+ *      d2 = (dx * dx + dy * dy) + dz * dz in float, every operation rounded to nearest, nothing contracted (the d2 of the
+ *      statistical filter).  Duplicate points are adjacent.
+ *   3. A cluster is a connected component of that graph.  Its label is the smallest record index, in the cloud's own order,
+ *      among its members; its size is the number of its members.  So the labels depend neither on launch geometry, nor on the
+ *      cell-sorted order the device works in, nor on which lane won an atomic.
+ *   4. MM3D_CLUSTERS_MIN_SIZE keeps a valid point iff its cluster's size is at least min_size (>= 1; 1 keeps exactly the valid
+ *      points).  MM3D_CLUSTERS_LARGEST keeps the members of the largest cluster, among clusters of equal size the one with the
+ *      smallest label; an empty cloud, or one with no valid point, gives an empty result.  The result is the kept records in
+ *      the cloud's order, colour included.
+ *   - options.tolerance == 0 means 2 * params.resolution behind the whole-map calls: two centroids of face-adjacent voxels of
+ *     the down-sampled cloud are always closer than that, so a densely sampled surface stays one cluster whatever its
+ *     orientation.
+ *   - The setting reaches the context's mm3d_set_streams helpers in either order of the two calls, and every device of a
+ *     device-list context; only a map's features change, and those travel in the bundles, so device lists and shards carry it.
+ *     Every rank of a sharded call must use the same setting.  Nothing is drawn from rand().  The result is an integer function
+ *     of the cloud alone: bit-identical for every stream count, driver, batch and cache setting.
+ *   - The map cache's map key holds (method, min_size, tolerance), zeros under MM3D_CLUSTERS_OFF. */
+typedef enum { MM3D_CLUSTERS_OFF = 0, MM3D_CLUSTERS_MIN_SIZE = 1, MM3D_CLUSTERS_LARGEST = 2 } mm3d_cluster_method;
+typedef struct mm3d_cluster_options {
+  int method;                 /* MM3D_CLUSTERS_* */
+  int min_size;               /* >= 1; read by MM3D_CLUSTERS_MIN_SIZE */
+  double tolerance;           /* metres, finite and >= 0; 0 = 2 * params.resolution */
+} mm3d_cluster_options;
+void mm3d_cluster_options_default(mm3d_cluster_options *o);       /* MM3D_CLUSTERS_OFF, 100, 0.0 */
+/* MM3D_EINVAL: ctx or options NULL, an unknown method, min_size < 1, a tolerance negative or not finite (the values are checked
+ * whatever the method).  After a refused call the selection is what it was. */
+int mm3d_set_cluster_filter(mm3d_ctx *ctx, const mm3d_cluster_options *options);
+int mm3d_get_cluster_filter(const mm3d_ctx *ctx, mm3d_cluster_options *options);   /* MM3D_EINVAL for NULL */
+typedef struct mm3d_cluster_stats {
+  long long points, valid, kept;      /* n, the valid points, the size of the result (mm3d_cluster_labels: the valid points) */
+  long long clusters, kept_clusters;  /* components, and those of them that were kept (mm3d_cluster_labels: all) */
+  long long largest;                  /* the size of the largest cluster, 0 without a valid point */
+} mm3d_cluster_stats;
+/* The cluster filter's last run on this context: mm3d_remove_small_clusters, or mm3d_map_features with a method selected (all
+ * zero before the first).  MM3D_EINVAL for NULL. */
+int mm3d_last_cluster_stats(const mm3d_ctx *ctx, mm3d_cluster_stats *stats);
 /* What refines a pair's initial estimate where params.refine_transform is set (off the reference's path; MM3D_REFINE_ICP by
  * default: the ICP that mm3d_set_icp_method selects, which mm3d_get_icp_method keeps answering whatever the refinement is).
  * MM3D_REFINE_NDT runs the Normal Distributions Transform in the ICP's place: a Gauss-Newton form of point-to-distribution
@@ -542,6 +591,22 @@ int mm3d_remove_outliers_statistical(mm3d_ctx *ctx, const mm3d_cloud *in, int me
 /* Diagnostics of the k'-nearest search, process-wide, collected on contexts with mm3d_set_debug on (a host wait per call):
  * out[0] queries, out[1] those that looked past their first 3 x 3 x 3 box of cells, out[2] those a second launch served. */
 void mm3d_debug_outlier_search(long long out[3], int reset);
+/* Euclidean clustering (not a reference function; mm3d_set_cluster_filter states the rule and puts it behind the whole-map
+ * calls).  mm3d_cluster_labels is steps 1 - 3 alone: labels[i] = the smallest record index of point i's cluster, -1 for an
+ * invalid point, in the cloud's order; stats (may be NULL) receives the counts, with nothing removed.
+ * mm3d_remove_small_clusters is the whole rule on a caller's cloud, whatever the context's setting, and leaves its counts for
+ * mm3d_last_cluster_stats; the result keeps the input's voxel lattice and carries the kept points' bounding box, as
+ * mm3d_remove_outliers' does.  One host wait each beyond what the cloud's bounding box and its grid cost.
+ *   - MM3D_EINVAL: a NULL argument (stats excepted); a tolerance that is not finite or not > 0; an unknown method or
+ *     MM3D_CLUSTERS_OFF; min_size < 1 (checked whatever the method); capacity below mm3d_cloud_size(points); a cloud of 2^31
+ *     points or more.  An empty cloud gives MM3D_OK and an empty result.
+ *   - Connected components by a lock-free union-find over the record indices, the candidates of a point taken from the
+ *     library's cell-sorted grid at a cell just above the tolerance (for a cloud spread over kilometres the cell grows, and
+ *     with it the candidates per point: the result depends neither on the cell, nor on launch geometry, nor on the order in
+ *     which anything arrives).  No size is refused: a cell that holds thousands of points -- a raw scan that was not
+ *     voxelised -- is processed correctly, and the scan is quadratic in the points of such a cell. */
+int mm3d_cluster_labels(mm3d_ctx *ctx, const mm3d_cloud *points, double tolerance, int *labels, size_t capacity, mm3d_cluster_stats *stats);
+int mm3d_remove_small_clusters(mm3d_ctx *ctx, const mm3d_cloud *in, double tolerance, int method, int min_size, mm3d_cloud **out);
 /* The Harris response of every point (HarrisKeypoint3D::responseHarris, what detectKeypoints(HARRIS)
  * thresholds and suppresses); dst receives mm3d_cloud_size(points) floats. */
 int mm3d_harris_response(mm3d_ctx *ctx, const mm3d_cloud *points, const mm3d_normals *normals, double radius,

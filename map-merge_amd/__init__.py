@@ -128,6 +128,38 @@ class OutlierStats(C.Structure):
         return {k: (float if t is C.c_double else int)(getattr(self, k)) for k, t in self._fields_}
 
 
+class ClusterMethod(enum.IntEnum):  # mm3d_cluster_method (not a reference enum)
+    OFF = 0
+    MIN_SIZE = 1
+    LARGEST = 2
+
+
+class ClusterOptions(C.Structure):
+    """mm3d_cluster_options (mm3d_set_cluster_filter); the defaults are mm3d_cluster_options_default's."""
+    _fields_ = [("method", C.c_int), ("min_size", C.c_int), ("tolerance", C.c_double)]
+
+    def __init__(self, **kw):
+        super().__init__()
+        lib().mm3d_cluster_options_default(C.byref(self))
+        kinds = dict(self._fields_)
+        for k, v in kw.items():
+            if k not in kinds:
+                raise TypeError("unknown cluster option " + k)
+            setattr(self, k, int(v) if kinds[k] is C.c_int else float(v))
+
+    def as_tuple(self):
+        return (int(self.method), int(self.min_size), float(self.tolerance))
+
+
+class ClusterStats(C.Structure):
+    """mm3d_cluster_stats"""
+    _fields_ = [("points", C.c_longlong), ("valid", C.c_longlong), ("kept", C.c_longlong), ("clusters", C.c_longlong),
+                ("kept_clusters", C.c_longlong), ("largest", C.c_longlong)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 class RefineMethod(enum.IntEnum):   # mm3d_refine_method (not a reference enum)
     ICP = 0
     NDT = 1
@@ -634,6 +666,25 @@ class Context:
         self._ck(lib().mm3d_last_outlier_stats(self._h, C.byref(st)))
         return st.as_dict()
 
+    def setClusterFilter(self, options=None, **kw):
+        """mm3d_set_cluster_filter: what drops the small connected components of a filtered map behind the whole-map calls.  A
+        ClusterOptions, or its fields as keywords (method=ClusterMethod.MIN_SIZE or LARGEST, min_size >= 1, tolerance=... in metres;
+        0 = twice params.resolution)."""
+        o = options if options is not None else ClusterOptions(**kw)
+        self._ck(lib().mm3d_set_cluster_filter(self._h, C.byref(o)))
+
+    def getClusterFilter(self) -> "ClusterOptions":
+        o = ClusterOptions()
+        self._ck(lib().mm3d_get_cluster_filter(self._h, C.byref(o)))
+        return o
+
+    @property
+    def last_cluster_stats(self) -> dict:
+        """mm3d_last_cluster_stats: the cluster filter's last run on this context."""
+        st = ClusterStats()
+        self._ck(lib().mm3d_last_cluster_stats(self._h, C.byref(st)))
+        return st.as_dict()
+
     def setRefinement(self, options=None, **kw):
         """mm3d_set_refinement: what refines a pair's initial estimate.  A RefineOptions, or its fields as keywords
         (method=RefineMethod.NDT, resolution=... in metres; 0 = the default multiple of params.resolution, neighbours=1 or 7,
@@ -812,6 +863,22 @@ class Context:
         cloud's mean of it plus stddev_mult standard deviations."""
         h = C.c_void_p()
         self._ck(lib().mm3d_remove_outliers_statistical(self._h, cloud._h, int(mean_k), C.c_double(stddev_mult), C.byref(h)))
+        return Cloud(self, h)
+
+    def clusterLabels(self, points: "Cloud", tolerance: float, with_stats: bool = False):
+        """mm3d_cluster_labels: every point's cluster label, int32 in the cloud's order -- the smallest record index of its
+        connected component under `tolerance`, -1 for a non-finite point.  with_stats: (labels, the counts as a dict)."""
+        out = np.empty(len(points), dtype=np.int32)
+        st = ClusterStats()
+        self._ck(lib().mm3d_cluster_labels(self._h, points._h, C.c_double(tolerance), out.ctypes.data_as(C.c_void_p), C.c_size_t(len(out)),
+                                           C.byref(st)))
+        return (out, st.as_dict()) if with_stats else out
+
+    def removeSmallClusters(self, cloud: "Cloud", tolerance: float, method=ClusterMethod.MIN_SIZE, min_size: int = 100) -> "Cloud":
+        """mm3d_remove_small_clusters: the points of the clusters of at least min_size points (MIN_SIZE), or of the largest
+        cluster (LARGEST), in the cloud's order."""
+        h = C.c_void_p()
+        self._ck(lib().mm3d_remove_small_clusters(self._h, cloud._h, C.c_double(tolerance), int(method), int(min_size), C.byref(h)))
         return Cloud(self, h)
 
     def siftCertOctave(self, points: "Cloud", min_scale: float, octave: int):

@@ -41,6 +41,7 @@ mm3d::StageSelection::StageSelection()
   mm3d_estimator_options_default(&estimator_options);
   mm3d_icp_sampling_options_default(&sampling_options);
   mm3d_outlier_options_default(&outlier_options);
+  mm3d_cluster_options_default(&cluster_options);
 }
 
 void mm3d::select_stages(mm3d_ctx *ctx, bool peers_follow, const std::function<void(StageSelection &)> &edit)
@@ -210,6 +211,10 @@ void mm3d_estimator_options_default(mm3d_estimator_options *o)
 void mm3d_outlier_options_default(mm3d_outlier_options *o)
 {
   if (o) *o = mm3d_outlier_options{MM3D_OUTLIERS_RADIUS, 16, 2.0};
+}
+void mm3d_cluster_options_default(mm3d_cluster_options *o)
+{
+  if (o) *o = mm3d_cluster_options{MM3D_CLUSTERS_OFF, 100, 0.0};
 }
 
 void mm3d_icp_sampling_options_default(mm3d_icp_sampling_options *o)

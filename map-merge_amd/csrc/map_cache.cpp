@@ -45,6 +45,11 @@ std::string feature_key(const mm3d_params *p, const StageSelection &sel)
   const mm3d_outlier_options &ol = sel.outlier_options;
   const bool stat = ol.method == MM3D_OUTLIERS_STATISTICAL;
   k.i32(stat ? ol.method : 0).i32(stat ? ol.mean_k : 0).f64(stat ? ol.stddev_mult : 0.0);
+  // what drops the small clusters of the filtered cloud (mm3d_set_cluster_filter): zeros while it is off, whatever the other
+  // two fields are; LARGEST does not read min_size
+  const mm3d_cluster_options &cf = sel.cluster_options;
+  const bool on = cf.method != MM3D_CLUSTERS_OFF;
+  k.i32(on ? cf.method : 0).i32(cf.method == MM3D_CLUSTERS_MIN_SIZE ? cf.min_size : 0).f64(on ? cf.tolerance : 0.0);
   return k.s;
 }
 

@@ -48,6 +48,8 @@ std::unique_ptr<mm3d_map> mm3d::map_features_impl(mm3d_ctx *ctx, const mm3d_clou
   std::unique_ptr<mm3d_cloud> filt(ctx->sel.outliers ? ctx->sel.outliers->filter(ctx, down.get(), ctx->sel.outlier_options, &ctx->last_outlier_stats)
                                                      : remove_outliers(ctx, down.get(), p->descriptor_radius, p->outliers_min_neighbours));
   down.reset();
+  // (mm3d_set_cluster_filter: the connected components too small to be structure leave before anything looks at the cloud)
+  if (ctx->sel.clusters) filt.reset(ctx->sel.clusters->filter(ctx, filt.get(), ctx->sel.cluster_options, p->resolution, &ctx->last_cluster_stats));
   // computeSurfaceNormals, then detectKeypoints(points, normals, type, keypoint_threshold, normal_radius, resolution)
   // (map_merging.cpp:225-233).  SIFT does not read the normals, and its first octave builds every point's sorted
   // neighbour list over a ball that contains the normals': the two stages share that launch (sift.hip), same bits.
