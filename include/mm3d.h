@@ -163,6 +163,15 @@ int mm3d_debug_sift_cert_octave(mm3d_ctx *ctx, const mm3d_cloud *points, double 
 void mm3d_debug_sift_cert_stats(long long out[8], int reset);
 /* test hook: octaves of at least n points take the certified path (default 15 000, MM3D_SIFT_CERT_MIN; n < 0 restores it) */
 void mm3d_debug_sift_cert_min(int n);
+/* test hook: the exact DoG of single points as the certified octaves compute it for the points their certificate leaves open
+ * (csrc/sift.hip::k_sift_dog_marked, one block per point).  The cloud of octave `octave` is built as
+ * mm3d_debug_sift_cert_octave builds it; out[5 k + s] receives the CPU path's float DoG(ids[k], s) -- the raw values, before
+ * anything is packed.  small_capacity != 0: the instantiation whose sort buffer holds 128 keys instead of 2048, so that
+ * ordinary neighbour lists are worked in several distance bands.  n_ids == 0 does nothing.  MM3D_EINVAL: no such octave, an id
+ * outside its cloud; MM3D_EUNSUPPORTED: a point has more neighbours at ONE distance than the sort buffer holds (its row is
+ * left as it was, the other rows are written). */
+int mm3d_debug_sift_dog_marked(mm3d_ctx *ctx, const mm3d_cloud *points, double min_scale, int octave, const int *ids, size_t n_ids,
+                               int small_capacity, float *out);
 /* test hook: the leaf of the VoxelGrid whose centroids the cloud's points are known to be (downSample's output and
  * removeOutliers' subset of it, R/src/features.cpp:19-40; every centroid within two leaves of a member of its voxel), 0 when
  * nothing is known -- what lets a grid build on the cloud skip its "did a cell outgrow the counting sort" wait */

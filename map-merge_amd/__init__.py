@@ -894,6 +894,16 @@ class Context:
                                                    bound.ctypes.data_as(C.c_void_p), C.c_size_t(n.value), C.byref(n)))
         return val, bound
 
+    def siftDogMarked(self, points: "Cloud", min_scale: float, octave: int, ids, small_capacity: bool = False) -> np.ndarray:
+        """Test hook (mm3d_debug_sift_dog_marked): the exact float DoG of the points `ids` of one octave's cloud, float32[len(ids), 5],
+        from the one-block-per-point kernel of the certified octaves.  small_capacity: the sort buffer of 128 keys (lists in
+        distance bands).  Raises Mm3dError with status -4 when a point does not fit the buffer; rows never written are NaN."""
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        out = np.full((len(ids), 5), np.nan, dtype=np.float32)
+        self._ck(lib().mm3d_debug_sift_dog_marked(self._h, points._h, C.c_double(min_scale), int(octave), ids.ctypes.data_as(C.c_void_p),
+                                                  C.c_size_t(len(ids)), 1 if small_capacity else 0, out.ctypes.data_as(C.c_void_p)))
+        return out
+
     def harrisResponse(self, points: "Cloud", normals: "Normals", radius: float) -> np.ndarray:
         """HarrisKeypoint3D::responseHarris of every point (what detectKeypoints(HARRIS) thresholds)."""
         out = np.zeros(max(len(points), 1), dtype=np.float32)

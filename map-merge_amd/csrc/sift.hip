@@ -17,6 +17,7 @@
 // points are closer than it (>= 25 <=> the violator is not among the 25 nearest).
 #include <atomic>
 #include <cfloat>
+#include <climits>
 #include <functional>
 #include <type_traits>
 #include <memory>
@@ -24,6 +25,7 @@
 #include "sorted_nb.hpp"
 #include "snb_lds.hpp"
 #include "sift_cert.hpp"
+#include "capi_guard.hpp"
 
 namespace mm3d {
 
@@ -592,6 +594,232 @@ static void sift_dog_fast_launch(Context *c, const mm3d_cloud *cur, const Grid &
               fl.ctl_dev(), fl.ov_items.get(), dogv, dogb, rlo2, rup2, need_exact);
 }
 
+// ---- the marked points' exact DoG: one block per point ----------------------------------------------------
+// Step 4 of the certified octave gives a few hundred scattered points (0.05 - 0.1 % of an octave) the CPU path's float DoG.
+// Until round 6 that was a launch of k_sift_dog_lds<SiftCfgLarge, false> on single-query items: 155 KB of LDS per block, so
+// every block waited for a CU nobody else held LDS on, and the hardware queue behind the launch waited with it.  The work
+// needs none of the eight-query arena machinery.  Here a block of four waves takes ONE point:
+//   * the members of its ball -- d2 < r2, d2 by FLANN's operations (dist2), the predicate of snb_sort_one -- are read from
+//     the octave grid's rows (a wave per row, no tile) and staged as 64-bit keys (d2 bits, original index): squared distances
+//     are non-negative floats, so the keys order like radiusSearch's (distance, index);
+//   * a bitonic sort of the keys in LDS;
+//   * 256 list entries at a time, every thread computes its entry's six weights and products (k_sift_dog_lds' expressions)
+//     into LDS, and twelve lanes add them up in list order: the only chains.  An entry beyond 3 sigma contributes +0.0f,
+//     which changes no sum: the CPU loop's `break`;
+//   * thread 0 then does for the point what k_sift_pack_marked did in a launch of its own: the interval check (counted in
+//     ctr->violations), dogv = the exact value, dogb = 0, the packed neighbour values and the contrast classes.
+// A ball with more than K members is worked in ascending distance BANDS [lo, hi) of d2 bits: hi is the largest edge with at
+// most K members below it (four counting passes, one byte of the edge each), every band is staged, sorted and added onto the
+// running sums.  More than K members at ONE distance cannot be held even so: the point is counted in *overflow and nothing is
+// written for it (the octave is then sent back to the sorted lists).  K = 2048 in the product (lists of 300 - 900 entries: one
+// band); K = 128 exists for the test hook, which lets small inputs exercise the bands.
+// LDS: 8 K + 13.4 KB = 29.4 KB at K = 2048 -- five blocks fit a CU beside the other streams' kernels.  No scratch.
+template <int K>
+struct alignas(16) SmLds {
+  unsigned long long key[K];
+  float term[2 * kScales][257];              // a chunk's value * w (rows 0 - 5) and w (6 - 11) per scale; 257: the twelve adding lanes hit twelve banks
+  uint64_t tab[32];
+  unsigned hist[256];
+  float sum[2 * kScales];
+  int cnt;
+  unsigned edge;
+};
+constexpr int kMarkedCap = 2048, kMarkedCapSmall = 128;
+static_assert(sizeof(SmLds<kMarkedCap>) <= 32768, "k_sift_dog_marked shares a CU with the other streams' kernels");
+
+template <int K>
+__global__ void __launch_bounds__(256)
+k_sift_dog_marked(const int *__restrict__ ids, const int *__restrict__ n_ids_dev, const float4 *__restrict__ pts /* original order: rgba */,
+                  GridView g /* .w = original index */, float radius, float r2, SiftScales sc,
+                  float *__restrict__ raw_out /* test hook: [n_ids][5] by list position, nothing else is written; else nullptr */,
+                  float *__restrict__ dogv, float *__restrict__ dogb, int n, float min_contrast, float4 *__restrict__ dogx,
+                  unsigned char *__restrict__ cls, CertCounters *__restrict__ ctr, int *__restrict__ overflow /* zeroed */)
+{
+  static_assert(K >= 2 && (K & (K - 1)) == 0, "the sort works on a power of two");
+  __shared__ SmLds<K> S;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if (tid < 32) lm::exp2f_tab_copy(S.tab, tid);              // (published by the first barrier below)
+  const int n_ids = *n_ids_dev;                              // (known to the device only: a fixed grid walks the list)
+  const unsigned r2b = __float_as_uint(r2);
+  const float ri = radius * 1.0001f + 1e-4f;
+  for (int k = (int)blockIdx.x; k < n_ids; k += (int)gridDim.x) {      // block-uniform
+    const int self = ids[k];
+    const float4 q = pts[self];
+    const int x0 = max(cell_floor(q.x - ri, g.minx, g.inv), 0), x1 = min(cell_floor(q.x + ri, g.minx, g.inv), g.dx - 1);
+    const int y0 = max(cell_floor(q.y - ri, g.miny, g.inv), 0), y1 = min(cell_floor(q.y + ri, g.miny, g.inv), g.dy - 1);
+    const int z0 = max(cell_floor(q.z - ri, g.minz, g.inv), 0), z1 = min(cell_floor(q.z + ri, g.minz, g.inv), g.dz - 1);
+    const int ny = y1 - y0 + 1, nz = z1 - z0 + 1;
+    const int nrows = (x0 <= x1 && ny > 0 && nz > 0) ? ny * nz : 0;
+    // f(member, d2 bits, original index) for every point of the box, all 64 lanes of a wave together (f may ballot)
+    auto visit = [&](auto &&f) {
+      for (int r = wave; r < nrows; r += 4) {
+        const int z = z0 + r / ny, y = y0 + r % ny;
+        const int row = (z * g.dy + y) * g.dx;
+        const int b = g.cell_start[row + x0], e = g.cell_start[row + x1 + 1];
+        for (int j0 = b; j0 < e; j0 += kWave) {
+          const int j = j0 + lane;
+          const bool in = j < e;
+          const float4 cd = g.pts[in ? j : b];
+          const float d2 = dist2(q.x, q.y, q.z, cd.x, cd.y, cd.z);
+          f(in && d2 < r2, __float_as_uint(d2), __float_as_uint(cd.w));
+        }
+      }
+    };
+    // the block's sum of `mine` (three barriers: S.cnt's earlier readers are done, cleared, added)
+    auto block_total = [&](int mine) {
+      __syncthreads();
+      if (tid == 0) S.cnt = 0;
+      __syncthreads();
+      const int w = wave_sum(mine);
+      if (lane == 0 && w) atomicAdd(&S.cnt, w);
+      __syncthreads();
+      return S.cnt;
+    };
+    float acc = 0.0f;                          // thread t < 6: the numerator of scale t; 6 <= t < 12: the denominator of scale t - 6
+    unsigned lo = 0u;                          // the members with d2 bits in [lo, r2b) are still to be added
+    bool failed = false;
+    for (;;) {                                 // bands (every condition is block-uniform)
+      int mine = 0;
+      visit([&](bool mem, unsigned bits, unsigned) { mine += (mem && bits >= lo) ? 1 : 0; });
+      const int rem = block_total(mine);
+      unsigned hi = r2b;
+      if (rem > K) {
+        // the largest edge with at most K members in [lo, edge): byte by byte from the top, `base` members lie below the
+        // edge's fixed bytes
+        unsigned hp = 0u;
+        int base = 0;
+        for (int sh = 24; sh >= 0; sh -= 8) {
+          __syncthreads();
+          S.hist[tid] = 0u;
+          __syncthreads();
+          visit([&](bool mem, unsigned bits, unsigned) {
+            if (mem && bits >= lo && (sh == 24 || (bits >> (sh + 8)) == (hp >> (sh + 8)))) atomicAdd(&S.hist[(bits >> sh) & 255u], 1u);
+          });
+          __syncthreads();
+          if (tid == 0) {
+            int a = base;
+            unsigned d = 0u;
+            for (unsigned j = 0; j < 255u; ++j) {
+              const int nxt = a + (int)S.hist[j];
+              if (nxt > K) break;
+              a = nxt;
+              d = j + 1u;
+            }
+            S.edge = d;
+            S.cnt = a;
+          }
+          __syncthreads();
+          hp |= S.edge << sh;
+          base = S.cnt;
+        }
+        hi = hp;
+        if (hi <= lo) { failed = true; break; }            // more than K members at the distance `lo`
+      }
+      // stage the band's keys
+      __syncthreads();
+      if (tid == 0) S.cnt = 0;
+      __syncthreads();
+      visit([&](bool mem, unsigned bits, unsigned idx) {
+        const bool kp = mem && bits >= lo && bits < hi;
+        const unsigned long long m = ballot(kp);
+        if (m) {
+          int b0 = 0;
+          if (lane == 0) b0 = atomicAdd(&S.cnt, __popcll(m));
+          b0 = __builtin_amdgcn_readfirstlane(b0);
+          const int d = snb_mbcnt(m, b0);
+          if (kp && d < K) S.key[d] = ((unsigned long long)bits << 32) | idx;
+        }
+      });
+      __syncthreads();
+      const int m = S.cnt;
+      if (m > K) { failed = true; break; }                 // (the count above says it cannot happen)
+      if (m > 0) {
+        int P = 2;
+        while (P < m) P <<= 1;
+        for (int i = m + tid; i < P; i += 256) S.key[i] = ~0ull;
+        __syncthreads();
+        for (int kk = 2; kk <= P; kk <<= 1) {
+          for (int j = kk >> 1; j > 0; j >>= 1) {
+            for (int i = tid; i < P; i += 256) {
+              const int ixj = i ^ j;
+              if (ixj > i) {
+                const unsigned long long a = S.key[i], b = S.key[ixj];
+                if ((a > b) == ((i & kk) == 0)) { S.key[i] = b; S.key[ixj] = a; }
+              }
+            }
+            __syncthreads();
+          }
+        }
+        // the sums, 256 list entries at a time
+        for (int c0 = 0; c0 < m; c0 += 256) {
+          const int e = c0 + tid;
+          float tv[kScales], tw[kScales];
+#pragma unroll
+          for (int s = 0; s < kScales; ++s) { tv[s] = 0.0f; tw[s] = 0.0f; }
+          if (e < m) {
+            const unsigned long long key = S.key[e];
+            const float d2 = __uint_as_float((unsigned)(key >> 32));
+            const float val = intensity_of(pts[(unsigned)key].w);
+#pragma unroll
+            for (int s = 0; s < kScales; ++s) {
+              if (d2 <= sc.thr9[s]) {
+                // -0.5f * d2 / sigma_sqr, the division correctly rounded (k_sift_dog has the argument)
+                const float w = lm::expf_glibc_t<false>(lm::fdiv_const(-0.5f * d2, sc.sigma_sqr[s], sc.rcp[s]), [&](unsigned i) { return S.tab[i]; });
+                tw[s] = w;
+                tv[s] = __fmul_rn(val, w);
+              }
+            }
+          }
+#pragma unroll
+          for (int s = 0; s < kScales; ++s) { S.term[s][tid] = tv[s]; S.term[kScales + s][tid] = tw[s]; }
+          __syncthreads();
+          if (tid < 2 * kScales) {
+            const int cn = min(256, m - c0);
+            const float *t = S.term[tid];
+            for (int u = 0; u < cn; ++u) acc = __fadd_rn(acc, t[u]);
+          }
+          __syncthreads();
+        }
+      }
+      if (hi == r2b) break;
+      lo = hi;
+    }
+    if (failed) {
+      if (tid == 0) atomicAdd(overflow, 1);
+      continue;
+    }
+    if (tid < 2 * kScales) S.sum[tid] = acc;
+    __syncthreads();
+    if (tid == 0) {
+      float ex[kDog];
+      float prev = S.sum[0] / S.sum[kScales];
+#pragma unroll
+      for (int s = 1; s < kScales; ++s) {
+        const float cur = S.sum[s] / S.sum[kScales + s];
+        ex[s - 1] = cur - prev;
+        prev = cur;
+      }
+      if (raw_out) {
+#pragma unroll
+        for (int s = 0; s < kDog; ++s) raw_out[(size_t)k * kDog + s] = ex[s];
+      } else {
+        // the exact values replace the point's intervals; the bound is checked
+        bool bad = false;
+#pragma unroll
+        for (int s = 0; s < kDog; ++s) {
+          float l, h;
+          cert_interval(dogv[(size_t)self * kDog + s], dogb[(size_t)self * kDog + s], l, h);
+          if (!(ex[s] >= l && ex[s] <= h)) bad = true;
+          dogv[(size_t)self * kDog + s] = ex[s];
+          dogb[(size_t)self * kDog + s] = 0.0f;
+        }
+        if (bad) atomicAdd(&ctr->violations, 1);
+        cert_pack_bounds(ex, ex, self, n, min_contrast, dogx, cls);
+      }
+    }
+  }
+}
+
 // One octave's keypoint flags by certified decisions.  flags ([3 n + 1] ints, zeroed) receives them; returns false when the
 // octave has to be taken by the sorted-list path instead (flags may then hold partial results: the caller clears them).
 static bool sift_octave_certified(Context *c, const mm3d_cloud *cur, const Grid &gr, int n_items, float max_radius, float r2,
@@ -599,10 +827,10 @@ static bool sift_octave_certified(Context *c, const mm3d_cloud *cur, const Grid 
 {
   const int n = (int)cur->n;
   const SfScales fs = cert_scales(sc, r2);
-  DevBuf<float> dogv(c, (size_t)n * kDog), dogb(c, (size_t)n * kDog), dog(c, (size_t)n * kDog);
+  DevBuf<float> dogv(c, (size_t)n * kDog), dogb(c, (size_t)n * kDog);
   DevBuf<float4> dogx(c, (size_t)n * 3);
   DevBuf<unsigned char> cls(c, (size_t)n);
-  // zeroed: CertCounters | list lengths: marked, -, candidates, wide candidates, open, wide open, -, - | need_exact [n] | open_p [n]
+  // zeroed: CertCounters | list lengths: marked, -, candidates, wide candidates, open, wide open, marked points that did not fit, - | need_exact [n] | open_p [n]
   const size_t z_head = sizeof(CertCounters) + 8 * sizeof(int);
   DevBuf<unsigned char> zeroed(c, z_head + 2 * (size_t)n);
   MM3D_HIP(hipMemsetAsync(zeroed.get(), 0, z_head + 2 * (size_t)n, c->stream));
@@ -635,32 +863,26 @@ static bool sift_octave_certified(Context *c, const mm3d_cloud *cur, const Grid 
   MM3D_LAUNCH(c, "sift_extrema_one", 0.0, k_sift_extrema_one<false>, dim3(one_blocks), dim3(256), 0, (const int *)cids.get(), (const int *)n_cids,
               (const float4 *)cur->pts.get(), gr.view(), (const float *)rup2.get(), fs.T[kScales - 1], (const float4 *)dogx.get(), n, (const float *)dogv.get(),
               (const float *)dogb.get(), (const unsigned char *)cls.get(), flags, need_exact, open_p, ctr);
-  // 4. the marked points: exact DoG floats from the sorted lists (single-query items, the number known to the device only)
-  DevBuf<float4> mq(c, (size_t)n);
-  DevBuf<int2> mitems(c, (size_t)n);
-  DevBuf<int> mids(c, (size_t)n), mident(c, (size_t)n);
-  MM3D_LAUNCH(c, "sift_collect", n * 1.0, k_sift_collect, dim3(div_up(n, 256)), dim3(256), 0, (const unsigned char *)need_exact,
-              (const float4 *)cur->pts.get(), n, mq.get(), mitems.get(), mids.get(), mident.get(), n_marked_dev);
-  const size_t extra_lds = sizeof(float) * 64 * kScales + 256;
-  SnbLaunch<SiftCfgLarge> sl(c, n, extra_lds);
-  // (a few hundred single-query items, a block each: 64 blocks of four items measured slower inside the step -- 410 against 270 us per
-  // launch -- although every block of this configuration waits for a whole CU's LDS)
-  const unsigned exact_blocks = std::min(sl.blocks, 256u);
-  MM3D_LAUNCH(c, "sift_dog_exact", 0.0, (k_sift_dog_lds<SiftCfgLarge, false>), dim3(exact_blocks), dim3(64 * SiftCfgLarge::kWaves), 0,
-              (const float4 *)mq.get(), (const int2 *)mitems.get(), 0, gr.view(), (const float4 *)cur->pts.get(), max_radius, r2, sc, sl.ctl_dev(),
-              sl.ov_items.get(), dog.get(), (int *)nullptr, (unsigned char *)nullptr, (const int *)mident.get(), (const int *)n_marked_dev, 0.0f,
-              (float4 *)nullptr);
-  MM3D_LAUNCH(c, "sift_pack", 0.0, k_sift_pack_marked, dim3(std::min(div_up(n, 256), 64u)), dim3(256), 0, (const int *)mids.get(), (const int *)n_marked_dev,
-              (const float *)dog.get(), dogv.get(), dogb.get(), n, min_contrast, dogx.get(), cls.get(), ctr);
+  // 4. the marked points: exact DoG floats, a block per point, which also replaces the point's intervals and packs them again
+  // (k_sift_dog_marked; the number of points is known to the device only, a few hundred: one pass of the grid.  30 KB of LDS
+  // per block: until round 6 this was k_sift_dog_lds<SiftCfgLarge, false> on single-query items, whose every block waited for
+  // a whole CU's LDS -- 250 us per launch inside the 16-stream step against 58 us alone)
+  DevBuf<int> mids(c, (size_t)n);
+  int *n_ov_marked = n_marked_dev + 6;
+  MM3D_LAUNCH(c, "sift_collect", n * 1.0, k_sift_collect_ids, dim3(div_up(n, 256)), dim3(256), 0, (const unsigned char *)need_exact, 0xffu, n, mids.get(),
+              n_marked_dev);
+  MM3D_LAUNCH(c, "sift_dog_marked", 0.0, (k_sift_dog_marked<kMarkedCap>), dim3(256), dim3(256), 0, (const int *)mids.get(), (const int *)n_marked_dev,
+              (const float4 *)cur->pts.get(), gr.view(), max_radius, r2, sc, (float *)nullptr, dogv.get(), dogb.get(), n, min_contrast, dogx.get(),
+              cls.get(), ctr, n_ov_marked);
   // 5. the open points again, on the collapsed intervals
   MM3D_LAUNCH(c, "sift_collect", n * 1.0, k_sift_collect_ids, dim3(div_up(n, 256)), dim3(256), 0, (const unsigned char *)open_p, 1u, n, oids2.get(), n_oids);
   MM3D_LAUNCH(c, "sift_extrema_fin", 0.0, k_sift_extrema_one<true>, dim3(64), dim3(256), 0, (const int *)oids2.get(), (const int *)n_oids,
               (const float4 *)cur->pts.get(), gr.view(), (const float *)rup2.get(), fs.T[kScales - 1], (const float4 *)dogx.get(), n, (const float *)dogv.get(),
               (const float *)dogb.get(), (const unsigned char *)cls.get(), flags, need_exact, open_p, ctr);
-  int *h = (int *)c->pin(64);      // [0..7] CertCounters, [8] marked, [9] exact launch's overflow, [10] fast launch's overflow items
+  int *h = (int *)c->pin(64);      // [0..7] CertCounters, [8] marked, [9] marked points k_sift_dog_marked could not hold, [10] fast launch's overflow items
   MM3D_HIP(hipMemcpyAsync(h, ctr, sizeof(CertCounters), hipMemcpyDeviceToHost, c->stream));
   MM3D_HIP(hipMemcpyAsync(h + 8, n_marked_dev, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  MM3D_HIP(hipMemcpyAsync(h + 9, &sl.ctl_dev()->ov_count, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  MM3D_HIP(hipMemcpyAsync(h + 9, n_ov_marked, sizeof(int), hipMemcpyDeviceToHost, c->stream));
   MM3D_HIP(hipMemcpyAsync(h + 10, &fl.ctl_dev()->ov_count, sizeof(int), hipMemcpyDeviceToHost, c->stream));
   // the keypoint positions and their number ride on the same wait (thrown away when the octave is sent back)
   exclusive_scan_int(c, flags, pos, (size_t)n * 3 + 1);
@@ -681,29 +903,44 @@ static bool sift_octave_certified(Context *c, const mm3d_cloud *cur, const Grid 
 
 // test hook: val* and B of one octave (0-based) of detectKeypoints(SIFT) on `points`, downloaded; returns the octave
 // cloud's size (0: the octave does not exist).  Nothing is written when the size exceeds `capacity`.
-size_t debug_sift_cert_octave(Context *c, const mm3d_cloud *points, double min_scale, int octave, float *val_host, float *bound_host, size_t capacity)
+// the cloud, the scales and the radius of octave `octave` (0-based) of detectKeypoints(SIFT) on `points`, for the test hooks;
+// false: the octave does not exist
+struct DebugOctave {
+  std::unique_ptr<mm3d_cloud> cloud;
+  SiftScales sc;
+  float scale, max_radius, r2;
+};
+static bool debug_octave(Context *c, const mm3d_cloud *points, double min_scale, int octave, DebugOctave &o)
 {
-  std::unique_ptr<mm3d_cloud> cur;
   const mm3d_cloud *input = points;
   float scale = (float)min_scale;
   for (int oct = 0; oct <= octave; ++oct) {
     std::unique_ptr<mm3d_cloud> next(downsample(c, input, (double)scale));
-    cur = std::move(next);
-    input = cur.get();
-    if (cur->n < 25) return 0;
+    o.cloud = std::move(next);
+    input = o.cloud.get();
+    if (o.cloud->n < 25) return false;
     if (oct < octave) scale *= 2;
   }
-  const mm3d_cloud *oc = cur.get();
   float scales[kScales];
   for (int i = 0; i < kScales; ++i) scales[i] = scale * powf(2.0f, (1.0f * (float)i - 1.0f) / 3.0f);
-  SiftScales sc;
   for (int i = 0; i < kScales; ++i) {
-    sc.sigma_sqr[i] = powf(scales[i], 2.0f);
-    sc.thr9[i] = 9 * sc.sigma_sqr[i];
-    sc.rcp[i] = (float)(1.0 / (double)sc.sigma_sqr[i]);
+    o.sc.sigma_sqr[i] = powf(scales[i], 2.0f);
+    o.sc.thr9[i] = 9 * o.sc.sigma_sqr[i];
+    o.sc.rcp[i] = (float)(1.0 / (double)o.sc.sigma_sqr[i]);
   }
-  const float max_radius = 3.0f * scales[kScales - 1];
-  const float r2 = (float)((double)max_radius * (double)max_radius);
+  o.scale = scale;
+  o.max_radius = 3.0f * scales[kScales - 1];
+  o.r2 = (float)((double)o.max_radius * (double)o.max_radius);
+  return true;
+}
+
+size_t debug_sift_cert_octave(Context *c, const mm3d_cloud *points, double min_scale, int octave, float *val_host, float *bound_host, size_t capacity)
+{
+  DebugOctave o;
+  if (!debug_octave(c, points, min_scale, octave, o)) return 0;
+  const mm3d_cloud *oc = o.cloud.get();
+  const SiftScales &sc = o.sc;
+  const float scale = o.scale, max_radius = o.max_radius, r2 = o.r2;
   const size_t n = oc->n;
   if (n > capacity) return n;
   cloud_hilbert(c, oc, 2.5f * scale);
@@ -719,6 +956,43 @@ size_t debug_sift_cert_octave(Context *c, const mm3d_cloud *points, double min_s
   MM3D_HIP(hipMemcpyAsync(bound_host, dogb.get(), n * kDog * sizeof(float), hipMemcpyDeviceToHost, c->stream));
   c->sync();
   return n;
+}
+
+// test hook (mm3d_debug_sift_dog_marked): k_sift_dog_marked alone over `ids` of the same octave cloud, the raw DoG floats
+// before anything is packed; small_capacity: the instantiation with K = 128, so that short lists take the band path.
+// Throws MM3D_EUNSUPPORTED when a point could not be held (its row of `out` is left as it was; the other rows are written).
+static void debug_sift_dog_marked(Context *c, const mm3d_cloud *points, double min_scale, int octave, const int *ids, size_t n_ids, int small_capacity,
+                                  float *out)
+{
+  if (n_ids == 0) return;
+  DebugOctave o;
+  if (!debug_octave(c, points, min_scale, octave, o)) throw Error(MM3D_EINVAL, "mm3d_debug_sift_dog_marked: no such octave");
+  const mm3d_cloud *oc = o.cloud.get();
+  MM3D_REQUIRE(oc->n_finite == oc->n, "mm3d_debug_sift_dog_marked: the octave cloud holds non-finite points");
+  for (size_t i = 0; i < n_ids; ++i)
+    if (ids[i] < 0 || (size_t)ids[i] >= oc->n) throw Error(MM3D_EINVAL, "mm3d_debug_sift_dog_marked: an id outside the octave cloud");
+  MM3D_REQUIRE(n_ids <= (size_t)INT_MAX / kDog, "mm3d_debug_sift_dog_marked: too many ids");
+  const Grid &gr = cloud_grid(c, oc, o.max_radius * 0.5f);
+  DevBuf<int> d_ids(c, n_ids), d_ctl(c, 2);              // d_ctl: [0] the number of ids, [1] points that did not fit
+  DevBuf<float> d_out(c, n_ids * kDog);
+  int *h_ctl = (int *)c->pin(64), *h_ov = h_ctl + 2;      // (pinned: the copies are asynchronous)
+  h_ctl[0] = (int)n_ids;
+  h_ctl[1] = 0;
+  MM3D_HIP(hipMemcpyAsync(d_ids.get(), ids, n_ids * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  MM3D_HIP(hipMemcpyAsync(d_ctl.get(), h_ctl, 2 * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  MM3D_HIP(hipMemcpyAsync(d_out.get(), out, n_ids * kDog * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  if (small_capacity)
+    MM3D_LAUNCH(c, "sift_dog_marked", 0.0, (k_sift_dog_marked<kMarkedCapSmall>), dim3(256), dim3(256), 0, (const int *)d_ids.get(), (const int *)d_ctl.get(),
+                (const float4 *)oc->pts.get(), gr.view(), o.max_radius, o.r2, o.sc, d_out.get(), (float *)nullptr, (float *)nullptr, (int)oc->n, 0.0f,
+                (float4 *)nullptr, (unsigned char *)nullptr, (CertCounters *)nullptr, d_ctl.get() + 1);
+  else
+    MM3D_LAUNCH(c, "sift_dog_marked", 0.0, (k_sift_dog_marked<kMarkedCap>), dim3(256), dim3(256), 0, (const int *)d_ids.get(), (const int *)d_ctl.get(),
+                (const float4 *)oc->pts.get(), gr.view(), o.max_radius, o.r2, o.sc, d_out.get(), (float *)nullptr, (float *)nullptr, (int)oc->n, 0.0f,
+                (float4 *)nullptr, (unsigned char *)nullptr, (CertCounters *)nullptr, d_ctl.get() + 1);
+  MM3D_HIP(hipMemcpyAsync(out, d_out.get(), n_ids * kDog * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  MM3D_HIP(hipMemcpyAsync(h_ov, d_ctl.get() + 1, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  c->sync();
+  if (*h_ov > 0) throw Error(MM3D_EUNSUPPORTED, "mm3d_debug_sift_dog_marked: a point has more neighbours at one distance than the sort buffer holds");
 }
 
 // normals_radius > 0 and normals_out: the caller also wants computeSurfaceNormals(points, normals_radius) (it is about to
@@ -924,3 +1198,13 @@ extern "C" void mm3d_debug_snb_stats_sift(unsigned long long *out, int reset)
 #endif
 
 }  // namespace mm3d
+
+// the C entry point of the marked-point probe (include/mm3d.h) lives with its kernel, like nn.hip's mm3d_debug_nn_search: the
+// host-only builds of the library link capi.cpp without this file
+extern "C" int mm3d_debug_sift_dog_marked(mm3d_ctx *ctx, const mm3d_cloud *points, double min_scale, int octave, const int *ids, size_t n_ids,
+                                          int small_capacity, float *out)
+{
+  if (!points || !(min_scale > 0.0) || !std::isfinite(min_scale) || octave < 0 || octave > 16) return MM3D_EINVAL;
+  if (n_ids && (!ids || !out)) return MM3D_EINVAL;
+  return mm3d::guarded(ctx, [&] { mm3d::debug_sift_dog_marked(ctx, points, min_scale, octave, ids, n_ids, small_capacity, out); });
+}

@@ -23,7 +23,7 @@
 //      a neighbour CERTAINLY below decides "no", no neighbour POSSIBLY below-or-equal decides "yes", anything else is open --
 //      the point and the neighbours whose comparison is open are marked.
 //   4. the marked points (0.05 - 0.1 % of an octave on the headline maps, scripts/sift_price.py) get the CPU path's exact
-//      DoG floats from k_sift_dog_lds on single-query items; their intervals collapse to points and the test of the open
+//      DoG floats from k_sift_dog_marked (sift.hip: one block per point); their intervals collapse to points and the test of the open
 //      points is taken again: every comparison that was open is now exact against exact, every other one stays decided
 //      (the exact value lies inside the old interval), so nothing is open afterwards.
 //
@@ -313,12 +313,10 @@ __device__ __forceinline__ void cert_interval(float v, float b, float &lo, float
 // values first: k_sift_reject reads one row and a half;
 // cls: bit s = |DoG(s + 1)| may reach the contrast (candidate), bit 3 + s = it certainly does (live).
 // dogb == nullptr: dogv holds the CPU path's floats themselves (the octaves on the sorted lists, sift.hip).
-__device__ __forceinline__ void cert_pack_point(const float *__restrict__ dogv, const float *__restrict__ dogb, int i, int n, float min_contrast,
-                                                float4 *__restrict__ dogx, unsigned char *__restrict__ cls)
+// (cert_pack_bounds: the same from the point's five intervals in registers)
+__device__ __forceinline__ void cert_pack_bounds(const float (&lo)[kCertDog], const float (&hi)[kCertDog], int i, int n, float min_contrast,
+                                                 float4 *__restrict__ dogx, unsigned char *__restrict__ cls)
 {
-  float lo[kCertDog], hi[kCertDog];
-#pragma unroll
-  for (int s = 0; s < kCertDog; ++s) cert_interval(dogv[(size_t)i * kCertDog + s], dogb ? dogb[(size_t)i * kCertDog + s] : 0.0f, lo[s], hi[s]);
   float mnhi[3], mnlo[3], mxlo[3], mxhi[3];
   unsigned c = 0;
 #pragma unroll
@@ -334,6 +332,15 @@ __device__ __forceinline__ void cert_pack_point(const float *__restrict__ dogv, 
   dogx[(size_t)n + i] = make_float4(mxlo[1], mxlo[2], mnlo[0], mnlo[1]);
   dogx[2 * (size_t)n + i] = make_float4(mnlo[2], mxhi[0], mxhi[1], mxhi[2]);
   cls[i] = (unsigned char)c;
+}
+
+__device__ __forceinline__ void cert_pack_point(const float *__restrict__ dogv, const float *__restrict__ dogb, int i, int n, float min_contrast,
+                                                float4 *__restrict__ dogx, unsigned char *__restrict__ cls)
+{
+  float lo[kCertDog], hi[kCertDog];
+#pragma unroll
+  for (int s = 0; s < kCertDog; ++s) cert_interval(dogv[(size_t)i * kCertDog + s], dogb ? dogb[(size_t)i * kCertDog + s] : 0.0f, lo[s], hi[s]);
+  cert_pack_bounds(lo, hi, i, n, min_contrast, dogx, cls);
 }
 
 // counters of one octave's certified run (device words, copied to the host at the octave's sync)
@@ -503,45 +510,7 @@ __global__ void k_sift_pack_iv(const float *__restrict__ dogv, const float *__re
 }
 
 
-// the marked points' exact DoG floats (`dog`, written by k_sift_dog_lds) replace their intervals; the bound is checked
-__global__ void k_sift_pack_marked(const int *__restrict__ ids, const int *__restrict__ n_ids, const float *__restrict__ dog,
-                                   float *__restrict__ dogv, float *__restrict__ dogb, int n, float min_contrast,
-                                   float4 *__restrict__ dogx, unsigned char *__restrict__ cls, CertCounters *__restrict__ ctr)
-{
-  const int total = *n_ids;           // (known to the device only: a modest grid walks the list)
-  for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < total; k += gridDim.x * blockDim.x) {
-    const int i = ids[k];
-    bool bad = false;
-#pragma unroll
-    for (int s = 0; s < kCertDog; ++s) {
-      const float ex = dog[(size_t)i * kCertDog + s];
-      float lo, hi;
-      cert_interval(dogv[(size_t)i * kCertDog + s], dogb[(size_t)i * kCertDog + s], lo, hi);
-      if (!(ex >= lo && ex <= hi)) bad = true;
-      dogv[(size_t)i * kCertDog + s] = ex;
-      dogb[(size_t)i * kCertDog + s] = 0.0f;
-    }
-    if (bad) atomicAdd(&ctr->violations, 1);
-    cert_pack_point(dogv, dogb, i, n, min_contrast, dogx, cls);
-  }
-}
-
-// the points with mark[i] != 0 as single-query work items: q[k] = (x, y, z, index), items[k] = (k, 1), ids[k] = index,
-// ident[k] = k (k_sift_dog_lds' sub_items)
-__global__ void k_sift_collect(const unsigned char *__restrict__ mark, const float4 *__restrict__ pts, int n, float4 *__restrict__ q,
-                               int2 *__restrict__ items, int *__restrict__ ids, int *__restrict__ ident, int *__restrict__ count)
-{
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n || !mark[i]) return;
-  const int k = atomicAdd(count, 1);
-  const float4 p = pts[i];
-  q[k] = make_float4(p.x, p.y, p.z, __int_as_float(i));
-  items[k] = make_int2(k, 1);
-  ids[k] = i;
-  ident[k] = k;
-}
-
-// the points with sel[i] & mask, as the id list of k_sift_extrema_one
+// the points with sel[i] & mask, as the id list of k_sift_extrema_one and of k_sift_dog_marked (sift.hip)
 __global__ void k_sift_collect_ids(const unsigned char *__restrict__ sel, unsigned mask, int n, int *__restrict__ ids, int *__restrict__ n_ids)
 {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
