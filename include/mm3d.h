@@ -140,6 +140,9 @@ int mm3d_debug_libm(mm3d_ctx *ctx, int fn, const float *x, const float *y, int n
  * of the SPFH's exact pair features, their branch (0 no switch, 1 switched, 2 f4 == 0: the oracle's mo_pair_features code),
  * the exact path's three bins, the certified path's (pair_bins_fast) ok flag and its three bins (csrc/fpfh.hip) */
 int mm3d_debug_pair_bins(mm3d_ctx *ctx, const float *p1, const float *n1, const float *p2, const float *n2, int n, int *out);
+/* test hook, host code only (no context, no device): out[i] = the float chain "0 + incr[i] + incr[i] + ..." (hits[i] additions,
+ * round to nearest even) as the SPFH kernel's epilogue replays it for a bin, in O(binades) (csrc/spfh_replay.hpp) */
+void mm3d_debug_spfh_replay(const float *incr, const unsigned *hits, int n, float *out);
 /* test hook: every wave-wide reduction / scan of csrc/device_util.hpp (DPP / permlane network) next to the shuffle loop it
  * replaced (kept in csrc/libm_debug.hip), on the same input: n elements (a multiple of 256: whole blocks of four waves), every
  * lane's result of the new form in out_new and of the old one in out_old, element type as the input's.

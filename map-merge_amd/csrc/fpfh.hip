@@ -12,6 +12,7 @@
 // Algorithmic traffic: SPFH 156 B per support point; weighting 132 B per gathered row.
 #include "sorted_nb.hpp"
 #include "capi_guard.hpp"
+#include "spfh_replay.hpp"
 
 namespace mm3d {
 
@@ -214,15 +215,18 @@ __device__ __forceinline__ bool pair_bins_fast(const float4 &p1, const float4 &n
 // can reach through LDS together with the candidates' normals, and bins the pairs inside every live
 // lane's radius.  Every hit of one point adds the SAME float 100/(|N|-1), so a bin's value depends
 // only on its hit count: hits are counted in integers (LDS) in whatever order they are processed, and
-// the float chain "0 + incr + incr + ..." of the CPU loop is replayed once per bin at the end, bit for bit.
+// the float chain "0 + incr + incr + ..." of the CPU loop is replayed at the end, bit for bit: as integer arithmetic on
+// the float's bit pattern, one linear piece per binade, the pieces shared by the point's 33 bins (spfh_replay.hpp).
 //
 // The expensive part is the pair feature (~300 VALU instructions: atan2f, two square roots, five
 // IEEE divisions, three double bin computations), so (a) its lanes must be full and (b) it should run
 // once per PAIR, not once per histogram:
-//  (a) per tile the cheap in-radius test leaves a per-lane bitset; the (owner lane, candidate) hits of the
-//      whole wave are numbered by a prefix sum, written to an LDS pool and dealt to the 64 lanes: a lane
-//      works on ANY point's hit (the owner's position and normal are in LDS) and bumps the owner's counters
-//      with LDS atomics.  Trip count = total hits / 64 instead of the largest per-lane hit count.
+//  (a) per tile the cheap in-radius test runs candidate by candidate (broadcast LDS reads) and its lane mask numbers that
+//      candidate's (owner lane, candidate) hits: they go to an LDS pool, candidate-major, in the same pass, and are dealt to the
+//      64 lanes: a lane works on ANY point's hit (the owner's position and normal are in LDS) and bumps the owner's counters
+//      with LDS atomics.  Trip count = total hits / 64 instead of the largest per-lane hit count.  (Until the bookkeeping was
+//      trimmed the test left a per-lane bitset, a prefix sum over the lanes numbered the hits owner-major and every lane
+//      walked its own bits into the pool: -DMM3D_SPFH_MASKS=0)
 //  (b) computePairFeatures(p, q) and (q, p) return the same bits unless the pair is a tie of its two angles
 //      (pair_features above), and a quarter of a point's neighbours are among the 256 consecutive points of
 //      its BLOCK (kSpfhWaves waves, whose points and counters share the block's LDS).  A candidate that is a
@@ -241,17 +245,41 @@ constexpr int kSpfhPool = MM3D_SPFH_POOL;
 #define MM3D_SPFH_WAVES 4
 #endif
 constexpr int kSpfhWaves = MM3D_SPFH_WAVES;
-#ifdef MM3D_SPFH_STATS
+#if defined(MM3D_SPFH_STATS) || defined(MM3D_SPFH_PHASES)
 __device__ unsigned long long g_spfh_stats[16];  // 0 waves, 1 candidates tested per wave, 2 in-radius hits, 3 pooled hits, 4 second votes, 5 ties, 6 live points,
-                                                 // 7 pooled hits the certified bins refused, 8 (-DMM3D_SPFH_VERIFY) certified bins that differ from the exact ones
+                                                 // 7 pooled hits the certified bins refused, 8 (-DMM3D_SPFH_VERIFY) certified bins that differ from the exact ones;
+                                                 // -DMM3D_SPFH_PHASES (a build of its own: the event counts above are an atomic per lane and event, which the
+                                                 // clocks would mostly measure), shader-clock ticks summed over waves: 9 the box streaming as a whole, 10 in-radius
+                                                 // pass, 11 pool fill, 12 pair loop, 13 epilogue, 14 the whole wave up to the barrier, 15 waves (staging = 9 - 10 - 11 - 12)
+#endif
+#ifdef MM3D_SPFH_STATS
 #define MM3D_SPFH_STAT(i_, v_) atomicAdd(&g_spfh_stats[i_], (unsigned long long)(v_))
 #else
 #define MM3D_SPFH_STAT(i_, v_)
+#endif
+#ifdef MM3D_SPFH_PHASES
+#define SPFH_TICK(var_) const long long var_ = clock64()
+#define SPFH_TOCK(acc_, from_) do { acc_ += clock64() - (from_); } while (0)
+#define SPFH_PHASE(i_, v_) atomicAdd(&g_spfh_stats[i_], (unsigned long long)(v_))
+#else
+#define SPFH_TICK(var_)
+#define SPFH_TOCK(acc_, from_)
 #endif
 #ifndef MM3D_SPFH_FAST
 #define MM3D_SPFH_FAST 1
 #endif
 constexpr bool kSpfhFast = MM3D_SPFH_FAST != 0;   // 0: every pair through pair_features (the A/B)
+// the bookkeeping around the pair features, each with the form it replaced behind 0 (the A/B; the same bits either way):
+#ifndef MM3D_SPFH_MASKS
+#define MM3D_SPFH_MASKS 1                        // 1: per-candidate lane masks and a candidate-major pool filled in the in-radius pass; 0: per-lane bitsets, owner-major pool
+#endif
+#ifndef MM3D_SPFH_DEAL
+#define MM3D_SPFH_DEAL MM3D_SPFH_MASKS           // 1: lane l bins the pool's entries i * 64 + l; 0: l * per + i
+#endif
+constexpr bool kSpfhDealStriped = MM3D_SPFH_DEAL != 0;
+#ifndef MM3D_SPFH_REPLAY
+#define MM3D_SPFH_REPLAY 1                       // 1: a point's 33 float chains from the chain's pieces (spfh_replay.hpp: O(binades)); 0: one addition per hit
+#endif
 constexpr int kSpfhT = 64 * kSpfhWaves;       // points per block
 constexpr int kSpfhNone = 0xFFFF;             // a candidate that is not a live point of the block: above every offset
 __global__ void __launch_bounds__(kSpfhT)
@@ -270,7 +298,11 @@ k_spfh(const float4 *__restrict__ q_pts, const int2 *__restrict__ items, int n_i
   __shared__ unsigned hist[kDim][kSpfhT / 2];
   __shared__ unsigned short s_pool[kSpfhWaves][kSpfhPool];
   const unsigned bid = xcd_remap(blockIdx.x, gridDim.x);
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+#ifdef MM3D_SPFH_PHASES
+  long long tk_radius = 0, tk_fill = 0, tk_pair = 0;
+#endif
+  SPFH_TICK(t_wave);
   const int item0 = (int)bid * kSpfhWaves;
   const int blk_first = items[item0].x;                      // (the grid has no block without an item)
   const int last_item = min(item0 + kSpfhWaves, n_items) - 1;
@@ -305,11 +337,16 @@ k_spfh(const float4 *__restrict__ q_pts, const int2 *__restrict__ items, int n_i
     const float4 *sp = s_pts[wave];
     const float4 *sn = s_nrm[wave];
     unsigned short *pool = s_pool[wave];
+#if MM3D_SPFH_MASKS
+    const float qx = live ? q.x : __int_as_float(0x7fc00000);   // a NaN fails every in-radius test
+#endif
+    SPFH_TICK(t_box);
     wave_stream_box<kSpfhTile, 1>(
         g, x0, x1, y0, y1, z0, z1, s_pts[wave], s_nrm[wave], s_off[wave], s_beg[wave], lane,
         [&](int j, float4 (&out)[1]) { out[0] = nrm_sorted[j]; },
         [&](int n_tile) {
           if (lane == 0) MM3D_SPFH_STAT(1, n_tile);
+          SPFH_TICK(t_radius);
           // the staged normal's .w is the candidate's Hilbert position if it is a support point (-1 otherwise): a live
           // point of this block becomes its block offset in the POINT's .w (the original index is not needed any more:
           // "is it me" is an offset test), everything else kSpfhNone
@@ -317,53 +354,20 @@ k_spfh(const float4 *__restrict__ q_pts, const int2 *__restrict__ items, int n_i
             const int hp = __float_as_int(s_nrm[wave][lane].w), off = hp - blk_first;
             s_pts[wave][lane].w = __int_as_float((hp >= 0 && off >= 0 && off < blk_count) ? off : kSpfhNone);
           }
+#if MM3D_SPFH_MASKS
+          else s_pts[wave][lane].x = __int_as_float(0x7fc00000);   // the slots behind the tile fail every in-radius test: whole groups are tested
+#endif
           wave_lds_fence();
-          unsigned all[kSpfhTile / 32], todo[kSpfhTile / 32];
-#pragma unroll
-          for (int gq = 0; gq < kSpfhTile / 32; ++gq) {
-            unsigned bits = 0, skip = 0;
-            if (gq * 32 < n_tile) {                           // wave-uniform
-#pragma unroll 4
-              for (int b = 0; b < 32; ++b) {
-                const float4 p = sp[gq * 32 + b];             // slots >= n_tile hold stale points: masked off below
-                bits |= (dist2(q.x, q.y, q.z, p.x, p.y, p.z) < r2) ? (1u << b) : 0u;
-                // the pair belongs to the end point with the lower block offset (== : the point itself, "p_idx == indices[idx]")
-                skip |= (__float_as_int(p.w) <= my_off) ? (1u << b) : 0u;
-              }
-              const int rem = n_tile - gq * 32;
-              if (rem < 32) bits &= (1u << rem) - 1u;
-            }
-            all[gq] = live ? bits : 0u;
-            todo[gq] = all[gq] & ~skip;
-          }
-          cnt += __popc(all[0]) + __popc(all[1]);
-          const int mine = __popc(todo[0]) + __popc(todo[1]);
-          MM3D_SPFH_STAT(2, __popc(all[0]) + __popc(all[1]));
-          MM3D_SPFH_STAT(3, mine);
-          // number the wave's hits: exclusive prefix of the per-lane counts
-          const int incl = wave_scan_incl(mine);
-          const int total = __builtin_amdgcn_readlane(incl, kWave - 1);
-          const int first = incl - mine;
-          for (int base = 0; base < total; base += kSpfhPool) {   // one chunk unless nearly every lane hits every candidate
-            {
-              unsigned m0 = todo[0], m1 = todo[1];
-              int r = first;
-              while (m0 | m1) {
-                int k;
-                if (m0) { k = __ffs((int)m0) - 1; m0 &= m0 - 1u; }
-                else { k = 32 + __ffs((int)m1) - 1; m1 &= m1 - 1u; }
-                if (r >= base && r < base + kSpfhPool) pool[r - base] = (unsigned short)((lane << 6) | k);
-                ++r;
-              }
-            }
-            wave_lds_fence();
-            const int n = min(kSpfhPool, total - base);
-            // Lane l takes the entries l * per .. l * per + per - 1: the pool is numbered owner by owner, so 64 CONSECUTIVE
-            // entries are mostly one owner's hits, whose votes all land in the two banks of that owner's counter column;
-            // entries `per` apart belong to different owners and spread over the banks.
+          // bins the n hits of the pool: the wave's 64 lanes take 64 entries at a time
+          auto bin_pool = [&](int n) {
+            SPFH_TICK(t_pair);
+            // An owner-major pool (MM3D_SPFH_MASKS=0): lane l takes the entries l * per .. l * per + per - 1 -- 64 CONSECUTIVE entries
+            // are mostly one owner's hits, whose votes all land in the two banks of that owner's counter column; entries `per`
+            // apart belong to different owners and spread over the banks.  A candidate-major pool has up to 64 different owners
+            // side by side: lane l takes the entries i * 64 + l (MM3D_SPFH_DEAL=1; 0 deals it the other way, for the A/B).
             const int per = (n + kWave - 1) / kWave;
             for (int i = 0; i < per; ++i) {
-              const int e = lane * per + i;
+              const int e = kSpfhDealStriped ? i * kWave + lane : lane * per + i;
               const bool act = e < n;
               const unsigned ent = act ? pool[e] : 0u;
               const int o = wave_off0 + (int)(ent >> 6), k = (int)(ent & 63u);
@@ -414,22 +418,150 @@ k_spfh(const float4 *__restrict__ q_pts, const int2 *__restrict__ items, int n_i
               }
             }
             wave_lds_fence();
+            SPFH_TOCK(tk_pair, t_pair);
+          };
+#if MM3D_SPFH_MASKS
+          // Candidate by candidate: the in-radius test's own lane mask (one v_cmp) numbers the candidate's hits -- position =
+          // hits pooled so far + the set bits below the lane --, the neighbour count takes the test's bit as it is, and the pool
+          // fills candidate-major in the same pass: no per-lane bitsets, no prefix sum over the lanes, no serial walk over a
+          // lane's bits.  kSpfhGroup candidates are read ahead of their tests; a chunk ends where a whole group's hits might not
+          // fit any more (a tile can produce 64 x 64 hits).
+          constexpr int kSpfhGroup = 8;
+          static_assert(kSpfhTile % kSpfhGroup == 0 && kSpfhPool >= 2 * kSpfhGroup * kWave, "a chunk must hold a group's hits");
+          const int lane6 = lane << 6;
+          for (int b0 = 0; b0 < n_tile;) {                    // one round unless nearly every lane hits every candidate
+            SPFH_TICK(t_chunk);
+            int n = 0;
+#ifdef MM3D_SPFH_STATS
+            int st_all = 0;
+#endif
+            for (; b0 < n_tile && n <= kSpfhPool - kSpfhGroup * kWave; b0 += kSpfhGroup) {
+              float4 p[kSpfhGroup];
+#pragma unroll
+              for (int u = 0; u < kSpfhGroup; ++u) p[u] = sp[b0 + u];              // (slots >= n_tile hold NaN)
+#pragma unroll
+              for (int u = 0; u < kSpfhGroup; ++u) {
+                const bool c_in = dist2(qx, q.y, q.z, p[u].x, p[u].y, p[u].z) < r2;     // (qx of a lane that is not live is NaN)
+                // the pair belongs to the end point with the lower block offset (== : the point itself, "p_idx == indices[idx]")
+                const bool c_lo = __float_as_int(p[u].w) > my_off;
+                // (each mask is a comparison's own result; their conjunction is scalar work)
+                const unsigned long long m = ballot(c_in) & ballot(c_lo);
+                cnt += c_in ? 1 : 0;
+#ifdef MM3D_SPFH_STATS
+                st_all += c_in ? 1 : 0;
+#endif
+                if (c_in & c_lo) (pool + n)[__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u))] = (unsigned short)(lane6 | (b0 + u));
+                n += __popcll(m);
+              }
+            }
+            MM3D_SPFH_STAT(2, st_all);
+            if (lane == 0) MM3D_SPFH_STAT(3, n);
+            wave_lds_fence();
+            SPFH_TOCK(tk_radius, t_chunk);
+            bin_pool(n);
           }
+#else
+          unsigned all[kSpfhTile / 32], todo[kSpfhTile / 32];
+#pragma unroll
+          for (int gq = 0; gq < kSpfhTile / 32; ++gq) {
+            unsigned bits = 0, skip = 0;
+            if (gq * 32 < n_tile) {                           // wave-uniform
+#pragma unroll 4
+              for (int b = 0; b < 32; ++b) {
+                const float4 p = sp[gq * 32 + b];             // slots >= n_tile hold stale points: masked off below
+                bits |= (dist2(q.x, q.y, q.z, p.x, p.y, p.z) < r2) ? (1u << b) : 0u;
+                // the pair belongs to the end point with the lower block offset (== : the point itself, "p_idx == indices[idx]")
+                skip |= (__float_as_int(p.w) <= my_off) ? (1u << b) : 0u;
+              }
+              const int rem = n_tile - gq * 32;
+              if (rem < 32) bits &= (1u << rem) - 1u;
+            }
+            all[gq] = live ? bits : 0u;
+            todo[gq] = all[gq] & ~skip;
+          }
+          cnt += __popc(all[0]) + __popc(all[1]);
+          const int mine = __popc(todo[0]) + __popc(todo[1]);
+          MM3D_SPFH_STAT(2, __popc(all[0]) + __popc(all[1]));
+          MM3D_SPFH_STAT(3, mine);
+          // number the wave's hits: exclusive prefix of the per-lane counts
+          const int incl = wave_scan_incl(mine);
+          const int total = __builtin_amdgcn_readlane(incl, kWave - 1);
+          const int first = incl - mine;
+          SPFH_TOCK(tk_radius, t_radius);
+          for (int base = 0; base < total; base += kSpfhPool) {   // one chunk unless nearly every lane hits every candidate
+            SPFH_TICK(t_fill);
+            {
+              unsigned m0 = todo[0], m1 = todo[1];
+              int r = first;
+              while (m0 | m1) {
+                int k;
+                if (m0) { k = __ffs((int)m0) - 1; m0 &= m0 - 1u; }
+                else { k = 32 + __ffs((int)m1) - 1; m1 &= m1 - 1u; }
+                if (r >= base && r < base + kSpfhPool) pool[r - base] = (unsigned short)((lane << 6) | k);
+                ++r;
+              }
+            }
+            wave_lds_fence();
+            SPFH_TOCK(tk_fill, t_fill);
+            bin_pool(min(kSpfhPool, total - base));
+          }
+#endif
         },
         // only points within the radius of the patch's bounding box can be in range
         KeepNearBox{lx, hx, ly, hy, lz, hz, ri * ri});
+#ifdef MM3D_SPFH_PHASES
+    if (lane == 0) {
+      SPFH_PHASE(9, clock64() - t_box); SPFH_PHASE(10, tk_radius); SPFH_PHASE(11, tk_fill); SPFH_PHASE(12, tk_pair); SPFH_PHASE(15, 1);
+    }
+#endif
   }
   __syncthreads();                                            // all votes are in (other waves vote into this wave's columns)
+#ifdef MM3D_SPFH_PHASES
+  if (lane == 0) SPFH_PHASE(14, clock64() - t_wave);   // (up to the block's barrier: the wave's own work and its wait for the others)
+  const int stat_lane = __ffsll((long long)ballot(live)) - 1;
+#endif
   if (!live) return;
+  SPFH_TICK(t_epi);
   if (cnt > 65535) { atomicExch(error, 1); return; }
   const float hist_incr = 100.0f / (float)(cnt - 1);
   float *o = spfh + (size_t)pos[self] * kDim;
+#if MM3D_SPFH_REPLAY
+  // All 33 chains of a point add the same float: the chain's pieces (spfh_replay.hpp: a bin's bits are c + hits r between two
+  // breakpoints, one or two pieces per binade) are made ONCE per point, as far as its fullest bin needs them, and every bin
+  // takes its bits from the last piece that starts at or below its hits.
+  unsigned hits[kDim], bits[kDim], hmax = 0u;
+#pragma unroll
+  for (int b = 0; b < kDim; ++b) {
+    hits[b] = (hist[b][my_off >> 1] >> ((my_off & 1) << 4)) & 0xffffu;
+    hmax = max(hmax, hits[b]);
+    bits[b] = 0u;                                             // no hit: +0
+  }
+  const unsigned xb = __float_as_uint(hist_incr) & 0x7fffffffu;
+  if (xb != 0u && xb < 0x7f800000u) {
+    SpfhChain ch = spfh_chain_begin(hist_incr);
+    while (ch.h <= hmax && !ch.done) {
+      unsigned first, c0, r;
+      spfh_chain_piece(ch, first, c0, r);
+#pragma unroll
+      for (int b = 0; b < kDim; ++b) bits[b] = hits[b] >= first ? c0 + __umul24(hits[b], r) : bits[b];   // (hits < 2^16, r < 2^24: v_mad_u32_u24)
+    }
+  } else if (hmax) {                                          // (100 / 0 with a vote: cannot happen -- a point with one neighbour has none)
+#pragma unroll
+    for (int b = 0; b < kDim; ++b) bits[b] = __float_as_uint(spfh_replay(hist_incr, hits[b]));
+  }
+#pragma unroll
+  for (int b = 0; b < kDim; ++b) o[b] = __uint_as_float(bits[b]);
+#else
   for (int b = 0; b < kDim; ++b) {
     const unsigned hits = (hist[b][my_off >> 1] >> ((my_off & 1) << 4)) & 0xffffu;
     float v = 0.0f;
     for (unsigned i = 0; i < hits; ++i) v += hist_incr;
     o[b] = v;
   }
+#endif
+#ifdef MM3D_SPFH_PHASES
+  if (lane == stat_lane) SPFH_PHASE(13, clock64() - t_epi);
+#endif
 }
 
 // 3. weighting (FPFHEstimation::weightPointSPFHSignature): per keypoint, over its neighbours IN radiusSearch's
@@ -684,7 +816,13 @@ extern "C" int mm3d_debug_pair_bins(mm3d_ctx *ctx, const float *p1, const float 
   return mm3d::guarded(ctx, [&] { mm3d::debug_pair_bins(ctx, p1, n1, p2, n2, n, out); });
 }
 
-#ifdef MM3D_SPFH_STATS
+// host code only: the chain replay of the SPFH epilogue (csrc/spfh_replay.hpp) as the host compiles it
+extern "C" void mm3d_debug_spfh_replay(const float *incr, const unsigned *hits, int n, float *out)
+{
+  for (int i = 0; i < n; ++i) out[i] = mm3d::spfh_replay(incr[i], hits[i]);
+}
+
+#if defined(MM3D_SPFH_STATS) || defined(MM3D_SPFH_PHASES)
 extern "C" void mm3d_debug_spfh_stats(unsigned long long *out, int reset)
 {
   (void)hipDeviceSynchronize();
