@@ -112,6 +112,49 @@ inline mm3d_cluster_options parse_clusters(const char *value)
   o.method = largest ? MM3D_CLUSTERS_LARGEST : MM3D_CLUSTERS_MIN_SIZE;
   return o;
 }
+// MM3D_SMOOTH=mls, mls:<order> or mls:<order>:<radius>, each with @maps or @composed behind it if only one place is meant: moving
+// least squares smooths the estimation context's filtered maps before their normals, and the composed map between two voxel
+// passes (mm3d_set_smoothing; mls alone keeps mm3d_smooth_options_default's order 2, no radius means three times the resolution in
+// force); off or unset runs nothing.  Anything else throws.
+inline mm3d_smooth_options parse_smooth(const char *value)
+{
+  mm3d_smooth_options o;
+  o.method = MM3D_SMOOTH_OFF;
+  o.order = 2;
+  o.min_neighbours = 6;
+  o.where = MM3D_SMOOTH_MAPS | MM3D_SMOOTH_COMPOSED;
+  o.radius = 0.0;
+  const std::string v = value ? value : "";
+  if (v.empty() || v == "off") return o;
+  std::string head = v;
+  const size_t at = v.find('@');
+  bool ok = true;
+  if (at != std::string::npos) {
+    const std::string where = v.substr(at + 1);
+    head = v.substr(0, at);
+    if (where == "maps") o.where = MM3D_SMOOTH_MAPS;
+    else if (where == "composed") o.where = MM3D_SMOOTH_COMPOSED;
+    else ok = false;
+  }
+  ok = ok && head.compare(0, 3, "mls") == 0 && (head.size() == 3 || head[3] == ':');
+  if (ok && head.size() > 3) {
+    const char *s = head.c_str() + 4;
+    char *end = nullptr;
+    const long k = std::strtol(s, &end, 10);
+    ok = end == s + 1 && (*end == '\0' || *end == ':') && (k == 1 || k == 2);
+    o.order = (int)k;
+    if (ok && *end == ':') {
+      s = end + 1;
+      o.radius = std::strtod(s, &end);
+      ok = end != s && *end == '\0' && std::isfinite(o.radius) && o.radius > 0.0 && ((*s >= '0' && *s <= '9') || *s == '.');
+    }
+  }
+  if (!ok)
+    throw std::runtime_error("mm3d: MM3D_SMOOTH must be off, mls, mls:<order 1 or 2> or mls:<order>:<radius > 0>, with @maps or "
+                             "@composed behind it at the most, not '" + v + "'");
+  o.method = MM3D_SMOOTH_MLS;
+  return o;
+}
 // MM3D_REFINE=ndt or ndt:<resolution in metres>: the estimation context's pair stage refines with NDT in the ICP's place
 // (mm3d_set_refinement; without a resolution, the library's default multiple of params.resolution; the other options keep
 // mm3d_refine_options_default's values); icp or unset keeps the ICP that MM3D_ICP selects.  Anything else throws.
@@ -476,6 +519,7 @@ inline mm3d_ctx *ctx()
   // MM3D_KEYPOINTS=uniform[:<leaf>]: parse_keypoints above; it works on a device list too.
   // MM3D_OUTLIERS=statistical[:<mean_k>[:<stddev_mult>]]: parse_outliers above; it works on a device list too.
   // MM3D_CLUSTERS=min_size:<n>[:<tolerance>] or largest[:<tolerance>]: parse_clusters above; it works on a device list too.
+  // MM3D_SMOOTH=mls[:<order>[:<radius>]][@maps|@composed]: parse_smooth above; it works on a device list too.
   // MM3D_REFINE=ndt[:<resolution>]: parse_refine above.  Not available on a device list: ndt with MM3D_DEVICES set as well throws.
   // MM3D_COARSE=correlative[:<cell>]: parse_coarse above.  Not available on a device list: correlative with MM3D_DEVICES set as well throws.
   // MM3D_CONFIDENCE=overlap[:<voxel>]: parse_confidence above.  Not available on a device list: overlap with MM3D_DEVICES set as well throws.
@@ -501,6 +545,7 @@ inline mm3d_ctx *ctx()
     const mm3d_keypoint_options keypoints = parse_keypoints(std::getenv("MM3D_KEYPOINTS"));
     const mm3d_outlier_options outliers = parse_outliers(std::getenv("MM3D_OUTLIERS"));
     const mm3d_cluster_options clusters = parse_clusters(std::getenv("MM3D_CLUSTERS"));
+    const mm3d_smooth_options smooth = parse_smooth(std::getenv("MM3D_SMOOTH"));
     mm3d_refine_options refine = parse_refine(std::getenv("MM3D_REFINE"));
     if (refine.method == MM3D_REFINE_NDT && std::getenv("MM3D_DEVICES") && *std::getenv("MM3D_DEVICES"))
       throw std::runtime_error("mm3d: MM3D_REFINE=ndt is not available with MM3D_DEVICES (a device list carries no voxel tables)");
@@ -541,6 +586,8 @@ inline mm3d_ctx *ctx()
       throw std::runtime_error("mm3d: MM3D_OUTLIERS was refused (mean_k must be 1 .. 64, stddev_mult finite and not negative)");
     if (clusters.method != MM3D_CLUSTERS_OFF && mm3d_set_cluster_filter(e, &clusters) != MM3D_OK)
       throw std::runtime_error("mm3d: MM3D_CLUSTERS was refused (min_size must be at least 1, the tolerance finite and not negative)");
+    if (smooth.method != MM3D_SMOOTH_OFF && mm3d_set_smoothing(e, &smooth) != MM3D_OK)
+      throw std::runtime_error("mm3d: MM3D_SMOOTH was refused (the order must be 1 or 2, the radius finite and not negative)");
     if (refine.method != MM3D_REFINE_ICP && mm3d_set_refinement(e, &refine) != MM3D_OK)
       throw std::runtime_error("mm3d: MM3D_REFINE was refused (the resolution must be a positive float with a finite reciprocal)");
     if (coarse.method != MM3D_COARSE_NONE && mm3d_set_coarse_alignment(e, &coarse) != MM3D_OK)
@@ -563,7 +610,14 @@ inline mm3d_ctx *ctx()
 }
 inline mm3d_ctx *compose_ctx()
 {
-  static mm3d_ctx *c = make_ctx(1);
+  // MM3D_SMOOTH with the composed map in it (parse_smooth): composeMaps smooths between two voxel passes
+  static mm3d_ctx *c = [] {
+    mm3d_ctx *e = make_ctx(1);
+    const mm3d_smooth_options smooth = parse_smooth(std::getenv("MM3D_SMOOTH"));
+    if (smooth.method != MM3D_SMOOTH_OFF && mm3d_set_smoothing(e, &smooth) != MM3D_OK)
+      throw std::runtime_error("mm3d: MM3D_SMOOTH was refused (the order must be 1 or 2, the radius finite and not negative)");
+    return e;
+  }();
   return c;
 }
 inline void check(mm3d_ctx *c, int st)

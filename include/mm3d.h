@@ -476,6 +476,75 @@ typedef struct mm3d_cluster_stats {
 /* The cluster filter's last run on this context: mm3d_remove_small_clusters, or mm3d_map_features with a method selected (all
  * zero before the first).  MM3D_EINVAL for NULL. */
 int mm3d_last_cluster_stats(const mm3d_ctx *ctx, mm3d_cluster_stats *stats);
+/* What smooths a map's points (off the reference's path; MM3D_SMOOTH_OFF by default: nothing runs).  Moving least squares: every
+ * point is moved onto the Gaussian-weighted plane fitted to its neighbours within a radius, or onto the quadratic fitted over
+ * that plane.  Two places ask it, each behind a bit of `where`:
+ *   MM3D_SMOOTH_MAPS      every place that builds a map behind a whole-map call -- mm3d_map_features, mm3d_estimate_maps_transforms
+ *                         on one stream or many, on a device list (mm3d_create_devices) and mm3d_shard_begin -- runs
+ *                         mm3d_smooth_cloud(the cloud that left the outlier filter and the cluster filter, radius, order,
+ *                         min_neighbours) before the normals; keypoints and descriptors are the existing stages on the new cloud.
+ *                         After the filters, because a stray blob would pull the surface towards itself.
+ *   MM3D_SMOOTH_COMPOSED  mm3d_compose_maps on this context returns downsample(smooth(downsample(cat, res), radius), res): where
+ *                         two maps overlap, the ICP's residual leaves two copies of every wall a few centimetres apart, and one
+ *                         voxel pass keeps both.  The first pass bounds the density the fit sees, the last turns the fused
+ *                         layers back into one point per voxel.  Without the bit, or OFF, the call is the reference's, byte for byte.
+ * mm3d_params does not change.  No parity with pcl::MovingLeastSquares is claimed: PCL fits an unweighted plane, drops points with
+ * few neighbours and carries upsampling modes; none of that is here.
+ *   The rule, for a cloud of n 16-byte records, a radius r finite and > 0, an order 1 or 2 and min_neighbours >= 3:
+ *   1. A record is valid when its three coordinates are finite.  An invalid record is copied unchanged, is nobody's neighbour and
+ *      has state INVALID.
+ *   2. The neighbours of a valid point i are the valid j with (double)d2 <= r * r, the product formed in double, where
+ *      d2 = (dx * dx + dy * dy) + dz * dz in float, every operation rounded to nearest, nothing contracted (the d2 of the
+ *      statistical filter and the cluster filter).  Point i itself and exact duplicates count.  count_i is their number; with
+ *      count_i < min_neighbours the state is FEW and the point stays.
+ *   3. Everything from here on is in double, in coordinates relative to the query point, q_j = (double)p_j - (double)p_i per
+ *      coordinate -- exact differences, so the rule does not care how far the map is from the origin.
+ *      w_j = exp(-(double)d2_j / (r * r)); mu = sum(w q) / sum(w); C = sum(w (q - mu)(q - mu)^T) / sum(w);
+ *      lambda0 <= lambda1 <= lambda2 the eigenvalues of C, n a unit eigenvector of lambda0 (its sign does not matter).  The state
+ *      is DEGENERATE and the point stays when the trace is not > 0, when lambda1 - lambda0 <= 1e-6 * trace, or when anything is
+ *      not finite: a line, a single repeated point.  The foot of the plane is o = (mu . n) n, the query point projected on it.
+ *   4. Order 1: the displacement is o, the state PLANE.
+ *   5. Order 2 needs count_i >= 6; with fewer, step 4.  With any orthonormal u, v perpendicular to n (the fitted value at the
+ *      origin does not depend on the choice: the full quadratic basis is closed under rotation) and, per neighbour, e = q - o,
+ *      a = e.u / r, b = e.v / r, h = e.n: minimise sum w (c0 + c1 a + c2 b + c3 a^2 + c4 a b + c5 b^2 - h)^2 through the normal
+ *      equations M c = g, solved by an unpivoted LDLt.  A pivot at or below 1e-9 * trace(M) / 6 means singular (points on one
+ *      conic): step 4.  The displacement is o + c0 n, the state POLYNOMIAL; if it is not finite or longer than r, step 4.
+ *   6. The output record is (float)((double)p + displacement) per coordinate, the colour untouched; same n, same order.
+ *   - options.radius == 0 means 3 * the resolution in force (params.resolution for the maps, mm3d_compose_maps' for the composed
+ *     map): a voxel-filtered surface then has about 28 neighbours per point, enough for six coefficients, and the ball is still
+ *     thinner than a wall is from its neighbour.
+ *   - The result is a function of the cloud and the four numbers alone: the sums run in the cell-sorted order of the stage's grid
+ *     with lane-strided partials and a fixed tree, never in the order of an atomic or of the launch geometry -- bit-identical for
+ *     every stream count, batch, driver and cache setting.  The sums stream: a ball that holds every point of the cloud is legal.
+ *   - The smoothed cloud is no voxel grid's output any more, and is not treated as one by the stages behind it.
+ *   - The setting reaches the context's mm3d_set_streams helpers in either order of the two calls, and every device of a
+ *     device-list context; only a map's points change, and those travel in the bundles, so device lists and shards carry it.
+ *     Every rank of a sharded call must use the same setting.  Nothing is drawn from rand().
+ *   - The map cache's map key holds (method, order, min_neighbours, radius), zeros unless the method is MLS and MM3D_SMOOTH_MAPS
+ *     is set. */
+typedef enum { MM3D_SMOOTH_OFF = 0, MM3D_SMOOTH_MLS = 1 } mm3d_smooth_method;
+enum { MM3D_SMOOTH_MAPS = 1, MM3D_SMOOTH_COMPOSED = 2 };          /* bits of `where` */
+enum { MM3D_SMOOTH_INVALID = 0, MM3D_SMOOTH_FEW = 1, MM3D_SMOOTH_DEGENERATE = 2, MM3D_SMOOTH_PLANE = 3, MM3D_SMOOTH_POLYNOMIAL = 4 };   /* a record's state */
+typedef struct mm3d_smooth_options {
+  int method;          /* MM3D_SMOOTH_* */
+  int order;           /* 1 or 2 */
+  int min_neighbours;  /* >= 3 */
+  int where;           /* MM3D_SMOOTH_MAPS | MM3D_SMOOTH_COMPOSED, not 0 */
+  double radius;       /* finite, >= 0; 0 = 3 * the resolution in force */
+} mm3d_smooth_options;                                            /* 24 bytes */
+void mm3d_smooth_options_default(mm3d_smooth_options *o);         /* OFF, 2, 6, MAPS | COMPOSED, 0.0 */
+/* MM3D_EINVAL: ctx or options NULL, an unknown method, an order other than 1 and 2, min_neighbours < 3, `where` 0 or with an
+ * unknown bit, a radius negative or not finite (the values are checked whatever the method).  After a refused call the selection
+ * is what it was.  No context is refused. */
+int mm3d_set_smoothing(mm3d_ctx *ctx, const mm3d_smooth_options *options);
+int mm3d_get_smoothing(const mm3d_ctx *ctx, mm3d_smooth_options *options);   /* MM3D_EINVAL for NULL */
+typedef struct mm3d_smooth_stats {
+  long long points, valid, few, degenerate, plane, polynomial;   /* n, the valid records, and those of them in each state */
+  double max_displacement;                                       /* the longest displacement, 0 when nothing moved */
+} mm3d_smooth_stats;
+/* The smoothing's last run on this context: mm3d_smooth_cloud, mm3d_map_features or mm3d_compose_maps with the method selected (all
+ * zero before the first).  MM3D_EINVAL for NULL. */
+int mm3d_last_smooth_stats(const mm3d_ctx *ctx, mm3d_smooth_stats *stats);
 /* What refines a pair's initial estimate where params.refine_transform is set (off the reference's path; MM3D_REFINE_ICP by
  * default: the ICP that mm3d_set_icp_method selects, which mm3d_get_icp_method keeps answering whatever the refinement is).
  * MM3D_REFINE_NDT runs the Normal Distributions Transform in the ICP's place: a Gauss-Newton form of point-to-distribution
@@ -619,6 +688,21 @@ void mm3d_debug_outlier_search(long long out[3], int reset);
  *     voxelised -- is processed correctly, and the scan is quadratic in the points of such a cell. */
 int mm3d_cluster_labels(mm3d_ctx *ctx, const mm3d_cloud *points, double tolerance, int *labels, size_t capacity, mm3d_cluster_stats *stats);
 int mm3d_remove_small_clusters(mm3d_ctx *ctx, const mm3d_cloud *in, double tolerance, int method, int min_size, mm3d_cloud **out);
+/* Moving-least-squares smoothing (not a reference function; mm3d_set_smoothing states the rule and puts it behind the whole-map
+ * calls).  mm3d_smooth_displacements is steps 1 - 5 alone, in the cloud's order: disp receives 3 n doubles, zero where the point
+ * stays; state (may be NULL) the n states MM3D_SMOOTH_INVALID .. MM3D_SMOOTH_POLYNOMIAL; neighbours (may be NULL) the n count_i,
+ * 0 for an invalid record; stats (may be NULL) the counts.  mm3d_smooth_cloud is the whole rule on a caller's cloud, whatever the
+ * context's setting, and leaves its counts for mm3d_last_smooth_stats.  One host wait each beyond what the cloud's bounding box
+ * and its grid cost.
+ *   - MM3D_EINVAL: a NULL argument (state, neighbours and stats excepted); a radius that is not finite or not > 0; an order other
+ *     than 1 and 2; min_neighbours < 3; a cloud of 2^31 points or more.  MM3D_ECAPACITY: capacity below mm3d_cloud_size(points).
+ *     An empty cloud gives MM3D_OK, an empty result and zero stats.
+ *   - A wave per point on the library's cell-sorted grid at a cell just above the radius (for a cloud spread over kilometres the
+ *     cell grows, and with it the candidates per point, never the neighbours).  No size is refused: the sums stream, and a ball
+ *     that holds thousands of points is quadratic in them. */
+int mm3d_smooth_displacements(mm3d_ctx *ctx, const mm3d_cloud *points, double radius, int order, int min_neighbours,
+                              double *disp, int *state, int *neighbours, size_t capacity, mm3d_smooth_stats *stats);
+int mm3d_smooth_cloud(mm3d_ctx *ctx, const mm3d_cloud *in, double radius, int order, int min_neighbours, mm3d_cloud **out);
 /* The Harris response of every point (HarrisKeypoint3D::responseHarris, what detectKeypoints(HARRIS)
  * thresholds and suppresses); dst receives mm3d_cloud_size(points) floats. */
 int mm3d_harris_response(mm3d_ctx *ctx, const mm3d_cloud *points, const mm3d_normals *normals, double radius,
@@ -727,7 +811,8 @@ int mm3d_estimate_maps_transforms(mm3d_ctx *ctx, const mm3d_cloud_view *clouds, 
                                   const mm3d_params *params, float *out_T, size_t *n_out,
                                   mm3d_pair_result *pairs, size_t *n_pairs);
 /* composeMaps (map_merging.h:99, map_merging.cpp:277-305): *out = NULL for n == 0 (nullptr in
- * the reference); n != n_transforms -> MM3D_EINVAL (the reference throws). */
+ * the reference); n != n_transforms -> MM3D_EINVAL (the reference throws).  On a context with mm3d_set_smoothing's
+ * MM3D_SMOOTH_COMPOSED the result is smoothed between two voxel passes (see there); otherwise it is the reference's. */
 int mm3d_compose_maps(mm3d_ctx *ctx, const mm3d_cloud *const *clouds, size_t n, const float *transforms,
                       size_t n_transforms, double resolution, mm3d_cloud **out);
 

@@ -160,6 +160,50 @@ class ClusterStats(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class SmoothMethod(enum.IntEnum):   # mm3d_smooth_method (not a reference enum)
+    OFF = 0
+    MLS = 1
+
+
+class SmoothWhere(enum.IntFlag):    # the bits of mm3d_smooth_options.where
+    MAPS = 1
+    COMPOSED = 2
+
+
+class SmoothState(enum.IntEnum):    # MM3D_SMOOTH_INVALID .. MM3D_SMOOTH_POLYNOMIAL: a record's state under the rule
+    INVALID = 0
+    FEW = 1
+    DEGENERATE = 2
+    PLANE = 3
+    POLYNOMIAL = 4
+
+
+class SmoothOptions(C.Structure):
+    """mm3d_smooth_options (mm3d_set_smoothing); the defaults are mm3d_smooth_options_default's."""
+    _fields_ = [("method", C.c_int), ("order", C.c_int), ("min_neighbours", C.c_int), ("where", C.c_int), ("radius", C.c_double)]
+
+    def __init__(self, **kw):
+        super().__init__()
+        lib().mm3d_smooth_options_default(C.byref(self))
+        kinds = dict(self._fields_)
+        for k, v in kw.items():
+            if k not in kinds:
+                raise TypeError("unknown smoothing option " + k)
+            setattr(self, k, int(v) if kinds[k] is C.c_int else float(v))
+
+    def as_tuple(self):
+        return (int(self.method), int(self.order), int(self.min_neighbours), int(self.where), float(self.radius))
+
+
+class SmoothStats(C.Structure):
+    """mm3d_smooth_stats"""
+    _fields_ = [("points", C.c_longlong), ("valid", C.c_longlong), ("few", C.c_longlong), ("degenerate", C.c_longlong),
+                ("plane", C.c_longlong), ("polynomial", C.c_longlong), ("max_displacement", C.c_double)]
+
+    def as_dict(self):
+        return {k: (float if t is C.c_double else int)(getattr(self, k)) for k, t in self._fields_}
+
+
 class RefineMethod(enum.IntEnum):   # mm3d_refine_method (not a reference enum)
     ICP = 0
     NDT = 1
@@ -685,6 +729,26 @@ class Context:
         self._ck(lib().mm3d_last_cluster_stats(self._h, C.byref(st)))
         return st.as_dict()
 
+    def setSmoothing(self, options=None, **kw):
+        """mm3d_set_smoothing: moving-least-squares smoothing of a map's filtered points before its normals (where & MAPS) and of
+        the composed map between two voxel passes (where & COMPOSED).  A SmoothOptions, or its fields as keywords
+        (method=SmoothMethod.MLS, order=1 or 2, min_neighbours >= 3, where=SmoothWhere.MAPS | SmoothWhere.COMPOSED, radius=... in
+        metres; 0 = three times the resolution in force)."""
+        o = options if options is not None else SmoothOptions(**kw)
+        self._ck(lib().mm3d_set_smoothing(self._h, C.byref(o)))
+
+    def getSmoothing(self) -> "SmoothOptions":
+        o = SmoothOptions()
+        self._ck(lib().mm3d_get_smoothing(self._h, C.byref(o)))
+        return o
+
+    @property
+    def last_smooth_stats(self) -> dict:
+        """mm3d_last_smooth_stats: the smoothing's last run on this context."""
+        st = SmoothStats()
+        self._ck(lib().mm3d_last_smooth_stats(self._h, C.byref(st)))
+        return st.as_dict()
+
     def setRefinement(self, options=None, **kw):
         """mm3d_set_refinement: what refines a pair's initial estimate.  A RefineOptions, or its fields as keywords
         (method=RefineMethod.NDT, resolution=... in metres; 0 = the default multiple of params.resolution, neighbours=1 or 7,
@@ -879,6 +943,25 @@ class Context:
         cluster (LARGEST), in the cloud's order."""
         h = C.c_void_p()
         self._ck(lib().mm3d_remove_small_clusters(self._h, cloud._h, C.c_double(tolerance), int(method), int(min_size), C.byref(h)))
+        return Cloud(self, h)
+
+    def smoothDisplacements(self, points: "Cloud", radius: float, order: int = 2, min_neighbours: int = 6):
+        """mm3d_smooth_displacements: (disp float64[n, 3], state int32[n], neighbours int32[n], the counts as a dict) of the
+        moving-least-squares rule, in the cloud's order; a point that stays has a zero displacement."""
+        n = len(points)
+        disp = np.zeros((n, 3), dtype=np.float64)
+        state = np.zeros(n, dtype=np.int32)
+        count = np.zeros(n, dtype=np.int32)
+        st = SmoothStats()
+        self._ck(lib().mm3d_smooth_displacements(self._h, points._h, C.c_double(radius), int(order), int(min_neighbours),
+                                                 disp.ctypes.data_as(C.c_void_p), state.ctypes.data_as(C.c_void_p),
+                                                 count.ctypes.data_as(C.c_void_p), C.c_size_t(n), C.byref(st)))
+        return disp, state, count, st.as_dict()
+
+    def smoothCloud(self, cloud: "Cloud", radius: float, order: int = 2, min_neighbours: int = 6) -> "Cloud":
+        """mm3d_smooth_cloud: the cloud with every valid point moved by the moving-least-squares rule, same size and order."""
+        h = C.c_void_p()
+        self._ck(lib().mm3d_smooth_cloud(self._h, cloud._h, C.c_double(radius), int(order), int(min_neighbours), C.byref(h)))
         return Cloud(self, h)
 
     def siftCertOctave(self, points: "Cloud", min_scale: float, octave: int):

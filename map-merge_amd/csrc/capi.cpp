@@ -42,6 +42,7 @@ mm3d::StageSelection::StageSelection()
   mm3d_icp_sampling_options_default(&sampling_options);
   mm3d_outlier_options_default(&outlier_options);
   mm3d_cluster_options_default(&cluster_options);
+  mm3d_smooth_options_default(&smooth_options);
 }
 
 void mm3d::select_stages(mm3d_ctx *ctx, bool peers_follow, const std::function<void(StageSelection &)> &edit)
@@ -215,6 +216,10 @@ void mm3d_outlier_options_default(mm3d_outlier_options *o)
 void mm3d_cluster_options_default(mm3d_cluster_options *o)
 {
   if (o) *o = mm3d_cluster_options{MM3D_CLUSTERS_OFF, 100, 0.0};
+}
+void mm3d_smooth_options_default(mm3d_smooth_options *o)
+{
+  if (o) *o = mm3d_smooth_options{MM3D_SMOOTH_OFF, 2, 6, MM3D_SMOOTH_MAPS | MM3D_SMOOTH_COMPOSED, 0.0};
 }
 
 void mm3d_icp_sampling_options_default(mm3d_icp_sampling_options *o)
@@ -791,6 +796,15 @@ int mm3d_compose_maps(mm3d_ctx *ctx, const mm3d_cloud *const *clouds, size_t n, 
   return guarded(ctx, [&] {
     std::unique_ptr<mm3d_cloud> cat(transform_concat(ctx, clouds, n, transforms));
     *out = downsample(ctx, cat.get(), resolution);
+    // (mm3d_set_smoothing with MM3D_SMOOTH_COMPOSED: the layers that the pairs' residuals left side by side are fused between two
+    // voxel passes -- the first bounds the density the kernel sees, the last makes one point per voxel of what came together)
+    if (ctx->sel.smoother && (ctx->sel.smooth_options.where & MM3D_SMOOTH_COMPOSED)) {
+      std::unique_ptr<mm3d_cloud> first(*out);
+      *out = nullptr;
+      std::unique_ptr<mm3d_cloud> smooth(ctx->sel.smoother->smooth(ctx, first.get(), ctx->sel.smooth_options, resolution, &ctx->last_smooth_stats));
+      first.reset();
+      *out = downsample(ctx, smooth.get(), resolution);
+    }
   });
 }
 

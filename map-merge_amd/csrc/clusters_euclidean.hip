@@ -4,8 +4,8 @@
 // Not a reference stage.
 //
 // One pass family per cloud, one host wait (the compaction's):
-//   cloud_grid     the library's cell-sorted grid at a cell just above the tolerance (cc_cell), so that a point's neighbours
-//                  lie in its 3 x 3 x 3 cells; where the cell had to grow, in as many cells as cover the tolerance (cc_reach)
+//   cloud_grid     the library's cell-sorted grid at a cell just above the tolerance (radius_grid.hpp: radius_cell), so that a point's neighbours
+//                  lie in its 3 x 3 x 3 cells; where the cell had to grow, in as many cells as cover the tolerance (radius_reach)
 //   k_cc_init      parent[i] = i for a valid record, -1 for an invalid one: a forest over the ORIGINAL record indices
 //   k_cc_hook      a lane per cell-sorted point i walks the candidates of its box of cells; for an adjacent candidate of larger
 //                  index it finds both roots and hangs the larger under the smaller with a compare-and-swap.  A parent is
@@ -25,6 +25,7 @@
 #include "capi_guard.hpp"
 #include "drivers.hpp"
 #include "device_util.hpp"
+#include "radius_grid.hpp"
 
 namespace mm3d {
 
@@ -32,8 +33,6 @@ namespace {
 
 constexpr int kCcThreads = 256;
 constexpr int kCcSweepBlocks = 512;           // k_cc_flatten, k_cc_roots: this many blocks stride over the records (2048 waves)
-constexpr double kCcCellFactor = 1.01;      // the cell over the tolerance: neighbours in adjacent cells whatever the rounding (cc_reach)
-constexpr double kCcAxisCells = 1000.0;     // cells per axis at the most, as the statistical filter's grid: the cell grows instead
 
 // The forest is read and written by lanes of every workgroup at once: relaxed device-scope accesses, which the compiler neither
 // caches in a register nor tears.  A stale value is harmless by construction -- every value a word ever held is an ancestor of
@@ -218,38 +217,6 @@ k_cc_keep(const int *__restrict__ labels, const int *__restrict__ size, int n, i
 bool cc_tolerance_ok(double tolerance, bool zero_ok) { return std::isfinite(tolerance) && (tolerance > 0.0 || (zero_ok && tolerance == 0.0)); }
 bool cc_method_ok(int method, bool off_ok) { return method == MM3D_CLUSTERS_MIN_SIZE || method == MM3D_CLUSTERS_LARGEST || (off_ok && method == MM3D_CLUSTERS_OFF); }
 
-// The grid's cell: just above the tolerance, so that the box is 3^3 cells and as few candidates as can be.  Bounds as the
-// statistical filter's: at most kCcAxisCells cells per axis and about eight cells per point (the table's memory) -- a cloud
-// spread over kilometres gets a larger cell and more candidates per point, never another result.
-float cc_cell(const mm3d_cloud *in, double tolerance)
-{
-  double e[3];
-  for (int a = 0; a < 3; ++a) e[a] = std::max(0.0, (double)in->bmax[a] - (double)in->bmin[a]);
-  const double emax = std::max(e[0], std::max(e[1], e[2]));
-  double cell = std::min(tolerance * kCcCellFactor, 1e30);
-  cell = std::max(cell, emax / kCcAxisCells);
-  if (!(cell >= 1e-30) || !std::isfinite(cell)) cell = 1e-30;
-  const double cap = std::max(8.0 * (double)in->n_finite, 32768.0);
-  for (;;) {
-    const double cells = (std::floor(e[0] / cell) + 2) * (std::floor(e[1] / cell) + 2) * (std::floor(e[2] / cell) + 2);
-    if (!(cells > cap)) break;
-    cell *= 1.26;
-  }
-  return (float)cell;
-}
-
-// How many cells to either side of a point's own hold everything within the tolerance of it, for the grid that cloud_grid
-// returned (whose cell is the asked one or larger; a grid found under a colliding key may differ in the last digits).  Two
-// adjacent points are at most tolerance * (1 + 3e-7) apart -- d2 carries three roundings -- and each point's cell coordinate
-// (v - min) * inv carries at most 4e-7 of its value, which is below the cells per axis.  So their coordinates differ by less than
-// the integer returned, and their cells by at most that.  Clamping a cell into the grid only brings cells together.
-int cc_reach(const Grid &g, double tolerance)
-{
-  const double axis = (double)std::max(g.dims[0], std::max(g.dims[1], g.dims[2]));
-  const double span = tolerance / (double)g.cell * (1.0 + 1e-6) + 2.0 * 4e-7 * axis + 1e-6;
-  return (int)std::min(std::floor(span) + 1.0, axis);
-}
-
 struct CcWork {
   DevBuf<int> labels, size;               // [n] each: the flattened forest; a root's slot holds its cluster's size
   DevBuf<unsigned long long> ctl;         // k_cc_roots' three words
@@ -269,8 +236,8 @@ void cc_components(Context *c, const mm3d_cloud *in_, double tolerance, int min_
   MM3D_LAUNCH(c, "cc_init", n * 20.0, k_cc_init, blocks, threads, 0, in->pts.get(), n, w.labels.get());
   cloud_bbox(c, in);
   if (in->n_finite > 1) {
-    const Grid &g = cloud_grid(c, in, cc_cell(in, tolerance));
-    const int s = cc_reach(g, tolerance);
+    const Grid &g = cloud_grid(c, in, radius_cell(in, tolerance));
+    const int s = radius_reach(g, tolerance);
     MM3D_LAUNCH(c, "cc_hook", g.n * (16.0 + 8.0), k_cc_hook, dim3(div_up((size_t)g.n, kCcThreads)), threads, 0, g.view(), s, tolerance * tolerance,
                 w.labels.get());
   }

@@ -50,6 +50,11 @@ std::string feature_key(const mm3d_params *p, const StageSelection &sel)
   const mm3d_cluster_options &cf = sel.cluster_options;
   const bool on = cf.method != MM3D_CLUSTERS_OFF;
   k.i32(on ? cf.method : 0).i32(cf.method == MM3D_CLUSTERS_MIN_SIZE ? cf.min_size : 0).f64(on ? cf.tolerance : 0.0);
+  // what smooths the filtered cloud before the normals (mm3d_set_smoothing): zeros unless the method is MLS and the maps ask it
+  // (the composed map is no bundle's business)
+  const mm3d_smooth_options &sm = sel.smooth_options;
+  const bool mls = sm.method == MM3D_SMOOTH_MLS && (sm.where & MM3D_SMOOTH_MAPS);
+  k.i32(mls ? sm.method : 0).i32(mls ? sm.order : 0).i32(mls ? sm.min_neighbours : 0).f64(mls ? sm.radius : 0.0);
   return k.s;
 }
 

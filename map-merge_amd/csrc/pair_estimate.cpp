@@ -50,6 +50,10 @@ std::unique_ptr<mm3d_map> mm3d::map_features_impl(mm3d_ctx *ctx, const mm3d_clou
   down.reset();
   // (mm3d_set_cluster_filter: the connected components too small to be structure leave before anything looks at the cloud)
   if (ctx->sel.clusters) filt.reset(ctx->sel.clusters->filter(ctx, filt.get(), ctx->sel.cluster_options, p->resolution, &ctx->last_cluster_stats));
+  // (mm3d_set_smoothing with MM3D_SMOOTH_MAPS: after the filters -- a stray blob would pull the surface towards itself -- and
+  // before everything that reads the points; the new cloud's voxel_leaf is 0)
+  if (ctx->sel.smoother && (ctx->sel.smooth_options.where & MM3D_SMOOTH_MAPS))
+    filt.reset(ctx->sel.smoother->smooth(ctx, filt.get(), ctx->sel.smooth_options, p->resolution, &ctx->last_smooth_stats));
   // computeSurfaceNormals, then detectKeypoints(points, normals, type, keypoint_threshold, normal_radius, resolution)
   // (map_merging.cpp:225-233).  SIFT does not read the normals, and its first octave builds every point's sorted
   // neighbour list over a ball that contains the normals': the two stages share that launch (sift.hip), same bits.

@@ -23,10 +23,11 @@ struct EstimatorMethodBase;
 struct IcpSamplerBase;
 struct OutlierFilterBase;
 struct ClusterFilterBase;
+struct SmootherBase;
 
 // The opt-in stages of a context's pipeline (mm3d_set_icp_method, mm3d_set_alignment, mm3d_set_keypoints, mm3d_set_refinement,
 // mm3d_set_coarse_alignment, mm3d_set_confidence, mm3d_set_icp_rejection, mm3d_set_icp_color, mm3d_set_icp_generalized,
-// mm3d_set_estimator, mm3d_set_icp_sampling, mm3d_set_outlier_filter, mm3d_set_cluster_filter): a null method = the reference's stage.  The methods are process-wide
+// mm3d_set_estimator, mm3d_set_icp_sampling, mm3d_set_outlier_filter, mm3d_set_cluster_filter, mm3d_set_smoothing): a null method = the reference's stage.  The methods are process-wide
 // objects of their kernel files that hold no state and are not owned.  Every context has its own copy of the record; only
 // select_stages (drivers.hpp) changes one, and it and mm3d_set_streams hand the root's copy to the helpers.
 struct StageSelection {
@@ -42,6 +43,7 @@ struct StageSelection {
   const IcpSamplerBase *sampler = nullptr;             // what the ICP searches with: a sample of the source map in the place of all of it
   const OutlierFilterBase *outliers = nullptr;         // what filters a down-sampled map in removeOutliers' place
   const ClusterFilterBase *clusters = nullptr;         // what drops the small connected components of the filtered map
+  const SmootherBase *smoother = nullptr;              // what smooths a filtered map before its normals, and the composed map
   mm3d_alignment_options align_options;
   mm3d_keypoint_options keypoint_options;
   mm3d_refine_options refine_options;
@@ -54,7 +56,8 @@ struct StageSelection {
   mm3d_icp_sampling_options sampling_options;          // `sampler` is non-null exactly while their method is not NONE
   mm3d_outlier_options outlier_options;                // `outliers` is non-null exactly while their method is STATISTICAL
   mm3d_cluster_options cluster_options;                // `clusters` is non-null exactly while their method is not OFF
-  StageSelection();                                    // capi.cpp: the options are the twelve mm3d_*_options_default's
+  mm3d_smooth_options smooth_options;                  // `smoother` is non-null exactly while their method is MLS; `where` says which places ask it
+  StageSelection();                                    // capi.cpp: the options are the thirteen mm3d_*_options_default's
   // the ICP of the pair stage rejects correspondences (mm3d_set_icp_rejection)
   bool rejecting() const { return reject_options.one_to_one || reject_options.distance != MM3D_REJECT_NONE; }
   int icp_method() const;                              // MM3D_ICP_*
@@ -106,6 +109,7 @@ struct mm3d_ctx : mm3d::Context {
   mm3d_icp_sampling_stats last_sampling_stats{0, 0, 0, 0, 0};            // (mm3d_last_icp_sampling_stats)
   mm3d_outlier_stats last_outlier_stats{0, 0, 0, 0, 0.0, 0.0, 0.0};      // (mm3d_last_outlier_stats)
   mm3d_cluster_stats last_cluster_stats{0, 0, 0, 0, 0, 0};               // (mm3d_last_cluster_stats)
+  mm3d_smooth_stats last_smooth_stats{0, 0, 0, 0, 0, 0, 0.0};            // (mm3d_last_smooth_stats)
   // mm3d_set_streams: helper contexts (one HIP stream + one host thread each while a call is running)
   // that mm3d_estimate_maps_transforms deals maps and pairs to; owned by this context
   std::vector<mm3d_ctx *> helpers;
@@ -534,6 +538,15 @@ struct ClusterFilterBase {
   // the kept records of `in` in its order, a new cloud complete on c's stream (one wait: its size); o.tolerance == 0 stands for
   // 2 * resolution; stats (may be null) receives the counts
   virtual mm3d_cloud *filter(Context *c, const mm3d_cloud *in, const mm3d_cluster_options &o, double resolution, mm3d_cluster_stats *stats) const = 0;
+};
+// What smooths a map's filtered cloud before its normals, and the composed map between its two voxel passes (mm3d_set_smoothing; the
+// one concrete class is smooth_mls.hip's).  Like ClusterFilterBase, pair_estimate.cpp and capi.cpp only see this interface, so the
+// host code links without the new kernels (tests/host_san); a null pointer on the context means that no such step runs.
+struct SmootherBase {
+  virtual ~SmootherBase() = default;
+  // the records of `in` in its order, every valid one moved by the rule, a new cloud complete on c's stream (one wait: the
+  // counts) whose voxel_leaf is 0; o.radius == 0 stands for 3 * resolution; stats (may be null) receives the counts
+  virtual mm3d_cloud *smooth(Context *c, const mm3d_cloud *in, const mm3d_smooth_options &o, double resolution, mm3d_smooth_stats *stats) const = 0;
 };
 struct PairCounts { int n_correspondences = 0, n_inliers = 0, icp_correspondences = 0; };
 // ICP (optional) from a guess on the device (guess_dev != null) or on the host, then transformScore
