@@ -6,7 +6,7 @@
 // audit row 16c).  Everything that decides is an integer count: nothing depends on launch geometry or arrival order.
 //
 // The signature of a map, built once per map and option set (corr_build_signature), one host wait -- the one that sizes it:
-//   k_corr_range    the 2-D cell index range of the counted points (ordered-uint atomics, one set per block)
+//   corr_range      the 2-D cell index range of the counted points (lattice.hpp::k_lattice_range, as every stage of the global lattice)
 //   k_corr_keys     a lane per point: ((cell relative to the range's minimum, i most significant) << 1) | class, class 0 =
 //                   structure, 1 = ground; points of neither class get the key that sorts last
 //   radix sort      (key, input index) pairs, stable: a (cell, class) becomes a run in ascending input index
@@ -36,13 +36,13 @@
 #include "drivers.hpp"
 #include "map_kept.hpp"
 #include "icp_solve6.hpp"
+#include "lattice.hpp"
 #include "scan_fused.hpp"
 
 namespace mm3d {
 
 namespace {
 
-constexpr uint32_t kCorrInvalid = 0xFFFFFFFFu;
 // the dense maps hold one word per cell of the 2-D cell box: at most 2^24 cells; the accumulator at most 2^26 words
 // (include/mm3d.h and INTEGRATION.md "Size limits" state both)
 constexpr double kCorrMaxCells = 16777216.0;
@@ -53,63 +53,26 @@ constexpr int kCorrMaxF = 16;
 constexpr int kCorrFitMin = 16;                       // ground pairs a plane fit needs
 constexpr double kCorrMaxSlope = 0.36397023426620234;  // tan 20 deg
 
-__device__ __forceinline__ float corr_index(float x, float inv) { return floorf(__fmul_rn(x, inv)); }
 // the centre of cell i of side c: one add, one multiply
 __device__ __forceinline__ float corr_centre(int i, float c) { return __fmul_rn(__fadd_rn((float)i, 0.5f), c); }
 __host__ __device__ inline int floor_div(int a, int b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
 
-struct CorrFrame { double mn[2], d[2]; bool overflow; };
-__host__ __device__ inline CorrFrame corr_frame(const unsigned *range /* min i j, max i j (ordered) */)
+// the 2-D cell box of the range words is within the limits: its cells, and minima that the int arithmetic on them can take
+// (false for the inf or NaN of an infinite index or an untouched range)
+__host__ __device__ inline bool corr_fits(const LatticeFrame<2> &f)
 {
-  CorrFrame f;
-  for (int a = 0; a < 2; ++a) {
-    f.mn[a] = (double)ord2f(range[a]);
-    f.d[a] = ((double)ord2f(range[2 + a]) - f.mn[a]) + 1.0;
-  }
-  f.overflow = !(f.d[0] * f.d[1] <= kCorrMaxCells) || !(fabs(f.mn[0]) < 1e9) || !(fabs(f.mn[1]) < 1e9);   // (inf or NaN indices too)
-  return f;
+  return f.cells <= kCorrMaxCells && fabs(f.mn[0]) < 1e9 && fabs(f.mn[1]) < 1e9;
 }
 
-__device__ __forceinline__ bool corr_counted(const float4 &p, const float4 &nr)
-{
-  return isfinite(p.x) && isfinite(p.y) && isfinite(p.z) && isfinite(nr.x) && isfinite(nr.y) && isfinite(nr.z);
-}
-
-__global__ void __launch_bounds__(256)
-k_corr_range(const float4 *__restrict__ pts, const float4 *__restrict__ nrm, int n, float inv, unsigned *__restrict__ range)
-{
-  float lo[2] = {INFINITY, INFINITY}, hi[2] = {-INFINITY, -INFINITY};
-  int cnt = 0;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-    const float4 p = pts[i];
-    if (!corr_counted(p, nrm[i])) continue;
-    const float f[2] = {corr_index(p.x, inv), corr_index(p.y, inv)};
-#pragma unroll
-    for (int a = 0; a < 2; ++a) { lo[a] = fminf(lo[a], f[a]); hi[a] = fmaxf(hi[a], f[a]); }
-    ++cnt;
+// the counted points: finite, with a finite normal
+struct CorrCounted {
+  const float4 *nrm;
+  __device__ __forceinline__ static bool ok(const float4 &p, const float4 &nr)
+  {
+    return isfinite(p.x) && isfinite(p.y) && isfinite(p.z) && isfinite(nr.x) && isfinite(nr.y) && isfinite(nr.z);
   }
-#pragma unroll
-  for (int a = 0; a < 2; ++a) { lo[a] = wave_min_f(lo[a]); hi[a] = wave_max_f(hi[a]); }
-  cnt = wave_sum(cnt);
-  __shared__ float s_lo[4][2], s_hi[4][2];
-  __shared__ int s_cnt[4];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) {
-#pragma unroll
-    for (int a = 0; a < 2; ++a) { s_lo[wave][a] = lo[a]; s_hi[wave][a] = hi[a]; }
-    s_cnt[wave] = cnt;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0 && s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3] > 0) {
-#pragma unroll
-    for (int a = 0; a < 2; ++a) {
-      float l = s_lo[0][a], h = s_hi[0][a];
-      for (int w = 1; w < 4; ++w) { l = fminf(l, s_lo[w][a]); h = fmaxf(h, s_hi[w][a]); }
-      atomicMin(&range[a], f2ord(l));
-      atomicMax(&range[2 + a], f2ord(h));
-    }
-  }
-}
+  __device__ __forceinline__ bool operator()(int i, const float4 &p) const { return ok(p, nrm[i]); }
+};
 
 __global__ void __launch_bounds__(256)
 k_corr_keys(const float4 *__restrict__ pts, const float4 *__restrict__ nrm, int n, float inv, float wall_nz, float ground_nz,
@@ -119,13 +82,13 @@ k_corr_keys(const float4 *__restrict__ pts, const float4 *__restrict__ nrm, int 
   if (i >= n) return;
   const float4 p = pts[i], nr = nrm[i];
   vals[i] = (uint32_t)i;
-  uint32_t key = kCorrInvalid;
-  if (corr_counted(p, nr)) {
+  uint32_t key = kLatticeInvalid;
+  if (CorrCounted::ok(p, nr)) {
     const float az = fabsf(nr.z);
     const int cls = az <= wall_nz ? 0 : az >= ground_nz ? 1 : -1;
-    const CorrFrame f = corr_frame(range);
-    if (cls >= 0 && !f.overflow) {                        // (a box beyond the limit: the host refuses it, the runs are not read)
-      const uint32_t ri = (uint32_t)((double)corr_index(p.x, inv) - f.mn[0]), rj = (uint32_t)((double)corr_index(p.y, inv) - f.mn[1]);
+    const LatticeFrame<2> f = lattice_frame<2>(range);
+    if (cls >= 0 && corr_fits(f)) {                       // (a box beyond the limit: the host refuses it, the runs are not read)
+      const uint32_t ri = (uint32_t)((double)lattice_index(p.x, inv) - f.mn[0]), rj = (uint32_t)((double)lattice_index(p.y, inv) - f.mn[1]);
       key = ((ri * (uint32_t)f.d[1] + rj) << 1) | (uint32_t)cls;      // < 2^25
     }
   }
@@ -139,7 +102,7 @@ struct CorrHeadLoad {
   __device__ __forceinline__ int operator()(size_t j) const
   {
     const uint32_t k = keys[j];
-    if (k == kCorrInvalid || (k & 1u) != cls || (j > 0 && keys[j - 1] == k)) return 0;
+    if (k == kLatticeInvalid || (k & 1u) != cls || (j > 0 && keys[j - 1] == k)) return 0;
     const size_t last = j + (size_t)(min_points - 1);
     return last < n && keys[last] == k ? 1 : 0;
   }
@@ -322,10 +285,10 @@ k_corr_fine(CorrPair P, const uint32_t *__restrict__ cand, const int4 *__restric
       ry = __fadd_rn(__fmul_rn(y.y, px), __fmul_rn(y.x, py));
     }
     for (int a = -P.F; a <= P.F; ++a) {
-      const float ci = corr_index(__fadd_rn(rx, __fmul_rn((float)(u * P.F + a), P.c)), P.inv) - (float)T.mn[0];
+      const float ci = lattice_index(__fadd_rn(rx, __fmul_rn((float)(u * P.F + a), P.c)), P.inv) - (float)T.mn[0];
       const bool in_i = si < ns && ci >= 0.0f && ci < (float)T.dims[0];
       for (int b = -P.F; b <= P.F; ++b) {
-        const float cj = corr_index(__fadd_rn(ry, __fmul_rn((float)(v * P.F + b), P.c)), P.inv) - (float)T.mn[1];
+        const float cj = lattice_index(__fadd_rn(ry, __fmul_rn((float)(v * P.F + b), P.c)), P.inv) - (float)T.mn[1];
         const bool hit = in_i && cj >= 0.0f && cj < (float)T.dims[1] && T.dil[(size_t)(int)ci * T.dims[1] + (int)cj] != 0;
         const int c = __popcll(ballot(hit));
         if (lane == 0 && c) atomicAdd(&cnt[(a + P.F) * W + (b + P.F)], c);
@@ -409,7 +372,7 @@ k_corr_finish(CorrPair P, const uint32_t *__restrict__ cand_keys, const uint32_t
     const float px = corr_centre(gc.x, P.c), py = corr_centre(gc.y, P.c);
     const float xf = __fadd_rn(__fsub_rn(__fmul_rn(y.x, px), __fmul_rn(y.y, py)), sx);
     const float yf = __fadd_rn(__fadd_rn(__fmul_rn(y.y, px), __fmul_rn(y.x, py)), sy);
-    const float ci = corr_index(xf, P.inv) - (float)T.mn[0], cj = corr_index(yf, P.inv) - (float)T.mn[1];
+    const float ci = lattice_index(xf, P.inv) - (float)T.mn[0], cj = lattice_index(yf, P.inv) - (float)T.mn[1];
     if (!(ci >= 0.0f && ci < (float)T.dims[0] && cj >= 0.0f && cj < (float)T.dims[1])) continue;
     const float ht = T.gh[(size_t)(int)ci * T.dims[1] + (int)cj];
     if (!(ht == ht)) continue;                            // NaN: no ground cell there
@@ -465,13 +428,6 @@ k_corr_finish(CorrPair P, const uint32_t *__restrict__ cand_keys, const uint32_t
 }
 
 // ---------------------------------------------------------------- host
-bool corr_cell_ok(double cell)
-{
-  if (!(cell > 0.0) || !std::isfinite(cell)) return false;
-  const float cf = (float)cell;
-  return cf > 0.0f && std::isfinite(cf) && std::isfinite(1.0f / cf);
-}
-
 // everything but the cell's "0 = default", which only mm3d_set_coarse_alignment admits
 bool corr_options_ok(const mm3d_coarse_options *o)
 {
@@ -493,7 +449,7 @@ bool corr_same_options(const mm3d_coarse_options &a, const mm3d_coarse_options &
 // else reads it).  o.cell > 0.
 std::unique_ptr<CoarseSignature> corr_build_signature(Context *c, const mm3d_cloud *pts, const mm3d_normals *nrm, const mm3d_coarse_options &o)
 {
-  MM3D_REQUIRE(corr_cell_ok(o.cell), "correlative alignment: the cell must be positive and finite, as a float and its reciprocal too");
+  MM3D_REQUIRE(lattice_side_ok(o.cell), "correlative alignment: the cell must be positive and finite, as a float and its reciprocal too");
   MM3D_REQUIRE(nrm->n == pts->n, "correlative alignment: one normal per point");
   MM3D_REQUIRE(pts->n < ((size_t)1 << 31), "correlative alignment: more than 2^31 - 1 points");
   std::unique_ptr<CoarseSignature> sg(new CoarseSignature());
@@ -504,12 +460,7 @@ std::unique_ptr<CoarseSignature> corr_build_signature(Context *c, const mm3d_clo
   if (n == 0) return sg;
   const unsigned blocks = div_up((size_t)n, 256);
   DevBuf<unsigned> range(c, 8);                           // min i j, max i j | structure cells, ground cells
-  unsigned *h = (unsigned *)c->pin(64);
-  const unsigned init[8] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u, 0u, 0u, 0u};
-  std::memcpy(h, init, sizeof(init));
-  MM3D_HIP(hipMemcpyAsync(range.get(), h, sizeof(init), hipMemcpyHostToDevice, c->stream));
-  MM3D_LAUNCH(c, "corr_range", n * 32.0, k_corr_range, dim3(std::min<unsigned>(div_up((size_t)n, 256 * 8), 512)), dim3(256), 0, pts->pts.get(),
-              nrm->nrm.get(), n, sg->inv, range.get());
+  lattice_range<2>(c, "corr_range", n * 32.0, pts->pts.get(), n, sg->inv, CorrCounted{nrm->nrm.get()}, range.get());
   DevBuf<uint32_t> keys(c, n), vals(c, n), keys2(c, n), vals2(c, n);
   MM3D_LAUNCH(c, "corr_keys", n * 40.0, k_corr_keys, dim3(blocks), dim3(256), 0, pts->pts.get(), nrm->nrm.get(), n, sg->inv, (float)o.wall_nz,
               (float)o.ground_nz, (const unsigned *)range.get(), keys.get(), vals.get());
@@ -524,8 +475,8 @@ std::unique_ptr<CoarseSignature> corr_build_signature(Context *c, const mm3d_clo
   c->sync();                                              // the one wait: what sizes the signature
   const int ns = (int)hr[4], ng = (int)hr[5];
   if (ns == 0 && ng == 0) return sg;                      // no cell of either class (no counted point among them)
-  const CorrFrame f = corr_frame(hr);
-  if (f.overflow)
+  const LatticeFrame<2> f = lattice_frame<2>(hr);
+  if (!corr_fits(f))
     throw Error(MM3D_EUNSUPPORTED, "correlative alignment: the map's 2-D cell box holds more than 2^24 cells at this cell size");
   CorrDense D;
   for (int a = 0; a < 2; ++a) {
@@ -724,7 +675,7 @@ const CoarseCorrelative g_correlative;
 int corr_call_check(mm3d_ctx *ctx, const mm3d_cloud *s, const mm3d_normals *sn, const mm3d_cloud *t, const mm3d_normals *tn,
                     const mm3d_coarse_options *o)
 {
-  if (!ctx || !s || !sn || !corr_options_ok(o) || !corr_cell_ok(o->cell)) return MM3D_EINVAL;
+  if (!ctx || !s || !sn || !corr_options_ok(o) || !lattice_side_ok(o->cell)) return MM3D_EINVAL;
   if ((t || tn) && (!t || !tn)) return MM3D_EINVAL;
   if (sn->n != s->n || (t && tn->n != t->n)) {
     ctx->err = "correlative alignment: the normals must be one per point";
@@ -744,7 +695,7 @@ extern "C" {
 int mm3d_set_coarse_alignment(mm3d_ctx *ctx, const mm3d_coarse_options *options)
 {
   if (!ctx || !corr_options_ok(options)) return MM3D_EINVAL;
-  if (options->cell != 0.0 && !corr_cell_ok(options->cell)) return MM3D_EINVAL;     // (also catches NaN)
+  if (options->cell != 0.0 && !lattice_side_ok(options->cell)) return MM3D_EINVAL;     // (also catches NaN)
   std::lock_guard<std::mutex> lock(ctx->mu);        // (no call is running while the method changes)
   const bool corr = options->method == MM3D_COARSE_CORRELATIVE;
   if (corr && refused_on_device_list(ctx, "mm3d_set_coarse_alignment: the correlative alignment is not available on a device-list context"))

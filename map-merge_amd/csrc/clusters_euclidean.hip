@@ -15,7 +15,7 @@
 //   k_cc_roots     the number of clusters, of clusters of at least min_size, and the arg-max over (size, smaller label) as an
 //                  atomic max on a packed 64-bit key, folded per block first -- all integer, so order-free
 //   k_cc_keep      a lane per record: its cluster's size against min_size, or its label against the arg-max's
-//   compact        grid.hip::compact_points, behind whose wait the counts come back too
+//   compact        grid.hip::cloud_of_kept, behind whose wait the counts come back too
 // No wave waits for another: the walk towards a root only descends, a failed swap means that another lane hooked that root, and
 // every other loop is counted.  One launch of k_cc_hook serves any topology -- a chain through hundreds of cells like a blob in
 // one -- so there are no rounds for the host to bound.
@@ -274,19 +274,9 @@ mm3d_cloud *remove_small_clusters(Context *c, const mm3d_cloud *in, double toler
   unsigned long long *h = (unsigned long long *)c->pin(64);
   std::memset(h, 0, 64);
   MM3D_HIP(hipMemcpyAsync(h, w.ctl.get(), 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-  DevBuf<float4> out;
-  unsigned box[7];
-  const size_t m = compact_points(c, in->pts.get(), keep.get(), n, out, box);   // the one wait: count, box and the counts above
-  if (n >= ((size_t)1 << 20) && m * 2 < n) {            // as in the radius filter: a large, mostly empty bound-sized buffer is not kept
-    DevBuf<float4> fit(c, m);
-    if (m) MM3D_HIP(hipMemcpyAsync(fit.get(), out.get(), m * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
-    c->settle();
-    out = std::move(fit);
-  }
+  size_t m = 0;
+  mm3d_cloud *res = cloud_of_kept(c, in, keep.get(), true, &m);      // the one wait: count, box and the counts above (a subset of a voxel grid's centroids)
   if (stats) cc_stats(in, h, method, (long long)m, stats);
-  mm3d_cloud *res = cloud_from_device(c, std::move(out), m);
-  cloud_set_bbox(res, box);
-  res->voxel_leaf = in->voxel_leaf;                     // a subset of a voxel grid's centroids
   return res;
 }
 

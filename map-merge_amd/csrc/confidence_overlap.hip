@@ -21,8 +21,8 @@
 
 #include "capi_guard.hpp"
 #include "drivers.hpp"
+#include "lattice.hpp"
 #include "map_kept.hpp"
-#include "device_util.hpp"
 
 namespace mm3d {
 
@@ -42,9 +42,6 @@ constexpr unsigned long long kI0 = 0x1111111111111111ull, kI3 = 0x88888888888888
 constexpr unsigned long long kJ0 = 0x000F000F000F000Full, kJ3 = 0xF000F000F000F000ull;
 constexpr unsigned long long kK0 = 0x000000000000FFFFull, kK3 = 0xFFFF000000000000ull;
 
-// the voxel index of one coordinate as a float: floor of ONE float multiply (ndt.hip and keypoints_uniform.hip likewise)
-__device__ __forceinline__ float ovl_index(float x, float inv) { return floorf(__fmul_rn(x, inv)); }
-
 __global__ void __launch_bounds__(256)
 k_ovl_mark(const float4 *__restrict__ pts, int n, float inv, OvlBox box, unsigned long long *__restrict__ occ, int *__restrict__ cnt)
 {
@@ -52,7 +49,7 @@ k_ovl_mark(const float4 *__restrict__ pts, int n, float inv, OvlBox box, unsigne
   if (i >= n) return;
   const float4 p = pts[i];
   if (!(isfinite(p.x) && isfinite(p.y) && isfinite(p.z))) return;
-  const float f[3] = {ovl_index(p.x, inv), ovl_index(p.y, inv), ovl_index(p.z, inv)};
+  const float f[3] = {lattice_index(p.x, inv), lattice_index(p.y, inv), lattice_index(p.z, inv)};
   int v[3], b[3], c[3];
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
@@ -180,14 +177,6 @@ __global__ void __launch_bounds__(256) k_ovl_score(const OvlJob *__restrict__ jo
   }
 }
 
-// voxel as the rule reads it: a positive finite float with a finite reciprocal
-bool ovl_voxel_ok(double v)
-{
-  if (!(v > 0.0) || !std::isfinite(v)) return false;
-  const float f = (float)v;
-  return f > 0.0f && std::isfinite(f) && std::isfinite(1.0f / f);
-}
-
 // everything but the voxel's "0 = default", which only mm3d_set_confidence admits
 bool ovl_options_ok(const mm3d_confidence_options *o)
 {
@@ -211,7 +200,7 @@ OvlBox ovl_box(const OverlapTable &t)
 // corners bound every point's.
 std::unique_ptr<OverlapTable> ovl_build_table(Context *c, const mm3d_cloud *cl, double voxel, int min_points, int view_margin)
 {
-  MM3D_REQUIRE(ovl_voxel_ok(voxel), "overlap confidence: the voxel must be positive and finite, as a float and its reciprocal too");
+  MM3D_REQUIRE(lattice_side_ok(voxel), "overlap confidence: the voxel must be positive and finite, as a float and its reciprocal too");
   MM3D_REQUIRE(cl->n < ((size_t)1 << 31), "overlap confidence: more than 2^31 - 1 points");
   std::unique_ptr<OverlapTable> t(new OverlapTable());
   t->voxel = voxel; t->min_points = min_points; t->view_margin = view_margin;
@@ -221,7 +210,7 @@ std::unique_ptr<OverlapTable> ovl_build_table(Context *c, const mm3d_cloud *cl, 
   if (cl->n_finite == 0) return t;                       // every lookup reads 0
   double words = 1.0;
   for (int a = 0; a < 3; ++a) {
-    const float lo = floorf(cl->bmin[a] * t->inv), hi = floorf(cl->bmax[a] * t->inv);
+    const float lo = lattice_index(cl->bmin[a], t->inv), hi = lattice_index(cl->bmax[a], t->inv);
     if (!(std::fabs(lo) < kOvlIndexLimit) || !(std::fabs(hi) < kOvlIndexLimit))
       throw Error(MM3D_EUNSUPPORTED, "overlap confidence: a voxel index of magnitude 2^30 or more at this voxel size");
     const int v_lo = (int)lo, v_hi = (int)hi;
@@ -373,7 +362,7 @@ extern "C" {
 int mm3d_set_confidence(mm3d_ctx *ctx, const mm3d_confidence_options *options)
 {
   if (!ctx || !ovl_options_ok(options)) return MM3D_EINVAL;
-  if (options->voxel != 0.0 && !ovl_voxel_ok(options->voxel)) return MM3D_EINVAL;     // (also catches NaN)
+  if (options->voxel != 0.0 && !lattice_side_ok(options->voxel)) return MM3D_EINVAL;     // (also catches NaN)
   std::lock_guard<std::mutex> lock(ctx->mu);        // (no call is running while the method changes)
   const bool ovl = options->method == MM3D_CONFIDENCE_OVERLAP;
   if (ovl && refused_on_device_list(ctx, "mm3d_set_confidence: the overlap confidence is not available on a device-list context"))
@@ -399,7 +388,7 @@ int mm3d_last_confidence_stats(const mm3d_ctx *ctx, mm3d_overlap_stats *stats)
 int mm3d_transform_overlap(mm3d_ctx *ctx, const mm3d_cloud *source, const mm3d_cloud *target, const float T[16],
                            const mm3d_confidence_options *options, mm3d_overlap_stats *stats)
 {
-  if (!ctx || !source || !target || !T || !stats || !ovl_options_ok(options) || !ovl_voxel_ok(options->voxel)) return MM3D_EINVAL;
+  if (!ctx || !source || !target || !T || !stats || !ovl_options_ok(options) || !lattice_side_ok(options->voxel)) return MM3D_EINVAL;
   std::memset(stats, 0, sizeof(*stats));
   return guarded(ctx, [&] {
     // (both tables are decided -- and may be refused -- before either is read)
@@ -415,7 +404,7 @@ int mm3d_transform_overlap(mm3d_ctx *ctx, const mm3d_cloud *source, const mm3d_c
 int mm3d_debug_overlap_table(mm3d_ctx *ctx, const mm3d_cloud *cloud, const mm3d_confidence_options *options, int box[12],
                              unsigned long long *words, size_t word_cap, unsigned char *view, size_t view_cap)
 {
-  if (!ctx || !cloud || !box || !ovl_options_ok(options) || !ovl_voxel_ok(options->voxel)) return MM3D_EINVAL;
+  if (!ctx || !cloud || !box || !ovl_options_ok(options) || !lattice_side_ok(options->voxel)) return MM3D_EINVAL;
   if ((word_cap && !words) || (view_cap && !view)) return MM3D_EINVAL;
   std::memset(box, 0, 12 * sizeof(int));
   return guarded(ctx, [&] {

@@ -10,7 +10,7 @@
 #include <algorithm>
 #include <climits>
 
-#include "device_util.hpp"
+#include "lattice.hpp"
 #include "scan_fused.hpp"
 
 namespace mm3d {
@@ -25,9 +25,9 @@ __global__ void k_voxel_keys(const float4 *__restrict__ pts, int n, float inv, i
   float4 p = pts[i];
   vals[i] = (uint32_t)i;
   if (!(isfinite(p.x) && isfinite(p.y) && isfinite(p.z))) { keys[i] = 0xFFFFFFFFu; return; }
-  int ijk0 = (int)(floorf(__fmul_rn(p.x, inv)) - (float)minbx);
-  int ijk1 = (int)(floorf(__fmul_rn(p.y, inv)) - (float)minby);
-  int ijk2 = (int)(floorf(__fmul_rn(p.z, inv)) - (float)minbz);
+  int ijk0 = (int)(lattice_index(p.x, inv) - (float)minbx);
+  int ijk1 = (int)(lattice_index(p.y, inv) - (float)minby);
+  int ijk2 = (int)(lattice_index(p.z, inv) - (float)minbz);
   keys[i] = (uint32_t)(ijk0 + ijk1 * mul1 + ijk2 * mul2);
 }
 
@@ -109,9 +109,9 @@ __global__ void k_voxel_identity(const float4 *__restrict__ pts, int n, float in
   auto key_of = [&](const float4 &p, bool &ok) {
     ok = isfinite(p.x) && isfinite(p.y) && isfinite(p.z) && __float_as_uint(p.x) != 0x80000000u && __float_as_uint(p.y) != 0x80000000u &&
          __float_as_uint(p.z) != 0x80000000u;
-    const int ijk0 = (int)(floorf(__fmul_rn(p.x, inv)) - (float)minbx);
-    const int ijk1 = (int)(floorf(__fmul_rn(p.y, inv)) - (float)minby);
-    const int ijk2 = (int)(floorf(__fmul_rn(p.z, inv)) - (float)minbz);
+    const int ijk0 = (int)(lattice_index(p.x, inv) - (float)minbx);
+    const int ijk1 = (int)(lattice_index(p.y, inv) - (float)minby);
+    const int ijk2 = (int)(lattice_index(p.z, inv) - (float)minbz);
     return (uint32_t)(ijk0 + ijk1 * mul1 + ijk2 * mul2);
   };
   bool ok, ok_prev = true;
@@ -215,16 +215,7 @@ mm3d_cloud *downsample(Context *c, const mm3d_cloud *in_, double resolution)
     sort_pairs_u32(c, keys.get(), keys2.get(), vals.get(), vals2.get(), n, 32);
   }
   const size_t nvox = h[16];
-  // The output was allocated at its bound (one wait for the whole filter).  A large cloud that shrank to less than half of it
-  // (2 M raw points -> 200 k voxels would keep 32 MB for the cloud's lifetime, times sixteen streams) moves to a buffer
-  // of its size; small or well-filled ones stay (a copy dispatch per SIFT octave would cost the headline more than the
-  // memory is worth: 406 k -> 100 k points is 6.5 MB for the octave's lifetime).
-  if (bound >= ((size_t)1 << 20) && nvox * 2 < bound) {
-    DevBuf<float4> fit(c, nvox);
-    if (nvox) MM3D_HIP(hipMemcpyAsync(fit.get(), out.get(), nvox * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
-    c->settle();                                      // (`out` returns to the pool behind the copy)
-    out = std::move(fit);
-  }
+  refit_points(c, out, nvox, bound);                  // (the output was allocated at its bound: one wait for the whole filter)
   mm3d_cloud *res = cloud_from_device(c, std::move(out), nvox);
   unsigned box[8];
   box_of_slots(h + 32, cblocks, box);
@@ -276,19 +267,7 @@ mm3d_cloud *remove_outliers(Context *c, const mm3d_cloud *in, double radius, int
                   g.view(), (float)radius, thr, need, keep.get());
     }
   }
-  DevBuf<float4> out;
-  unsigned box[7];
-  size_t m = compact_points(c, in->pts.get(), keep.get(), n, out, box);     // (the kept points' bounding box comes back with the count)
-  if (n >= ((size_t)1 << 20) && m * 2 < n) {           // as in downsample: a large, mostly empty bound-sized buffer is not kept
-    DevBuf<float4> fit(c, m);
-    if (m) MM3D_HIP(hipMemcpyAsync(fit.get(), out.get(), m * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
-    c->settle();
-    out = std::move(fit);
-  }
-  mm3d_cloud *res = cloud_from_device(c, std::move(out), m);
-  cloud_set_bbox(res, box);
-  res->voxel_leaf = in->voxel_leaf;                    // a subset of a voxel grid's centroids
-  return res;
+  return cloud_of_kept(c, in, keep.get(), true);       // (a subset of a voxel grid's centroids; the kept points' box comes back with the count)
 }
 
 // ---------------------------------------------------------------- composeMaps: transform + concat

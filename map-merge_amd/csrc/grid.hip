@@ -860,6 +860,36 @@ size_t compact_points(Context *c, const float4 *in, const int *flags, size_t n, 
   return (size_t)r[0];
 }
 
+// The re-fit rule of every output that is allocated at its bound so that its producer waits once: a large buffer of which less
+// than half is used (2 M raw points -> 200 k voxels would keep 32 MB for the cloud's lifetime, times sixteen streams) moves to
+// a buffer of its size; small or well-filled ones stay (a copy dispatch per SIFT octave would cost the headline more than the
+// memory is worth: 406 k -> 100 k points is 6.5 MB for the octave's lifetime).  The bound-sized buffer returns to the pool
+// behind the copy: settle before the move.
+void refit_points(Context *c, DevBuf<float4> &out, size_t m, size_t bound)
+{
+  if (bound < ((size_t)1 << 20) || m * 2 >= bound) return;
+  DevBuf<float4> fit(c, m);
+  if (m) MM3D_HIP(hipMemcpyAsync(fit.get(), out.get(), m * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
+  c->settle();
+  out = std::move(fit);
+}
+
+// The tail of every stage that returns a subset of its input: the flagged points of `in` in their order as a cloud of its
+// own, with its bounding box.  One wait, compact_points' -- a caller's pinned read-back enqueued before this call is home when
+// it returns.  inherits_leaf: the subset of a voxel grid's centroids is still one point per voxel of that leaf.
+mm3d_cloud *cloud_of_kept(Context *c, const mm3d_cloud *in, const int *flags, bool inherits_leaf, size_t *kept)
+{
+  DevBuf<float4> out;
+  unsigned box[7];
+  const size_t m = compact_points(c, in->pts.get(), flags, in->n, out, box);
+  refit_points(c, out, m, in->n);
+  mm3d_cloud *res = cloud_from_device(c, std::move(out), m);
+  cloud_set_bbox(res, box);
+  if (inherits_leaf) res->voxel_leaf = in->voxel_leaf;
+  if (kept) *kept = m;
+  return res;
+}
+
 // a cloud whose producer reduced its bounding box (scan_fused.hpp::BoxAcc): no k_bbox launch, no wait
 void cloud_set_bbox(mm3d_cloud *cl, const unsigned box[7])
 {

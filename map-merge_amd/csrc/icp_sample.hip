@@ -12,7 +12,7 @@
 //   k_smp_select   the geometry of k_smp_bucket again: every point's stable rank inside its bucket -- within a wave a loop over
 //                  the distinct keys present (ballot, popcount of the lower lanes), across the block's waves through LDS, across
 //                  the blocks through k_smp_levels' prefixes -- and the keep flag floor((r+1) take / c) > floor(r take / c)
-//   compact        the library's ordered compaction (grid.hip::compact_points): the sample cloud, its bounding box, and the one
+//   compact        the library's ordered compaction (grid.hip::cloud_of_kept): the sample cloud, its bounding box, and the one
 //                  host wait; a stage call that wants the kept reference indices runs one more fused scan over the flags
 // Everything is integer arithmetic or one rounded f32 multiply and a compare, so the sample does not depend on the launch
 // geometry, the stream or what else runs.
@@ -282,21 +282,12 @@ mm3d_cloud *sample_icp_source(Context *c, const mm3d_cloud *in, const mm3d_norma
     *indices = DevBuf<int>(c, n);
     scan_fused(c, "icp_sample_indices", n * 8.0, (size_t)n, SmpFlagLoad{flags.get(), (size_t)n}, SmpIndexStore{indices->get()});
   }
-  DevBuf<float4> out;
-  unsigned box[7];
-  const size_t m = compact_points(c, in->pts.get(), flags.get(), (size_t)n, out, box);
+  size_t m = 0;
+  std::unique_ptr<mm3d_cloud> res(cloud_of_kept(c, in, flags.get(), false, &m));
   st.valid = h[0]; st.sampled = h[1]; st.level = h[2]; st.buckets = h[3];
   MM3D_REQUIRE(m == (size_t)h[1], "ICP sampling: the kept points are not the budget");
-  if ((size_t)n >= ((size_t)1 << 20) && m * 2 < (size_t)n) {       // as in the filters: a large, mostly empty bound-sized buffer is not kept
-    DevBuf<float4> fit(c, m);
-    if (m) MM3D_HIP(hipMemcpyAsync(fit.get(), out.get(), m * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
-    c->settle();
-    out = std::move(fit);
-  }
-  mm3d_cloud *res = cloud_from_device(c, std::move(out), m);
-  cloud_set_bbox(res, box);
   if (stats) *stats = st;
-  return res;
+  return res.release();
 }
 
 // the selected sampler: a map's sample lives on the map (map_kept.hpp), fresh only for equal options

@@ -5,11 +5,11 @@
 // (audit row 16b).
 //
 // The table of a target, built once per map (ndt_build_table), one host wait -- the one that sizes it:
-//   k_ndt_range    the voxel index range of the finite points (ordered-uint atomics, one set per block)
+//   ndt_range      the voxel index range of the finite points (lattice.hpp::k_lattice_range, as every stage of the global lattice)
 //   k_ndt_keys     a lane per point: voxel key relative to the range's minimum, i most significant, so that ascending keys
 //                  are ascending (i, j, k)
 //   radix sort     (key, input index) pairs, stable: a voxel becomes a run in ascending input index
-//   scan_fused     run heads -> the start of every voxel's run, their number and the number of finite points
+//   scan_fused     run heads (lattice.hpp::LatticeRunHead) -> the start of every voxel's run, their number and the number of finite points
 //   (the wait: range and counts; the records and the dense index are allocated)
 //   k_ndt_voxels   a wave per voxel: mean, covariance (two passes), regularisation and the closed-form inverse in double.
 //                  Lane l takes the run's positions l, l + 64, ... in ascending order and the 64 lane sums meet in wave_sum's
@@ -30,6 +30,7 @@
 #include "drivers.hpp"
 #include "map_kept.hpp"
 #include "icp_solve6.hpp"
+#include "lattice.hpp"
 #include "nn_core.hpp"
 #include "scan_fused.hpp"
 
@@ -51,65 +52,14 @@ constexpr int kNdtAcc = 30;
 
 namespace {
 
-constexpr uint32_t kNdtInvalid = 0xFFFFFFFFu;
 // the dense index holds one int32 per cell of the voxel bounding box: at most 2^26 cells (256 MiB) -- include/mm3d.h and
 // INTEGRATION.md "Size limits" state it
 constexpr double kNdtMaxCells = 67108864.0;
 // mm3d_set_refinement with resolution = 0: the voxel side is params.resolution times this (DESIGN.md section 7e has the measurement)
 constexpr double kNdtDefaultMultiple = 10.0;
 
-// the voxel index of one coordinate, as a float: floor of ONE float multiply (keypoints_uniform.hip forms its keys the same way)
-__device__ __forceinline__ float ndt_index(float x, float inv) { return floorf(__fmul_rn(x, inv)); }
-
-// What the range words say: the minimum index and the extent per axis, and whether the box is within the index limit.  The
-// indices are integer-valued floats, so their differences are exact in double wherever the product is small enough to matter.
-struct NdtFrame { double mn[3], d[3]; bool overflow; };
-__host__ __device__ inline NdtFrame ndt_frame(const unsigned *range)
-{
-  NdtFrame f;
-  for (int a = 0; a < 3; ++a) {
-    f.mn[a] = (double)ord2f(range[a]);
-    f.d[a] = ((double)ord2f(range[3 + a]) - f.mn[a]) + 1.0;
-  }
-  f.overflow = !((f.d[0] * f.d[1]) * f.d[2] <= kNdtMaxCells);      // (an infinite index makes this inf or NaN)
-  return f;
-}
-
-__global__ void __launch_bounds__(256)
-k_ndt_range(const float4 *__restrict__ pts, int n, float inv, unsigned *__restrict__ range /* min i j k, max i j k (ordered) */)
-{
-  float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-  int cnt = 0;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-    const float4 p = pts[i];
-    if (!(isfinite(p.x) && isfinite(p.y) && isfinite(p.z))) continue;
-    const float f[3] = {ndt_index(p.x, inv), ndt_index(p.y, inv), ndt_index(p.z, inv)};
-#pragma unroll
-    for (int a = 0; a < 3; ++a) { lo[a] = fminf(lo[a], f[a]); hi[a] = fmaxf(hi[a], f[a]); }
-    ++cnt;
-  }
-#pragma unroll
-  for (int a = 0; a < 3; ++a) { lo[a] = wave_min_f(lo[a]); hi[a] = wave_max_f(hi[a]); }
-  cnt = wave_sum(cnt);
-  __shared__ float s_lo[4][3], s_hi[4][3];
-  __shared__ int s_cnt[4];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) {
-#pragma unroll
-    for (int a = 0; a < 3; ++a) { s_lo[wave][a] = lo[a]; s_hi[wave][a] = hi[a]; }
-    s_cnt[wave] = cnt;                                   // (lane 0 holds the wave's sum)
-  }
-  __syncthreads();
-  if (threadIdx.x == 0 && s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3] > 0) {
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      float l = s_lo[0][a], h = s_hi[0][a];
-      for (int w = 1; w < 4; ++w) { l = fminf(l, s_lo[w][a]); h = fmaxf(h, s_hi[w][a]); }
-      atomicMin(&range[a], f2ord(l));
-      atomicMax(&range[3 + a], f2ord(h));
-    }
-  }
-}
+// the box of the range words is within the index limit (false for the inf or NaN of an infinite index or an untouched range)
+__host__ __device__ inline bool ndt_fits(const LatticeFrame<3> &f) { return f.cells <= kNdtMaxCells; }
 
 __global__ void __launch_bounds__(256)
 k_ndt_keys(const float4 *__restrict__ pts, int n, float inv, const unsigned *__restrict__ range, uint32_t *__restrict__ keys,
@@ -119,26 +69,17 @@ k_ndt_keys(const float4 *__restrict__ pts, int n, float inv, const unsigned *__r
   if (i >= n) return;
   const float4 p = pts[i];
   vals[i] = (uint32_t)i;
-  if (!(isfinite(p.x) && isfinite(p.y) && isfinite(p.z))) { keys[i] = kNdtInvalid; return; }
-  const NdtFrame f = ndt_frame(range);
+  if (!(isfinite(p.x) && isfinite(p.y) && isfinite(p.z))) { keys[i] = kLatticeInvalid; return; }
+  const LatticeFrame<3> f = lattice_frame<3>(range);
   uint32_t key = 0;                                       // (a box beyond the limit: the host refuses it, the runs are not read)
-  if (!f.overflow) {
-    const uint32_t ri = (uint32_t)((double)ndt_index(p.x, inv) - f.mn[0]), rj = (uint32_t)((double)ndt_index(p.y, inv) - f.mn[1]),
-                   rk = (uint32_t)((double)ndt_index(p.z, inv) - f.mn[2]);
+  if (ndt_fits(f)) {
+    const uint32_t ri = (uint32_t)((double)lattice_index(p.x, inv) - f.mn[0]), rj = (uint32_t)((double)lattice_index(p.y, inv) - f.mn[1]),
+                   rk = (uint32_t)((double)lattice_index(p.z, inv) - f.mn[2]);
     key = (ri * (uint32_t)f.d[1] + rj) * (uint32_t)f.d[2] + rk;     // < 2^26
   }
   keys[i] = key;
 }
 
-// a voxel starts where the sorted key changes; the non-finite points' key sorts last and starts nothing
-struct NdtHeadLoad {
-  const uint32_t *keys;
-  __device__ __forceinline__ int operator()(size_t j) const
-  {
-    const uint32_t k = keys[j];
-    return (k != kNdtInvalid && (j == 0 || keys[j - 1] != k)) ? 1 : 0;
-  }
-};
 // starts[v] = the sorted position at which voxel v's run begins; info[0] = voxels, info[1] = finite points (where the last run ends)
 struct NdtStartStore {
   const uint32_t *keys; size_t n; int *starts; unsigned *info;
@@ -146,7 +87,7 @@ struct NdtStartStore {
   {
     if (v) starts[prefix] = (int)j;
     if (j == n - 1) info[0] = (unsigned)(prefix + v);
-    if (keys[j] != kNdtInvalid && (j == n - 1 || keys[j + 1] == kNdtInvalid)) info[1] = (unsigned)(j + 1);
+    if (keys[j] != kLatticeInvalid && (j == n - 1 || keys[j + 1] == kLatticeInvalid)) info[1] = (unsigned)(j + 1);
   }
   __device__ __forceinline__ void done() const {}
 };
@@ -238,7 +179,7 @@ k_ndt_wave(const NdtJob *__restrict__ jobs)
     const float3 p = xform(Ts, sp.x, sp.y, sp.z);
     sx = p.x; sy = p.y; sz = p.z;
     // the point's voxel relative to the table's minimum, as floats: integer-valued, or inf / NaN, which fail every test below
-    const float rx = ndt_index(p.x, job.inv) - job.mn[0], ry = ndt_index(p.y, job.inv) - job.mn[1], rz = ndt_index(p.z, job.inv) - job.mn[2];
+    const float rx = lattice_index(p.x, job.inv) - job.mn[0], ry = lattice_index(p.y, job.inv) - job.mn[1], rz = lattice_index(p.z, job.inv) - job.mn[2];
     const float dx = (float)job.dims[0], dy = (float)job.dims[1], dz = (float)job.dims[2];
 #pragma unroll
     for (int nb = 0; nb < 7; ++nb) {
@@ -360,14 +301,6 @@ __global__ void __launch_bounds__(256) k_ndt_finalize(const NdtJob *__restrict__
   st->prev_mse = F;
 }
 
-// resolution as the rule reads it: a positive finite float with a finite reciprocal
-bool ndt_resolution_ok(double r)
-{
-  if (!(r > 0.0) || !std::isfinite(r)) return false;
-  const float rf = (float)r;
-  return rf > 0.0f && std::isfinite(rf) && std::isfinite(1.0f / rf);
-}
-
 // everything but the resolution's "0 = default", which only mm3d_set_refinement admits
 bool ndt_options_ok(const mm3d_refine_options *o)
 {
@@ -380,7 +313,7 @@ bool ndt_options_ok(const mm3d_refine_options *o)
 // The table of `tgt` at the given voxel side: complete on c's stream on return (the caller waits before anybody else reads it)
 std::unique_ptr<NdtTable> ndt_build_table(Context *c, const mm3d_cloud *tgt, double resolution, int min_points, double kappa)
 {
-  MM3D_REQUIRE(ndt_resolution_ok(resolution), "NDT: the resolution must be positive and finite, as a float and its reciprocal too");
+  MM3D_REQUIRE(lattice_side_ok(resolution), "NDT: the resolution must be positive and finite, as a float and its reciprocal too");
   MM3D_REQUIRE(tgt->n < ((size_t)1 << 31), "NDT: more than 2^31 - 1 target points");
   std::unique_ptr<NdtTable> t(new NdtTable());
   t->resolution = resolution; t->min_points = min_points; t->regularisation = kappa;
@@ -389,24 +322,20 @@ std::unique_ptr<NdtTable> ndt_build_table(Context *c, const mm3d_cloud *tgt, dou
   if (n == 0) return t;
   const unsigned blocks = div_up((size_t)n, 256);
   DevBuf<unsigned> range(c, 8);                           // min i j k, max i j k | voxels, finite points
-  unsigned *h = (unsigned *)c->pin(64);
-  std::memcpy(h, kBoxInit, sizeof(kBoxInit));             // min words FFFFFFFF, max words 0 (device_util.hpp::f2ord), counts 0
-  MM3D_HIP(hipMemcpyAsync(range.get(), h, sizeof(kBoxInit), hipMemcpyHostToDevice, c->stream));
-  MM3D_LAUNCH(c, "ndt_range", n * 16.0, k_ndt_range, dim3(std::min<unsigned>(div_up((size_t)n, 256 * 8), 512)), dim3(256), 0, tgt->pts.get(), n,
-              t->inv, range.get());
+  lattice_range<3>(c, "ndt_range", n * 16.0, tgt->pts.get(), n, t->inv, LatticeFinite{}, range.get());
   DevBuf<uint32_t> keys(c, n), vals(c, n), keys2(c, n), vals2(c, n);
   MM3D_LAUNCH(c, "ndt_keys", n * 24.0, k_ndt_keys, dim3(blocks), dim3(256), 0, tgt->pts.get(), n, t->inv, (const unsigned *)range.get(),
               keys.get(), vals.get());
   sort_pairs_u32(c, keys.get(), keys2.get(), vals.get(), vals2.get(), (size_t)n, 32);
   DevBuf<int> starts(c, n);                               // (at most one voxel per point)
-  scan_fused(c, "ndt_runs", n * 8.0, (size_t)n, NdtHeadLoad{keys2.get()}, NdtStartStore{keys2.get(), (size_t)n, starts.get(), range.get() + 6});
+  scan_fused(c, "ndt_runs", n * 8.0, (size_t)n, LatticeRunHead{keys2.get()}, NdtStartStore{keys2.get(), (size_t)n, starts.get(), range.get() + 6});
   unsigned *hr = (unsigned *)c->pin(64);
   MM3D_HIP(hipMemcpyAsync(hr, range.get(), 32, hipMemcpyDeviceToHost, c->stream));
   c->sync();                                              // the one wait: what sizes the table
   const int n_voxels = (int)hr[6], n_finite = (int)hr[7];
   if (n_voxels == 0) return t;                            // no finite point
-  const NdtFrame f = ndt_frame(hr);
-  if (f.overflow)
+  const LatticeFrame<3> f = lattice_frame<3>(hr);
+  if (!ndt_fits(f))
     throw Error(MM3D_EUNSUPPORTED, "NDT: the target's voxel bounding box needs more than 2^26 index cells at this resolution");
   for (int a = 0; a < 3; ++a) { t->mn[a] = (float)f.mn[a]; t->dims[a] = (int)f.d[a]; }
   t->n_voxels = n_voxels;
@@ -484,7 +413,7 @@ extern "C" {
 int mm3d_set_refinement(mm3d_ctx *ctx, const mm3d_refine_options *options)
 {
   if (!ctx || !ndt_options_ok(options)) return MM3D_EINVAL;
-  if (options->resolution != 0.0 && !ndt_resolution_ok(options->resolution)) return MM3D_EINVAL;     // (also catches NaN)
+  if (options->resolution != 0.0 && !lattice_side_ok(options->resolution)) return MM3D_EINVAL;     // (also catches NaN)
   std::lock_guard<std::mutex> lock(ctx->mu);        // (no call is running while the method changes)
   const bool ndt = options->method == MM3D_REFINE_NDT;
   if (ndt && refused_on_device_list(ctx, "mm3d_set_refinement: NDT is not available on a device-list context")) return MM3D_EUNSUPPORTED;
@@ -507,7 +436,7 @@ int mm3d_estimate_transform_ndt(mm3d_ctx *ctx, const mm3d_cloud *source, const m
                                 const mm3d_refine_options *options, int max_iterations, double eps, float T[16])
 {
   if (!ctx || !source || !target || !initial_guess || !T || !ndt_options_ok(options)) return MM3D_EINVAL;
-  if (!ndt_resolution_ok(options->resolution)) return MM3D_EINVAL;
+  if (!lattice_side_ok(options->resolution)) return MM3D_EINVAL;
   return guarded(ctx, [&] {
     std::unique_ptr<NdtTable> t = ndt_build_table(ctx, target, options->resolution, options->min_points, options->regularisation);
     IcpScoreJob J;
@@ -521,7 +450,7 @@ int mm3d_estimate_transform_ndt(mm3d_ctx *ctx, const mm3d_cloud *source, const m
 int mm3d_debug_ndt_voxels(mm3d_ctx *ctx, const mm3d_cloud *target, const mm3d_refine_options *options, int *ijk, int *count, float *mean,
                           float *icov, unsigned char *valid, size_t cap, size_t *n_voxels)
 {
-  if (!ctx || !target || !n_voxels || !ndt_options_ok(options) || !ndt_resolution_ok(options->resolution)) return MM3D_EINVAL;
+  if (!ctx || !target || !n_voxels || !ndt_options_ok(options) || !lattice_side_ok(options->resolution)) return MM3D_EINVAL;
   if (cap && (!ijk || !count || !mean || !icov || !valid)) return MM3D_EINVAL;
   *n_voxels = 0;
   return guarded(ctx, [&] {

@@ -15,7 +15,7 @@
 //   k_sor_partials  S, Q and the valid count of 4096 points per block in a fixed order, doubles, no atomics
 //   k_sor_threshold one lane adds the blocks' partials in block order and leaves mu, sigma, t
 //   k_sor_keep      a lane per point: valid and d <= t
-//   compact         grid.hip::compact_points, behind whose wait the statistics come back too
+//   compact         grid.hip::cloud_of_kept, behind whose wait the statistics come back too
 // A query's result is a function of the multiset of its candidates' d2 alone, so nothing depends on which pass served it, on
 // the order the list was filled in, or on the launch geometry.
 #include <atomic>
@@ -402,23 +402,13 @@ mm3d_cloud *remove_outliers_statistical(Context *c, const mm3d_cloud *in, int me
   }
   MM3D_LAUNCH(c, "sor_keep", n * 12.0, k_sor_keep, dim3(div_up(n, 256)), dim3(256), 0, in->pts.get(), (const double *)d.get(), (const SorStats *)dst, n,
               kk > 0 ? 0 : 1, keep.get());
-  DevBuf<float4> out;
-  unsigned box[7];
-  const size_t m = compact_points(c, in->pts.get(), keep.get(), n, out, box);   // the one wait: count, box and the statistics
-  if (n >= ((size_t)1 << 20) && m * 2 < n) {            // as in the radius filter: a large, mostly empty bound-sized buffer is not kept
-    DevBuf<float4> fit(c, m);
-    if (m) MM3D_HIP(hipMemcpyAsync(fit.get(), out.get(), m * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
-    c->settle();
-    out = std::move(fit);
-  }
+  size_t m = 0;
+  mm3d_cloud *res = cloud_of_kept(c, in, keep.get(), true, &m);      // the one wait: count, box and the statistics (a subset of a voxel grid's centroids)
   st.valid = kk > 0 ? h->valid : (long long)in->n_finite;
   st.kept = (long long)m;
   st.k = kk;
   st.mean = h->mean; st.stddev = h->stddev; st.threshold = h->threshold;
   if (stats) *stats = st;
-  mm3d_cloud *res = cloud_from_device(c, std::move(out), m);
-  cloud_set_bbox(res, box);
-  res->voxel_leaf = in->voxel_leaf;                     // a subset of a voxel grid's centroids
   return res;
 }
 

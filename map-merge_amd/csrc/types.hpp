@@ -328,6 +328,10 @@ const std::vector<float4> &cloud_host(Context *c, const mm3d_cloud *cl, bool wai
 // ordered compaction: keeps in[i] where flags[i] != 0, preserving order; returns kept count
 size_t compact_points(Context *c, const float4 *in, const int *flags, size_t n, DevBuf<float4> &out, unsigned *box_host = nullptr);   // box_host: 7 words for cloud_set_bbox
 void cloud_set_bbox(mm3d_cloud *cl, const unsigned box[7]);
+// out holds m points in a buffer of `bound`: moved to a buffer of m when that one is large and mostly empty (grid.hip has the rule)
+void refit_points(Context *c, DevBuf<float4> &out, size_t m, size_t bound);
+// the points of `in` whose flag is set, in order, as a new cloud with its box (one wait); the input's voxel_leaf when asked
+mm3d_cloud *cloud_of_kept(Context *c, const mm3d_cloud *in, const int *flags, bool inherits_leaf, size_t *kept = nullptr);
 void exclusive_scan_int(Context *c, const int *in, int *out, size_t n);
 // one chained-scan launch's share of the context's scan state (grid.hip::scan_prepare; scan_fused.hpp)
 constexpr int kScanItems = 16, kScanTile = 256 * kScanItems;

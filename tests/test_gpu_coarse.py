@@ -358,6 +358,30 @@ def test_signature_cell_by_cell(mm, scene):
     c.close()
 
 
+def test_signature_when_blocks_of_the_range_launch_count_nothing(mm):
+    """4 100 rows make the cell-range launch three blocks.  Every row below 4 096 is not counted -- the point is not a number
+    in the even rows, the normal in the odd ones -- so the four counted rows fall to one block and the other two count nothing;
+    then no row is counted, no block counts anything, the range words keep their initial values and the signature has no cell."""
+    rng = np.random.default_rng(9)
+    xyz = rng.uniform(-40, 40, (4100, 3)).astype(F32)
+    nrm = np.tile(np.array([[1, 0, 0], [0, 0, 1]], dtype=F32), (2050, 1))
+    xyz[np.arange(0, 4096, 2), np.arange(2048) % 3] = np.nan
+    nrm[np.arange(1, 4096, 2), np.arange(2048) % 3] = np.array([np.nan, np.inf] * 1024, dtype=F32)
+    xyz[4096:] = [[1.6, -0.7, 0.0], [1.1, -0.8, 0.25], [1.9, -0.6, 1.0], [1.2, -0.9, 0.75]]      # walls in cell (3, -2), ground in (2, -2)
+    c = mm.Context(0)
+    opt = dict(method=CORRELATIVE, cell=0.5, cell_factor=2, min_points=2)
+    ref = restate_signature(xyz, nrm, 0.5, 2, min_points=2)
+    got = c.correlativeSignature(c.cloud(records(xyz)), c.normals(normal_records(nrm)), **opt)
+    assert ref["structure"].tolist() == [[3, -2, 2]] and ref["ground"].tolist() == [[2, -2, 2]] and ref["coarse"].tolist() == [[1, -1]]
+    for k in ("structure", "ground", "coarse"):
+        assert np.array_equal(got[k], ref[k]), k
+    assert got["ground_height"].tolist() == ref["ground_height"].tolist() == [0.5]
+    nrm[4096:, 2] = np.nan
+    got = c.correlativeSignature(c.cloud(records(xyz)), c.normals(normal_records(nrm)), **opt)
+    assert all(len(v) == 0 for v in got.values())
+    c.close()
+
+
 def test_literal_signature_and_votes(mm):
     c = mm.Context(0)
     got = c.correlativeSignature(c.cloud(records(TEN_POINTS)), c.normals(normal_records(TEN_NORMALS)), method=CORRELATIVE, cell=0.5,

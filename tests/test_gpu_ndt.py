@@ -198,9 +198,8 @@ def _table_scene(min_points):
     return pts[rng.permutation(len(pts))]
 
 
-@pytest.mark.parametrize("min_points,kappa", [(6, 0.01), (4, 1.0)])
-def test_voxel_table_voxel_by_voxel(mm, min_points, kappa):
-    pts = _table_scene(min_points)
+def _check_table(mm, pts, min_points, kappa):
+    """The device's table of pts at 1 m against the restatement's, voxel by voxel; returns the restatement's."""
     ref = restate_table(pts, 1.0, min_points, kappa)
     c = mm.Context(0)
     got, n = c.ndtVoxels(c.cloud(_records(pts)), method=NDT, resolution=1.0, min_points=min_points, regularisation=kappa)
@@ -209,9 +208,6 @@ def test_voxel_table_voxel_by_voxel(mm, min_points, kappa):
     assert n == len(keys) and [tuple(r) for r in got["ijk"].tolist()] == keys        # the set, and its ascending order
     assert got["count"].tolist() == [ref[k][0] for k in keys]
     assert got["valid"].tolist() == [ref[k][2] is not None for k in keys]
-    assert (20, 20, 20) in ref and ref[(20, 20, 20)][0] == min_points - 1 and ref[(20, 20, 20)][2] is None
-    assert ref[(-21, 7, -10)][0] == min_points and ref[(-21, 7, -10)][2] is None     # coincident points: trace 0
-    assert sum(v[2] is not None for v in ref.values()) > 100
     for row, k in enumerate(keys):
         cnt, mu, P = ref[k]
         ulp = np.spacing(np.abs(mu.astype(np.float32)))
@@ -221,6 +217,32 @@ def test_voxel_table_voxel_by_voxel(mm, min_points, kappa):
         else:
             tol = 4.0 * 2.0 ** -24 * np.abs(P).max()
             assert (np.abs(got["icov"][row].astype(np.float64) - P) <= tol).all(), (k, got["icov"][row], P)
+    return ref
+
+
+@pytest.mark.parametrize("min_points,kappa", [(6, 0.01), (4, 1.0)])
+def test_voxel_table_voxel_by_voxel(mm, min_points, kappa):
+    ref = _check_table(mm, _table_scene(min_points), min_points, kappa)
+    assert (20, 20, 20) in ref and ref[(20, 20, 20)][0] == min_points - 1 and ref[(20, 20, 20)][2] is None
+    assert ref[(-21, 7, -10)][0] == min_points and ref[(-21, 7, -10)][2] is None     # coincident points: trace 0
+    assert sum(v[2] is not None for v in ref.values()) > 100
+
+
+def test_voxel_table_when_blocks_of_the_range_launch_count_nothing(mm):
+    """4 100 rows make the index-range launch three blocks.  Every row below 4 096 has a coordinate that is not a number, so the
+    four finite rows fall to one block and the other two count nothing; then no row is finite, no block counts anything, the
+    range words keep their initial values and the table has no voxel."""
+    rng = np.random.default_rng(9)
+    pts = rng.uniform(-40, 40, (4100, 3)).astype(np.float32)
+    pts[np.arange(4096), np.arange(4096) % 3] = np.array([np.nan, np.inf, -np.inf, np.nan] * 1024, dtype=np.float32)
+    pts[4096:] = [[2.2, -2.9, 0.1], [2.7, -2.3, 0.6], [2.4, -2.5, 0.9], [2.8, -2.8, 0.3]]    # min_points of them in voxel (2, -3, 0)
+    ref = _check_table(mm, pts, 4, 0.01)
+    assert list(ref) == [(2, -3, 0)] and ref[(2, -3, 0)][0] == 4 and ref[(2, -3, 0)][2] is not None
+    pts[4096:, 2] = np.nan
+    c = mm.Context(0)
+    got, n = c.ndtVoxels(c.cloud(_records(pts)), method=NDT, resolution=1.0, min_points=4)
+    c.close()
+    assert n == 0 and all(len(v) == 0 for v in got.values())
 
 
 # ---------------------------------------------------------------- 3. against the restatement

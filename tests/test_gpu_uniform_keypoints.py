@@ -194,6 +194,19 @@ def test_rule_on_equidistant_points_nonfinite_rows_and_extremes(mm, ctx):
     assert _check_rule(mm, ctx, _pts(mm, huge), 1e37) > 0
 
 
+def test_rule_when_blocks_of_the_range_launch_count_nothing(mm, ctx):
+    """4 100 rows make the index-range launch three blocks.  Every row below 4 096 has a coordinate that is not a number, so the
+    four finite rows fall to one block and the other two count nothing; then no row is finite, no block counts anything, the
+    range words keep their initial values and the keypoints are the empty cloud."""
+    rng = np.random.default_rng(9)
+    xyz = rng.uniform(-40, 40, (4100, 3)).astype(np.float32)
+    xyz[np.arange(4096), np.arange(4096) % 3] = np.nan
+    xyz[4096:] = [[0.1, 0.1, 0.1], [0.2, 0.2, 0.2], [5.3, -2.2, 0.7], [-7.9, 3.1, 1.4]]      # the first two share a voxel
+    assert _check_rule(mm, ctx, _pts(mm, xyz), 0.5) == 3
+    xyz[4096:, 1] = np.inf
+    assert _check_rule(mm, ctx, _pts(mm, xyz), 0.5) == 0
+
+
 def test_empty_cloud_and_invalid_arguments(mm, ctx):
     L = mm.lib()
     empty = ctx.cloud(np.empty(0, dtype=mm.POINT))
