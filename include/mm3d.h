@@ -120,6 +120,15 @@ int mm3d_last_icp_converged(const mm3d_ctx *ctx);
 void mm3d_set_debug(mm3d_ctx *ctx, int on);
 long long mm3d_debug_knn_fallback_rows(mm3d_ctx *ctx);
 long long mm3d_debug_knn_rows(mm3d_ctx *ctx);
+/* which routes the descriptor k-NN took on this context while mm3d_set_debug was on: one bit per route, read and cleared */
+#define MM3D_KNN_PATH_SMALL 1u      /* small problems: plain brute force */
+#define MM3D_KNN_PATH_LIST 2u       /* rows of 2 / 33 floats: candidate lists, every candidate re-ranked */
+#define MM3D_KNN_PATH_FILTER 4u     /* rows of 2 / 33 floats against many targets: the threshold filter */
+#define MM3D_KNN_PATH_LIST_WIDE 8u  /* rows of 125 floats: candidate lists, the pruned re-rank */
+#define MM3D_KNN_PATH_WIDE_BF16 16u /* rows beyond 128 floats: the split-bf16 selector */
+#define MM3D_KNN_PATH_WIDE_F32 32u  /* rows beyond 128 floats: the f32 selector (MM3D_KNN_WIDE_BF16=0) */
+#define MM3D_KNN_PATH_ANY 64u       /* k beyond 16 */
+unsigned mm3d_debug_knn_paths(mm3d_ctx *ctx);
 /* host waits for the context's stream (and its mm3d_set_streams workers') since the context was made: out[0] = their number,
  * out[1] = nanoseconds spent in them */
 void mm3d_debug_waits(mm3d_ctx *ctx, long long out[2]);

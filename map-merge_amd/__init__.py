@@ -524,6 +524,14 @@ def sift_cert_stats(reset=False):
     return list(out)
 
 
+def knn_paths(ctx):
+    """mm3d_debug_knn_paths: the routes the descriptor k-NN took on this context while mm3d_set_debug was on, one bit per route
+    (1 small brute force, 2 lists, 4 filter, 8 lists of 125-wide rows, 16 wide bf16, 32 wide f32, 64 any k); read and cleared."""
+    f = lib().mm3d_debug_knn_paths
+    f.restype = C.c_uint
+    return int(f(ctx._h))
+
+
 def sacia_stats(reset=False, collect=-1):
     """Process-wide counters of SAC-IA's certified pick (mm3d_debug_sacia_stats): pairs scored, pairs decided without a float
     chain, candidate hypotheses the intervals left, chains run.  collect = 1 / 0 switches the collection on / off."""

@@ -377,6 +377,14 @@ void mm3d_set_debug(mm3d_ctx *ctx, int on)
   if (!ctx) return;
   ctx->debug = on != 0;
   ctx->knn_fallback_rows = ctx->knn_rows = 0;
+  ctx->knn_paths = 0;
+}
+unsigned mm3d_debug_knn_paths(mm3d_ctx *ctx)
+{
+  if (!ctx) return 0;
+  const unsigned m = ctx->knn_paths;
+  ctx->knn_paths = 0;
+  return m;
 }
 long long mm3d_debug_knn_fallback_rows(mm3d_ctx *ctx) { return ctx ? ctx->knn_fallback_rows : 0; }
 long long mm3d_debug_knn_rows(mm3d_ctx *ctx) { return ctx ? ctx->knn_rows : 0; }

@@ -38,6 +38,9 @@ constexpr int kListLen = 8;      // per-lane candidate list of the MFMA stage (8
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
+// which route a search took (MM3D_KNN_PATH_*), kept while mm3d_set_debug is on: mm3d_debug_knn_paths
+static inline void knn_took(Context *c, unsigned route) { if (c->debug) c->knn_paths |= route; }
+
 // ---------------------------------------------------------------- exact brute force (VALU)
 // one thread per query row (registers), target rows staged through LDS in tiles of 64 and
 // broadcast-read by every lane.  Used for small problems and for rows that fail the certificate.
@@ -183,8 +186,12 @@ __global__ void k_knn_prep(const float *__restrict__ X, int n, int ntiles, int i
       }
     }
   } else if (is_target) {
-    // padding targets: a'.b' = 1e30, never a candidate ahead of a real row
-    v = (kk == kD + 1) ? 1e30f : 0.0f;
+    // padding targets: a'.b' = 0 x (finite) + inf x 1 = +inf (the query's column kD + 1 is the constant 1, so no inf x 0 meets a
+    // real query), and +inf never compares below a list entry or a threshold: a padding row is never kept, whatever the rows'
+    // magnitude.  (A large finite value, 1e30 once, lies AHEAD of real rows of magnitude 1e15 and filled lists that were then
+    // taken for empty.)  Padding QUERIES are all zeros: their products with a padding target are NaN, compare false as well,
+    // and belong to rows that are never written.
+    v = (kk == kD + 1) ? INFINITY : 0.0f;
   }
   Xp[e] = v;
 }
@@ -884,7 +891,9 @@ __global__ void k_knn_prep_bf(const float *__restrict__ X, int n, int ntiles, in
         exact_piece = true;
       }
     } else if (is_target) {
-      v = (kk == kD + 3) ? 1e30f : 0.0f;            // padding targets: a'.b' = 1e30, never ahead of a real row
+      // padding targets: +inf in bf16 against the query's exact 1 (hi 1, lo 0): the hi x hi product is +inf, the hi x lo one
+      // inf x 0 = NaN -- +inf or NaN, the sum never compares below a list entry (see k_knn_prep)
+      v = (kk == kD + 3) ? INFINITY : 0.0f;
       exact_piece = true;
     }
     const unsigned h = knn_bf16_rn(v);
@@ -1364,6 +1373,7 @@ static void desc_knn_impl(Context *c, const mm3d_desc *A, const mm3d_desc *B, in
   if (na == 0) return;
   const float *Ad = A->data.get(), *Bd = B->data.get();
   if ((double)na * nb < 65536.0 || nb < 64) {
+    knn_took(c, MM3D_KNN_PATH_SMALL);
     MM3D_LAUNCH(c, "desc_knn_exact", ((double)na + nb) * kD * 4.0, (k_knn_exact<kD>), dim3(div_up(na, 128)), dim3(128), 0, Ad, na,
                 Bd, nb, k, (const int *)nullptr, (const int *)nullptr, na, idx.get(), d2.get());
     return;
@@ -1402,6 +1412,7 @@ static void desc_knn_impl(Context *c, const mm3d_desc *A, const mm3d_desc *B, in
   if (kD < 64 && nb_tiles >= 64 && k + kThetaExtra <= 32 && !no_filter) {
    if constexpr (kD < 64) {
     // short rows against many targets: thresholds from a sample of the target tiles, then the filtered product
+    knn_took(c, MM3D_KNN_PATH_FILTER);
     const int ns_tiles = div_up(nb_tiles, kSampleStep);
     int sparts = 1;
     while (sparts < 4 && na_tiles * sparts < 512 && ns_tiles / (kSlices * sparts * 2) >= 2) sparts *= 2;
@@ -1431,6 +1442,7 @@ static void desc_knn_impl(Context *c, const mm3d_desc *A, const mm3d_desc *B, in
    }
   } else {
     // each part keeps its own 8 lists per query
+    knn_took(c, kD >= 64 ? MM3D_KNN_PATH_LIST_WIDE : MM3D_KNN_PATH_LIST);
     const int n_lists = kLists * parts;
     DevBuf<float> cand_d(c, (size_t)na * n_lists * kListLen);
     DevBuf<int> cand_i(c, (size_t)na * n_lists * kListLen);
@@ -1477,6 +1489,7 @@ static void desc_knn_wide_impl(Context *c, const mm3d_desc *A, const mm3d_desc *
   const int fb_groups = div_up(na, kWideFbRows);
   if ((double)na * nb < 65536.0 || nb < 64) {
     // small problems: brute force for every row
+    knn_took(c, MM3D_KNN_PATH_SMALL);
     MM3D_LAUNCH(c, "iota", na * 4.0, k_knn_iota, dim3(div_up(na, 256)), dim3(256), 0, fb_rows.get(), na, (int *)(meta.get() + 1));
     MM3D_LAUNCH(c, "desc_knn_fallback", ((double)na + nb) * kD * 4.0, (k_knn_exact_wide<kD>), dim3(fb_groups < 64 ? fb_groups : 64, kFbParts),
                 dim3(64), 0, Ad, Bd, nb, k, (const int *)fb_rows.get(), (const int *)nullptr, na, part_keys.get());
@@ -1487,6 +1500,7 @@ static void desc_knn_wide_impl(Context *c, const mm3d_desc *A, const mm3d_desc *
   }
   const int na_tiles = (na + 31) / 32, nb_tiles = (nb + 31) / 32;
   const bool bf = knn_wide_bf16();
+  knn_took(c, bf ? MM3D_KNN_PATH_WIDE_BF16 : MM3D_KNN_PATH_WIDE_F32);
   constexpr int kChunks = knn_kp16(kD) / 16;
   DevBuf<float> Ap(c, bf ? (size_t)na_tiles * kChunks * 64 * 8 : (size_t)na_tiles * kSteps * 64);
   MM3D_HIP(hipMemsetAsync(meta.get(), 0, 16, c->stream));
@@ -1605,6 +1619,7 @@ static void desc_knn_any(Context *c, const mm3d_desc *A, const mm3d_desc *B, int
 {
   const int na = (int)A->n, nb = (int)B->n, dim = A->dim;
   if (dim > kAnyMaxDim) throw Error(MM3D_EUNSUPPORTED, "descriptor k-NN: rows wider than 2048 floats");
+  knn_took(c, MM3D_KNN_PATH_ANY);
   idx = DevBuf<int>(c, (size_t)na * k);
   d2 = DevBuf<float>(c, (size_t)na * k);
   if (na == 0) return;
