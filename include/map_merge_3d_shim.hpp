@@ -155,6 +155,60 @@ inline mm3d_smooth_options parse_smooth(const char *value)
   o.method = MM3D_SMOOTH_MLS;
   return o;
 }
+// MM3D_PLANES=remove or set_aside, then :<max_planes> and :<distance> if given, then @<x>,<y>,<z>,<degrees> or @any at most: the
+// dominant planes of the estimation context's filtered maps leave, or are set aside while MM3D_CLUSTERS looks at the rest
+// (mm3d_set_planes; what is not given keeps mm3d_plane_options_default's value: one plane, half of params.resolution, within 10
+// degrees of z); off or unset runs nothing.  Anything else throws.
+inline mm3d_plane_options parse_planes(const char *value)
+{
+  mm3d_plane_options o;
+  o.method = MM3D_PLANES_OFF;
+  o.max_planes = 1; o.samples = 1024; o.refit = 1; o.seed = 1u;
+  o.distance = 0.0; o.min_fraction = 0.05;
+  o.axis[0] = 0.0; o.axis[1] = 0.0; o.axis[2] = 1.0;
+  o.max_angle_deg = 10.0;
+  const std::string v = value ? value : "";
+  if (v.empty() || v == "off") return o;
+  const size_t at = v.find('@');
+  const std::string head = v.substr(0, at), tail = at == std::string::npos ? "" : v.substr(at + 1);
+  const bool remove = head.compare(0, 6, "remove") == 0 && (head.size() == 6 || head[6] == ':');
+  const bool aside = head.compare(0, 9, "set_aside") == 0 && (head.size() == 9 || head[9] == ':');
+  bool ok = remove || aside;
+  const size_t name = remove ? 6 : 9;
+  auto digit = [](char c) { return c >= '0' && c <= '9'; };
+  if (ok && head.size() > name) {
+    const char *s = head.c_str() + name + 1;
+    char *end = nullptr;
+    const long k = std::strtol(s, &end, 10);
+    ok = end != s && (*end == '\0' || *end == ':') && k >= 1 && k <= 8 && digit(*s);
+    o.max_planes = (int)k;
+    if (ok && *end == ':') {
+      s = end + 1;
+      o.distance = std::strtod(s, &end);
+      ok = end != s && *end == '\0' && std::isfinite(o.distance) && o.distance > 0.0 && (digit(*s) || *s == '.');
+    }
+  }
+  if (ok && at != std::string::npos) {
+    if (tail == "any") o.axis[2] = 0.0;
+    else {
+      double f[4];
+      const char *s = tail.c_str();
+      for (int k = 0; ok && k < 4; ++k) {
+        char *end = nullptr;
+        f[k] = std::strtod(s, &end);
+        ok = end != s && std::isfinite(f[k]) && (digit(*s) || *s == '.' || *s == '-') && *end == (k < 3 ? ',' : '\0');
+        s = end + 1;
+      }
+      ok = ok && (f[0] != 0.0 || f[1] != 0.0 || f[2] != 0.0) && f[3] >= 0.0 && f[3] <= 90.0;
+      if (ok) { o.axis[0] = f[0]; o.axis[1] = f[1]; o.axis[2] = f[2]; o.max_angle_deg = f[3]; }
+    }
+  }
+  if (!ok)
+    throw std::runtime_error("mm3d: MM3D_PLANES must be off, remove or set_aside, then :<max_planes 1 .. 8> and :<distance > 0> if "
+                             "wanted, then @<x>,<y>,<z>,<degrees 0 .. 90> or @any at most, not '" + v + "'");
+  o.method = remove ? MM3D_PLANES_REMOVE : MM3D_PLANES_SET_ASIDE;
+  return o;
+}
 // MM3D_REFINE=ndt or ndt:<resolution in metres>: the estimation context's pair stage refines with NDT in the ICP's place
 // (mm3d_set_refinement; without a resolution, the library's default multiple of params.resolution; the other options keep
 // mm3d_refine_options_default's values); icp or unset keeps the ICP that MM3D_ICP selects.  Anything else throws.
@@ -519,6 +573,7 @@ inline mm3d_ctx *ctx()
   // MM3D_KEYPOINTS=uniform[:<leaf>]: parse_keypoints above; it works on a device list too.
   // MM3D_OUTLIERS=statistical[:<mean_k>[:<stddev_mult>]]: parse_outliers above; it works on a device list too.
   // MM3D_CLUSTERS=min_size:<n>[:<tolerance>] or largest[:<tolerance>]: parse_clusters above; it works on a device list too.
+  // MM3D_PLANES=remove|set_aside[:<max_planes>[:<distance>]][@<x>,<y>,<z>,<degrees>|@any]: parse_planes above; it works on a device list too.
   // MM3D_SMOOTH=mls[:<order>[:<radius>]][@maps|@composed]: parse_smooth above; it works on a device list too.
   // MM3D_REFINE=ndt[:<resolution>]: parse_refine above.  Not available on a device list: ndt with MM3D_DEVICES set as well throws.
   // MM3D_COARSE=correlative[:<cell>]: parse_coarse above.  Not available on a device list: correlative with MM3D_DEVICES set as well throws.
@@ -545,6 +600,7 @@ inline mm3d_ctx *ctx()
     const mm3d_keypoint_options keypoints = parse_keypoints(std::getenv("MM3D_KEYPOINTS"));
     const mm3d_outlier_options outliers = parse_outliers(std::getenv("MM3D_OUTLIERS"));
     const mm3d_cluster_options clusters = parse_clusters(std::getenv("MM3D_CLUSTERS"));
+    const mm3d_plane_options planes = parse_planes(std::getenv("MM3D_PLANES"));
     const mm3d_smooth_options smooth = parse_smooth(std::getenv("MM3D_SMOOTH"));
     mm3d_refine_options refine = parse_refine(std::getenv("MM3D_REFINE"));
     if (refine.method == MM3D_REFINE_NDT && std::getenv("MM3D_DEVICES") && *std::getenv("MM3D_DEVICES"))
@@ -586,6 +642,8 @@ inline mm3d_ctx *ctx()
       throw std::runtime_error("mm3d: MM3D_OUTLIERS was refused (mean_k must be 1 .. 64, stddev_mult finite and not negative)");
     if (clusters.method != MM3D_CLUSTERS_OFF && mm3d_set_cluster_filter(e, &clusters) != MM3D_OK)
       throw std::runtime_error("mm3d: MM3D_CLUSTERS was refused (min_size must be at least 1, the tolerance finite and not negative)");
+    if (planes.method != MM3D_PLANES_OFF && mm3d_set_planes(e, &planes) != MM3D_OK)
+      throw std::runtime_error("mm3d: MM3D_PLANES was refused (max_planes must be 1 .. 8, the distance finite and not negative, the angle 0 .. 90)");
     if (smooth.method != MM3D_SMOOTH_OFF && mm3d_set_smoothing(e, &smooth) != MM3D_OK)
       throw std::runtime_error("mm3d: MM3D_SMOOTH was refused (the order must be 1 or 2, the radius finite and not negative)");
     if (refine.method != MM3D_REFINE_ICP && mm3d_set_refinement(e, &refine) != MM3D_OK)

@@ -485,6 +485,87 @@ typedef struct mm3d_cluster_stats {
 /* The cluster filter's last run on this context: mm3d_remove_small_clusters, or mm3d_map_features with a method selected (all
  * zero before the first).  MM3D_EINVAL for NULL. */
 int mm3d_last_cluster_stats(const mm3d_ctx *ctx, mm3d_cluster_stats *stats);
+/* What takes the dominant planes out of a filtered map (off the reference's path; MM3D_PLANES_OFF by default: nothing runs).  The
+ * cluster filter removes what floats; a person, a robot or a chair stands on the floor, and through the floor it is connected to
+ * every wall.  With a method selected, every place that filters a map behind a whole-map call -- mm3d_map_features,
+ * mm3d_estimate_maps_transforms on one stream or many, on a device list (mm3d_create_devices) and mm3d_shard_begin -- runs the
+ * rule below on the cloud that left the outlier filter, radius or statistical:
+ *   MM3D_PLANES_REMOVE     the plane records leave; the cluster filter, if selected, then runs on what is left.  What users of
+ *                          pcl::SACSegmentation and Open3D's segment_plane do to the ground of an outdoor map before matching.
+ *   MM3D_PLANES_SET_ASIDE  with a cluster filter selected, the cluster filter runs on the records labelled MM3D_PLANE_NONE; the
+ *                          map is the set-aside plane records in the cloud's order, followed by the cluster filter's result, which
+ *                          is in the cloud's order too; invalid records are dropped.  Without a cluster filter nothing runs and
+ *                          the map is what it would be with MM3D_PLANES_OFF.
+ * A map that the stage empties is handled like one the outlier filter emptied.  MLS smoothing, normals, keypoints and descriptors
+ * are the existing stages on the new cloud.  mm3d_params does not change.
+ *   The rule, for a cloud of n 16-byte records (no parity with pcl::SACSegmentation is claimed: its random stream and its model
+ *   refinement are not reproduced):
+ *   1. A record is valid when its three coordinates are finite.  Invalid records get the label MM3D_PLANE_INVALID; they are never
+ *      drawn, never counted and never kept.  n_valid counts the valid ones.
+ *   2. The stop threshold is T = max(3, ceil(min_fraction * (double)n_valid)).
+ *   3. Round p = 0 .. max_planes - 1 works on R_p, the valid records that have no plane yet, in the cloud's order, m = |R_p|.
+ *      m < 3 ends the rule.
+ *   4. Word j of draw h of round p is mix((((uint64)seed << 32) | ((uint64)p << 24) | h) + (j + 1) * 0x9E3779B97F4A7C15 mod 2^64),
+ *      mix being splitmix64's finaliser as mm3d_set_alignment states it, and bounded(w, n) = ((w >> 32) * n) >> 32.  Three distinct
+ *      ranks in R_p, by the prerejective alignment's recipe: i0 = bounded(w0, m); i1 = bounded(w1, m - 1), plus one if >= i0;
+ *      i2 = bounded(w2, m - 2), plus one if >= min(i0, i1), then plus one if >= max(i0, i1).  The stream is a function of
+ *      (seed, p, h, m) alone: nothing is drawn from the context's rand() replay, mm3d_srand has no say.
+ *   5. With a, b, c the three records, everything from here on in double, every operation rounded to nearest, nothing contracted:
+ *      u = (double)b - (double)a and v = (double)c - (double)a per coordinate; nrm = u x v, each component u_i * v_j - u_j * v_i;
+ *      len2 = (nx*nx + ny*ny) + nz*nz.  The draw is degenerate unless len2 > 1e-12 * ((u.u) * (v.v)), the dots written
+ *      (x*x + y*y) + z*z: collinear records and duplicates.  With a non-zero axis the draw is off axis unless
+ *      dn * dn >= (c2 * len2) * aa, where dn = (nx*ax + ny*ay) + nz*az, aa = (ax*ax + ay*ay) + az*az and
+ *      c2 = cos(max_angle_deg * pi / 180)^2 from the host's libm cos (the degenerate test comes first).  Degenerate and off-axis
+ *      draws have no count and cannot win; stats.degenerate and stats.off_axis count them over all rounds, stats.draws all draws.
+ *   6. The count of a surviving draw is the number of q in R_p with s * s <= (distance * distance) * len2, where
+ *      s = (nx*dx + ny*dy) + nz*dz and d = (double)q - (double)a per coordinate.  No square root and no division: an integer.
+ *   7. The winner is the highest count, ties to the lower h.  Without a surviving draw, or with the winner's count below T, the
+ *      rule ends and round p finds no plane.  stats.rounds counts the rounds that drew, this last one included.
+ *   8. With refit == 1, over the winner's inliers: N, S = sum q and P = sum q q^T with q = (double)p_i - (double)a, summed in
+ *      double in a fixed order that depends on R_p alone (blocks of 4096 ranks: a lane's sixteen in ascending order, the wave's
+ *      fixed tree, the four waves in order, the blocks in order); mu = S / N, C = P / N - mu mu^T; lambda0 <= lambda1 <= lambda2
+ *      and the unit eigenvector n' of lambda0 by cyclic Jacobi in double.  The refit plane goes through c = (double)a + mu; its
+ *      inliers over R_p are the q with |s'| <= distance, s' = (n'x*dx + n'y*dy) + n'z*dz and d = (double)q - c.  It is adopted iff
+ *      the trace is > 0, lambda1 - lambda0 > 1e-6 * trace, everything is finite, with an axis (n'.axis)^2 >= c2 * aa, and it has
+ *      at least as many inliers as the hypothesis.  Otherwise the hypothesis plane and its inliers stand.
+ *   9. The adopted plane's inliers get the label p.  planes[p] holds the unit normal, d with n.x + d = 0 in world coordinates
+ *      (d = -((nx*ax + ny*ay) + nz*az) through a, or through c after a refit), the inlier count, the winning h and whether the
+ *      refit was adopted.  The hypothesis' normal is nrm / sqrt(len2).  Sign with an axis: n.axis >= 0; without one: nz > 0, or
+ *      nz == 0 and ny > 0, or both zero and nx > 0.
+ *   - Why 1024 draws by default: a plane that holds the share f of the remaining points is missed with probability at most
+ *     (1 - f^3)^samples: below 3e-4 for f = 0.2, not negligible for f = 0.1, where a user raises samples.
+ *   - Why the test is relative to a: the differences of two floats are exact in double, so the rule does not care how far the map
+ *     is from the origin.
+ *   - options.distance == 0 means params.resolution / 2 behind the whole-map calls.
+ *   - The setting reaches the context's mm3d_set_streams helpers in either order of the two calls, and every device of a
+ *     device-list context; only a map's points change, and those travel in the bundles, so device lists and shards carry it.
+ *     Every rank of a sharded call must use the same setting.  replay_method and batch_only stay as they are.  The result is
+ *     bit-identical for every stream count, driver, batch and cache setting, the planes' doubles included.
+ *   - The map cache's map key holds all nine option fields, zeros under MM3D_PLANES_OFF. */
+typedef enum { MM3D_PLANES_OFF = 0, MM3D_PLANES_REMOVE = 1, MM3D_PLANES_SET_ASIDE = 2 } mm3d_plane_method;
+enum { MM3D_PLANE_NONE = -1, MM3D_PLANE_INVALID = -2 };           /* labels that name no plane */
+typedef struct mm3d_plane_options {
+  int method;              /* MM3D_PLANES_* (not read by the stage calls) */
+  int max_planes;          /* 1 .. 8 */
+  int samples;             /* draws per plane, 1 .. 65536 */
+  int refit;               /* 0 or 1 */
+  unsigned seed;           /* any value */
+  double distance;         /* metres, finite, >= 0; 0 = params.resolution / 2 behind the whole-map calls */
+  double min_fraction;     /* of the cloud's valid points, 0 .. 1 */
+  double axis[3];          /* finite; the zero vector = any orientation */
+  double max_angle_deg;    /* 0 .. 90 */
+} mm3d_plane_options;      /* 72 bytes */
+typedef struct mm3d_plane { double normal[3]; double d; long long inliers; int draw; int refit; } mm3d_plane;   /* 48 bytes */
+typedef struct mm3d_plane_stats { long long points, valid, on_planes, kept, draws, degenerate, off_axis; int planes; int rounds; } mm3d_plane_stats;
+void mm3d_plane_options_default(mm3d_plane_options *o);   /* OFF, 1, 1024, 1, 1, 0.0, 0.05, (0, 0, 1), 10.0 */
+/* MM3D_EINVAL: ctx or options NULL, an unknown method, and any value outside its range above (the values are checked whatever
+ * the method).  After a refused call the selection is what it was. */
+int mm3d_set_planes(mm3d_ctx *ctx, const mm3d_plane_options *options);
+int mm3d_get_planes(const mm3d_ctx *ctx, mm3d_plane_options *options);   /* MM3D_EINVAL for NULL */
+/* The plane stage's last run on this context: mm3d_remove_planes, or mm3d_map_features with a method selected (all zero, no plane,
+ * before the first).  mm3d_last_planes copies min(*n, capacity) records; MM3D_EINVAL for NULL or a negative capacity. */
+int mm3d_last_plane_stats(const mm3d_ctx *ctx, mm3d_plane_stats *stats);
+int mm3d_last_planes(const mm3d_ctx *ctx, mm3d_plane *planes, int capacity, int *n);
 /* What smooths a map's points (off the reference's path; MM3D_SMOOTH_OFF by default: nothing runs).  Moving least squares: every
  * point is moved onto the Gaussian-weighted plane fitted to its neighbours within a radius, or onto the quadratic fitted over
  * that plane.  Two places ask it, each behind a bit of `where`:
@@ -697,6 +778,22 @@ void mm3d_debug_outlier_search(long long out[3], int reset);
  *     voxelised -- is processed correctly, and the scan is quadratic in the points of such a cell. */
 int mm3d_cluster_labels(mm3d_ctx *ctx, const mm3d_cloud *points, double tolerance, int *labels, size_t capacity, mm3d_cluster_stats *stats);
 int mm3d_remove_small_clusters(mm3d_ctx *ctx, const mm3d_cloud *in, double tolerance, int method, int min_size, mm3d_cloud **out);
+/* Plane segmentation by RANSAC (not a reference function; mm3d_set_planes states the rule and puts it behind the whole-map
+ * calls).  mm3d_segment_planes is the rule on a caller's cloud, whatever the context's setting: labels receives, in the cloud's
+ * order, the round p of a record's plane, MM3D_PLANE_NONE or MM3D_PLANE_INVALID; planes the *n_planes records found; stats (may
+ * be NULL) the counts.  mm3d_remove_planes returns the records labelled MM3D_PLANE_NONE, in the cloud's order, colour included,
+ * and leaves its counts and planes for mm3d_last_plane_stats and mm3d_last_planes; the result keeps the input's voxel lattice and
+ * carries the kept points' bounding box, as mm3d_remove_outliers' does.  options.method is not read.  One host wait each: every
+ * round is enqueued, a round that finds no plane raises a flag on the device at which the later rounds' kernels return, and
+ * nothing comes back before the end, whatever samples and max_planes are.
+ *   - MM3D_EINVAL: a NULL argument (stats excepted); an option outside its range; distance not > 0; capacity below
+ *     mm3d_cloud_size(points); a cloud of 2^31 points or more.  `planes` must have room for options.max_planes records.  An
+ *     empty cloud gives MM3D_OK, no plane and an empty result.
+ *   - samples x m point-to-plane tests per round, in double as the rule states them: a block keeps its points in registers and
+ *     walks the hypotheses, the lanes' votes folded by ballot into integer counts, so no order can move them. */
+int mm3d_segment_planes(mm3d_ctx *ctx, const mm3d_cloud *points, const mm3d_plane_options *options, int *labels, size_t capacity,
+                        mm3d_plane *planes, int *n_planes, mm3d_plane_stats *stats);
+int mm3d_remove_planes(mm3d_ctx *ctx, const mm3d_cloud *in, const mm3d_plane_options *options, mm3d_cloud **out);
 /* Moving-least-squares smoothing (not a reference function; mm3d_set_smoothing states the rule and puts it behind the whole-map
  * calls).  mm3d_smooth_displacements is steps 1 - 5 alone, in the cloud's order: disp receives 3 n doubles, zero where the point
  * stays; state (may be NULL) the n states MM3D_SMOOTH_INVALID .. MM3D_SMOOTH_POLYNOMIAL; neighbours (may be NULL) the n count_i,

@@ -160,6 +160,54 @@ class ClusterStats(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class PlaneMethod(enum.IntEnum):    # mm3d_plane_method (not a reference enum)
+    OFF = 0
+    REMOVE = 1
+    SET_ASIDE = 2
+
+
+PLANE_NONE, PLANE_INVALID = -1, -2      # MM3D_PLANE_NONE, MM3D_PLANE_INVALID: labels that name no plane
+
+
+class PlaneOptions(C.Structure):
+    """mm3d_plane_options (mm3d_set_planes); the defaults are mm3d_plane_options_default's."""
+    _fields_ = [("method", C.c_int), ("max_planes", C.c_int), ("samples", C.c_int), ("refit", C.c_int), ("seed", C.c_uint),
+                ("distance", C.c_double), ("min_fraction", C.c_double), ("axis", C.c_double * 3), ("max_angle_deg", C.c_double)]
+
+    def __init__(self, **kw):
+        super().__init__()
+        lib().mm3d_plane_options_default(C.byref(self))
+        kinds = dict(self._fields_)
+        for k, v in kw.items():
+            if k not in kinds:
+                raise TypeError("unknown plane option " + k)
+            if k == "axis":
+                self.axis = (C.c_double * 3)(*[float(x) for x in v])
+            else:
+                setattr(self, k, float(v) if kinds[k] is C.c_double else int(v))
+
+    def as_tuple(self):
+        return (int(self.method), int(self.max_planes), int(self.samples), int(self.refit), int(self.seed), float(self.distance),
+                float(self.min_fraction), tuple(float(x) for x in self.axis), float(self.max_angle_deg))
+
+
+class Plane(C.Structure):
+    """mm3d_plane: normal . x + d = 0, the inliers, the winning draw, whether the refit was adopted"""
+    _fields_ = [("normal", C.c_double * 3), ("d", C.c_double), ("inliers", C.c_longlong), ("draw", C.c_int), ("refit", C.c_int)]
+
+    def as_dict(self):
+        return dict(normal=tuple(float(x) for x in self.normal), d=float(self.d), inliers=int(self.inliers), draw=int(self.draw), refit=int(self.refit))
+
+
+class PlaneStats(C.Structure):
+    """mm3d_plane_stats"""
+    _fields_ = [("points", C.c_longlong), ("valid", C.c_longlong), ("on_planes", C.c_longlong), ("kept", C.c_longlong),
+                ("draws", C.c_longlong), ("degenerate", C.c_longlong), ("off_axis", C.c_longlong), ("planes", C.c_int), ("rounds", C.c_int)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 class SmoothMethod(enum.IntEnum):   # mm3d_smooth_method (not a reference enum)
     OFF = 0
     MLS = 1
@@ -737,6 +785,33 @@ class Context:
         self._ck(lib().mm3d_last_cluster_stats(self._h, C.byref(st)))
         return st.as_dict()
 
+    def setPlanes(self, options=None, **kw):
+        """mm3d_set_planes: what takes the dominant planes out of a filtered map behind the whole-map calls, before the cluster
+        filter.  A PlaneOptions, or its fields as keywords (method=PlaneMethod.REMOVE or SET_ASIDE, max_planes 1 .. 8, samples,
+        refit, seed, distance=... in metres; 0 = half of params.resolution, min_fraction, axis=(x, y, z), max_angle_deg)."""
+        o = options if options is not None else PlaneOptions(**kw)
+        self._ck(lib().mm3d_set_planes(self._h, C.byref(o)))
+
+    def getPlanes(self) -> "PlaneOptions":
+        o = PlaneOptions()
+        self._ck(lib().mm3d_get_planes(self._h, C.byref(o)))
+        return o
+
+    @property
+    def last_plane_stats(self) -> dict:
+        """mm3d_last_plane_stats: the plane stage's last run on this context."""
+        st = PlaneStats()
+        self._ck(lib().mm3d_last_plane_stats(self._h, C.byref(st)))
+        return st.as_dict()
+
+    @property
+    def last_planes(self) -> list:
+        """mm3d_last_planes: the planes of the plane stage's last run on this context, as dicts."""
+        arr = (Plane * 8)()
+        n = C.c_int(0)
+        self._ck(lib().mm3d_last_planes(self._h, arr, 8, C.byref(n)))
+        return [arr[i].as_dict() for i in range(min(n.value, 8))]
+
     def setSmoothing(self, options=None, **kw):
         """mm3d_set_smoothing: moving-least-squares smoothing of a map's filtered points before its normals (where & MAPS) and of
         the composed map between two voxel passes (where & COMPOSED).  A SmoothOptions, or its fields as keywords
@@ -951,6 +1026,26 @@ class Context:
         cluster (LARGEST), in the cloud's order."""
         h = C.c_void_p()
         self._ck(lib().mm3d_remove_small_clusters(self._h, cloud._h, C.c_double(tolerance), int(method), int(min_size), C.byref(h)))
+        return Cloud(self, h)
+
+    def segmentPlanes(self, points: "Cloud", options=None, **kw):
+        """mm3d_segment_planes: (labels int32[n] in the cloud's order -- the round of a record's plane, PLANE_NONE or
+        PLANE_INVALID --, the planes as dicts, the counts as a dict).  A PlaneOptions, or its fields as keywords; the method is
+        not read."""
+        o = options if options is not None else PlaneOptions(**kw)
+        out = np.empty(len(points), dtype=np.int32)
+        arr = (Plane * 8)()
+        n = C.c_int(0)
+        st = PlaneStats()
+        self._ck(lib().mm3d_segment_planes(self._h, points._h, C.byref(o), out.ctypes.data_as(C.c_void_p), C.c_size_t(len(out)), arr,
+                                           C.byref(n), C.byref(st)))
+        return out, [arr[i].as_dict() for i in range(n.value)], st.as_dict()
+
+    def removePlanes(self, cloud: "Cloud", options=None, **kw) -> "Cloud":
+        """mm3d_remove_planes: the records that lie on none of the planes found, in the cloud's order."""
+        o = options if options is not None else PlaneOptions(**kw)
+        h = C.c_void_p()
+        self._ck(lib().mm3d_remove_planes(self._h, cloud._h, C.byref(o), C.byref(h)))
         return Cloud(self, h)
 
     def smoothDisplacements(self, points: "Cloud", radius: float, order: int = 2, min_neighbours: int = 6):

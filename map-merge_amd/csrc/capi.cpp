@@ -43,6 +43,7 @@ mm3d::StageSelection::StageSelection()
   mm3d_outlier_options_default(&outlier_options);
   mm3d_cluster_options_default(&cluster_options);
   mm3d_smooth_options_default(&smooth_options);
+  mm3d_plane_options_default(&plane_options);
 }
 
 void mm3d::select_stages(mm3d_ctx *ctx, bool peers_follow, const std::function<void(StageSelection &)> &edit)
@@ -216,6 +217,10 @@ void mm3d_outlier_options_default(mm3d_outlier_options *o)
 void mm3d_cluster_options_default(mm3d_cluster_options *o)
 {
   if (o) *o = mm3d_cluster_options{MM3D_CLUSTERS_OFF, 100, 0.0};
+}
+void mm3d_plane_options_default(mm3d_plane_options *o)
+{
+  if (o) *o = mm3d_plane_options{MM3D_PLANES_OFF, 1, 1024, 1, 1u, 0.0, 0.05, {0.0, 0.0, 1.0}, 10.0};
 }
 void mm3d_smooth_options_default(mm3d_smooth_options *o)
 {

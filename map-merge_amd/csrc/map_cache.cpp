@@ -55,6 +55,13 @@ std::string feature_key(const mm3d_params *p, const StageSelection &sel)
   const mm3d_smooth_options &sm = sel.smooth_options;
   const bool mls = sm.method == MM3D_SMOOTH_MLS && (sm.where & MM3D_SMOOTH_MAPS);
   k.i32(mls ? sm.method : 0).i32(mls ? sm.order : 0).i32(mls ? sm.min_neighbours : 0).f64(mls ? sm.radius : 0.0);
+  // what takes the planes out of the filtered cloud (mm3d_set_planes): all nine fields, zeros while it is off
+  const mm3d_plane_options &pl = sel.plane_options;
+  const bool pon = pl.method != MM3D_PLANES_OFF;
+  k.i32(pon ? pl.method : 0).i32(pon ? pl.max_planes : 0).i32(pon ? pl.samples : 0).i32(pon ? pl.refit : 0).i32(pon ? (int)pl.seed : 0);
+  k.f64(pon ? pl.distance : 0.0).f64(pon ? pl.min_fraction : 0.0);
+  for (int a = 0; a < 3; ++a) k.f64(pon ? pl.axis[a] : 0.0);
+  k.f64(pon ? pl.max_angle_deg : 0.0);
   return k.s;
 }
 

@@ -48,8 +48,15 @@ std::unique_ptr<mm3d_map> mm3d::map_features_impl(mm3d_ctx *ctx, const mm3d_clou
   std::unique_ptr<mm3d_cloud> filt(ctx->sel.outliers ? ctx->sel.outliers->filter(ctx, down.get(), ctx->sel.outlier_options, &ctx->last_outlier_stats)
                                                      : remove_outliers(ctx, down.get(), p->descriptor_radius, p->outliers_min_neighbours));
   down.reset();
+  // (mm3d_set_planes: the dominant planes leave, or are set aside while the cluster filter looks at the rest; the stage calls the
+  // cluster filter itself, so that what stands on a floor is a cluster of its own when the filter sees it)
+  if (ctx->sel.planes) {
+    mm3d_cloud *res = ctx->sel.planes->filter(ctx, filt.get(), ctx->sel.plane_options, p->resolution, ctx->sel.clusters, ctx->sel.cluster_options,
+                                              &ctx->last_plane_stats, ctx->last_planes, &ctx->last_cluster_stats);
+    if (res != filt.get()) filt.reset(res);
+  }
   // (mm3d_set_cluster_filter: the connected components too small to be structure leave before anything looks at the cloud)
-  if (ctx->sel.clusters) filt.reset(ctx->sel.clusters->filter(ctx, filt.get(), ctx->sel.cluster_options, p->resolution, &ctx->last_cluster_stats));
+  else if (ctx->sel.clusters) filt.reset(ctx->sel.clusters->filter(ctx, filt.get(), ctx->sel.cluster_options, p->resolution, &ctx->last_cluster_stats));
   // (mm3d_set_smoothing with MM3D_SMOOTH_MAPS: after the filters -- a stray blob would pull the surface towards itself -- and
   // before everything that reads the points; the new cloud's voxel_leaf is 0)
   if (ctx->sel.smoother && (ctx->sel.smooth_options.where & MM3D_SMOOTH_MAPS))

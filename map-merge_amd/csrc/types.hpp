@@ -24,10 +24,11 @@ struct IcpSamplerBase;
 struct OutlierFilterBase;
 struct ClusterFilterBase;
 struct SmootherBase;
+struct PlaneFilterBase;
 
 // The opt-in stages of a context's pipeline (mm3d_set_icp_method, mm3d_set_alignment, mm3d_set_keypoints, mm3d_set_refinement,
 // mm3d_set_coarse_alignment, mm3d_set_confidence, mm3d_set_icp_rejection, mm3d_set_icp_color, mm3d_set_icp_generalized,
-// mm3d_set_estimator, mm3d_set_icp_sampling, mm3d_set_outlier_filter, mm3d_set_cluster_filter, mm3d_set_smoothing): a null method = the reference's stage.  The methods are process-wide
+// mm3d_set_estimator, mm3d_set_icp_sampling, mm3d_set_outlier_filter, mm3d_set_cluster_filter, mm3d_set_smoothing, mm3d_set_planes): a null method = the reference's stage.  The methods are process-wide
 // objects of their kernel files that hold no state and are not owned.  Every context has its own copy of the record; only
 // select_stages (drivers.hpp) changes one, and it and mm3d_set_streams hand the root's copy to the helpers.
 struct StageSelection {
@@ -44,6 +45,7 @@ struct StageSelection {
   const OutlierFilterBase *outliers = nullptr;         // what filters a down-sampled map in removeOutliers' place
   const ClusterFilterBase *clusters = nullptr;         // what drops the small connected components of the filtered map
   const SmootherBase *smoother = nullptr;              // what smooths a filtered map before its normals, and the composed map
+  const PlaneFilterBase *planes = nullptr;             // what takes the dominant planes out of the filtered map, before the cluster filter
   mm3d_alignment_options align_options;
   mm3d_keypoint_options keypoint_options;
   mm3d_refine_options refine_options;
@@ -57,7 +59,8 @@ struct StageSelection {
   mm3d_outlier_options outlier_options;                // `outliers` is non-null exactly while their method is STATISTICAL
   mm3d_cluster_options cluster_options;                // `clusters` is non-null exactly while their method is not OFF
   mm3d_smooth_options smooth_options;                  // `smoother` is non-null exactly while their method is MLS; `where` says which places ask it
-  StageSelection();                                    // capi.cpp: the options are the thirteen mm3d_*_options_default's
+  mm3d_plane_options plane_options;                    // `planes` is non-null exactly while their method is not OFF
+  StageSelection();                                    // capi.cpp: the options are the fourteen mm3d_*_options_default's
   // the ICP of the pair stage rejects correspondences (mm3d_set_icp_rejection)
   bool rejecting() const { return reject_options.one_to_one || reject_options.distance != MM3D_REJECT_NONE; }
   int icp_method() const;                              // MM3D_ICP_*
@@ -110,6 +113,8 @@ struct mm3d_ctx : mm3d::Context {
   mm3d_outlier_stats last_outlier_stats{0, 0, 0, 0, 0.0, 0.0, 0.0};      // (mm3d_last_outlier_stats)
   mm3d_cluster_stats last_cluster_stats{0, 0, 0, 0, 0, 0};               // (mm3d_last_cluster_stats)
   mm3d_smooth_stats last_smooth_stats{0, 0, 0, 0, 0, 0, 0.0};            // (mm3d_last_smooth_stats)
+  mm3d_plane_stats last_plane_stats{0, 0, 0, 0, 0, 0, 0, 0, 0};          // (mm3d_last_plane_stats)
+  mm3d_plane last_planes[8] = {};                                        // (mm3d_last_planes: the first last_plane_stats.planes of them)
   // mm3d_set_streams: helper contexts (one HIP stream + one host thread each while a call is running)
   // that mm3d_estimate_maps_transforms deals maps and pairs to; owned by this context
   std::vector<mm3d_ctx *> helpers;
@@ -551,6 +556,21 @@ struct SmootherBase {
   // the records of `in` in its order, every valid one moved by the rule, a new cloud complete on c's stream (one wait: the
   // counts) whose voxel_leaf is 0; o.radius == 0 stands for 3 * resolution; stats (may be null) receives the counts
   virtual mm3d_cloud *smooth(Context *c, const mm3d_cloud *in, const mm3d_smooth_options &o, double resolution, mm3d_smooth_stats *stats) const = 0;
+};
+// What takes the dominant planes out of a map's filtered cloud behind the whole-map calls (mm3d_set_planes; the one concrete class
+// is planes_ransac.hip's).  Like ClusterFilterBase, pair_estimate.cpp only sees this interface, so the host code links without
+// the new kernels (tests/host_san); a null pointer on the context means that no such step runs.  The cluster filter comes with
+// the call, since MM3D_PLANES_SET_ASIDE composes the two: the composition stays inside the kernel file.
+struct PlaneFilterBase {
+  virtual ~PlaneFilterBase() = default;
+  // The map's cloud after the plane stage AND the cluster filter (`clusters` may be null: none selected), complete on c's stream.
+  // REMOVE: the records without a plane, then the cluster filter on them.  SET_ASIDE: the plane records in the cloud's order, then
+  // the cluster filter's result on the rest; without a cluster filter nothing runs and `in` is returned as a plain copy of the
+  // pointer (the caller keeps its cloud).  o.distance == 0 stands for resolution / 2.  stats and planes (8 records) receive the
+  // plane stage's counts and planes, cluster_stats (may be null) the cluster filter's.
+  virtual mm3d_cloud *filter(Context *c, mm3d_cloud *in, const mm3d_plane_options &o, double resolution, const ClusterFilterBase *clusters,
+                             const mm3d_cluster_options &cluster_options, mm3d_plane_stats *stats, mm3d_plane *planes,
+                             mm3d_cluster_stats *cluster_stats) const = 0;
 };
 struct PairCounts { int n_correspondences = 0, n_inliers = 0, icp_correspondences = 0; };
 // ICP (optional) from a guess on the device (guess_dev != null) or on the host, then transformScore
