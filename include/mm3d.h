@@ -188,6 +188,18 @@ int mm3d_debug_sift_dog_marked(mm3d_ctx *ctx, const mm3d_cloud *points, double m
  * removeOutliers' subset of it, R/src/features.cpp:19-40; every centroid within two leaves of a member of its voxel), 0 when
  * nothing is known -- what lets a grid build on the cloud skip its "did a cell outgrow the counting sort" wait */
 float mm3d_debug_cloud_voxel_leaf(const mm3d_cloud *cloud);
+/* test hook, process-wide like mm3d_debug_icp_rejection_split: the neighbour capacity the FIRST launch of the four kernels
+ * that keep a neighbour list in LDS is given -- PFH / PFHRGB, SHOT, SC3D (1024 each) and the Harris corner refinement (2048).
+ * A keypoint with more neighbours goes to the second launch of the same kernel with its list in global scratch; the LDS
+ * arrays keep their size and the scratch pass is sized as always.  0 = the compile-time capacities; otherwise a power of two
+ * from 64 to 2048, and a kernel whose own capacity is smaller keeps its own.  Anything else changes nothing.  Returns the
+ * PREVIOUS value. */
+int mm3d_debug_feature_lds_cap(int cap);
+/* test hook: process-wide counters of that second launch since the last reset, two per kernel family in the order PFH / PFHRGB,
+ * SHOT, SC3D, Harris refinement: out[2 f] the rows handed to the scratch pass, out[2 f + 1] the largest scratch capacity per
+ * row chosen (PFH: the largest neighbour count; SHOT, SC3D: the power of two from 1024 that holds it; Harris: the power of two
+ * from 2048 that holds twice it).  Both are values the host downloads anyway: counting adds no launch and no wait. */
+void mm3d_debug_feature_overflow(long long out[8], int reset);
 /* test / study hook of SAC-IA's certified pick (csrc/registration.hip::k_sacia_select; R/src/matching.cpp:142-194 ->
  * SampleConsensusInitialAlignment keeps the hypothesis of the lowest error sum): process-wide counters since the last reset --
  * out[0] pairs scored, [1] pairs whose winner the sums in double decided (no float chain was run), [2] candidate hypotheses

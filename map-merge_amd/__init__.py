@@ -600,6 +600,21 @@ def icp_rejection_split(split=-1):
     return int(lib().mm3d_debug_icp_rejection_split(int(split)))
 
 
+def feature_lds_cap(cap):
+    """mm3d_debug_feature_lds_cap: the neighbour capacity the first launch of PFH / PFHRGB, SHOT, SC3D and the Harris refinement
+    is given (a power of two from 64 to 2048; 0: the compile-time capacities again); larger neighbourhoods take the scratch pass.
+    Returns the previous value; anything else changes nothing."""
+    return int(lib().mm3d_debug_feature_lds_cap(int(cap)))
+
+
+def feature_overflow(reset=False):
+    """Process-wide counters of the scratch passes (mm3d_debug_feature_overflow): (rows sent to scratch, largest capacity per row
+    chosen) for PFH / PFHRGB, SHOT, SC3D and the Harris refinement, in that order."""
+    out = (C.c_longlong * 8)()
+    lib().mm3d_debug_feature_overflow(out, 1 if reset else 0)
+    return list(out)
+
+
 def icp_color_split(split=-1):
     """mm3d_debug_icp_color_split: force every coloured ICP launch to one work item per wave (1) or per block (4); 0: chosen by
     size again; negative: leave as it is.  Returns the value in force."""

@@ -387,7 +387,7 @@ mm3d_cloud *detect_keypoints_harris(Context *c, const mm3d_cloud *points, const 
   MM3D_HIP(hipMemsetAsync(overflow.get(), 0, ((size_t)nc + 3) * sizeof(int), c->stream));
   MM3D_LAUNCH(c, "harris_refine", nc * 10.0 * 120.0 * 40.0, k_harris_refine, dim3(nc), dim3(64), 0, corners.get(), nc, g.view(),
               (const float4 *)points->pts.get(), (const float4 *)normals->nrm.get(), (float)sr, r2, (const int *)nullptr,
-              (unsigned long long *)nullptr, kHarrisCap, overflow.get());
+              (unsigned long long *)nullptr, feature_lds_cap(kHarrisCap), overflow.get());
   MM3D_HIP(hipMemcpyAsync(h, overflow.get(), sizeof(int), hipMemcpyDeviceToHost, c->stream));
   MM3D_HIP(hipMemcpyAsync(h + 1, overflow.get() + nc + 1, sizeof(int), hipMemcpyDeviceToHost, c->stream));
   c->sync();
@@ -399,6 +399,7 @@ mm3d_cloud *detect_keypoints_harris(Context *c, const mm3d_cloud *points, const 
     while (cap < 2 * h[1]) cap <<= 1;
     if ((double)n_over * cap * 8.0 > 8e9) throw Error(MM3D_EUNSUPPORTED, "HARRIS: neighbourhoods too large for the refinement (reduce normal_radius)");
     DevBuf<unsigned long long> scratch(c, (size_t)n_over * cap);
+    feature_overflow_note(3, n_over, cap);
     MM3D_LAUNCH(c, "harris_emit", n_over * 32.0, k_harris_restore, dim3(div_up(n_over, 64)), dim3(64), 0, (const float4 *)points->pts.get(),
                 (const int *)kept.get(), (const int *)(overflow.get() + 1), n_over, corners.get());
     MM3D_LAUNCH(c, "harris_refine", n_over * 10.0 * cap * 40.0, k_harris_refine, dim3(n_over), dim3(64), 0, corners.get(), nc, g.view(),

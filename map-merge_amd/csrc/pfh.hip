@@ -16,6 +16,8 @@
 // reproduced from the (distance, index) keys.
 // Algorithmic work: m (m-1) / 2 pair features per keypoint (~300 VALU instructions each); bytes: 32 B
 // per gathered neighbour + 500 B per descriptor.
+#include <atomic>
+
 #include "device_util.hpp"
 
 namespace mm3d {
@@ -266,7 +268,7 @@ static mm3d_desc *compute_pfh_impl(Context *c, const mm3d_cloud *points, const m
   MM3D_HIP(hipMemsetAsync(overflow.get(), 0, ((size_t)nk + 2) * sizeof(int), c->stream));
   MM3D_LAUNCH(c, "pfh", nk * (200.0 * 32.0 + kDim * 4.0), (k_pfh<kRgb>), dim3(nk), dim3(256), 0, (const float4 *)keypoints->pts.get(), nk,
               g.view(), (const float4 *)normals->nrm.get(), (const float4 *)points->pts.get(), (float)radius, r2, (const int *)nullptr,
-              (PfhNb *)nullptr, kPfhCap, raw.get(), valid.get(), overflow.get());
+              (PfhNb *)nullptr, feature_lds_cap(kPfhCap), raw.get(), valid.get(), overflow.get());
   int *h = (int *)c->pin(64);
   MM3D_HIP(hipMemcpyAsync(h, overflow.get(), sizeof(int), hipMemcpyDeviceToHost, c->stream));
   MM3D_HIP(hipMemcpyAsync(h + 1, overflow.get() + nk + 1, sizeof(int), hipMemcpyDeviceToHost, c->stream));
@@ -277,6 +279,7 @@ static mm3d_desc *compute_pfh_impl(Context *c, const mm3d_cloud *points, const m
     const double bytes = (double)n_over * max_m * sizeof(PfhNb);
     if (bytes > 8e9) throw Error(MM3D_EUNSUPPORTED, "PFH: neighbourhoods too large for the scratch pass (reduce descriptor_radius)");
     DevBuf<PfhNb> scratch(c, (size_t)n_over * max_m);
+    feature_overflow_note(0, n_over, max_m);
     MM3D_LAUNCH(c, "pfh", n_over * (max_m * 32.0 + kDim * 4.0), (k_pfh<kRgb>), dim3(n_over), dim3(256), 0,
                 (const float4 *)keypoints->pts.get(), nk, g.view(), (const float4 *)normals->nrm.get(), (const float4 *)points->pts.get(),
                 (float)radius, r2, (const int *)(overflow.get() + 1), scratch.get(), max_m, raw.get(), valid.get(), overflow.get());
@@ -341,4 +344,40 @@ mm3d_desc *compute_pfhrgb(Context *c, const mm3d_cloud *points, const mm3d_norma
   return compute_pfh_impl<true>(c, points, normals, keypoints, radius);
 }
 
+// test hooks shared with shot.hip, sc3d.hip and harris.hip (types.hpp)
+static std::atomic<int> g_feature_lds_cap{0};          // mm3d_debug_feature_lds_cap: 0 (the compile-time capacities) or 64 .. 2048
+static std::atomic<long long> g_feature_overflow[8];   // mm3d_debug_feature_overflow: per family, rows and the largest capacity
+
+int feature_lds_cap(int compiled)
+{
+  const int forced = g_feature_lds_cap.load();
+  return forced > 0 && forced < compiled ? forced : compiled;
+}
+
+void feature_overflow_note(int family, int rows, int cap)
+{
+  g_feature_overflow[2 * family] += rows;
+  long long seen = g_feature_overflow[2 * family + 1].load();
+  while (seen < cap && !g_feature_overflow[2 * family + 1].compare_exchange_weak(seen, cap)) {}
+}
+
 }  // namespace mm3d
+
+extern "C" {
+
+int mm3d_debug_feature_lds_cap(int cap)
+{
+  const int before = mm3d::g_feature_lds_cap.load();
+  if (cap == 0 || (cap >= 64 && cap <= 2048 && (cap & (cap - 1)) == 0)) mm3d::g_feature_lds_cap.store(cap);
+  return before;
+}
+
+void mm3d_debug_feature_overflow(long long out[8], int reset)
+{
+  for (int i = 0; i < 8; ++i) {
+    if (out) out[i] = mm3d::g_feature_overflow[i].load();
+    if (reset) mm3d::g_feature_overflow[i] = 0;
+  }
+}
+
+}  // extern "C"

@@ -284,8 +284,8 @@ mm3d_desc *compute_sc3d(Context *c, const mm3d_cloud *points, const mm3d_normals
   MM3D_HIP(hipMemsetAsync(overflow.get(), 0, ((size_t)nk + 2) * sizeof(int), c->stream));
   MM3D_LAUNCH(c, "sc3d", nk * (200.0 * 36.0 + 7920.0), k_sc3d, dim3(nk), dim3(64), 0, (const float4 *)keypoints->pts.get(), nk, g.view(),
               (const float4 *)points->pts.get(), (const float4 *)normals->nrm.get(), (const int *)density.get(), (const float *)tab.get(),
-              (const float *)rnd.get(), (const int *)rpos.get(), (float)radius, r2, (const int *)nullptr, (unsigned long long *)nullptr, kScCap,
-              raw.get(), valid.get(), overflow.get());
+              (const float *)rnd.get(), (const int *)rpos.get(), (float)radius, r2, (const int *)nullptr, (unsigned long long *)nullptr,
+              feature_lds_cap(kScCap), raw.get(), valid.get(), overflow.get());
   int *h = (int *)c->pin(64);
   MM3D_HIP(hipMemcpyAsync(h, overflow.get(), sizeof(int), hipMemcpyDeviceToHost, c->stream));
   MM3D_HIP(hipMemcpyAsync(h + 1, overflow.get() + nk + 1, sizeof(int), hipMemcpyDeviceToHost, c->stream));
@@ -296,6 +296,7 @@ mm3d_desc *compute_sc3d(Context *c, const mm3d_cloud *points, const mm3d_normals
     while (cap < h[1]) cap <<= 1;
     if ((double)n_over * cap * 8.0 > 8e9) throw Error(MM3D_EUNSUPPORTED, "SC3D: neighbourhoods too large for the scratch pass (reduce descriptor_radius)");
     DevBuf<unsigned long long> scratch(c, (size_t)n_over * cap);
+    feature_overflow_note(2, n_over, cap);
     MM3D_LAUNCH(c, "sc3d", n_over * (cap * 36.0 + 7920.0), k_sc3d, dim3(n_over), dim3(64), 0, (const float4 *)keypoints->pts.get(), nk, g.view(),
                 (const float4 *)points->pts.get(), (const float4 *)normals->nrm.get(), (const int *)density.get(), (const float *)tab.get(),
                 (const float *)rnd.get(), (const int *)rpos.get(), (float)radius, r2, (const int *)(overflow.get() + 1), scratch.get(), cap,

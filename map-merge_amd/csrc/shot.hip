@@ -454,7 +454,8 @@ mm3d_desc *compute_shot(Context *c, const mm3d_cloud *points, const mm3d_normals
   MM3D_HIP(hipMemsetAsync(overflow.get(), 0, ((size_t)nk + 2) * sizeof(int), c->stream));
   MM3D_LAUNCH(c, "shot", nk * (200.0 * 48.0 * 3.0 + 5412.0), k_shot, dim3(nk), dim3(64), 0, (const float4 *)keypoints->pts.get(), nk, g.view(),
               (const float4 *)points->pts.get(), (const float4 *)normals->nrm.get(), (const float4 *)lab.get(), (const float *)lut.get(),
-              (float)radius, radius, r2, (const int *)nullptr, (unsigned long long *)nullptr, kShotCap, raw.get(), rf.get(), valid.get(),
+              (float)radius, radius, r2, (const int *)nullptr, (unsigned long long *)nullptr, feature_lds_cap(kShotCap), raw.get(), rf.get(),
+              valid.get(),
               overflow.get());
   int *h = (int *)c->pin(64);
   MM3D_HIP(hipMemcpyAsync(h, overflow.get(), sizeof(int), hipMemcpyDeviceToHost, c->stream));
@@ -467,6 +468,7 @@ mm3d_desc *compute_shot(Context *c, const mm3d_cloud *points, const mm3d_normals
     const double bytes = (double)n_over * cap * sizeof(unsigned long long);
     if (bytes > 8e9) throw Error(MM3D_EUNSUPPORTED, "SHOT: neighbourhoods too large for the scratch pass (reduce descriptor_radius)");
     DevBuf<unsigned long long> scratch(c, (size_t)n_over * cap);
+    feature_overflow_note(1, n_over, cap);
     MM3D_LAUNCH(c, "shot", n_over * (cap * 48.0 * 3.0 + 5412.0), k_shot, dim3(n_over), dim3(64), 0, (const float4 *)keypoints->pts.get(), nk,
                 g.view(), (const float4 *)points->pts.get(), (const float4 *)normals->nrm.get(), (const float4 *)lab.get(),
                 (const float *)lut.get(), (float)radius, radius, r2, (const int *)(overflow.get() + 1), scratch.get(), cap, raw.get(),

@@ -381,6 +381,11 @@ mm3d_desc *compute_pfh(Context *c, const mm3d_cloud *points, const mm3d_normals 
 mm3d_desc *compute_pfhrgb(Context *c, const mm3d_cloud *points, const mm3d_normals *normals,
                           mm3d_cloud *keypoints, double radius);
 
+// test hooks of the four kernels that keep a neighbour list in LDS (pfh.hip holds the state; mm3d_debug_feature_lds_cap,
+// mm3d_debug_feature_overflow).  family: 0 PFH / PFHRGB, 1 SHOT, 2 SC3D, 3 the Harris refinement.
+int feature_lds_cap(int compiled);                          // the capacity the first launch is given
+void feature_overflow_note(int family, int rows, int cap);  // a scratch pass of `rows` rows with `cap` entries each
+
 void debug_libm(Context *c, int fn, const float *x_host, const float *y_host, int n, float *out_host);
 void debug_float_chain(Context *c, const float *incr_host, const unsigned *hits_host, int n, float *out_host);
 // sift.hip, test hooks of the certified SIFT decision (sift_cert.hpp): the unsorted scale space of ONE octave -- val* and the
