@@ -231,6 +231,20 @@ typedef struct mm3d_nn_search_info {
 } mm3d_nn_search_info;
 int mm3d_debug_nn_search(mm3d_ctx *ctx, const mm3d_cloud *source, const mm3d_cloud *target, const float T[16], double range,
                          int convention, int split, int *idx, float *d2, mm3d_nn_search_info *info);
+/* test hook: the Hilbert order and the wave work items of a cloud as every neighbourhood stage uses them (csrc/grid.hip:
+ * cloud_hilbert).  The cell is max(0.25, min_cell, largest box side / 1023); the finite points are sorted, stably, by (Hilbert
+ * index of their x, y column << 10 | z cell); a work item starts at the first point, at every change of the 8 x 8 column block
+ * (key >> 16) and at every 64th point.  order[cloud size]: the original index of the j-th sorted point, -1 behind the finite
+ * points.  items[items_cap][2]: {first sorted point, count <= 64} per item; *n_items of them (an error if more than items_cap:
+ * cloud size / 64 + 16386 always suffices).  The cloud must not have been used by a stage yet: the order is cached on it. */
+int mm3d_debug_hilbert_order(mm3d_ctx *ctx, const mm3d_cloud *cloud, float min_cell, int *order, int *items, size_t items_cap, int *n_items);
+/* test hook: the counting sort behind the voxel filter (csrc/grid.hip) on n > 0 host keys, each below key_range <= 2^32 - 1 or
+ * 0xFFFFFFFF (a point in no voxel: it stays out of the result; not allowed with no_invalid_keys != 0, the caller's promise
+ * that there is none).  keys_out / idx_out [n]: the valid keys in ascending order, ties by ascending index, and their indices;
+ * entries behind them read 0xFFFFFFFF.  A bin (key / ceil(key_range / 2^22)) that holds more than 1024 keys sets *too_long,
+ * and nothing is sorted: both arrays read 0xFFFFFFFF throughout. */
+int mm3d_debug_counting_sort(mm3d_ctx *ctx, const uint32_t *keys, size_t n, uint64_t key_range, int no_invalid_keys, uint32_t *keys_out,
+                             uint32_t *idx_out, int *too_long);
 /* SAC-IA draws from libc rand() in the reference (process-global, glibc seed 1).  The context
  * carries its own replay of that generator; mm3d_srand re-seeds it (srand semantics). */
 void mm3d_srand(mm3d_ctx *ctx, unsigned seed);

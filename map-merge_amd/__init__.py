@@ -1454,6 +1454,30 @@ class Context:
                                             d2.ctypes.data_as(C.c_void_p), C.byref(info)))
         return idx[:n], d2[:n], info.as_dict()
 
+    def debugHilbertOrder(self, points, min_cell=0.25):
+        """mm3d_debug_hilbert_order: the Hilbert order and the wave work items of a fresh cloud.  Returns (order int32[finite
+        points]: original index of every sorted point, items int32[m][2]: first sorted point and count per item)."""
+        n = len(points)
+        cap = n // 64 + 16386
+        order = np.full(max(n, 1), -1, dtype=np.int32)
+        items = np.zeros((cap, 2), dtype=np.int32)
+        m = C.c_int(0)
+        self._ck(lib().mm3d_debug_hilbert_order(self._h, points._h, C.c_float(min_cell), order.ctypes.data_as(C.c_void_p),
+                                                items.ctypes.data_as(C.c_void_p), C.c_size_t(cap), C.byref(m)))
+        order = order[:n]
+        return order[order >= 0], items[:m.value]
+
+    def debugCountingSort(self, keys, key_range, no_invalid_keys=False):
+        """mm3d_debug_counting_sort: the voxel filter's counting sort on host keys.  Returns (keys_out uint32[n], idx_out
+        uint32[n], too_long bool); entries behind the valid keys, and everything when too_long, read 0xFFFFFFFF."""
+        k = np.ascontiguousarray(keys, dtype=np.uint32)
+        ko, io = np.zeros(len(k), dtype=np.uint32), np.zeros(len(k), dtype=np.uint32)
+        tl = C.c_int(0)
+        self._ck(lib().mm3d_debug_counting_sort(self._h, k.ctypes.data_as(C.c_void_p), C.c_size_t(len(k)), C.c_uint64(int(key_range)),
+                                                int(bool(no_invalid_keys)), ko.ctypes.data_as(C.c_void_p), io.ctypes.data_as(C.c_void_p),
+                                                C.byref(tl)))
+        return ko, io, bool(tl.value)
+
     def debugColorGradients(self, points, normals, options=None, **kw):
         """mm3d_debug_color_gradients: the gradient records of `points` with `normals`, float32[n][4]: gx gy gz I."""
         o = options if options is not None else IcpColorOptions(**kw)

@@ -62,14 +62,15 @@ __device__ __forceinline__ float3 xform(const float *T, float x, float y, float 
   return r;
 }
 
-__device__ __forceinline__ int cell_floor(float v, float mn, float inv)
+// (host too: cloud_hilbert bounds its column table by this expression of the box's corner; the tree is built without contraction)
+__host__ __device__ __forceinline__ int cell_floor(float v, float mn, float inv)
 {
   float f = floorf((v - mn) * inv);
   f = fminf(fmaxf(f, -1048576.0f), 1048576.0f);
   return (int)f;
 }
 
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+__host__ __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // Visit every point of the grid that can lie within `r` of q: (2s+1)^2 contiguous row spans.
 // f(const float4 &p) -> bool; returning false stops the walk early.

@@ -31,6 +31,24 @@ __global__ void k_voxel_keys(const float4 *__restrict__ pts, int n, float inv, i
   keys[i] = (uint32_t)(ijk0 + ijk1 * mul1 + ijk2 * mul2);
 }
 
+// The same key together with the counting sort's first step (grid.hip: counting_sort_begin / _finish): the point's arrival rank in
+// its key's bin comes from the histogram's atomic, in the launch that has the key in a register -- k_cs_count read the keys back
+// only to do that.  No iota either: only the radix fallback wants one (downsample).
+__global__ void k_voxel_keys_count(const float4 *__restrict__ pts, int n, float inv, int minbx, int minby, int minbz, int mul1, int mul2,
+                                   uint32_t divisor, uint32_t *__restrict__ keys, int *__restrict__ counts, uint32_t *__restrict__ ranks)
+{
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  float4 p = pts[i];
+  if (!(isfinite(p.x) && isfinite(p.y) && isfinite(p.z))) { keys[i] = 0xFFFFFFFFu; return; }
+  int ijk0 = (int)(lattice_index(p.x, inv) - (float)minbx);
+  int ijk1 = (int)(lattice_index(p.y, inv) - (float)minby);
+  int ijk2 = (int)(lattice_index(p.z, inv) - (float)minbz);
+  const uint32_t key = (uint32_t)(ijk0 + ijk1 * mul1 + ijk2 * mul2);
+  keys[i] = key;
+  if (key != 0xFFFFFFFFu) ranks[i] = (uint32_t)atomicAdd(&counts[key / divisor], 1);      // (k_cs_count's rule for that key)
+}
+
 // a voxel starts where the sorted key changes (non-finite points carry the key 0xFFFFFFFF and sort last); the fused scan
 // numbers the voxels and writes every voxel's first position (scan_fused.hpp: one launch for heads + scan + starts)
 struct VoxelHeadLoad {
@@ -179,14 +197,23 @@ mm3d_cloud *downsample(Context *c, const mm3d_cloud *in_, double resolution)
   }
   const int *min_b = vs.min_b, *div_b = vs.div_b;
   const int mul1 = div_b[0], mul2 = div_b[0] * div_b[1];
+  // pcl::VoxelGrid sorts (voxel index, point) pairs; the order inside a voxel is the input order here (stable),
+  // by counting sort (grid.hip), or by rocPRIM's radix sort when some bin of the counting sort is very long
+  const uint64_t key_range = (uint64_t)div_b[0] * (uint64_t)div_b[1] * (uint64_t)div_b[2];
+#if MM3D_VOXEL_FUSED
+  DevBuf<uint32_t> keys(c, n), keys2(c, n), vals2(c, n);
+  const CountingSort cs = counting_sort_begin(c, n, key_range);
+  const DevPtr<int> too_long{cs.too_long()};
+  MM3D_LAUNCH(c, "voxel_keys", n * 28.0, k_voxel_keys_count, dim3(div_up(n, 256)), dim3(256), 0, in->pts.get(), n, inv,
+              min_b[0], min_b[1], min_b[2], mul1, mul2, cs.divisor, keys.get(), cs.counts.get(), cs.ranks.get());
+  counting_sort_finish(c, cs, keys.get(), n, keys2.get(), vals2.get(), in->n_finite == in->n);
+#else
   DevBuf<uint32_t> keys(c, n), vals(c, n), keys2(c, n), vals2(c, n);
   MM3D_LAUNCH(c, "voxel_keys", n * 24.0, k_voxel_keys, dim3(div_up(n, 256)), dim3(256), 0, in->pts.get(), n, inv,
               min_b[0], min_b[1], min_b[2], mul1, mul2, keys.get(), vals.get());
-  // pcl::VoxelGrid sorts (voxel index, point) pairs; the order inside a voxel is the input order here (stable),
-  // by counting sort (grid.hip), or by rocPRIM's radix sort when some bin of the counting sort is very long
   DevBuf<int> too_long(c, 1);
-  counting_sort_pairs_u32(c, keys.get(), n, (uint64_t)div_b[0] * (uint64_t)div_b[1] * (uint64_t)div_b[2], keys2.get(), vals2.get(),
-                          too_long.get(), in->n_finite == in->n);
+  counting_sort_pairs_u32(c, keys.get(), n, key_range, keys2.get(), vals2.get(), too_long.get(), in->n_finite == in->n);
+#endif
   // One wait for the whole filter: the centroid launch is sized by its bound and reads the voxel count on the device, so the
   // count, the counting sort's "bin too long" word and the centroids' bounding box come back together (the new cloud needs no
   // k_bbox launch and no wait of its own).
@@ -212,7 +239,14 @@ mm3d_cloud *downsample(Context *c, const mm3d_cloud *in_, double resolution)
     c->sync();
     if (attempt == 1 || !h[15]) break;
     // (a bin of the counting sort was too long and nothing was placed: the launches above found no voxel; radix sort, once more)
+#if MM3D_VOXEL_FUSED
+    DevBuf<uint32_t> vals(c, n);                      // (the input order as the radix sort's values: nobody else reads it)
+    iota_u32(c, vals.get(), n);
+#endif
     sort_pairs_u32(c, keys.get(), keys2.get(), vals.get(), vals2.get(), n, 32);
+#if MM3D_VOXEL_FUSED
+    c->settle();                                      // vals goes back to the pool after the sort
+#endif
   }
   const size_t nvox = h[16];
   refit_points(c, out, nvox, bound);                  // (the output was allocated at its bound: one wait for the whole filter)

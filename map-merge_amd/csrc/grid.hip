@@ -6,10 +6,13 @@
 // cloud; PCL rebuilds its tree per call and per pair.
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstring>
+#include <vector>
 
 #include <rocprim/rocprim.hpp>
 
+#include "capi_guard.hpp"
 #include "device_util.hpp"
 #include "scan_fused.hpp"
 
@@ -602,15 +605,16 @@ void grid_ensure_nblists(Context *c, const Grid &g_, int R)
 // far away, but never inside one block.
 // (counts / ranks != null: the counting sort's first step -- a point's arrival rank in its Hilbert column -- in the same launch)
 __global__ void k_hilbert_keys(const float4 *__restrict__ pts, int n, float minx, float miny, float minz, float inv,
-                               uint32_t *__restrict__ keys, uint32_t *__restrict__ vals, int *__restrict__ counts, uint32_t *__restrict__ ranks)
+                               uint32_t *__restrict__ keys, uint32_t *__restrict__ vals, int *__restrict__ counts, uint32_t *__restrict__ ranks,
+                               int col_max /* the column coordinates' bound: 2^k - 1, counts holds 4^k columns (cloud_hilbert) */)
 {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const float4 p = pts[i];
   vals[i] = (uint32_t)i;
   if (!(isfinite(p.x) && isfinite(p.y) && isfinite(p.z))) { keys[i] = 0xFFFFFFFFu; return; }
-  unsigned x = (unsigned)clampi(cell_floor(p.x, minx, inv), 0, 1023);
-  unsigned y = (unsigned)clampi(cell_floor(p.y, miny, inv), 0, 1023);
+  unsigned x = (unsigned)clampi(cell_floor(p.x, minx, inv), 0, col_max);
+  unsigned y = (unsigned)clampi(cell_floor(p.y, miny, inv), 0, col_max);
   const unsigned z = (unsigned)clampi(cell_floor(p.z, minz, inv), 0, 1023);
   unsigned d = 0;
   for (unsigned sft = 512; sft > 0; sft >>= 1) {
@@ -645,8 +649,19 @@ struct ItemHeadLoad {
   __device__ __forceinline__ bool head(size_t j) const { return j < (size_t)n && (j == 0 || (keys[j] >> 16) != (keys[j - 1] >> 16) || (j & 63) == 0); }
   __device__ __forceinline__ int operator()(size_t j) const { return (inert && *inert) ? 0 : (head(j) ? 1 : 0); }
 };
+// An item's count is the distance to the next head, which every 64th element is, or to the end of the points.  The fused scan
+// hands that distance over from its head masks (scan_fused.hpp: kNextFlag).  The earlier form walked the keys from every head
+// to the next one, up to 63 dependent loads in one lane of its wave.
 struct ItemFillStore {
   const uint32_t *keys; int n; int2 *items; int *n_items; const int *inert;
+#if MM3D_ITEM_NEXT
+  static constexpr bool kNextFlag = true;
+  __device__ __forceinline__ void operator()(size_t j, int prefix, int v, int next) const
+  {
+    if (j == (size_t)n) { *n_items = prefix; return; }        // (the scan runs over n + 1 elements: the last one carries the total)
+    if (v) items[prefix] = make_int2((int)j, min(next, n - (int)j));
+  }
+#else
   __device__ __forceinline__ void operator()(size_t j, int prefix, int v) const
   {
     if (j == (size_t)n) { *n_items = prefix; return; }        // (the scan runs over n + 1 elements: the last one carries the total)
@@ -656,6 +671,7 @@ struct ItemFillStore {
     while (cnt < 64 && j + cnt < (size_t)n && !h.head(j + cnt)) ++cnt;
     items[prefix] = make_int2((int)j, cnt);
   }
+#endif
   __device__ __forceinline__ void done() const {}
 };
 
@@ -674,8 +690,47 @@ __global__ void k_cs_count(const uint32_t *__restrict__ keys, int n, uint32_t di
   if (key == 0xFFFFFFFFu) return;               // non-finite point: stays out (the output's tail keeps its fill value)
   ranks[i] = (uint32_t)atomicAdd(&counts[key / divisor], 1);
 }
+// A member of a bin as the scatter leaves it: with MM3D_PLACE_PAIRS the (key, index) pair itself, so that the placing kernel
+// compares what it loads -- independent loads, several in flight -- and never follows an index into keys[]; without it the
+// index alone (the earlier form: slots[j], then keys[slots[j]], two dependent loads per member).
+#if MM3D_PLACE_PAIRS
+typedef uint2 SortSlot;
+__device__ __forceinline__ SortSlot sort_slot(uint32_t key, int i) { return make_uint2(key, (uint32_t)i); }
+// how many of slots[b, e) sort before (key, i): smaller key, or the same key and a smaller index
+__device__ __forceinline__ int sort_rank(const SortSlot *__restrict__ slots, const uint32_t *, int b, int e, uint32_t key, int i)
+{
+  const uint32_t ui = (uint32_t)i;
+  int r = 0, j = b;
+  for (; j + 4 <= e; j += 4) {
+    const uint2 m0 = slots[j], m1 = slots[j + 1], m2 = slots[j + 2], m3 = slots[j + 3];
+    r += (m0.x < key || (m0.x == key && m0.y < ui)) ? 1 : 0;
+    r += (m1.x < key || (m1.x == key && m1.y < ui)) ? 1 : 0;
+    r += (m2.x < key || (m2.x == key && m2.y < ui)) ? 1 : 0;
+    r += (m3.x < key || (m3.x == key && m3.y < ui)) ? 1 : 0;
+  }
+  for (; j < e; ++j) {
+    const uint2 m = slots[j];
+    r += (m.x < key || (m.x == key && m.y < ui)) ? 1 : 0;
+  }
+  return r;
+}
+#else
+typedef int SortSlot;
+__device__ __forceinline__ SortSlot sort_slot(uint32_t, int i) { return i; }
+__device__ __forceinline__ int sort_rank(const SortSlot *__restrict__ slots, const uint32_t *__restrict__ keys, int b, int e, uint32_t key, int i)
+{
+  int r = 0;
+  for (int j = b; j < e; ++j) {
+    const int o = slots[j];
+    const uint32_t ko = keys[o];
+    r += (ko < key || (ko == key && o < i)) ? 1 : 0;
+  }
+  return r;
+}
+#endif
+
 __global__ void k_cs_scatter(const uint32_t *__restrict__ keys, const uint32_t *__restrict__ ranks, const int *__restrict__ bin_start, int n,
-                             uint32_t divisor, int *__restrict__ slots, int *__restrict__ too_long)
+                             uint32_t divisor, SortSlot *__restrict__ slots, int *__restrict__ too_long)
 {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -683,10 +738,10 @@ __global__ void k_cs_scatter(const uint32_t *__restrict__ keys, const uint32_t *
   if (key == 0xFFFFFFFFu) return;
   const uint32_t bin = key / divisor;
   const int b = bin_start[bin];
-  slots[b + (int)ranks[i]] = i;
+  slots[b + (int)ranks[i]] = sort_slot(key, i);
   if (bin_start[bin + 1] - b > kCountSortBinMax) *too_long = 1;
 }
-__global__ void k_cs_place(const uint32_t *__restrict__ keys, const int *__restrict__ bin_start, const int *__restrict__ slots, int n,
+__global__ void k_cs_place(const uint32_t *__restrict__ keys, const int *__restrict__ bin_start, const SortSlot *__restrict__ slots, int n,
                            uint32_t divisor, const int *__restrict__ too_long, uint32_t *__restrict__ keys_out, uint32_t *__restrict__ idx_out)
 {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -695,14 +750,30 @@ __global__ void k_cs_place(const uint32_t *__restrict__ keys, const int *__restr
   if (key == 0xFFFFFFFFu) return;
   const uint32_t bin = key / divisor;
   const int b = bin_start[bin], e = bin_start[bin + 1];
-  int r = 0;
-  for (int j = b; j < e; ++j) {
-    const int o = slots[j];
-    const uint32_t ko = keys[o];
-    r += (ko < key || (ko == key && o < i)) ? 1 : 0;
-  }
+  const int r = sort_rank(slots, keys, b, e, key, i);
   keys_out[b + r] = key;
   idx_out[b + r] = (uint32_t)i;
+}
+
+static uint32_t counting_sort_divisor(uint64_t key_range)
+{
+  const uint32_t divisor = (uint32_t)((key_range + ((uint64_t)1 << 22) - 1) >> 22);
+  return divisor == 0 ? 1 : divisor;
+}
+
+// the scan, the scatter and the placing, once every key has its arrival rank in its bin
+static void counting_sort_place(Context *c, const uint32_t *keys, const uint32_t *ranks, const int *counts, int nbins, uint32_t divisor, int n,
+                                uint32_t *keys_out, uint32_t *idx_out, int *too_long)
+{
+  DevBuf<int> bin_start(c, (size_t)nbins + 1);
+  DevBuf<SortSlot> slots(c, (size_t)n);
+  exclusive_scan_int(c, counts, bin_start.get(), (size_t)nbins + 1);
+  MM3D_LAUNCH(c, "count_sort", n * 16.0, k_cs_scatter, dim3(div_up(n, 256)), dim3(256), 0, keys, ranks,
+              (const int *)bin_start.get(), n, divisor, slots.get(), too_long);
+  MM3D_LAUNCH(c, "count_sort", n * 24.0, k_cs_place, dim3(div_up(n, 256)), dim3(256), 0, keys, (const int *)bin_start.get(),
+              (const SortSlot *)slots.get(), n, divisor, (const int *)too_long, keys_out, idx_out);
+  // (the temporaries return to the pool when this function ends: the pool is stream-ordered per context, and the
+  // next user of these blocks runs on the same stream)
 }
 
 // keys_out / idx_out: n entries; entries beyond the finite keys read 0xFFFFFFFF / are unspecified.  too_long (device)
@@ -712,22 +783,38 @@ __global__ void k_cs_place(const uint32_t *__restrict__ keys, const int *__restr
 void counting_sort_pairs_u32(Context *c, const uint32_t *keys, int n, uint64_t key_range, uint32_t *keys_out, uint32_t *idx_out,
                              int *too_long, bool no_invalid_keys)
 {
-  uint32_t divisor = (uint32_t)((key_range + ((uint64_t)1 << 22) - 1) >> 22);
-  if (divisor == 0) divisor = 1;
+  const uint32_t divisor = counting_sort_divisor(key_range);
   const int nbins = (int)(key_range / divisor) + 1;
-  DevBuf<int> counts(c, (size_t)nbins + 1), bin_start(c, (size_t)nbins + 1), slots(c, (size_t)n);
+  DevBuf<int> counts(c, (size_t)nbins + 1);
   DevBuf<uint32_t> ranks(c, (size_t)n);
   MM3D_HIP(hipMemsetAsync(counts.get(), 0, ((size_t)nbins + 1) * sizeof(int), c->stream));
   MM3D_HIP(hipMemsetAsync(too_long, 0, sizeof(int), c->stream));
   if (!no_invalid_keys) MM3D_HIP(hipMemsetAsync(keys_out, 0xFF, (size_t)n * sizeof(uint32_t), c->stream));
   MM3D_LAUNCH(c, "count_sort", n * 12.0, k_cs_count, dim3(div_up(n, 256)), dim3(256), 0, keys, n, divisor, counts.get(), ranks.get());
-  exclusive_scan_int(c, counts.get(), bin_start.get(), (size_t)nbins + 1);
-  MM3D_LAUNCH(c, "count_sort", n * 16.0, k_cs_scatter, dim3(div_up(n, 256)), dim3(256), 0, keys, (const uint32_t *)ranks.get(),
-              (const int *)bin_start.get(), n, divisor, slots.get(), too_long);
-  MM3D_LAUNCH(c, "count_sort", n * 24.0, k_cs_place, dim3(div_up(n, 256)), dim3(256), 0, keys, (const int *)bin_start.get(),
-              (const int *)slots.get(), n, divisor, (const int *)too_long, keys_out, idx_out);
-  // (the temporaries return to the pool when this function ends: the pool is stream-ordered per context, and the
-  // next user of these blocks runs on the same stream)
+  counting_sort_place(c, keys, ranks.get(), counts.get(), nbins, divisor, n, keys_out, idx_out, too_long);
+}
+
+// (types.hpp has the contract of the two halves)
+CountingSort counting_sort_begin(Context *c, int n, uint64_t key_range)
+{
+  CountingSort cs;
+  cs.divisor = counting_sort_divisor(key_range);
+  cs.nbins = (int)(key_range / cs.divisor) + 1;
+  cs.counts = DevBuf<int>(c, (size_t)cs.nbins + 2);
+  cs.ranks = DevBuf<uint32_t>(c, (size_t)n);
+  MM3D_HIP(hipMemsetAsync(cs.counts.get(), 0, ((size_t)cs.nbins + 2) * sizeof(int), c->stream));   // (counts and the too_long word: one fill)
+  return cs;
+}
+
+void counting_sort_finish(Context *c, const CountingSort &cs, const uint32_t *keys, int n, uint32_t *keys_out, uint32_t *idx_out, bool no_invalid_keys)
+{
+  if (!no_invalid_keys) MM3D_HIP(hipMemsetAsync(keys_out, 0xFF, (size_t)n * sizeof(uint32_t), c->stream));
+  counting_sort_place(c, keys, cs.ranks.get(), cs.counts.get(), cs.nbins, cs.divisor, n, keys_out, idx_out, cs.too_long());
+}
+
+void iota_u32(Context *c, uint32_t *v, int n)
+{
+  if (n > 0) MM3D_LAUNCH(c, "iota", n * 4.0, k_iota_u32, dim3(div_up(n, 256)), dim3(256), 0, v, n);
 }
 
 // Hilbert order by counting sort on the column index (key >> 10, at most 2^20 columns): a point's arrival rank in
@@ -737,18 +824,18 @@ void counting_sort_pairs_u32(Context *c, const uint32_t *keys, int n, uint64_t k
 constexpr int kHilColumns = 1 << 20;
 constexpr int kHilColumnMax = 1024;      // longer columns (degenerate clouds) leave it to the radix sort
 __global__ void k_hil_scatter(const uint32_t *__restrict__ keys, const uint32_t *__restrict__ ranks, const int *__restrict__ col_start, int n,
-                              int *__restrict__ slots, int *__restrict__ too_long)
+                              SortSlot *__restrict__ slots, int *__restrict__ too_long)
 {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const uint32_t key = keys[i];
   if (key == 0xFFFFFFFFu) return;
   const int b = col_start[key >> 10];
-  slots[b + (int)ranks[i]] = i;
+  slots[b + (int)ranks[i]] = sort_slot(key, i);
   if (col_start[(key >> 10) + 1] - b > kHilColumnMax) *too_long = 1;
 }
 __global__ void k_hil_place(const float4 *__restrict__ pts, const uint32_t *__restrict__ keys, const int *__restrict__ col_start,
-                            const int *__restrict__ slots, int n, const int *__restrict__ too_long, float4 *__restrict__ out,
+                            const SortSlot *__restrict__ slots, int n, const int *__restrict__ too_long, float4 *__restrict__ out,
                             uint32_t *__restrict__ out_keys)
 {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -756,12 +843,7 @@ __global__ void k_hil_place(const float4 *__restrict__ pts, const uint32_t *__re
   const uint32_t key = keys[i];
   if (key == 0xFFFFFFFFu) return;
   const int b = col_start[key >> 10], e = col_start[(key >> 10) + 1];
-  int r = 0;
-  for (int j = b; j < e; ++j) {
-    const int o = slots[j];
-    const uint32_t ko = keys[o];
-    r += (ko < key || (ko == key && o < i)) ? 1 : 0;
-  }
+  const int r = sort_rank(slots, keys, b, e, key, i);
   float4 p = pts[i];
   p.w = __int_as_float(i);
   out[b + r] = p;
@@ -782,17 +864,31 @@ void cloud_hilbert(Context *c, const mm3d_cloud *cl_, float min_cell)
   const float cell = std::fmax(std::fmax(0.25f, min_cell), ext / 1023.0f);
   DevBuf<uint32_t> keys(c, total), vals(c, total), keys2(c, total);
   cl->hil_pts = DevBuf<float4>(c, n);
-  DevBuf<int> counts(c, kHilColumns + 2), col_start(c, kHilColumns + 1), slots(c, n);
+  // Columns: with both column coordinates below 2^k the Hilbert index is below 4^k (the levels above k see two zero bits, add
+  // nothing and only exchange x and y), so the table that is cleared and scanned has 4^k columns, not 2^20: 2^16 for a 60 m
+  // map at 0.25 m.  k comes from the box's upper corner through the kernel's own float expression (cell_floor is monotone in the
+  // coordinate, so no point's column exceeds the corner's), and the kernel clamps to 2^k - 1: a wrong k could change the
+  // order, never write outside the table.
+  const float inv = 1.0f / cell;
+  int col_bits = 10;
+#if MM3D_HIL_BOX
+  const int cmax = std::max(clampi(cell_floor(cl->bmax[0], cl->bmin[0], inv), 0, 1023), clampi(cell_floor(cl->bmax[1], cl->bmin[1], inv), 0, 1023));
+  for (col_bits = 0; (1 << col_bits) <= cmax; ++col_bits) {}
+#endif
+  const size_t ncol = (size_t)1 << (2 * col_bits);
+  static_assert(kHilColumns == 1 << 20, "ten bits per column coordinate");
+  DevBuf<int> counts(c, ncol + 2), col_start(c, ncol + 1);
+  DevBuf<SortSlot> slots(c, n);
   DevBuf<uint32_t> ranks(c, total);
-  MM3D_HIP(hipMemsetAsync(counts.get(), 0, (kHilColumns + 2) * sizeof(int), c->stream));   // (counts and the too_long word: one fill)
-  const DevPtr<int> too_long{counts.get() + kHilColumns + 1};
+  MM3D_HIP(hipMemsetAsync(counts.get(), 0, (ncol + 2) * sizeof(int), c->stream));   // (counts and the too_long word: one fill)
+  const DevPtr<int> too_long{counts.get() + ncol + 1};
   MM3D_LAUNCH(c, "hilbert_keys", total * 36.0, k_hilbert_keys, dim3(div_up(total, 256)), dim3(256), 0, cl->pts.get(), total,
-              cl->bmin[0], cl->bmin[1], cl->bmin[2], 1.0f / cell, keys.get(), vals.get(), counts.get(), ranks.get());
-  exclusive_scan_int(c, counts.get(), col_start.get(), kHilColumns + 1);
+              cl->bmin[0], cl->bmin[1], cl->bmin[2], inv, keys.get(), vals.get(), counts.get(), ranks.get(), (1 << col_bits) - 1);
+  exclusive_scan_int(c, counts.get(), col_start.get(), ncol + 1);
   MM3D_LAUNCH(c, "hilbert_sort", total * 16.0, k_hil_scatter, dim3(div_up(total, 256)), dim3(256), 0, (const uint32_t *)keys.get(),
               (const uint32_t *)ranks.get(), (const int *)col_start.get(), total, slots.get(), too_long.get());
   MM3D_LAUNCH(c, "hilbert_sort", total * 44.0, k_hil_place, dim3(div_up(total, 256)), dim3(256), 0, cl->pts.get(),
-              (const uint32_t *)keys.get(), (const int *)col_start.get(), (const int *)slots.get(), total, (const int *)too_long.get(),
+              (const uint32_t *)keys.get(), (const int *)col_start.get(), (const SortSlot *)slots.get(), total, (const int *)too_long.get(),
               cl->hil_pts.get(), keys2.get());
   // Work items: flag the heads, number them, write {first point, count} per head -- one launch (scan_fused.hpp) instead of
   // three.  The item array is sized by its bound (a head every 64 points plus one per column block: key >> 16 < 2^14); the
@@ -914,4 +1010,66 @@ int snb_cu_count(int device)
   return n;
 }
 
+// mm3d_debug_hilbert_order: cloud_hilbert on a cloud that has no order yet, read back
+static void debug_hilbert_order(Context *c, const mm3d_cloud *cl, float min_cell, int *order, int *items, size_t cap, int *n_items)
+{
+  MM3D_REQUIRE(!cl->hil_pts.get(), "mm3d_debug_hilbert_order: the cloud already carries an order");
+  cloud_hilbert(c, cl, min_cell);
+  for (size_t i = 0; i < cl->n; ++i) order[i] = -1;
+  *n_items = 0;
+  if (!cl->hil_pts.get()) return;                    // no finite point
+  const size_t nf = cl->n_finite, ni = (size_t)cl->n_wave_items;
+  MM3D_REQUIRE(ni <= cap, "mm3d_debug_hilbert_order: more items than the caller's array holds");
+  std::vector<float4> h(nf);
+  MM3D_HIP(hipMemcpyAsync(h.data(), cl->hil_pts.get(), nf * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+  if (ni) MM3D_HIP(hipMemcpyAsync(items, cl->wave_items.get(), ni * sizeof(int2), hipMemcpyDeviceToHost, c->stream));
+  c->sync();
+  for (size_t j = 0; j < nf; ++j) std::memcpy(&order[j], &h[j].w, sizeof(int));
+  *n_items = (int)ni;
+}
+
+// mm3d_debug_counting_sort: the counting sort of host keys as the voxel filter runs it, read back
+static void debug_counting_sort(Context *c, const uint32_t *keys, int n, uint64_t key_range, bool no_invalid_keys, uint32_t *keys_out,
+                                uint32_t *idx_out, int *too_long)
+{
+  DevBuf<uint32_t> d_keys(c, n), d_out(c, 2 * (size_t)n);
+  MM3D_HIP(hipMemcpyAsync(d_keys.get(), keys, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+  MM3D_HIP(hipMemsetAsync(d_out.get(), 0xFF, 2 * (size_t)n * sizeof(uint32_t), c->stream));      // (what a sort that gave up leaves)
+#if MM3D_VOXEL_FUSED
+  const CountingSort cs = counting_sort_begin(c, n, key_range);
+  const DevPtr<int> d_long{cs.too_long()};
+  MM3D_LAUNCH(c, "count_sort", n * 12.0, k_cs_count, dim3(div_up(n, 256)), dim3(256), 0, (const uint32_t *)d_keys.get(), n, cs.divisor,
+              cs.counts.get(), cs.ranks.get());
+  counting_sort_finish(c, cs, d_keys.get(), n, d_out.get(), d_out.get() + n, no_invalid_keys);
+#else
+  DevBuf<int> d_long(c, 1);
+  counting_sort_pairs_u32(c, d_keys.get(), n, key_range, d_out.get(), d_out.get() + n, d_long.get(), no_invalid_keys);
+#endif
+  MM3D_HIP(hipMemcpyAsync(keys_out, d_out.get(), (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  MM3D_HIP(hipMemcpyAsync(idx_out, d_out.get() + n, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  MM3D_HIP(hipMemcpyAsync(too_long, d_long.get(), sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  c->sync();
+}
+
 }  // namespace mm3d
+
+// the C entry points of the two probes (include/mm3d.h) live with their kernels, like nn.hip's mm3d_debug_nn_search: the
+// host-only builds of the library link capi.cpp without this file
+extern "C" int mm3d_debug_hilbert_order(mm3d_ctx *ctx, const mm3d_cloud *cloud, float min_cell, int *order, int *items, size_t items_cap,
+                                        int *n_items)
+{
+  if (!cloud || !n_items || !(min_cell >= 0.0f) || !std::isfinite(min_cell)) return MM3D_EINVAL;
+  if ((cloud->n && !order) || (items_cap && !items)) return MM3D_EINVAL;
+  return mm3d::guarded(ctx, [&] { mm3d::debug_hilbert_order(ctx, cloud, min_cell, order, items, items_cap, n_items); });
+}
+
+extern "C" int mm3d_debug_counting_sort(mm3d_ctx *ctx, const uint32_t *keys, size_t n, uint64_t key_range, int no_invalid_keys,
+                                        uint32_t *keys_out, uint32_t *idx_out, int *too_long)
+{
+  if (!keys || !keys_out || !idx_out || !too_long || n == 0 || n > (size_t)1 << 30) return MM3D_EINVAL;
+  if (key_range == 0 || key_range > 0xFFFFFFFFull) return MM3D_EINVAL;
+  for (size_t i = 0; i < n; ++i) {
+    if (keys[i] == 0xFFFFFFFFu ? no_invalid_keys != 0 : keys[i] >= key_range) return MM3D_EINVAL;      // a key outside the bins
+  }
+  return mm3d::guarded(ctx, [&] { mm3d::debug_counting_sort(ctx, keys, (int)n, key_range, no_invalid_keys != 0, keys_out, idx_out, too_long); });
+}

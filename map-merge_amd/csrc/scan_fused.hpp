@@ -80,6 +80,16 @@ inline void box_of_slots(const unsigned *slots, unsigned blocks, unsigned *box)
 }
 constexpr unsigned kBoxInit[8] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u, 0u, 0u};
 
+// A store that declares `static constexpr bool kNextFlag = true` (its load is 0 / 1) is called as store(i, prefix, value, next):
+// next = the distance from a set element i to the next set element, or 64 where none lies within 64 elements (0 for an unset
+// element).  Every thread leaves the 16-bit mask of its run in LDS and one wave evaluates the 64 flags behind the tile's end
+// through the same load, so the answer is a find-first-set over the thread's own mask and four neighbouring words: nobody
+// walks memory to find where its run of zeros ends.
+template <class S, class = void> struct scan_store_wants_next : std::false_type {};
+template <class S> struct scan_store_wants_next<S, std::void_t<decltype(S::kNextFlag)>> : std::bool_constant<S::kNextFlag> {};
+constexpr int kScanNextSpan = 64;
+static_assert(kScanNextSpan == 4 * kScanItems, "the look-ahead is four runs: four mask words behind a thread's own");
+
 template <class Load, class Store>
 __global__ void __launch_bounds__(256)
 k_scan_fused(size_t n, unsigned long long *status, unsigned *ticket, unsigned ticket_base, unsigned epoch, Load load, Store store)
@@ -98,6 +108,19 @@ k_scan_fused(size_t n, unsigned long long *status, unsigned *ticket, unsigned ti
 #pragma unroll
   for (int k = 0; k < kScanItems; ++k) sum += v[k];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  constexpr bool kNext = scan_store_wants_next<Store>::value;
+  __shared__ unsigned s_mask[kNext ? 256 + 4 : 1];
+  unsigned mask = 0;
+  if constexpr (kNext) {
+#pragma unroll
+    for (int k = 0; k < kScanItems; ++k) mask |= v[k] ? 1u << k : 0u;
+    s_mask[threadIdx.x] = mask;
+    if (wave == 0) {
+      const size_t j = (tile + 1) * kScanTile + (size_t)lane;
+      const unsigned long long behind = ballot(j < n && load(j) != 0);
+      if (lane < 4) s_mask[256 + lane] = (unsigned)(behind >> (16 * lane)) & 0xffffu;
+    }
+  }
   const int incl = wave_scan_incl(sum);
   if (lane == kWave - 1) s_wave[wave] = incl;
   __syncthreads();
@@ -131,10 +154,29 @@ k_scan_fused(size_t n, unsigned long long *status, unsigned *ticket, unsigned ti
   }
   __syncthreads();
   int run = s_prefix + wave_off + incl - sum;
+  if constexpr (kNext) {
+    // elements from the end of this thread's run to the next set flag (four independent LDS reads, and only by threads that hold a flag)
+    int after = kScanNextSpan;
+    if (mask) {
+      const unsigned long long m = (unsigned long long)s_mask[threadIdx.x + 1] | (unsigned long long)s_mask[threadIdx.x + 2] << 16 |
+                                   (unsigned long long)s_mask[threadIdx.x + 3] << 32 | (unsigned long long)s_mask[threadIdx.x + 4] << 48;
+      if (m) after = __ffsll((long long)m) - 1;
+    }
 #pragma unroll
-  for (int k = 0; k < kScanItems; ++k) {
-    if (base + k < n) store(base + k, run, v[k]);
-    run += v[k];
+    for (int k = 0; k < kScanItems; ++k) {
+      if (base + k < n) {
+        const unsigned later = k + 1 < kScanItems ? mask >> (k + 1) : 0u;
+        const int next = !v[k] ? 0 : (later ? __ffs((int)later) : min(kScanItems - k + after, kScanNextSpan));
+        store(base + k, run, v[k], next);
+      }
+      run += v[k];
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < kScanItems; ++k) {
+      if (base + k < n) store(base + k, run, v[k]);
+      run += v[k];
+    }
   }
   store.done();        // called by EVERY thread of the grid once, after its elements (a store that reduces something flushes here)
 }

@@ -344,6 +344,34 @@ struct ScanLaunchState { unsigned long long *status; unsigned *ticket; unsigned 
 ScanLaunchState scan_prepare(Context *c, size_t n);
 void counting_sort_pairs_u32(Context *c, const uint32_t *keys, int n, uint64_t key_range, uint32_t *keys_out, uint32_t *idx_out,
                              int *too_long, bool no_invalid_keys = false);
+// The search-structure kernels' A/B switches ("Dependent-load chains"): -DMM3D_...=0 builds the earlier form.
+#ifndef MM3D_ITEM_NEXT
+#define MM3D_ITEM_NEXT 1        // a work item's length from the fused scan's head masks, not from a walk over the keys
+#endif
+#ifndef MM3D_PLACE_PAIRS
+#define MM3D_PLACE_PAIRS 1      // the counting sorts scatter (key, index) pairs: the placing kernels read one level
+#endif
+#ifndef MM3D_VOXEL_FUSED
+#define MM3D_VOXEL_FUSED 1      // the voxel filter's keys come with their histogram; too_long shares the counts' fill
+#endif
+#ifndef MM3D_HIL_BOX
+#define MM3D_HIL_BOX 1          // the Hilbert columns' table is sized by the cloud's box (4^k columns), not 2^20
+#endif
+// The counting sort in two halves, for a caller whose own kernel makes the keys (filters.hip: the voxel key comes with its
+// histogram).  begin: the bins of key_range, the counts and the too_long word zeroed by ONE fill, the ranks' buffer.  The
+// caller's launch writes keys[i] and ranks[i] = atomicAdd(&counts[keys[i] / divisor], 1) for every key but 0xFFFFFFFF;
+// finish scans, scatters and places as counting_sort_pairs_u32 does.  too_long() is read after the caller's next wait, while
+// the object lives.
+struct CountingSort {
+  uint32_t divisor = 1;
+  int nbins = 0;
+  DevBuf<int> counts;             // nbins + 2: the bins, the scan's total, too_long
+  DevBuf<uint32_t> ranks;
+  int *too_long() const { return counts.get() + nbins + 1; }
+};
+CountingSort counting_sort_begin(Context *c, int n, uint64_t key_range);
+void counting_sort_finish(Context *c, const CountingSort &cs, const uint32_t *keys, int n, uint32_t *keys_out, uint32_t *idx_out, bool no_invalid_keys);
+void iota_u32(Context *c, uint32_t *v, int n);       // v[i] = i (the radix fallbacks' values)
 void sort_pairs_u32(Context *c, const uint32_t *kin, uint32_t *kout, const uint32_t *vin, uint32_t *vout,
                     size_t n, int end_bit);
 
