@@ -340,6 +340,67 @@ inline void check_icp_reject_devices(const mm3d_icp_rejection_options &o, const 
   if ((o.one_to_one || o.distance != MM3D_REJECT_NONE) && devices && *devices)
     throw std::runtime_error("mm3d: MM3D_ICP_REJECT is not available with MM3D_DEVICES (a device list runs the ICP without rejection)");
 }
+// MM3D_ICP_ROBUST=<kernel>[:<scale>[:<scale_start>[:<anneal>[:<tuning>]]]]: the estimation context's ICP weights its correspondences
+// (mm3d_set_icp_robust).  Kernels: l2, huber, cauchy, tukey, geman_mcclure; a value left out is
+// mm3d_icp_robust_options_default's (0.05, 0, 0.5, 0).  none or unset selects nothing.  An unknown kernel, an empty or malformed
+// value, a value out of range or a sixth field throw, as a malformed MM3D_ICP_REJECT does.
+inline mm3d_icp_robust_options parse_icp_robust(const char *value)
+{
+  mm3d_icp_robust_options o;
+  o.kernel = MM3D_ROBUST_OFF;
+  o.scale = 0.05;
+  o.scale_start = 0.0;
+  o.anneal = 0.5;
+  o.tuning = 0.0;
+  const std::string v = value ? value : "";
+  if (v.empty() || v == "none") return o;
+  static const char *const names[] = {"l2", "huber", "cauchy", "tukey", "geman_mcclure"};
+  double *const fields[] = {&o.scale, &o.scale_start, &o.anneal, &o.tuning};
+  bool ok = true;
+  int field = -1;
+  for (size_t a = 0; ok && a <= v.size(); ++field) {
+    size_t b = v.find(':', a);
+    if (b == std::string::npos) b = v.size();
+    const std::string term = v.substr(a, b - a);
+    if (field < 0) {
+      for (int k = 0; k < 5; ++k)
+        if (term == names[k]) o.kernel = MM3D_ROBUST_L2 + k;
+      ok = o.kernel != MM3D_ROBUST_OFF;
+    } else if (field < 4) {
+      char *end = nullptr;
+      const double x = std::strtod(term.c_str(), &end);
+      ok = !term.empty() && *end == '\0' && std::isfinite(x) && term.find_first_not_of("0123456789.eE+-") == std::string::npos;
+      *fields[field] = x;
+    } else {
+      ok = false;
+    }
+    a = b + 1;
+  }
+  ok = ok && o.scale > 0.0 && (o.scale_start == 0.0 || o.scale_start >= o.scale) && o.anneal > 0.0 && o.anneal <= 1.0 && o.tuning >= 0.0;
+  if (!ok)
+    throw std::runtime_error("mm3d: MM3D_ICP_ROBUST must be none or <l2|huber|cauchy|tukey|geman_mcclure>[:<scale > 0>[:<scale_start, 0 or >= "
+                             "scale>[:<anneal in (0, 1]>[:<tuning >= 0>]]]], not '" + v + "'");
+  return o;
+}
+// Not available on a device list (its devices' pair loops run the ICP without a kernel), nor together with an active
+// MM3D_ICP_REJECT, MM3D_ICP_COLOR, MM3D_ICP_GENERALIZED or MM3D_REFINE=ndt (the robust step has point-to-point's and
+// point-to-plane's terms only): each combination throws.
+inline void check_icp_robust_combinations(const mm3d_icp_robust_options &o, const mm3d_icp_rejection_options &reject,
+                                          const mm3d_icp_color_options &color, const mm3d_icp_generalized_options &generalized,
+                                          const mm3d_refine_options &refine, const char *devices)
+{
+  if (o.kernel == MM3D_ROBUST_OFF) return;
+  if (devices && *devices)
+    throw std::runtime_error("mm3d: MM3D_ICP_ROBUST is not available with MM3D_DEVICES (a device list runs the ICP without a robust kernel)");
+  if (reject.one_to_one || reject.distance != MM3D_REJECT_NONE)
+    throw std::runtime_error("mm3d: MM3D_ICP_ROBUST is not available with an active MM3D_ICP_REJECT (the robust ICP has no correspondence stage)");
+  if (color.enabled)
+    throw std::runtime_error("mm3d: MM3D_ICP_ROBUST is not available with an active MM3D_ICP_COLOR (the robust ICP has no colour term)");
+  if (generalized.enabled)
+    throw std::runtime_error("mm3d: MM3D_ICP_ROBUST is not available with an active MM3D_ICP_GENERALIZED (the robust ICP has no plane-to-plane term)");
+  if (refine.method == MM3D_REFINE_NDT)
+    throw std::runtime_error("mm3d: MM3D_ICP_ROBUST is not available with MM3D_REFINE=ndt (NDT has no correspondences to weight)");
+}
 // MM3D_ICP_COLOR=1 or <lambda>[:<radius in metres>]: the estimation context's pair stage runs coloured ICP (mm3d_set_icp_color).
 // 1 alone: mm3d_icp_color_options_default's lambda (0.968) -- lambda 1 itself, point-to-plane's terms, is spelt 1.0 -- and, as
 // without a radius, params.normal_radius.  0, none or unset leaves it off.  A lambda outside (0, 1], a radius that is not
@@ -579,6 +640,7 @@ inline mm3d_ctx *ctx()
   // MM3D_COARSE=correlative[:<cell>]: parse_coarse above.  Not available on a device list: correlative with MM3D_DEVICES set as well throws.
   // MM3D_CONFIDENCE=overlap[:<voxel>]: parse_confidence above.  Not available on a device list: overlap with MM3D_DEVICES set as well throws.
   // MM3D_ICP_REJECT=one_to_one+trimmed:0.7 ...: parse_icp_reject above.  Not available on a device list: an active value with MM3D_DEVICES set as well throws.
+  // MM3D_ICP_ROBUST=geman_mcclure:0.05[:<start>[:<anneal>[:<tuning>]]]: parse_icp_robust above.  Not available on a device list nor with an active MM3D_ICP_REJECT, MM3D_ICP_COLOR, MM3D_ICP_GENERALIZED or MM3D_REFINE=ndt: each throws.
   // MM3D_ICP_COLOR=1 or <lambda>[:<radius>]: parse_icp_color above.  Not available on a device list nor with an active MM3D_ICP_REJECT: either throws.
   // MM3D_ICP_GENERALIZED=1 or <epsilon>: parse_icp_generalized above.  Not available on a device list nor with an active MM3D_ICP_REJECT or MM3D_ICP_COLOR: each throws.
   // MM3D_ESTIMATOR=consistency[:<seeds>]: parse_estimator above.  Not available on a device list: consistency with MM3D_DEVICES set as well throws.
@@ -605,6 +667,8 @@ inline mm3d_ctx *ctx()
     mm3d_refine_options refine = parse_refine(std::getenv("MM3D_REFINE"));
     if (refine.method == MM3D_REFINE_NDT && std::getenv("MM3D_DEVICES") && *std::getenv("MM3D_DEVICES"))
       throw std::runtime_error("mm3d: MM3D_REFINE=ndt is not available with MM3D_DEVICES (a device list carries no voxel tables)");
+    const mm3d_icp_robust_options robust = parse_icp_robust(std::getenv("MM3D_ICP_ROBUST"));
+    check_icp_robust_combinations(robust, reject, color, generalized, refine, std::getenv("MM3D_DEVICES"));
     const mm3d_icp_sampling_options sampling = parse_icp_sample(std::getenv("MM3D_ICP_SAMPLE"));
     check_icp_sample_combinations(sampling, refine, color, generalized, std::getenv("MM3D_DEVICES"));
     const char *al = std::getenv("MM3D_ALIGN");
@@ -654,6 +718,8 @@ inline mm3d_ctx *ctx()
       throw std::runtime_error("mm3d: MM3D_CONFIDENCE was refused (the voxel must be a positive float with a finite reciprocal)");
     if ((reject.one_to_one || reject.distance != MM3D_REJECT_NONE) && mm3d_set_icp_rejection(e, &reject) != MM3D_OK)
       throw std::runtime_error(std::string("mm3d: MM3D_ICP_REJECT was refused: ") + mm3d_last_error(e));
+    if (robust.kernel != MM3D_ROBUST_OFF && mm3d_set_icp_robust(e, &robust) != MM3D_OK)
+      throw std::runtime_error(std::string("mm3d: MM3D_ICP_ROBUST was refused: ") + mm3d_last_error(e));
     if (color.enabled && mm3d_set_icp_color(e, &color) != MM3D_OK)
       throw std::runtime_error(std::string("mm3d: MM3D_ICP_COLOR was refused: ") + mm3d_last_error(e));
     if (generalized.enabled && mm3d_set_icp_generalized(e, &generalized) != MM3D_OK)

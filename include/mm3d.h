@@ -1276,6 +1276,92 @@ int mm3d_debug_icp_rejection(mm3d_ctx *ctx, const mm3d_cloud *source, const mm3d
  * everywhere; 1 or 4 = forced in every rejecting launch from now on; negative = no change.  Returns the value in force. */
 int mm3d_debug_icp_rejection_split(int split);
 
+/* ---------------------------------------------------------------- opt-in robust ICP
+ * mm3d_set_icp_robust gives the pair stage's ICP a robust loss: every matched correspondence enters the estimate with an
+ * M-estimator weight of its Euclidean d2 at a scale that is fixed before the iteration runs (a table that the host builds, so
+ * the weight is computed in the kernel that searches and sums: one fused launch and the finalize per iteration, no
+ * correspondence array, no select).  Geman-McClure on an annealed scale is Fast Global Registration's objective (Zhou, Park,
+ * Koltun, ECCV 2016) applied to ICP correspondences; it is the configuration whose recovery the tests assert.  Huber, Cauchy
+ * and Tukey ship with their measured table and no promise.  With kernel OFF (the default) the
+ * selection is inactive and the pair stage runs the kernels it always ran.
+ * The rule, for ONE iteration, 0-based index k, of the loop that mm3d_set_icp_method states (everything else is that loop):
+ *   1. match     step 1 of the rejection rule above, unchanged: a finite source point is carried by the current float T; its
+ *                exact float nearest target point is found (ties to the lowest index); it is matched when d2 <= max_d2.
+ *   2. scale     in double: s_0 = scale_start, s_{k+1} = s_k * anneal (IEEE multiplies, no pow); sigma_k = max(scale, s_k).
+ *                scale_start = 0 means no annealing: sigma_k = scale for every k.  The table of sigma_k, k < max_iterations,
+ *                is built on the host and uploaded once per batch.  final_k is sigma_k == scale.  (L2 reads no scale: its
+ *                table holds `scale` throughout, so every iteration is final.)
+ *   3. weight    in double: h = sigma_k * tuning, u2 = (double)d2 / (h * h), and
+ *                L2 w = 1;  HUBER w = 1 if u2 <= 1, else 1 / sqrt(u2);  CAUCHY w = 1 / (1 + u2);
+ *                TUKEY w = (1 - u2) * (1 - u2) if u2 < 1, else 0;  GEMAN_MCCLURE w = 1 / ((1 + u2) * (1 + u2)).
+ *                tuning = 0 selects 1.345 (HUBER), 2.385 (CAUCHY), 4.685 (TUKEY) and 1.0 (GEMAN_MCCLURE, L2).
+ *   4. estimate  the default kernels' terms (point-to-point's 17, point-to-plane's 30), each multiplied by w in double --
+ *                w * ((double)bqx * p.x), the d2 term w * (double)d2, the count term w -- are summed in the default kernels'
+ *                order, and sum w normalises the moments.  Both estimates weight by the match's Euclidean d2, the number the
+ *                rejectors threshold on.  A point-to-plane row needs a finite normal, as always; the "six rows" test counts
+ *                the rows with w > 0.  Two further sums are integers: `matched`, and `weighted`, the matches with w > 0.
+ *                The "fewer than 3" stop and icp_correspondences count `weighted`.  The MSE of the convergence test is
+ *                sum w d2 / sum w.
+ *   5. convergence  the max_iterations stop always applies; the rotation / translation test and the MSE test apply only in
+ *                iterations with final_k, so an annealing run cannot stop on a scale it is about to leave.  (The MSE of an
+ *                iteration without final_k is not recorded either: the first final_k iteration compares with DBL_MAX.)
+ * With kernel L2 the result, the iteration count and `converged` are the default ICP's, bit for bit, for either estimate.
+ * Results are bit-identical for every stream count, batch and cache setting.  Applies to the ICP of
+ * mm3d_estimate_maps_transforms and mm3d_pair_estimate with either mm3d_set_icp_method, and composes with
+ * mm3d_set_icp_sampling (the robust step searches with the sample); mm3d_estimate_transform_icp,
+ * mm3d_estimate_transform_icp_plane, transformScore and the overlap confidence do not read the setting.  Working memory per
+ * pair of a batch: 8 B per iteration of the scale table, shared by the batch; nothing per point. */
+typedef enum {
+  MM3D_ROBUST_OFF = 0, MM3D_ROBUST_L2 = 1, MM3D_ROBUST_HUBER = 2, MM3D_ROBUST_CAUCHY = 3, MM3D_ROBUST_TUKEY = 4,
+  MM3D_ROBUST_GEMAN_MCCLURE = 5
+} mm3d_robust_kernel;
+typedef struct mm3d_icp_robust_options {
+  int kernel;                /* MM3D_ROBUST_* */
+  double scale;              /* metres, > 0 and finite: the scale every run ends on */
+  double scale_start;        /* metres: 0 (no annealing), or >= scale and finite */
+  double anneal;             /* 0 < a <= 1 */
+  double tuning;             /* >= 0 and finite; 0 = the kernel's constant above */
+} mm3d_icp_robust_options;
+typedef struct mm3d_icp_robust_stats {  /* of the LAST iteration that ran */
+  long long matched;         /* finite source points whose nearest target point has d2 <= max_d2 */
+  long long weighted;        /* of those, the ones with w > 0: == the pair record's icp_correspondences */
+  double weight_sum;         /* sum w */
+  double scale;              /* that iteration's sigma_k (0 when none ran) */
+  int iterations, converged;
+} mm3d_icp_robust_stats;
+void mm3d_icp_robust_options_default(mm3d_icp_robust_options *o);   /* OFF, 0.05, 0, 0.5, 0 */
+/* The selection is active when kernel != MM3D_ROBUST_OFF.  MM3D_EINVAL: ctx or options NULL, an unknown kernel, a value outside
+ * its range above (the values are checked whatever the selection).  MM3D_EUNSUPPORTED: an active selection on a device-list
+ * context (mm3d_create_devices), or while a correspondence rejection (mm3d_set_icp_rejection), coloured ICP
+ * (mm3d_set_icp_color), generalized ICP (mm3d_set_icp_generalized) or NDT (mm3d_set_refinement) is active -- each of which in
+ * turn refuses to become active while a robust kernel is selected; mm3d_shard_begin returns MM3D_EUNSUPPORTED on a context
+ * with an active selection.  The setting reaches the context's mm3d_set_streams helpers, in either order, and is part of the
+ * map cache's pair key while active. */
+int mm3d_set_icp_robust(mm3d_ctx *ctx, const mm3d_icp_robust_options *options);
+int mm3d_get_icp_robust(const mm3d_ctx *ctx, mm3d_icp_robust_options *options);   /* MM3D_EINVAL for NULL */
+/* of the most recent pair whose ICP this context ran with a robust kernel (the last pair of a whole-map call on one stream, or
+ * the call below); all zero before there was one */
+int mm3d_last_icp_robust_stats(const mm3d_ctx *ctx, mm3d_icp_robust_stats *stats);
+/* ICP with the rule above from initial_guess, whatever the context's setting.  options->kernel OFF runs as L2.  target_normals
+ * NULL: the point-to-point estimate; else the point-to-plane one (normals in the target's order).  stats may be NULL.
+ * MM3D_EINVAL: a NULL argument, options out of range, normals whose count differs from the target's. */
+int mm3d_estimate_transform_icp_robust(mm3d_ctx *ctx, const mm3d_cloud *source, const mm3d_cloud *target,
+                                       const mm3d_normals *target_normals, const float initial_guess[16],
+                                       double max_correspondence_distance, const mm3d_icp_robust_options *options,
+                                       int max_iterations, double transformation_epsilon, float T[16],
+                                       mm3d_icp_robust_stats *stats);
+/* test hook: iteration k's search, weights and sums at T, without the finalize.  Per source point, in the caller's order: the
+ * matched target index (-1: none), the float d2 (+inf: none) and the double weight (0: none).  sums (may be NULL): the
+ * iteration's totals as the finalize kernel forms them, 19 doubles (the 17 point-to-point terms, matched, weighted) or, with
+ * normals, 32 (the 30 point-to-plane terms, matched, weighted).  split: 1 or 4, as in mm3d_debug_nn_search.  k >= 0.  stats (may
+ * be NULL): the counts, sum w and sigma_k; iterations and converged are 0. */
+int mm3d_debug_icp_robust(mm3d_ctx *ctx, const mm3d_cloud *source, const mm3d_cloud *target, const mm3d_normals *target_normals,
+                          const float T[16], double max_correspondence_distance, const mm3d_icp_robust_options *options, int k,
+                          int split, int *idx, float *d2, double *weight, double *sums, mm3d_icp_robust_stats *stats);
+/* test hook, process-wide like mm3d_debug_icp_rejection_split: 0 = one or four work items per block chosen by size, as
+ * everywhere; 1 or 4 = forced in every robust launch from now on; negative = no change.  Returns the value in force. */
+int mm3d_debug_icp_robust_split(int split);
+
 /* ---------------------------------------------------------------- opt-in coloured ICP
  * mm3d_set_icp_color puts a photometric term beside point-to-plane's in the pair stage's ICP (Park, Zhou, Koltun, "Colored Point
  * Cloud Registration Revisited", ICCV 2017; Open3D's registration_colored_icp is the known implementation, and no parity with it

@@ -354,6 +354,32 @@ class IcpRejectionOptions(C.Structure):
         return tuple(int(getattr(self, k)) if t is C.c_int else float(getattr(self, k)) for k, t in self._fields_)
 
 
+class RobustKernel(enum.IntEnum):   # mm3d_robust_kernel (not a reference enum)
+    OFF = 0
+    L2 = 1
+    HUBER = 2
+    CAUCHY = 3
+    TUKEY = 4
+    GEMAN_MCCLURE = 5
+
+
+class IcpRobustOptions(C.Structure):
+    """mm3d_icp_robust_options (mm3d_set_icp_robust); the defaults are mm3d_icp_robust_options_default's."""
+    _fields_ = [("kernel", C.c_int), ("scale", C.c_double), ("scale_start", C.c_double), ("anneal", C.c_double), ("tuning", C.c_double)]
+
+    def __init__(self, **kw):
+        super().__init__()
+        lib().mm3d_icp_robust_options_default(C.byref(self))
+        kinds = dict(self._fields_)
+        for k, v in kw.items():
+            if k not in kinds:
+                raise TypeError("unknown robust ICP option " + k)
+            setattr(self, k, int(v) if kinds[k] is C.c_int else float(v))
+
+    def as_tuple(self):
+        return tuple(int(getattr(self, k)) if t is C.c_int else float(getattr(self, k)) for k, t in self._fields_)
+
+
 class IcpColorOptions(C.Structure):
     """mm3d_icp_color_options (mm3d_set_icp_color); the defaults are mm3d_icp_color_options_default's."""
     _fields_ = [("enabled", C.c_int), ("lambda_geometric", C.c_double), ("gradient_radius", C.c_double), ("min_neighbours", C.c_int)]
@@ -457,6 +483,15 @@ class IcpRejectionStats(C.Structure):
 
     def as_dict(self):
         return {k: (float if t is C.c_float else int)(getattr(self, k)) for k, t in self._fields_}
+
+
+class IcpRobustStats(C.Structure):
+    """mm3d_icp_robust_stats"""
+    _fields_ = [("matched", C.c_longlong), ("weighted", C.c_longlong), ("weight_sum", C.c_double), ("scale", C.c_double),
+                ("iterations", C.c_int), ("converged", C.c_int)]
+
+    def as_dict(self):
+        return {k: (float if t is C.c_double else int)(getattr(self, k)) for k, t in self._fields_}
 
 
 class OverlapStats(C.Structure):
@@ -598,6 +633,12 @@ def icp_rejection_split(split=-1):
     """mm3d_debug_icp_rejection_split: force every rejecting launch to one work item per wave (1) or per block (4); 0: chosen by
     size again; negative: leave as it is.  Returns the value in force."""
     return int(lib().mm3d_debug_icp_rejection_split(int(split)))
+
+
+def icp_robust_split(split=-1):
+    """mm3d_debug_icp_robust_split: force every robust launch to one work item per wave (1) or per block (4); 0: chosen by size
+    again; negative: leave as it is.  Returns the value in force."""
+    return int(lib().mm3d_debug_icp_robust_split(int(split)))
 
 
 def feature_lds_cap(cap):
@@ -898,6 +939,24 @@ class Context:
         o = IcpRejectionOptions()
         self._ck(lib().mm3d_get_icp_rejection(self._h, C.byref(o)))
         return o
+
+    def setIcpRobust(self, options=None, **kw):
+        """mm3d_set_icp_robust: the robust kernel that weights the correspondences of the pair stage's ICP.  An IcpRobustOptions, or
+        its fields as keywords (kernel=RobustKernel.GEMAN_MCCLURE ..., scale=..., scale_start=..., anneal=..., tuning=...)."""
+        o = options if options is not None else IcpRobustOptions(**kw)
+        self._ck(lib().mm3d_set_icp_robust(self._h, C.byref(o)))
+
+    def getIcpRobust(self) -> "IcpRobustOptions":
+        o = IcpRobustOptions()
+        self._ck(lib().mm3d_get_icp_robust(self._h, C.byref(o)))
+        return o
+
+    @property
+    def last_icp_robust_stats(self) -> dict:
+        """mm3d_last_icp_robust_stats: the last iteration of the most recent robust ICP this context ran."""
+        st = IcpRobustStats()
+        self._ck(lib().mm3d_last_icp_robust_stats(self._h, C.byref(st)))
+        return st.as_dict()
 
     def setIcpColor(self, options=None, **kw):
         """mm3d_set_icp_color: coloured ICP in the pair stage.  An IcpColorOptions, or its fields as keywords (enabled=0 / 1,
@@ -1256,6 +1315,22 @@ class Context:
         self.last_icp_converged = lib().mm3d_last_icp_converged(self._h)
         return _Tout(T)
 
+    def estimateTransformICPRobust(self, source_points, target_points, target_normals, initial_guess, max_correspondence_distance,
+                                   options=None, max_iterations=100, transformation_epsilon=0.0, **kw):
+        """mm3d_estimate_transform_icp_robust: ICP with a robust kernel from initial_guess, whatever the context's setting.
+        target_normals None: the point-to-point estimate, else the point-to-plane one."""
+        o = options if options is not None else IcpRobustOptions(**kw)
+        g = _T(initial_guess)
+        T = np.zeros(16, dtype=np.float32)
+        st = IcpRobustStats()
+        self._ck(lib().mm3d_estimate_transform_icp_robust(
+            self._h, source_points._h, target_points._h, target_normals._h if target_normals is not None else None,
+            g.ctypes.data_as(C.c_void_p), C.c_double(max_correspondence_distance), C.byref(o), int(max_iterations),
+            C.c_double(transformation_epsilon), T.ctypes.data_as(C.c_void_p), C.byref(st)))
+        self.last_icp_iterations = lib().mm3d_last_icp_iterations(self._h)
+        self.last_icp_converged = lib().mm3d_last_icp_converged(self._h)
+        return _Tout(T)
+
     def estimateTransformICPColor(self, source_points, target_points, target_normals, initial_guess, max_correspondence_distance,
                                   options=None, max_iterations=100, transformation_epsilon=0.0, **kw):
         """mm3d_estimate_transform_icp_color: coloured ICP from initial_guess, whatever the context's setting and options.enabled
@@ -1501,6 +1576,25 @@ class Context:
                                                 idx.ctypes.data_as(C.c_void_p), d2.ctypes.data_as(C.c_void_p),
                                                 kept.ctypes.data_as(C.c_void_p), C.byref(st)))
         return idx[:n], d2[:n], kept[:n].astype(bool), st.as_dict()
+
+    def debugIcpRobust(self, source_points, target_points, target_normals, transform, max_correspondence_distance, options=None, k=0,
+                       split=1, **kw):
+        """mm3d_debug_icp_robust: iteration k's search, weights and sums at `transform`, without the finalize.  Returns (idx
+        int32[n], d2 float32[n], weight float64[n], sums float64[19 or 32], stats dict) in the source's own order."""
+        o = options if options is not None else IcpRobustOptions(**kw)
+        n = len(source_points)
+        idx = np.zeros(max(n, 1), dtype=np.int32)
+        d2 = np.zeros(max(n, 1), dtype=np.float32)
+        w = np.zeros(max(n, 1), dtype=np.float64)
+        sums = np.zeros(32 if target_normals is not None else 19, dtype=np.float64)
+        t = _T(transform)
+        st = IcpRobustStats()
+        self._ck(lib().mm3d_debug_icp_robust(self._h, source_points._h, target_points._h,
+                                             target_normals._h if target_normals is not None else None, t.ctypes.data_as(C.c_void_p),
+                                             C.c_double(max_correspondence_distance), C.byref(o), int(k), int(split),
+                                             idx.ctypes.data_as(C.c_void_p), d2.ctypes.data_as(C.c_void_p), w.ctypes.data_as(C.c_void_p),
+                                             sums.ctypes.data_as(C.c_void_p), C.byref(st)))
+        return idx[:n], d2[:n], w[:n], sums, st.as_dict()
 
     def transformScore(self, source_points, target_points, transform, max_distance) -> float:
         t = _T(transform)

@@ -36,6 +36,7 @@ mm3d::StageSelection::StageSelection()
   mm3d_coarse_options_default(&coarse_options);
   mm3d_confidence_options_default(&confidence_options);
   mm3d_icp_rejection_options_default(&reject_options);
+  mm3d_icp_robust_options_default(&robust_options);
   mm3d_icp_color_options_default(&color_options);
   mm3d_icp_generalized_options_default(&generalized_options);
   mm3d_estimator_options_default(&estimator_options);
@@ -197,6 +198,10 @@ void mm3d_confidence_options_default(mm3d_confidence_options *o)
 void mm3d_icp_rejection_options_default(mm3d_icp_rejection_options *o)
 {
   if (o) *o = mm3d_icp_rejection_options{0, MM3D_REJECT_NONE, 0.5, 0, 1.0};
+}
+void mm3d_icp_robust_options_default(mm3d_icp_robust_options *o)
+{
+  if (o) *o = mm3d_icp_robust_options{MM3D_ROBUST_OFF, 0.05, 0.0, 0.5, 0.0};
 }
 void mm3d_icp_color_options_default(mm3d_icp_color_options *o)
 {

@@ -389,6 +389,10 @@ int mm3d_set_icp_color(mm3d_ctx *ctx, const mm3d_icp_color_options *options)
       ctx->err = "mm3d_set_icp_color: not available while generalized ICP is enabled (mm3d_set_icp_generalized)";
       return MM3D_EUNSUPPORTED;
     }
+    if (ctx->sel.robust()) {                          // (the robust step has no colour variant)
+      ctx->err = "mm3d_set_icp_color: not available while a robust kernel is selected (mm3d_set_icp_robust)";
+      return MM3D_EUNSUPPORTED;
+    }
     if (ctx->sel.sampler) {                           // (the colour term reads the source's own records by index)
       ctx->err = "mm3d_set_icp_color: not available while an ICP source sampling is set (mm3d_set_icp_sampling)";
       return MM3D_EUNSUPPORTED;

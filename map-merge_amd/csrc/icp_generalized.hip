@@ -275,6 +275,10 @@ int mm3d_set_icp_generalized(mm3d_ctx *ctx, const mm3d_icp_generalized_options *
       ctx->err = "mm3d_set_icp_generalized: not available while coloured ICP is enabled (mm3d_set_icp_color)";
       return MM3D_EUNSUPPORTED;
     }
+    if (ctx->sel.robust()) {                          // (the robust step has no plane-to-plane variant)
+      ctx->err = "mm3d_set_icp_generalized: not available while a robust kernel is selected (mm3d_set_icp_robust)";
+      return MM3D_EUNSUPPORTED;
+    }
     if (ctx->sel.sampler) {                           // (the source's normals are indexed by the source's own order)
       ctx->err = "mm3d_set_icp_generalized: not available while an ICP source sampling is set (mm3d_set_icp_sampling)";
       return MM3D_EUNSUPPORTED;

@@ -562,6 +562,10 @@ int mm3d_set_icp_rejection(mm3d_ctx *ctx, const mm3d_icp_rejection_options *opti
     ctx->err = "mm3d_set_icp_rejection: not available while generalized ICP is enabled (mm3d_set_icp_generalized)";
     return MM3D_EUNSUPPORTED;
   }
+  if (active && ctx->sel.robust()) {      // (the robust step weights every match: it has no correspondence stage)
+    ctx->err = "mm3d_set_icp_rejection: not available while a robust kernel is selected (mm3d_set_icp_robust)";
+    return MM3D_EUNSUPPORTED;
+  }
   select_stages(ctx, false, [&](StageSelection &s) { s.reject_options = *options; });
   return MM3D_OK;
 }

@@ -1,0 +1,564 @@
+// icp_robust.hip -- a robust loss for the pair stage's ICP, opt-in (mm3d_set_icp_robust): every matched correspondence enters the
+// point-to-point or point-to-plane estimate with an M-estimator weight of its Euclidean d2 (L2, Huber, Cauchy, Tukey,
+// Geman-McClure) at a scale that is fixed BEFORE the iteration runs.  include/mm3d.h states the rule.
+//
+// The rejectors of icp_reject.hip need an order statistic of the iteration's own d2, so their iteration is a correspondence
+// stage of eight launches.  A weight at a known scale needs nothing but the lane's own match, so here the iteration keeps the
+// default ICP's two launches:
+//   k_rob_wave      nn_search_body.hpp's wave-cooperative search (the same include as k_nn_wave<0> and k_icp_plane_wave); the
+//                   scale sigma_k from the batch's table at the pair's st->iters; the lane's weight in double (one divide for u2,
+//                   one more for the reciprocal of Huber, Cauchy and Geman-McClure); the default kernels' terms, each times w,
+//                   through wave_sum and the block step into partials of the step's own width: the default layout plus
+//                   `matched` and `weighted` (19 doubles, or 32 with normals), in the default kernels' order.
+//   k_rob_finalize  one block per pair: the partials in k_icp_finalize's fixed order, Umeyama or the 6x6 solve on totals that
+//                   sum w normalises, Tinc, and the convergence tail behind the final_k gate.  The tails are copies of
+//                   k_icp_finalize's and k_icp_plane_finalize's (-ffp-contract=off: the same expressions round the same way), so
+//                   those two kernels are untouched and with L2 (w = 1.0, x * 1.0 = x) the state holds the default ICP's bits.
+// No correspondence array, no histogram, no select; per batch one table of doubles, per pair one 32-byte record.
+#include <atomic>
+#include <climits>
+#include <cmath>
+
+#include "capi_guard.hpp"
+#include "drivers.hpp"
+#include "icp_solve6.hpp"
+#include "nn_core.hpp"
+
+namespace mm3d {
+
+constexpr int kRobAcc = kAcc + 2;             // k_nn_wave<0>'s 17 (the count slot holds sum w) | matched | weighted
+constexpr int kRobPlaneAcc = kPlaneAcc + 2;   // k_icp_plane_wave's 30 (28: sum w, 29: rows with w > 0) | matched | weighted
+
+// What one pair's last iteration leaves behind, on the device beside the pair's IcpState and back on the host in the copy that
+// brings the states
+struct RobRecord {
+  double weight_sum, sigma;
+  long long matched, weighted;
+};
+// the search job plus what the robust step reads and writes beside it; nn.partials: [nblocks][kRobAcc], or [nblocks][kRobPlaneAcc]
+struct NnRobustJob {
+  NnJob nn;
+  const float4 *nrm;          // point-to-plane: the target's normals (tgt_ref's order); null: point-to-point
+  RobRecord *rec;
+  // mm3d_debug_icp_robust: every valid lane's match and weight, stored at the source point's ORIGINAL index; null otherwise
+  int *out_idx;
+  float *out_d2;
+  double *out_w;
+};
+// the options as the kernels take them: the kernel, its tuning constant resolved, the scale the run ends on, and the table
+struct RobOpts {
+  int kernel;
+  double tuning, scale;
+  const double *sigma;        // [n_sigma]: sigma_k for k < n_sigma, and sigma_{n_sigma - 1} from there on
+  int n_sigma;
+};
+
+__device__ __forceinline__ double rob_sigma(const RobOpts &o, int k) { return o.sigma[k < o.n_sigma ? k : o.n_sigma - 1]; }
+
+// step 3 of the rule.  h2 = (sigma_k tuning)^2.  Two divides stand in the code: u2's and the reciprocal's.
+__device__ __forceinline__ double rob_weight(int kernel, double d2, double h2)
+{
+  if (kernel == MM3D_ROBUST_L2) return 1.0;
+  const double u2 = d2 / h2;
+  if (kernel == MM3D_ROBUST_TUKEY) {
+    const double a = 1.0 - u2;
+    return u2 < 1.0 ? a * a : 0.0;
+  }
+  if (kernel == MM3D_ROBUST_HUBER && u2 <= 1.0) return 1.0;
+  const double b = 1.0 + u2;
+  const double den = kernel == MM3D_ROBUST_HUBER ? sqrt(u2) : kernel == MM3D_ROBUST_CAUCHY ? b : b * b;
+  return 1.0 / den;
+}
+
+template <int SPLIT, bool PLANE>
+__global__ void __launch_bounds__(256) MM3D_NN_ATTR
+k_rob_wave(const NnRobustJob *__restrict__ rjobs, RobOpts o, float max_d2, float rmax)
+{
+  constexpr int MODE = 0;                                // (nn_search_body.hpp: the keyed search, with the winner's index)
+  constexpr int NACC = PLANE ? kRobPlaneAcc : kRobAcc;
+  const NnRobustJob &rj = rjobs[blockIdx.y];
+  const NnJob &job = rj.nn;
+  if ((int)blockIdx.x >= job.nblocks) return;            // the grid is as wide as the batch's largest job
+  const float4 *__restrict__ src = job.src;
+  const int2 *__restrict__ items = job.items;
+  const int n_items = job.n_items;
+  const GridView g = job.g;
+  const float4 *__restrict__ tgt_ref = job.tgt_ref;
+  const float4 *__restrict__ nrm = rj.nrm;
+  const IcpState *__restrict__ st = job.st;
+  double *__restrict__ partials = job.partials;
+  const int max_ring = job.max_ring;
+  __shared__ float Ts[16];
+  __shared__ double red[4][NACC];
+  __shared__ __attribute__((aligned(16))) float s_cx[4][kTile], s_cy[4][kTile], s_cz[4][kTile];
+  __shared__ __attribute__((aligned(16))) unsigned s_cw[4][kTile];
+  __shared__ int s_off[4][kRows];
+  __shared__ int s_beg[4][kRows];
+  __shared__ unsigned long long s_merge[SPLIT == 4 ? 4 : 1][64];
+  if (st->done) return;
+  if (threadIdx.x < 16) Ts[threadIdx.x] = st->T[threadIdx.x];
+  __syncthreads();
+#include "nn_search_body.hpp"
+  if (SPLIT == 4 && wave != 0) return;     // the four waves hold the same result
+  const bool corr = valid && best <= max_d2;   // false for INFINITY / NaN
+  // the iteration's scale (block-uniform: the state is written by the finalize launch only)
+  const double h = rob_sigma(o, st->iters) * o.tuning, h2 = h * h;
+  const unsigned widx = (unsigned)(bkey & 0xffffffffull);
+  const double w = corr ? rob_weight(o.kernel, (double)best, h2) : 0.0;
+  const bool pos = w > 0.0;
+  if (rj.out_idx && valid) {
+    const int orig = __float_as_int(src[i].w);
+    rj.out_idx[orig] = corr ? (int)widx : -1;
+    rj.out_d2[orig] = corr ? best : INFINITY;
+    rj.out_w[orig] = w;
+  }
+  // one term at a time (formed, summed over the wave, stored), as k_icp_plane_wave does: the weight's divides share the
+  // registers the search has left
+  float bqx = 0.f, bqy = 0.f, bqz = 0.f;
+  double v[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  double r = 0.0, has_row = 0.0;
+  if (corr) {
+    if (!PLANE) {
+      const float4 bq = tgt_ref[widx];
+      bqx = bq.x; bqy = bq.y; bqz = bq.z;
+    } else {
+      const float4 n = nrm[widx];
+      if (isfinite(n.x) && isfinite(n.y) && isfinite(n.z)) {
+        const float4 d = tgt_ref[widx];
+        const double sx = p.x, sy = p.y, sz = p.z, nx = n.x, ny = n.y, nz = n.z;
+        v[0] = nz * sy - ny * sz;
+        v[1] = nx * sz - nz * sx;
+        v[2] = ny * sx - nx * sy;
+        v[3] = nx; v[4] = ny; v[5] = nz;
+        r = (nx * (double)d.x + ny * (double)d.y + nz * (double)d.z) - (nx * sx + ny * sy + nz * sz);
+        has_row = pos ? 1.0 : 0.0;
+      }
+    }
+  }
+  auto term = [&](int k) -> double {
+    if (k == NACC - 2) return corr ? 1.0 : 0.0;
+    if (k == NACC - 1) return pos ? 1.0 : 0.0;
+    if (!PLANE) {
+      // k_nn_wave<0>'s terms, times w
+      const float pc = (k % 3 == 0) ? p.x : (k % 3 == 1) ? p.y : p.z;
+      if (k < 3) return w * (double)pc;
+      if (k < 6) return w * (double)(k == 3 ? bqx : k == 4 ? bqy : bqz);
+      if (k < 15) return w * ((double)(k < 9 ? bqx : k < 12 ? bqy : bqz) * pc);
+      if (k == 15) return corr ? w * (double)best : 0.0;      // (best is +inf without a match)
+      return w;
+    }
+    // k_icp_plane_wave's terms, times w
+    if (k < 21) return w * (v[kUi[k]] * v[kUj[k]]);
+    if (k < 27) return w * (v[k - 21] * r);
+    if (k == 27) return corr ? w * (double)best : 0.0;
+    if (k == 28) return w;
+    return has_row;
+  };
+  // a wave none of whose points found a neighbour in range adds zeros without the reductions (as k_nn_wave does)
+  const bool any_corr = ballot(corr) != 0ull;       // wave-uniform
+  if (SPLIT == 4) {
+#pragma unroll
+    for (int k = 0; k < NACC; ++k) {
+      const double s = any_corr ? wave_sum(term(k)) : 0.0;
+      if (lane == 0) partials[(size_t)bid * NACC + k] = s;
+    }
+    return;
+  }
+#pragma unroll
+  for (int k = 0; k < NACC; ++k) {
+    const double s = any_corr ? wave_sum(term(k)) : 0.0;
+    if (lane == 0) red[wave][k] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x < NACC) {
+    const int k = threadIdx.x;
+    partials[(size_t)bid * NACC + k] = red[0][k] + red[1][k] + red[2][k] + red[3][k];
+  }
+}
+
+// the pair's totals in k_icp_finalize's order: a thread's blocks b = t, t + 256, ..., the wave, the four waves.  By all 256
+// threads of a block; tot is valid for every thread afterwards.
+template <int NACC>
+__device__ __forceinline__ void rob_totals(const NnJob &job, double (*red)[NACC], double *tot)
+{
+  const double *__restrict__ partials = job.partials;
+  const int split = job.split, n_items = job.n_items;
+  const int nblocks = (n_items + 3) >> 2;              // in units of four items, whichever kernel variant wrote them
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int k = 0; k < NACC; ++k) {
+    double acc = 0.0;
+    for (int b = threadIdx.x; b < nblocks; b += blockDim.x) acc += nn_block_partial_n<NACC>(partials, b, k, split, n_items);
+    const double s = wave_sum(acc);
+    if (lane == 0) red[wave][k] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x < NACC) tot[threadIdx.x] = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
+  __syncthreads();
+}
+
+// mm3d_debug_icp_robust: the totals the finalize kernel would read
+template <int NACC>
+__global__ void __launch_bounds__(256) k_rob_totals(const NnRobustJob *__restrict__ rjobs, double *__restrict__ out)
+{
+  __shared__ double red[4][NACC];
+  __shared__ double tot[NACC];
+  rob_totals<NACC>(rjobs[0].nn, red, tot);
+  if (threadIdx.x < NACC) out[threadIdx.x] = tot[threadIdx.x];
+}
+
+// final = Tinc * final, the iteration count and DefaultConvergenceCriteria::hasConverged behind the final_k gate: the tail of
+// k_icp_finalize and k_icp_plane_finalize.  One thread.
+__device__ __forceinline__ void rob_tail(IcpState *st, const float *Ti, bool final_k, double mse)
+{
+  float Tn[16];
+  for (int c = 0; c < 4; ++c)
+    for (int r = 0; r < 4; ++r) {
+      float a = 0.0f;
+      for (int k = 0; k < 4; ++k) a += Ti[k * 4 + r] * st->T[c * 4 + k];
+      Tn[c * 4 + r] = a;
+    }
+  for (int i = 0; i < 16; ++i) { st->T[i] = Tn[i]; st->Tinc[i] = Ti[i]; }
+  const int iters = ++st->iters;
+  if (iters >= st->max_iter) { st->converged = 1; st->done = 1; return; }
+  if (!final_k) return;      // (an annealing run does not stop on a scale it is about to leave)
+  const double cos_angle = 0.5 * ((double)Ti[0] + (double)Ti[5] + (double)Ti[10] - 1.0);
+  const double translation_sqr = (double)Ti[12] * Ti[12] + (double)Ti[13] * Ti[13] + (double)Ti[14] * Ti[14];
+  if (cos_angle >= st->rot_thresh && translation_sqr <= st->trans_thresh) { st->converged = 1; st->done = 1; return; }
+  if (fabs(mse - st->prev_mse) < 1e-12) { st->converged = 1; st->done = 1; return; }
+  st->prev_mse = mse;
+}
+
+template <bool PLANE>
+__global__ void __launch_bounds__(256) k_rob_finalize(const NnRobustJob *__restrict__ rjobs, RobOpts o)
+{
+  constexpr int NACC = PLANE ? kRobPlaneAcc : kRobAcc;
+  __shared__ double red[4][NACC];
+  __shared__ double tot[NACC];
+  const NnRobustJob &rj = rjobs[blockIdx.x];
+  IcpState *st = rj.nn.st;
+  if (st->done) return;
+  rob_totals<NACC>(rj.nn, red, tot);
+  if (threadIdx.x != 0) return;
+
+  const double sigma = rob_sigma(o, st->iters);
+  const bool final_k = sigma == o.scale;
+  const double wsum = tot[PLANE ? 28 : 16], weighted = tot[NACC - 1];
+  *rj.rec = RobRecord{wsum, sigma, (long long)tot[NACC - 2], (long long)weighted};
+  st->n_corr = (int)weighted;
+  if (weighted < 3.0) {   // min_number_correspondences_: "Not enough correspondences" -> not converged, stop
+    st->converged = 0;
+    st->done = 1;
+    return;
+  }
+  float Ti[16];
+  double mse;
+  if (!PLANE) {
+    // k_icp_finalize's Umeyama on the moments that sum w normalises
+    const double inv = 1.0 / wsum;
+    double mp[3] = {tot[0] * inv, tot[1] * inv, tot[2] * inv}, mq[3] = {tot[3] * inv, tot[4] * inv, tot[5] * inv};
+    double sg[9];
+    for (int r = 0; r < 3; ++r)
+      for (int c = 0; c < 3; ++c) sg[r * 3 + c] = tot[6 + r * 3 + c] * inv - mq[r] * mp[c];
+    double U[9], S[3], V[9];
+    svd3_shared(sg, U, S, V);
+    double Sd[3] = {1.0, 1.0, 1.0};
+    if (det3_shared(sg) < 0) Sd[2] = -1.0;
+    int rank = 0;
+    for (int i = 0; i < 3; ++i)
+      if (!(fabs(S[i]) <= fabs(S[0]) * 1e-5)) ++rank;
+    if (rank == 2) Sd[2] = (det3_shared(U) * det3_shared(V) > 0) ? 1.0 : -1.0;
+    for (int r = 0; r < 3; ++r)
+      for (int c = 0; c < 3; ++c) {
+        double a = 0;
+        for (int k = 0; k < 3; ++k) a += U[r * 3 + k] * Sd[k] * V[c * 3 + k];
+        Ti[c * 4 + r] = (float)a;
+      }
+    for (int r = 0; r < 3; ++r) {
+      const double a = mq[r] - ((double)Ti[0 * 4 + r] * mp[0] + (double)Ti[1 * 4 + r] * mp[1] + (double)Ti[2 * 4 + r] * mp[2]);
+      Ti[12 + r] = (float)a;
+    }
+    mse = tot[15] * inv;
+  } else {
+    // k_icp_plane_finalize's 6x6 system (a system scaled by sum w has the same solution: nothing is normalised)
+    double A[36], b[6], x[6];
+    for (int k = 0; k < 21; ++k) A[kUi[k] * 6 + kUj[k]] = A[kUj[k] * 6 + kUi[k]] = tot[k];
+    for (int i = 0; i < 6; ++i) b[i] = tot[21 + i];
+    const double trace = A[0] + A[7] + A[14] + A[21] + A[28] + A[35];
+    if (tot[29] < 6.0 || !solve6_ldlt(A, b, kPlanePivotTau * trace / 6.0, x)) {
+      // degenerate (fewer than six weighted rows, or a plane / line that leaves a direction free): stop, not converged, T unchanged
+      st->converged = 0;
+      st->done = 1;
+      return;
+    }
+    const double sa = sin(x[0]), ca = cos(x[0]), sb = sin(x[1]), cb = cos(x[1]), sgm = sin(x[2]), cg = cos(x[2]);
+    const double R[9] = {cg * cb, -sgm * ca + cg * sb * sa, sgm * sa + cg * sb * ca,
+                         sgm * cb, cg * ca + sgm * sb * sa, -cg * sa + sgm * sb * ca,
+                         -sb, cb * sa, cb * ca};
+    for (int rr = 0; rr < 3; ++rr)
+      for (int c = 0; c < 3; ++c) Ti[c * 4 + rr] = (float)R[rr * 3 + c];
+    Ti[12] = (float)x[3]; Ti[13] = (float)x[4]; Ti[14] = (float)x[5];
+    mse = tot[27] / wsum;
+  }
+  Ti[3] = Ti[7] = Ti[11] = 0.0f;
+  Ti[15] = 1.0f;
+  rob_tail(st, Ti, final_k, mse);
+}
+
+static double rob_tuning(const mm3d_icp_robust_options &o)
+{
+  if (o.tuning != 0.0) return o.tuning;
+  return o.kernel == MM3D_ROBUST_HUBER ? 1.345 : o.kernel == MM3D_ROBUST_CAUCHY ? 2.385 : o.kernel == MM3D_ROBUST_TUKEY ? 4.685 : 1.0;
+}
+
+// Step 2 of the rule: sigma_k = max(scale, s_k), s_0 = scale_start, s_{k+1} = s_k * anneal, for k < max_iterations -- cut where the
+// rest is constant (sigma_k has reached `scale`, or s_k no longer moves): the kernels read the last entry from there on.
+static std::vector<double> rob_table(const mm3d_icp_robust_options &o, int max_iterations)
+{
+  const bool scaled = o.kernel != MM3D_ROBUST_OFF && o.kernel != MM3D_ROBUST_L2;      // (L2 reads no scale: every iteration is final)
+  std::vector<double> t;
+  double s = scaled ? o.scale_start : 0.0;
+  for (int k = 0; k < std::max(max_iterations, 1); ++k) {
+    const double sigma = std::max(o.scale, s);
+    t.push_back(sigma);
+    const double next = s * o.anneal;
+    if (sigma == o.scale || next == s) break;
+    s = next;
+  }
+  return t;
+}
+
+static bool icp_robust_options_valid(const mm3d_icp_robust_options *o)
+{
+  if (o->kernel < MM3D_ROBUST_OFF || o->kernel > MM3D_ROBUST_GEMAN_MCCLURE) return false;
+  if (!(o->scale > 0.0) || !std::isfinite(o->scale)) return false;
+  if (!(o->scale_start == 0.0 || (o->scale_start >= o->scale && std::isfinite(o->scale_start)))) return false;
+  if (!(o->anneal > 0.0 && o->anneal <= 1.0)) return false;
+  if (!(o->tuning >= 0.0) || !std::isfinite(o->tuning)) return false;
+  // (h * h must be a positive finite double at both ends of the schedule: u2 = d2 / (h * h))
+  const double t = rob_tuning(*o), h0 = o->scale * t, h1 = std::max(o->scale, o->scale_start) * t;
+  return h0 * h0 > 0.0 && std::isfinite(h1 * h1);
+}
+
+static mm3d_icp_robust_stats rob_stats(const RobRecord &r, int iterations, int converged)
+{
+  return mm3d_icp_robust_stats{r.matched, r.weighted, r.weight_sum, r.sigma, iterations, converged};
+}
+
+static void launch_rob_wave(Context *c, const NnRobustJob *jobs_dev, const RobOpts &o, bool plane, int count, unsigned grid_x, bool split,
+                            float max_d2, float rmax, double bytes)
+{
+  const dim3 grid(grid_x, count);
+  if (split && plane) MM3D_LAUNCH(c, "icp_robust_corr_reduce", bytes, (k_rob_wave<4, true>), grid, dim3(256), 0, jobs_dev, o, max_d2, rmax);
+  else if (split) MM3D_LAUNCH(c, "icp_robust_corr_reduce", bytes, (k_rob_wave<4, false>), grid, dim3(256), 0, jobs_dev, o, max_d2, rmax);
+  else if (plane) MM3D_LAUNCH(c, "icp_robust_corr_reduce", bytes, (k_rob_wave<1, true>), grid, dim3(256), 0, jobs_dev, o, max_d2, rmax);
+  else MM3D_LAUNCH(c, "icp_robust_corr_reduce", bytes, (k_rob_wave<1, false>), grid, dim3(256), 0, jobs_dev, o, max_d2, rmax);
+}
+
+static std::atomic<int> g_forced_split{0};      // mm3d_debug_icp_robust_split: 0 (by size), 1 or 4
+
+namespace {
+// One iteration: the fused search / weight / reduce launch over the batch's NnRobustJobs and the robust finalize.  The pairs'
+// records ride behind the states; the table of scales sits behind the jobs in the pinned block and is uploaded with them.
+struct RobustStep final : IcpStep {
+  const mm3d_icp_robust_options opt;
+  const bool plane;
+  const std::vector<double> table;
+  StepJobs<NnRobustJob> jobs;
+  DevBuf<double> sigma;
+  double *sigma_host = nullptr;
+  RobRecord *rec_host = nullptr, *rec_dev = nullptr;
+  RobustStep(const mm3d_icp_robust_options &o, bool normals, int max_iterations) : opt(o), plane(normals), table(rob_table(o, max_iterations))
+  {
+    acc = plane ? kRobPlaneAcc : kRobAcc;
+    forced_split = g_forced_split.load();
+  }
+  RobOpts opts() const
+  {
+    return RobOpts{opt.kernel == MM3D_ROBUST_OFF ? (int)MM3D_ROBUST_L2 : opt.kernel, rob_tuning(opt), opt.scale, sigma.get(), (int)table.size()};
+  }
+  double bytes_per_point(const IcpScoreJob &) const override { return plane ? 28.0 : 12.0; }
+  void check(const IcpScoreJob &J) const override { if (plane) icp_plane_check(J); }
+  size_t pinned_bytes(int B) const override { return jobs.bytes(B) + ((table.size() * sizeof(double) + 15) & ~(size_t)15); }
+  size_t record_bytes(int B) const override { return sizeof(RobRecord) * B; }
+  void begin(Context *c, const IcpScoreJob *const *, int B, char *pinned, void *rh, void *rd) override
+  {
+    sigma_host = (double *)jobs.begin(c, B, pinned);
+    std::memcpy(sigma_host, table.data(), table.size() * sizeof(double));
+    sigma = DevBuf<double>(c, table.size());
+    rec_host = (RobRecord *)rh;
+    rec_dev = (RobRecord *)rd;
+  }
+  void bind(int b, const NnJob &q, const IcpScoreJob &J) override
+  {
+    jobs.host[b] = NnRobustJob{q, plane ? (const float4 *)J.tgt_normals->nrm.get() : nullptr, rec_dev + b, nullptr, nullptr, nullptr};
+    rec_host[b] = RobRecord{0.0, 0.0, 0, 0};
+  }
+  void upload(Context *c) override
+  {
+    jobs.upload(c);
+    MM3D_HIP(hipMemcpyAsync(sigma.get(), sigma_host, table.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  }
+  void iterate(Context *c, const IcpLaunch &L) override
+  {
+    const RobOpts o = opts();
+    launch_rob_wave(c, jobs.dev.get(), o, plane, L.count, L.grid_x, L.split, L.max_d2, L.rmax, L.bytes);
+    if (plane) MM3D_LAUNCH(c, "icp_robust_finalize", L.finalize_bytes, k_rob_finalize<true>, dim3(L.count), dim3(256), 0, (const NnRobustJob *)jobs.dev.get(), o);
+    else MM3D_LAUNCH(c, "icp_robust_finalize", L.finalize_bytes, k_rob_finalize<false>, dim3(L.count), dim3(256), 0, (const NnRobustJob *)jobs.dev.get(), o);
+  }
+  void close(int b, const IcpState &h, IcpScoreJob &J) override { J.robust_stats = rob_stats(rec_host[b], h.iters, h.converged); }
+};
+}  // namespace
+
+std::unique_ptr<IcpStep> icp_robust_step(const mm3d_icp_robust_options &opt, bool normals, int max_iterations)
+{
+  return std::unique_ptr<IcpStep>(new RobustStep(opt, normals, max_iterations));
+}
+
+// mm3d_debug_icp_robust: the search set-up as icp_batch derives it, iteration k's k_rob_wave at T with the split forced, every
+// source point's match and weight at its original index, and the totals as the finalize would read them
+static void debug_icp_robust(Context *c, const mm3d_cloud *src, const mm3d_cloud *tgt, const mm3d_normals *nrm, const float T[16],
+                             double max_corr_dist, const mm3d_icp_robust_options &opt, int k, int split, int *idx, float *d2, double *weight,
+                             double *sums, mm3d_icp_robust_stats *stats)
+{
+  const NnRange r = nn_range_icp(max_corr_dist);
+  const bool plane = nrm != nullptr;
+  const int nacc = plane ? kRobPlaneAcc : kRobAcc;
+  const std::vector<double> table = rob_table(opt, k < INT_MAX ? k + 1 : k);
+  const double sigma_k = table[std::min((size_t)k, table.size() - 1)];
+  mm3d_icp_robust_stats S{0, 0, 0.0, sigma_k, 0, 0};
+  std::vector<int> h_idx(src->n, -1);
+  std::vector<float> h_d2(src->n, INFINITY);
+  std::vector<double> h_w(src->n, 0.0), h_sums(nacc, 0.0);
+  const NnSearch s = nn_search(c, src, tgt, &r);
+  if (s.grid) {
+    const unsigned nblocks = nn_blocks(s.n_items, split == 4);
+    DevBuf<int> d_idx(c, src->n);
+    DevBuf<float> d_d2(c, src->n);
+    DevBuf<double> d_w(c, src->n), d_sums(c, nacc), d_sigma(c, table.size()), partials(c, (size_t)nblocks * nacc);
+    DevBuf<IcpState> st(c, 1);
+    DevBuf<NnRobustJob> d_job(c, 1);
+    const size_t table_bytes = table.size() * sizeof(double);
+    char *pinned = (char *)c->pin(sizeof(IcpState) + sizeof(NnRobustJob) + table_bytes + (size_t)nacc * sizeof(double) + 64);
+    IcpState *hs = (IcpState *)pinned;
+    NnRobustJob *hj = (NnRobustJob *)(hs + 1);
+    double *ht = (double *)(hj + 1), *hsum = ht + table.size();
+    std::memset(hs, 0, sizeof(IcpState));
+    std::memcpy(hs->T, T, 64);
+    hs->iters = k;
+    std::memcpy(ht, table.data(), table_bytes);
+    *hj = NnRobustJob{nn_job(s, split == 4, nblocks, st.get(), nullptr, partials.get(), nullptr), plane ? (const float4 *)nrm->nrm.get() : nullptr,
+                      nullptr, d_idx.get(), d_d2.get(), d_w.get()};
+    // (non-finite source points are in no work item: they keep -1 / +inf / 0)
+    MM3D_HIP(hipMemcpyAsync(d_idx.get(), h_idx.data(), src->n * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    MM3D_HIP(hipMemcpyAsync(d_d2.get(), h_d2.data(), src->n * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    MM3D_HIP(hipMemsetAsync(d_w.get(), 0, src->n * sizeof(double), c->stream));
+    MM3D_HIP(hipMemcpyAsync(st.get(), hs, sizeof(IcpState), hipMemcpyHostToDevice, c->stream));
+    MM3D_HIP(hipMemcpyAsync(d_job.get(), hj, sizeof(NnRobustJob), hipMemcpyHostToDevice, c->stream));
+    MM3D_HIP(hipMemcpyAsync(d_sigma.get(), ht, table_bytes, hipMemcpyHostToDevice, c->stream));
+    const RobOpts o{opt.kernel == MM3D_ROBUST_OFF ? (int)MM3D_ROBUST_L2 : opt.kernel, rob_tuning(opt), opt.scale, d_sigma.get(), (int)table.size()};
+    launch_rob_wave(c, d_job.get(), o, plane, 1, nblocks, split == 4, r.max_d2, r.rmax, s.ns * 36.0);
+    if (plane) MM3D_LAUNCH(c, "icp_robust_totals", nblocks * nacc * 8.0, k_rob_totals<kRobPlaneAcc>, dim3(1), dim3(256), 0, (const NnRobustJob *)d_job.get(), d_sums.get());
+    else MM3D_LAUNCH(c, "icp_robust_totals", nblocks * nacc * 8.0, k_rob_totals<kRobAcc>, dim3(1), dim3(256), 0, (const NnRobustJob *)d_job.get(), d_sums.get());
+    MM3D_HIP(hipMemcpyAsync(h_idx.data(), d_idx.get(), src->n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    MM3D_HIP(hipMemcpyAsync(h_d2.data(), d_d2.get(), src->n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    MM3D_HIP(hipMemcpyAsync(h_w.data(), d_w.get(), src->n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    MM3D_HIP(hipMemcpyAsync(hsum, d_sums.get(), (size_t)nacc * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    c->sync();
+    std::memcpy(h_sums.data(), hsum, (size_t)nacc * sizeof(double));
+    S.matched = (long long)h_sums[nacc - 2];
+    S.weighted = (long long)h_sums[nacc - 1];
+    S.weight_sum = h_sums[plane ? 28 : 16];
+  }
+  if (src->n) {
+    std::memcpy(idx, h_idx.data(), src->n * sizeof(int));
+    std::memcpy(d2, h_d2.data(), src->n * sizeof(float));
+    std::memcpy(weight, h_w.data(), src->n * sizeof(double));
+  }
+  if (sums) std::memcpy(sums, h_sums.data(), (size_t)nacc * sizeof(double));
+  if (stats) *stats = S;
+}
+
+}  // namespace mm3d
+
+using namespace mm3d;
+
+extern "C" {
+
+int mm3d_set_icp_robust(mm3d_ctx *ctx, const mm3d_icp_robust_options *options)
+{
+  if (!ctx || !options || !icp_robust_options_valid(options)) return MM3D_EINVAL;
+  std::lock_guard<std::mutex> lock(ctx->mu);        // (no call is running while the selection changes)
+  const bool active = options->kernel != MM3D_ROBUST_OFF;
+  if (active && refused_on_device_list(ctx, "mm3d_set_icp_robust: not available on a device-list context")) return MM3D_EUNSUPPORTED;
+  const char *other = !active ? nullptr
+                      : ctx->sel.rejecting() ? "a correspondence rejection is active (mm3d_set_icp_rejection)"
+                      : ctx->sel.color       ? "coloured ICP is enabled (mm3d_set_icp_color)"
+                      : ctx->sel.generalized ? "generalized ICP is enabled (mm3d_set_icp_generalized)"
+                      : ctx->sel.refine      ? "NDT is selected (mm3d_set_refinement)"
+                                             : nullptr;
+  if (other) {      // (k_rob_wave has point-to-point's and point-to-plane's terms only)
+    ctx->err = std::string("mm3d_set_icp_robust: not available while ") + other;
+    return MM3D_EUNSUPPORTED;
+  }
+  select_stages(ctx, false, [&](StageSelection &s) { s.robust_options = *options; });
+  return MM3D_OK;
+}
+
+int mm3d_get_icp_robust(const mm3d_ctx *ctx, mm3d_icp_robust_options *options)
+{
+  if (!ctx || !options) return MM3D_EINVAL;
+  *options = ctx->sel.robust_options;
+  return MM3D_OK;
+}
+
+int mm3d_last_icp_robust_stats(const mm3d_ctx *ctx, mm3d_icp_robust_stats *stats)
+{
+  if (!ctx || !stats) return MM3D_EINVAL;
+  *stats = ctx->last_robust_stats;
+  return MM3D_OK;
+}
+
+int mm3d_estimate_transform_icp_robust(mm3d_ctx *ctx, const mm3d_cloud *source, const mm3d_cloud *target, const mm3d_normals *target_normals,
+                                       const float initial_guess[16], double max_corr_dist, const mm3d_icp_robust_options *options,
+                                       int max_iterations, double eps, float T[16], mm3d_icp_robust_stats *stats)
+{
+  if (!source || !target || !initial_guess || !options || !T || !icp_robust_options_valid(options)) return MM3D_EINVAL;
+  if (target_normals && target_normals->n != target->n) {
+    if (ctx) ctx->err = "mm3d_estimate_transform_icp_robust: the normals do not match the target's points";
+    return MM3D_EINVAL;
+  }
+  return guarded(ctx, [&] {
+    IcpScoreJob J;
+    J.src = source; J.tgt = target; J.tgt_normals = target_normals;
+    J.robust = options;
+    std::memcpy(J.guess_host, initial_guess, sizeof(J.guess_host));
+    icp_score_batch(ctx, target_normals ? icp_plane_method() : nullptr, &J, 1, true, max_corr_dist, max_iterations, eps, false, 0.0);
+    std::memcpy(T, J.out.T, sizeof(J.out.T));
+    // (a pair with nothing to search ran no iteration: its record is the empty one)
+    J.robust_stats.iterations = J.out.iterations;
+    J.robust_stats.converged = J.out.converged;
+    ctx->last_robust_stats = J.robust_stats;
+    if (stats) *stats = J.robust_stats;
+  });
+}
+
+int mm3d_debug_icp_robust_split(int split)
+{
+  if (split == 0 || split == 1 || split == 4) g_forced_split.store(split);
+  return g_forced_split.load();
+}
+
+int mm3d_debug_icp_robust(mm3d_ctx *ctx, const mm3d_cloud *source, const mm3d_cloud *target, const mm3d_normals *target_normals,
+                          const float T[16], double max_correspondence_distance, const mm3d_icp_robust_options *options, int k, int split,
+                          int *idx, float *d2, double *weight, double *sums, mm3d_icp_robust_stats *stats)
+{
+  if (!source || !target || !T || !options || !icp_robust_options_valid(options) || (split != 1 && split != 4) || k < 0) return MM3D_EINVAL;
+  if (!(max_correspondence_distance >= 0.0) || !std::isfinite(max_correspondence_distance)) return MM3D_EINVAL;
+  if (source->n && (!idx || !d2 || !weight)) return MM3D_EINVAL;
+  if (target_normals && target_normals->n != target->n) return MM3D_EINVAL;
+  return guarded(ctx, [&] {
+    debug_icp_robust(ctx, source, target, target_normals, T, max_correspondence_distance, *options, k, split, idx, d2, weight, sums, stats);
+  });
+}
+
+}  // extern "C"

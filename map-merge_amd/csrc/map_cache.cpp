@@ -121,6 +121,12 @@ std::string pair_params_key(const mm3d_params *p, const StageSelection &sel)
   const mm3d_icp_sampling_options &smp = sel.sampling_options;
   const bool sampling = smp.method != MM3D_ICP_SAMPLE_NONE;
   k.i32(sampling ? smp.method : 0).f64(sampling ? smp.fraction : 0.0).i32(sampling ? smp.max_points : 0).i32(sampling ? smp.bins : 0);
+  // the ICP's robust kernel (mm3d_set_icp_robust): the five options while a kernel is selected, zeros otherwise (nothing reads the
+  // other values under OFF: whatever they are, its records are shared)
+  const mm3d_icp_robust_options &rob = sel.robust_options;
+  const bool robust = sel.robust();
+  k.i32(robust ? rob.kernel : 0).f64(robust ? rob.scale : 0.0).f64(robust ? rob.scale_start : 0.0).f64(robust ? rob.anneal : 0.0)
+      .f64(robust ? rob.tuning : 0.0);
   return k.s;
 }
 

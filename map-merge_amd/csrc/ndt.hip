@@ -421,6 +421,10 @@ int mm3d_set_refinement(mm3d_ctx *ctx, const mm3d_refine_options *options)
     ctx->err = "mm3d_set_refinement: NDT is not available while an ICP source sampling is set (mm3d_set_icp_sampling)";
     return MM3D_EUNSUPPORTED;
   }
+  if (ndt && ctx->sel.robust()) {                    // (NDT has no correspondences to weight)
+    ctx->err = "mm3d_set_refinement: NDT is not available while a robust kernel is selected (mm3d_set_icp_robust)";
+    return MM3D_EUNSUPPORTED;
+  }
   select_stages(ctx, false, [&](StageSelection &s) { s.refine = ndt ? &g_ndt : nullptr; s.refine_options = *options; });
   return MM3D_OK;
 }

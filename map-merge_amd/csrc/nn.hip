@@ -502,9 +502,13 @@ void icp_score_batch(Context *c, const IcpMethodBase *method, IcpScoreJob *jobs,
                      int max_iterations, double eps, bool want_score, double score_max_distance)
 {
   const mm3d_icp_rejection_options *reject = (run_icp && n_jobs) ? jobs[0].reject : nullptr;
-  const std::unique_ptr<IcpStep> step = method ? method->step(reject)
-                                        : reject ? icp_reject_step(*reject, false)
-                                                 : std::unique_ptr<IcpStep>(new PointStep());
+  // (a robust kernel, IcpScoreJob::robust, likewise: point-to-point's and point-to-plane's ICP then run icp_robust.hip's step)
+  const mm3d_icp_robust_options *robust = (run_icp && n_jobs) ? jobs[0].robust : nullptr;
+  const bool plain = !method || method == icp_plane_method();      // (the setters keep the other methods and a kernel apart)
+  const std::unique_ptr<IcpStep> step = robust && plain ? icp_robust_step(*robust, method != nullptr, max_iterations)
+                                        : method        ? method->step(reject)
+                                        : reject        ? icp_reject_step(*reject, false)
+                                                        : std::unique_ptr<IcpStep>(new PointStep());
   icp_batch(c, *step, jobs, n_jobs, run_icp, max_corr_dist, max_iterations, eps, want_score, score_max_distance);
 }
 

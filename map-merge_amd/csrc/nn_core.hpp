@@ -1,5 +1,5 @@
 // nn_core.hpp -- what the ICP / score tail of a pair estimate is made of, shared by nn.hip (the batch driver, the point-to-point
-// ICP and the score) and the files that put another ICP in its place (icp_plane.hip, icp_color.hip, icp_generalized.hip, icp_reject.hip, ndt.hip):
+// ICP and the score) and the files that put another ICP in its place (icp_plane.hip, icp_color.hip, icp_generalized.hip, icp_reject.hip, icp_robust.hip, ndt.hip):
 // the search knobs, the ICP state, the job layout and the wave helpers of the kernels; and, for the host, the set-up of one
 // search (NnSearch) and the interface through which a variant takes part in a batch (IcpStep).  The search itself is
 // nn_search_body.hpp (see there).
@@ -212,5 +212,9 @@ const IcpMethodBase *icp_plane_method();
 // icp_reject.hip (mm3d_set_icp_rejection): the step that puts a correspondence stage between the search and the sums of the
 // point-to-point ICP or, with normals, of point-to-plane
 std::unique_ptr<IcpStep> icp_reject_step(const mm3d_icp_rejection_options &opt, bool normals);
+
+// icp_robust.hip (mm3d_set_icp_robust): the step whose fused search weights every match by an M-estimator of its d2 before the
+// sums of the point-to-point ICP or, with normals, of point-to-plane; max_iterations sizes its table of scales
+std::unique_ptr<IcpStep> icp_robust_step(const mm3d_icp_robust_options &opt, bool normals, int max_iterations);
 
 }  // namespace mm3d

@@ -283,6 +283,7 @@ void mm3d::pairs_estimate_batch(mm3d_ctx *ctx, PairWork *w, size_t n, const mm3d
     jobs[i].guess_dev = fronts[i].on_device ? fronts[i].dT0.get() : nullptr;
     std::memcpy(jobs[i].guess_host, fronts[i].T0, sizeof(fronts[i].T0));
     if (sel.rejecting()) jobs[i].reject = &sel.reject_options;         // (mm3d_set_icp_rejection; NDT does not read it)
+    if (sel.robust()) jobs[i].robust = &sel.robust_options;            // (mm3d_set_icp_robust; point-to-point and point-to-plane read it)
     // (mm3d_set_icp_sampling: the ICP searches with the source map's sample, the score stays over the map)
     if (sel.sampler && p->refine_transform) jobs[i].icp_src = sel.sampler->sample(ctx, w[i].s, p, &ctx->last_sampling_stats);
   }
@@ -310,6 +311,7 @@ void mm3d::pairs_estimate_batch(mm3d_ctx *ctx, PairWork *w, size_t n, const mm3d
     out->confidence = 1.0 / jobs[i].out.score;
   }
   if (sel.rejecting() && !sel.refine && p->refine_transform && n) ctx->last_reject_stats = jobs[n - 1].reject_stats;
+  if (sel.robust() && p->refine_transform && n) ctx->last_robust_stats = jobs[n - 1].robust_stats;
   if (sel.confidence) {
     // the transforms are on the host: both maps' tables (made on first use), one launch and one wait for the whole batch
     std::vector<ConfidencePair> cp(n);

@@ -27,7 +27,7 @@ struct SmootherBase;
 struct PlaneFilterBase;
 
 // The opt-in stages of a context's pipeline (mm3d_set_icp_method, mm3d_set_alignment, mm3d_set_keypoints, mm3d_set_refinement,
-// mm3d_set_coarse_alignment, mm3d_set_confidence, mm3d_set_icp_rejection, mm3d_set_icp_color, mm3d_set_icp_generalized,
+// mm3d_set_coarse_alignment, mm3d_set_confidence, mm3d_set_icp_rejection, mm3d_set_icp_robust, mm3d_set_icp_color, mm3d_set_icp_generalized,
 // mm3d_set_estimator, mm3d_set_icp_sampling, mm3d_set_outlier_filter, mm3d_set_cluster_filter, mm3d_set_smoothing, mm3d_set_planes): a null method = the reference's stage.  The methods are process-wide
 // objects of their kernel files that hold no state and are not owned.  Every context has its own copy of the record; only
 // select_stages (drivers.hpp) changes one, and it and mm3d_set_streams hand the root's copy to the helpers.
@@ -52,6 +52,7 @@ struct StageSelection {
   mm3d_coarse_options coarse_options;
   mm3d_confidence_options confidence_options;
   mm3d_icp_rejection_options reject_options;           // the ICP's correspondence rejection: no method object, the jobs carry them
+  mm3d_icp_robust_options robust_options;              // the ICP's robust kernel: no method object, the jobs carry them
   mm3d_icp_color_options color_options;                // coloured ICP: `color` is non-null exactly while they are enabled
   mm3d_icp_generalized_options generalized_options;    // generalized ICP: `generalized` is non-null exactly while they are enabled
   mm3d_estimator_options estimator_options;            // `estimator` is non-null exactly while their method is CONSISTENCY
@@ -60,9 +61,11 @@ struct StageSelection {
   mm3d_cluster_options cluster_options;                // `clusters` is non-null exactly while their method is not OFF
   mm3d_smooth_options smooth_options;                  // `smoother` is non-null exactly while their method is MLS; `where` says which places ask it
   mm3d_plane_options plane_options;                    // `planes` is non-null exactly while their method is not OFF
-  StageSelection();                                    // capi.cpp: the options are the fourteen mm3d_*_options_default's
+  StageSelection();                                    // capi.cpp: the options are the fifteen mm3d_*_options_default's
   // the ICP of the pair stage rejects correspondences (mm3d_set_icp_rejection)
   bool rejecting() const { return reject_options.one_to_one || reject_options.distance != MM3D_REJECT_NONE; }
+  // the ICP of the pair stage weights its correspondences (mm3d_set_icp_robust)
+  bool robust() const { return robust_options.kernel != MM3D_ROBUST_OFF; }
   int icp_method() const;                              // MM3D_ICP_*
   // the pair's initial estimate is the prerejective alignment's
   bool prerejective(const mm3d_params *p) const { return !coarse && align && p->estimation_method == MM3D_EST_SAC_IA; }
@@ -72,7 +75,7 @@ struct StageSelection {
   // rand(), which is MATCHING's case in pair_rand_replay
   int replay_method(const mm3d_params *p) const { return coarse || prerejective(p) ? (int)MM3D_EST_MATCHING : (int)p->estimation_method; }
   // such a pair is estimated by pairs_estimate_batch alone (pair_estimate_impl hands it a batch of one)
-  bool batch_only(const mm3d_params *p) const { return icp || refine || coarse || confidence || color || generalized || rejecting() || prerejective(p) || consistency(p) || sampler; }
+  bool batch_only(const mm3d_params *p) const { return icp || refine || coarse || confidence || color || generalized || rejecting() || robust() || prerejective(p) || consistency(p) || sampler; }
 };
 
 // The feature / pair cache of mm3d_estimate_maps_transforms (mm3d_set_map_cache; the concrete class is map_cache.cpp's).  The
@@ -108,6 +111,7 @@ struct mm3d_ctx : mm3d::Context {
   mm3d_coarse_stats last_coarse_stats{0, 0, 0, 0, 0, -1, 0, 0};
   mm3d_overlap_stats last_confidence_stats{0, 0, 0, 0, 0, 0, 0.0};
   mm3d_icp_rejection_stats last_reject_stats{0, 0, 0, INFINITY, 0, 0};   // (mm3d_last_icp_rejection_stats)
+  mm3d_icp_robust_stats last_robust_stats{0, 0, 0.0, 0.0, 0, 0};         // (mm3d_last_icp_robust_stats)
   mm3d_estimator_stats last_estimator_stats{0, 0, 0, 0, -1, -1, 0};      // (mm3d_last_estimator_stats)
   mm3d_icp_sampling_stats last_sampling_stats{0, 0, 0, 0, 0};            // (mm3d_last_icp_sampling_stats)
   mm3d_outlier_stats last_outlier_stats{0, 0, 0, 0, 0.0, 0.0, 0.0};      // (mm3d_last_outlier_stats)
@@ -464,6 +468,11 @@ struct IcpScoreJob {
   // NDT does not read it.  reject_stats: the last iteration's counts.
   const mm3d_icp_rejection_options *reject = nullptr;
   mm3d_icp_rejection_stats reject_stats{0, 0, 0, INFINITY, 0, 0};
+  // robust kernel (mm3d_set_icp_robust; icp_robust.hip): non-null = the point-to-point and point-to-plane ICP run the robust step
+  // with these options (the same for every job of a batch); the other methods do not read it.  robust_stats: the last
+  // iteration's counts.
+  const mm3d_icp_robust_options *robust = nullptr;
+  mm3d_icp_robust_stats robust_stats{0, 0, 0.0, 0.0, 0, 0};
   // coloured ICP (mm3d_set_icp_color; icp_color.hip): the target's gradient records on the device, in its order, and the weight
   // of the geometric rows (the same for every job of a batch)
   const float4 *tgt_color = nullptr;
@@ -479,7 +488,8 @@ struct IcpScoreJob {
 };
 struct IcpStep;      // nn_core.hpp
 // The ICP + score tail of a batch of pairs (nn.hip) with `method`'s ICP; null: the reference's point-to-point ICP.  When the ICP
-// runs and the jobs carry rejection options, a method that can reject correspondences does.  The score stays point-to-point.
+// runs and the jobs carry rejection options, a method that can reject correspondences does; when they carry a robust kernel, the
+// point-to-point and point-to-plane ICP run icp_robust.hip's step.  The score stays point-to-point.
 void icp_score_batch(Context *c, const IcpMethodBase *method, IcpScoreJob *jobs, int n_jobs, bool run_icp, double max_corr_dist,
                      int max_iterations, double eps, bool want_score, double score_max_distance);
 // What stands in the place of the pair stage's point-to-point ICP on a context: point-to-plane (mm3d_set_icp_method,
