@@ -340,6 +340,61 @@ inline void check_icp_reject_devices(const mm3d_icp_rejection_options &o, const 
   if ((o.one_to_one || o.distance != MM3D_REJECT_NONE) && devices && *devices)
     throw std::runtime_error("mm3d: MM3D_ICP_REJECT is not available with MM3D_DEVICES (a device list runs the ICP without rejection)");
 }
+// MM3D_ICP_REJECT_GEOMETRY=<term>[+<term>]: the estimation context's ICP drops correspondences by the maps' geometry
+// (mm3d_set_icp_geometry_rejection).  Terms: boundary[:<radius in metres > 0>] (without a value: params.normal_radius),
+// normals[:<degrees in (0, 90]>] (without a value: mm3d_icp_geometry_options_default's 45).  none or unset selects nothing.  A term
+// twice, an unknown term or a value out of range throw, as a malformed MM3D_ICP_REJECT does.
+inline mm3d_icp_geometry_options parse_icp_reject_geometry(const char *value)
+{
+  mm3d_icp_geometry_options o;
+  o.boundary = 0;
+  o.boundary_radius = 0.0;
+  o.boundary_angle_deg = 90.0;
+  o.boundary_min_neighbours = 3;
+  o.normals = 0;
+  o.normal_angle_deg = 45.0;
+  const std::string v = value ? value : "";
+  if (v.empty() || v == "none") return o;
+  bool ok = true;
+  for (size_t a = 0; ok && a <= v.size();) {
+    size_t b = v.find('+', a);
+    if (b == std::string::npos) b = v.size();
+    const std::string term = v.substr(a, b - a);
+    const size_t colon = term.find(':');
+    const std::string name = term.substr(0, colon);
+    double x = 0.0;
+    if (colon != std::string::npos) {
+      const char *s = term.c_str() + colon + 1;
+      char *end = nullptr;
+      x = std::strtod(s, &end);
+      ok = end != s && *end == '\0' && std::isfinite(x) && x > 0.0;
+    }
+    if (name == "boundary") {
+      ok = ok && !o.boundary;
+      o.boundary = 1;
+      if (colon != std::string::npos) o.boundary_radius = x;
+    } else if (name == "normals") {
+      ok = ok && !o.normals && (colon == std::string::npos || x <= 90.0);
+      o.normals = 1;
+      if (colon != std::string::npos) o.normal_angle_deg = x;
+    } else {
+      ok = false;
+    }
+    a = b + 1;
+  }
+  if (!ok)
+    throw std::runtime_error("mm3d: MM3D_ICP_REJECT_GEOMETRY must be none or terms joined by '+' out of boundary[:<radius > 0>], "
+                             "normals[:<degrees in (0, 90]>], not '" + v + "'");
+  return o;
+}
+// Not available on a device list (its bundles carry neither normals nor flags): an active value with MM3D_DEVICES throws.  The
+// other combinations the library refuses (coloured, generalized and robust ICP; normals with MM3D_ICP_SAMPLE) throw where the
+// value is set, with the library's text.
+inline void check_icp_reject_geometry_devices(const mm3d_icp_geometry_options &o, const char *devices)
+{
+  if ((o.boundary || o.normals) && devices && *devices)
+    throw std::runtime_error("mm3d: MM3D_ICP_REJECT_GEOMETRY is not available with MM3D_DEVICES (a device list carries no normals or flags)");
+}
 // MM3D_ICP_ROBUST=<kernel>[:<scale>[:<scale_start>[:<anneal>[:<tuning>]]]]: the estimation context's ICP weights its correspondences
 // (mm3d_set_icp_robust).  Kernels: l2, huber, cauchy, tukey, geman_mcclure; a value left out is
 // mm3d_icp_robust_options_default's (0.05, 0, 0.5, 0).  none or unset selects nothing.  An unknown kernel, an empty or malformed
@@ -650,6 +705,8 @@ inline mm3d_ctx *ctx()
     check_estimator_devices(estimator, std::getenv("MM3D_DEVICES"));
     const mm3d_icp_rejection_options reject = parse_icp_reject(std::getenv("MM3D_ICP_REJECT"));
     check_icp_reject_devices(reject, std::getenv("MM3D_DEVICES"));
+    const mm3d_icp_geometry_options reject_geometry = parse_icp_reject_geometry(std::getenv("MM3D_ICP_REJECT_GEOMETRY"));
+    check_icp_reject_geometry_devices(reject_geometry, std::getenv("MM3D_DEVICES"));
     const mm3d_icp_color_options color = parse_icp_color(std::getenv("MM3D_ICP_COLOR"));
     check_icp_color_combinations(color, reject, std::getenv("MM3D_DEVICES"));
     const mm3d_icp_generalized_options generalized = parse_icp_generalized(std::getenv("MM3D_ICP_GENERALIZED"));
@@ -728,6 +785,9 @@ inline mm3d_ctx *ctx()
       throw std::runtime_error(std::string("mm3d: MM3D_ESTIMATOR was refused: ") + mm3d_last_error(e));
     if (sampling.method != MM3D_ICP_SAMPLE_NONE && mm3d_set_icp_sampling(e, &sampling) != MM3D_OK)
       throw std::runtime_error(std::string("mm3d: MM3D_ICP_SAMPLE was refused: ") + mm3d_last_error(e));
+    // (last: the library refuses it beside coloured, generalized and robust ICP, and its normals term beside a sampling)
+    if ((reject_geometry.boundary || reject_geometry.normals) && mm3d_set_icp_geometry_rejection(e, &reject_geometry) != MM3D_OK)
+      throw std::runtime_error(std::string("mm3d: MM3D_ICP_REJECT_GEOMETRY was refused: ") + mm3d_last_error(e));
     return e;
   }();
   return c;

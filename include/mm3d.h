@@ -1276,6 +1276,100 @@ int mm3d_debug_icp_rejection(mm3d_ctx *ctx, const mm3d_cloud *source, const mm3d
  * everywhere; 1 or 4 = forced in every rejecting launch from now on; negative = no change.  Returns the value in force. */
 int mm3d_debug_icp_rejection_split(int split);
 
+/* ---------------------------------------------------------------- opt-in geometric ICP rejectors
+ * mm3d_set_icp_geometry_rejection adds two rejectors that read the maps' geometry to the correspondence stage above: a
+ * correspondence is dropped when its TARGET point lies on the edge of the target's surface (Turk and Levoy 1994; PCL's
+ * BoundaryEstimation with CorrespondenceRejectionBoundaryPoints), and when the two points' normals disagree (PCL's
+ * CorrespondenceRejectorSurfaceNormal).  The algorithms, not their floats: no parity with PCL is claimed.  With the default
+ * options the selection is inactive and the pair stage runs the kernels it always ran.
+ *
+ * The boundary flag of point i of a cloud with one normal n per point, radius r, angle theta, minimum k.  All arithmetic is
+ * double, every step is ONE IEEE operation, nothing is contracted; differences of two floats promoted to double are exact, so
+ * the rule does not see how far the map is from the origin.
+ *   - i gets flag 0 unless its coordinates and its normal are finite and the normal is not (0, 0, 0).
+ *   - Its neighbours are the points j with finite coordinates, delta = p_j - p_i != 0 and (dx dx + dy dy) + dz dz <= r * r.
+ *   - Tangent frame, no square root, no division: e is the coordinate axis of the smallest |n_k| (ties to the lowest k),
+ *     u = e x n, v = n x u, each component (a b) - (c d).
+ *   - The direction of j is (x, y) = (u . delta, v . delta), a dot being (a b + c d) + e f.  x == 0 && y == 0 (a neighbour
+ *     along the normal) is no direction and is skipped.
+ *   - c = cos(theta) from the host's libm, but exactly 0 at 90 and exactly -1 at 180; c2 = c * c.  With cross = ax by - ay bx,
+ *     dot = ax bx + ay by, direction b FILLS THE WEDGE of direction a when
+ *       b lies counter-clockwise of a by an angle in (0, 180]:  cross > 0 || (cross == 0 && dot < 0),       and that angle
+ *       is at most theta:   c >= 0:  dot >= 0 && dot * dot >= c2 * ((a . a) * (b . b))
+ *                           c <  0:  dot >= 0 || dot * dot <= c2 * ((a . a) * (b . b)).
+ *   - i is a boundary point iff it has at least k directions and SOME direction's wedge is filled by no other direction:
+ *     PCL's "largest angular gap > theta" as an existence test.  No sort, no atan2, no sum: the flag does not depend on the
+ *     order in which neighbours arrive.  A gap of exactly theta is no boundary.
+ *
+ * Step 1b of the rejection rule above, between "match" and "one_to_one".  A matched correspondence (source point s, target
+ * point t) is dropped
+ *     with reason 1 when boundary is set and t's flag is set; else
+ *     with reason 2 when normals is set and the normals disagree: m = R n_s in float, R the rotation of the current float T,
+ *                   each component (R_k0 nx + R_k1 ny) + R_k2 nz; then in double d = (mx tx + my ty) + mz tz, and they AGREE
+ *                   when d * d >= c2n * (((mx mx + my my) + mz mz) * ((tx tx + ty ty) + tz tz)), c2n = cos(normal_angle_deg)^2
+ *                   (exactly 0 at 90).  |cos|, because every map orients its normals towards its own origin.  A non-finite or
+ *                   zero normal on either side disagrees.
+ * A dropped correspondence does not compete for one-to-one ownership and is in no order statistic; steps 2 - 4 run on the
+ * rest, unchanged, and the rejection statistics' `matched` counts the rest.  With nothing dropped the result is that of the
+ * rejection rule alone, bit for bit. */
+typedef struct mm3d_icp_geometry_options {
+  int boundary;                 /* 0 / 1: drop a correspondence whose TARGET point is a boundary point */
+  double boundary_radius;       /* metres, finite, >= 0; 0 = params.normal_radius behind the whole-map calls */
+  double boundary_angle_deg;    /* (0, 180]; PCL's default is 90 */
+  int boundary_min_neighbours;  /* >= 3 (PCL: fewer than 3 neighbours is never a boundary) */
+  int normals;                  /* 0 / 1: drop a correspondence whose two normals disagree */
+  double normal_angle_deg;      /* (0, 90] */
+} mm3d_icp_geometry_options;
+typedef struct mm3d_icp_geometry_stats {   /* of the LAST iteration that ran */
+  long long matched, on_boundary, normal_mismatch, passed;   /* passed = matched - on_boundary - normal_mismatch */
+  long long target_boundary_points;                          /* flagged points of the target map (0 when boundary is 0) */
+} mm3d_icp_geometry_stats;
+void mm3d_icp_geometry_options_default(mm3d_icp_geometry_options *o);   /* 0, 0.0, 90, 3, 0, 45 */
+/* The selection is active when boundary || normals; an active selection makes the pair stage's point-to-point and
+ * point-to-plane ICP take the rejecting step even when mm3d_set_icp_rejection rejects nothing.  Behind the whole-map calls the
+ * normals are the maps' (normal_radius) and a map keeps its flags (made by mm3d_map_prepare or on first use, remade when radius,
+ * angle or minimum change).  MM3D_EINVAL: a NULL argument, a value outside its range above (checked whatever the bits are).
+ * MM3D_EUNSUPPORTED: an active selection on a device-list context (mm3d_create_devices); while coloured, generalized or robust
+ * ICP is enabled (each of which in turn refuses while this selection is active); normals == 1 while an ICP source sampling is
+ * set (mm3d_set_icp_sampling, which in turn refuses then: a sample has no normals of its own; boundary alone combines with
+ * it); mm3d_shard_begin returns MM3D_EUNSUPPORTED on a context with an active selection.  NDT does not read the setting, nor
+ * do mm3d_estimate_transform_icp*, mm3d_estimate_transform, the score and the overlap confidence.  The six fields are part of
+ * the map cache's pair key while active. */
+int mm3d_set_icp_geometry_rejection(mm3d_ctx *ctx, const mm3d_icp_geometry_options *options);
+int mm3d_get_icp_geometry_rejection(const mm3d_ctx *ctx, mm3d_icp_geometry_options *options);   /* MM3D_EINVAL for NULL */
+/* of the most recent pair whose ICP this context ran with an active selection (or the stage call below); zeros before */
+int mm3d_last_icp_geometry_stats(const mm3d_ctx *ctx, mm3d_icp_geometry_stats *stats);
+/* The boundary flags of the rule above for every point of `points` with `normals` (one per point), in the caller's order:
+ * flags[i] = 0 / 1 for i < the cloud's size, which `capacity` must reach; *n_boundary (may be NULL) their sum.  Correct for
+ * any neighbourhood size.  MM3D_EINVAL: a NULL argument, radius not finite or <= 0, angle outside (0, 180], min_neighbours
+ * < 3, normals whose count differs, a capacity too small. */
+int mm3d_boundary_points(mm3d_ctx *ctx, const mm3d_cloud *points, const mm3d_normals *normals, double radius, double angle_deg,
+                         int min_neighbours, unsigned char *flags, size_t capacity, long long *n_boundary);
+/* ICP with the rejection rule and its step 1b from initial_guess, whatever the context's settings.  point_to_plane 0 / 1 selects
+ * the estimate.  source_normals may be NULL when normals == 0; target_normals may be NULL when neither bit nor point_to_plane
+ * needs them (boundary needs them: the flags are made here, with boundary_radius, which must be > 0).  Either stats may be
+ * NULL.  MM3D_EINVAL: a NULL argument otherwise, options out of range, normals whose count differs from their cloud's. */
+int mm3d_estimate_transform_icp_rejecting_geometry(mm3d_ctx *ctx, const mm3d_cloud *source, const mm3d_normals *source_normals,
+                                                   const mm3d_cloud *target, const mm3d_normals *target_normals, int point_to_plane,
+                                                   const float initial_guess[16], double max_correspondence_distance,
+                                                   const mm3d_icp_rejection_options *rejection_options,
+                                                   const mm3d_icp_geometry_options *geometry_options, int max_iterations,
+                                                   double transformation_epsilon, float T[16],
+                                                   mm3d_icp_rejection_stats *rejection_stats, mm3d_icp_geometry_stats *geometry_stats);
+/* test hook: ONE iteration's correspondence stage (steps 1, 1b, 2, 3) at T, operands as in the call above.  Per source point, in
+ * the caller's order: the nearest target index (-1: none within the distance, or a non-finite source point), the float d2
+ * (+inf: none) and a reason: 0 kept, 1 boundary, 2 normals, 3 one-to-one, 4 distance (none within
+ * max_correspondence_distance, or cut by TRIMMED / MEDIAN).  split: 1 or 4.  Either stats may be NULL. */
+int mm3d_debug_icp_geometry(mm3d_ctx *ctx, const mm3d_cloud *source, const mm3d_normals *source_normals, const mm3d_cloud *target,
+                            const mm3d_normals *target_normals, const float T[16], double max_correspondence_distance,
+                            const mm3d_icp_rejection_options *rejection_options, const mm3d_icp_geometry_options *geometry_options,
+                            int split, int *idx, float *d2, unsigned char *reason, mm3d_icp_rejection_stats *rejection_stats,
+                            mm3d_icp_geometry_stats *geometry_stats);
+/* test hook, process-wide like mm3d_debug_feature_lds_cap: the directions a wave of the boundary kernel keeps in LDS; a
+ * neighbourhood with more takes the path that streams the other directions again from the grid.  cap in [1, 512] sets it, 0
+ * restores the compiled value (512), negative = no change.  Returns the value in force. */
+int mm3d_debug_boundary_lds_cap(int cap);
+
 /* ---------------------------------------------------------------- opt-in robust ICP
  * mm3d_set_icp_robust gives the pair stage's ICP a robust loss: every matched correspondence enters the estimate with an
  * M-estimator weight of its Euclidean d2 at a scale that is fixed before the iteration runs (a table that the host builds, so

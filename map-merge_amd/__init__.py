@@ -354,6 +354,24 @@ class IcpRejectionOptions(C.Structure):
         return tuple(int(getattr(self, k)) if t is C.c_int else float(getattr(self, k)) for k, t in self._fields_)
 
 
+class IcpGeometryOptions(C.Structure):
+    """mm3d_icp_geometry_options (mm3d_set_icp_geometry_rejection); the defaults are mm3d_icp_geometry_options_default's."""
+    _fields_ = [("boundary", C.c_int), ("boundary_radius", C.c_double), ("boundary_angle_deg", C.c_double),
+                ("boundary_min_neighbours", C.c_int), ("normals", C.c_int), ("normal_angle_deg", C.c_double)]
+
+    def __init__(self, **kw):
+        super().__init__()
+        lib().mm3d_icp_geometry_options_default(C.byref(self))
+        kinds = dict(self._fields_)
+        for k, v in kw.items():
+            if k not in kinds:
+                raise TypeError("unknown ICP geometry option " + k)
+            setattr(self, k, int(v) if kinds[k] is C.c_int else float(v))
+
+    def as_tuple(self):
+        return tuple(int(getattr(self, k)) if t is C.c_int else float(getattr(self, k)) for k, t in self._fields_)
+
+
 class RobustKernel(enum.IntEnum):   # mm3d_robust_kernel (not a reference enum)
     OFF = 0
     L2 = 1
@@ -483,6 +501,15 @@ class IcpRejectionStats(C.Structure):
 
     def as_dict(self):
         return {k: (float if t is C.c_float else int)(getattr(self, k)) for k, t in self._fields_}
+
+
+class IcpGeometryStats(C.Structure):
+    """mm3d_icp_geometry_stats"""
+    _fields_ = [("matched", C.c_longlong), ("on_boundary", C.c_longlong), ("normal_mismatch", C.c_longlong), ("passed", C.c_longlong),
+                ("target_boundary_points", C.c_longlong)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
 class IcpRobustStats(C.Structure):
@@ -639,6 +666,12 @@ def icp_robust_split(split=-1):
     """mm3d_debug_icp_robust_split: force every robust launch to one work item per wave (1) or per block (4); 0: chosen by size
     again; negative: leave as it is.  Returns the value in force."""
     return int(lib().mm3d_debug_icp_robust_split(int(split)))
+
+
+def boundary_lds_cap(cap=-1):
+    """mm3d_debug_boundary_lds_cap: the directions a wave of the boundary kernel keeps in LDS (1 .. 512; 0 restores the compiled
+    value; negative asks).  Returns the value in force."""
+    return int(lib().mm3d_debug_boundary_lds_cap(int(cap)))
 
 
 def feature_lds_cap(cap):
@@ -940,6 +973,18 @@ class Context:
         self._ck(lib().mm3d_get_icp_rejection(self._h, C.byref(o)))
         return o
 
+    def setIcpGeometryRejection(self, options=None, **kw):
+        """mm3d_set_icp_geometry_rejection: the geometric rejectors of the pair stage's ICP.  An IcpGeometryOptions, or its fields as
+        keywords (boundary=0 / 1, boundary_radius=..., boundary_angle_deg=..., boundary_min_neighbours=..., normals=0 / 1,
+        normal_angle_deg=...)."""
+        o = options if options is not None else IcpGeometryOptions(**kw)
+        self._ck(lib().mm3d_set_icp_geometry_rejection(self._h, C.byref(o)))
+
+    def getIcpGeometryRejection(self) -> "IcpGeometryOptions":
+        o = IcpGeometryOptions()
+        self._ck(lib().mm3d_get_icp_geometry_rejection(self._h, C.byref(o)))
+        return o
+
     def setIcpRobust(self, options=None, **kw):
         """mm3d_set_icp_robust: the robust kernel that weights the correspondences of the pair stage's ICP.  An IcpRobustOptions, or
         its fields as keywords (kernel=RobustKernel.GEMAN_MCCLURE ..., scale=..., scale_start=..., anneal=..., tuning=...)."""
@@ -1002,6 +1047,13 @@ class Context:
         """mm3d_last_icp_rejection_stats: the last iteration of the most recent rejecting ICP this context ran."""
         st = IcpRejectionStats()
         self._ck(lib().mm3d_last_icp_rejection_stats(self._h, C.byref(st)))
+        return st.as_dict()
+
+    @property
+    def last_icp_geometry_stats(self) -> dict:
+        """mm3d_last_icp_geometry_stats: step 1b's counts in the last iteration of the most recent such ICP this context ran."""
+        st = IcpGeometryStats()
+        self._ck(lib().mm3d_last_icp_geometry_stats(self._h, C.byref(st)))
         return st.as_dict()
 
     def lastConfidenceStats(self) -> dict:
@@ -1315,6 +1367,34 @@ class Context:
         self.last_icp_converged = lib().mm3d_last_icp_converged(self._h)
         return _Tout(T)
 
+    def boundaryPoints(self, points, normals, radius, angle_deg=90.0, min_neighbours=3):
+        """mm3d_boundary_points: (flags bool[n] in the points' order, their number)."""
+        n = len(points)
+        flags = np.zeros(max(n, 1), dtype=np.uint8)
+        count = C.c_longlong(0)
+        self._ck(lib().mm3d_boundary_points(self._h, points._h, normals._h, C.c_double(radius), C.c_double(angle_deg), int(min_neighbours),
+                                            flags.ctypes.data_as(C.c_void_p), C.c_size_t(flags.size), C.byref(count)))
+        return flags[:n].astype(bool), int(count.value)
+
+    def estimateTransformICPRejectingGeometry(self, source_points, source_normals, target_points, target_normals, initial_guess,
+                                              max_correspondence_distance, rejection=None, geometry=None, point_to_plane=False,
+                                              max_iterations=100, transformation_epsilon=0.0):
+        """mm3d_estimate_transform_icp_rejecting_geometry: ICP with correspondence rejection and its geometric step 1b from
+        initial_guess, whatever the context's settings.  Returns (T, rejection stats dict, geometry stats dict)."""
+        ro = rejection if rejection is not None else IcpRejectionOptions()
+        go = geometry if geometry is not None else IcpGeometryOptions()
+        g = _T(initial_guess)
+        T = np.zeros(16, dtype=np.float32)
+        rs, gs = IcpRejectionStats(), IcpGeometryStats()
+        self._ck(lib().mm3d_estimate_transform_icp_rejecting_geometry(
+            self._h, source_points._h, source_normals._h if source_normals is not None else None, target_points._h,
+            target_normals._h if target_normals is not None else None, int(bool(point_to_plane)), g.ctypes.data_as(C.c_void_p),
+            C.c_double(max_correspondence_distance), C.byref(ro), C.byref(go), int(max_iterations), C.c_double(transformation_epsilon),
+            T.ctypes.data_as(C.c_void_p), C.byref(rs), C.byref(gs)))
+        self.last_icp_iterations = lib().mm3d_last_icp_iterations(self._h)
+        self.last_icp_converged = lib().mm3d_last_icp_converged(self._h)
+        return _Tout(T), rs.as_dict(), gs.as_dict()
+
     def estimateTransformICPRobust(self, source_points, target_points, target_normals, initial_guess, max_correspondence_distance,
                                    options=None, max_iterations=100, transformation_epsilon=0.0, **kw):
         """mm3d_estimate_transform_icp_robust: ICP with a robust kernel from initial_guess, whatever the context's setting.
@@ -1576,6 +1656,25 @@ class Context:
                                                 idx.ctypes.data_as(C.c_void_p), d2.ctypes.data_as(C.c_void_p),
                                                 kept.ctypes.data_as(C.c_void_p), C.byref(st)))
         return idx[:n], d2[:n], kept[:n].astype(bool), st.as_dict()
+
+    def debugIcpGeometry(self, source_points, source_normals, target_points, target_normals, transform, max_correspondence_distance,
+                         rejection=None, geometry=None, split=1):
+        """mm3d_debug_icp_geometry: one iteration's correspondence stage with step 1b at `transform`.  Returns (idx int32[n], d2
+        float32[n], reason uint8[n], rejection stats dict, geometry stats dict) in the source's own order."""
+        ro = rejection if rejection is not None else IcpRejectionOptions()
+        go = geometry if geometry is not None else IcpGeometryOptions()
+        n = len(source_points)
+        idx = np.zeros(max(n, 1), dtype=np.int32)
+        d2 = np.zeros(max(n, 1), dtype=np.float32)
+        reason = np.zeros(max(n, 1), dtype=np.uint8)
+        t = _T(transform)
+        rs, gs = IcpRejectionStats(), IcpGeometryStats()
+        self._ck(lib().mm3d_debug_icp_geometry(
+            self._h, source_points._h, source_normals._h if source_normals is not None else None, target_points._h,
+            target_normals._h if target_normals is not None else None, t.ctypes.data_as(C.c_void_p),
+            C.c_double(max_correspondence_distance), C.byref(ro), C.byref(go), int(split), idx.ctypes.data_as(C.c_void_p),
+            d2.ctypes.data_as(C.c_void_p), reason.ctypes.data_as(C.c_void_p), C.byref(rs), C.byref(gs)))
+        return idx[:n], d2[:n], reason[:n], rs.as_dict(), gs.as_dict()
 
     def debugIcpRobust(self, source_points, target_points, target_normals, transform, max_correspondence_distance, options=None, k=0,
                        split=1, **kw):

@@ -10,7 +10,7 @@ BUILD=${BUILD_DIR:-build}
 OUT=${OUT:-libmm3d.so}
 mkdir -p $BUILD
 . csrc/host_sources.sh    # MM3D_HOST_SOURCES: the files without a kernel
-SRCS="libm_debug.hip grid.hip filters.hip normals.hip sift.hip harris.hip fpfh.hip pfh.hip rsd.hip shot.hip sc3d.hip desc_knn.hip registration.hip nn.hip icp_plane.hip icp_reject.hip icp_robust.hip icp_color.hip icp_generalized.hip icp_sample.hip ndt.hip align_prerej.hip align_correlative.hip estimate_consistency.hip confidence_overlap.hip keypoints_uniform.hip outliers_statistical.hip clusters_euclidean.hip planes_ransac.hip smooth_mls.hip map_cache.hip $MM3D_HOST_SOURCES map_cache.cpp"
+SRCS="libm_debug.hip grid.hip filters.hip normals.hip sift.hip harris.hip fpfh.hip pfh.hip rsd.hip shot.hip sc3d.hip desc_knn.hip registration.hip nn.hip icp_plane.hip icp_reject.hip icp_geometry.hip icp_robust.hip icp_color.hip icp_generalized.hip icp_sample.hip ndt.hip align_prerej.hip align_correlative.hip estimate_consistency.hip confidence_overlap.hip keypoints_uniform.hip outliers_statistical.hip clusters_euclidean.hip planes_ransac.hip smooth_mls.hip map_cache.hip $MM3D_HOST_SOURCES map_cache.cpp"
 OBJS=""
 pids=()
 for s in $SRCS; do

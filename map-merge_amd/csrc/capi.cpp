@@ -45,6 +45,7 @@ mm3d::StageSelection::StageSelection()
   mm3d_cluster_options_default(&cluster_options);
   mm3d_smooth_options_default(&smooth_options);
   mm3d_plane_options_default(&plane_options);
+  mm3d_icp_geometry_options_default(&geometry_options);
 }
 
 void mm3d::select_stages(mm3d_ctx *ctx, bool peers_follow, const std::function<void(StageSelection &)> &edit)
@@ -199,6 +200,11 @@ void mm3d_icp_rejection_options_default(mm3d_icp_rejection_options *o)
 {
   if (o) *o = mm3d_icp_rejection_options{0, MM3D_REJECT_NONE, 0.5, 0, 1.0};
 }
+void mm3d_icp_geometry_options_default(mm3d_icp_geometry_options *o)
+{
+  if (o) *o = mm3d_icp_geometry_options{0, 0.0, 90.0, 3, 0, 45.0};
+}
+
 void mm3d_icp_robust_options_default(mm3d_icp_robust_options *o)
 {
   if (o) *o = mm3d_icp_robust_options{MM3D_ROBUST_OFF, 0.05, 0.0, 0.5, 0.0};

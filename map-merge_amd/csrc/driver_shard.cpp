@@ -63,6 +63,7 @@ int mm3d_shard_begin(mm3d_ctx *ctx, const mm3d_cloud_view *clouds, size_t n, con
     if (sel.refine) throw Error(MM3D_EUNSUPPORTED, "mm3d_shard_begin: shard bundles carry no voxel tables for NDT");
     if (sel.align) throw Error(MM3D_EUNSUPPORTED, "mm3d_shard_begin: the ranks' pair loops run SAC-IA, not the prerejective alignment");
     if (sel.rejecting()) throw Error(MM3D_EUNSUPPORTED, "mm3d_shard_begin: the ranks' pair loops run the ICP without correspondence rejection");
+    if (sel.geometric()) throw Error(MM3D_EUNSUPPORTED, "mm3d_shard_begin: the ranks' pair loops run the ICP without the geometric rejectors");
     if (sel.robust()) throw Error(MM3D_EUNSUPPORTED, "mm3d_shard_begin: the ranks' pair loops run the ICP without a robust kernel");
     if (sel.color) throw Error(MM3D_EUNSUPPORTED, "mm3d_shard_begin: shard bundles carry no colour gradients for coloured ICP");
     if (sel.generalized) throw Error(MM3D_EUNSUPPORTED, "mm3d_shard_begin: shard bundles carry no normals for generalized ICP");

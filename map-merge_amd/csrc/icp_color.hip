@@ -385,6 +385,10 @@ int mm3d_set_icp_color(mm3d_ctx *ctx, const mm3d_icp_color_options *options)
       ctx->err = "mm3d_set_icp_color: not available while a correspondence rejection is active (mm3d_set_icp_rejection)";
       return MM3D_EUNSUPPORTED;
     }
+    if (ctx->sel.geometric()) {      // (step 1b is the rejecting step's)
+      ctx->err = "mm3d_set_icp_color: not available while a geometric rejector is active (mm3d_set_icp_geometry_rejection)";
+      return MM3D_EUNSUPPORTED;
+    }
     if (ctx->sel.generalized) {
       ctx->err = "mm3d_set_icp_color: not available while generalized ICP is enabled (mm3d_set_icp_generalized)";
       return MM3D_EUNSUPPORTED;

@@ -271,6 +271,10 @@ int mm3d_set_icp_generalized(mm3d_ctx *ctx, const mm3d_icp_generalized_options *
       ctx->err = "mm3d_set_icp_generalized: not available while a correspondence rejection is active (mm3d_set_icp_rejection)";
       return MM3D_EUNSUPPORTED;
     }
+    if (ctx->sel.geometric()) {      // (step 1b is the rejecting step's)
+      ctx->err = "mm3d_set_icp_generalized: not available while a geometric rejector is active (mm3d_set_icp_geometry_rejection)";
+      return MM3D_EUNSUPPORTED;
+    }
     if (ctx->sel.color) {
       ctx->err = "mm3d_set_icp_generalized: not available while coloured ICP is enabled (mm3d_set_icp_color)";
       return MM3D_EUNSUPPORTED;

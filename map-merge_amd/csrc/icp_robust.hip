@@ -492,6 +492,7 @@ int mm3d_set_icp_robust(mm3d_ctx *ctx, const mm3d_icp_robust_options *options)
   if (active && refused_on_device_list(ctx, "mm3d_set_icp_robust: not available on a device-list context")) return MM3D_EUNSUPPORTED;
   const char *other = !active ? nullptr
                       : ctx->sel.rejecting() ? "a correspondence rejection is active (mm3d_set_icp_rejection)"
+                      : ctx->sel.geometric() ? "a geometric rejector is active (mm3d_set_icp_geometry_rejection)"
                       : ctx->sel.color       ? "coloured ICP is enabled (mm3d_set_icp_color)"
                       : ctx->sel.generalized ? "generalized ICP is enabled (mm3d_set_icp_generalized)"
                       : ctx->sel.refine      ? "NDT is selected (mm3d_set_refinement)"

@@ -327,6 +327,10 @@ int mm3d_set_icp_sampling(mm3d_ctx *ctx, const mm3d_icp_sampling_options *option
       ctx->err = "mm3d_set_icp_sampling: not available while NDT is selected (mm3d_set_refinement)";
       return MM3D_EUNSUPPORTED;
     }
+    if (ctx->sel.geometry_options.normals) {      // (a sample has no normals of its own index; the boundary rejector is target-side)
+      ctx->err = "mm3d_set_icp_sampling: not available while the normal rejector is active (mm3d_set_icp_geometry_rejection)";
+      return MM3D_EUNSUPPORTED;
+    }
     if (ctx->sel.color) {
       ctx->err = "mm3d_set_icp_sampling: not available while coloured ICP is enabled (mm3d_set_icp_color)";
       return MM3D_EUNSUPPORTED;

@@ -101,6 +101,11 @@ std::string pair_params_key(const mm3d_params *p, const StageSelection &sel)
   const bool rejecting = sel.rejecting();
   k.i32(rejecting ? rej.one_to_one : 0).i32(rejecting ? rej.distance : 0).f64(rejecting ? rej.overlap_ratio : 0.0)
       .i32(rejecting ? rej.min_correspondences : 0).f64(rejecting ? rej.median_factor : 0.0);
+  // the geometric rejectors (mm3d_set_icp_geometry_rejection): the six options while the selection is active, zeros otherwise
+  const mm3d_icp_geometry_options &geo = sel.geometry_options;
+  const bool geometric = sel.geometric();
+  k.i32(geometric ? geo.boundary : 0).f64(geometric ? geo.boundary_radius : 0.0).f64(geometric ? geo.boundary_angle_deg : 0.0)
+      .i32(geometric ? geo.boundary_min_neighbours : 0).i32(geometric ? geo.normals : 0).f64(geometric ? geo.normal_angle_deg : 0.0);
   // coloured ICP (mm3d_set_icp_color): the four options while enabled, zeros otherwise (a disabled selection's other values
   // are read by nothing: whatever they are, its records are shared)
   const mm3d_icp_color_options &col = sel.color_options;
@@ -166,7 +171,8 @@ struct Entry {
                               map->coarse->dil.size() + map->coarse->gh.size() * 4 : 0) +   // (signature: correlative alignment only)
            (map->overlap ? map->overlap->near.size() * 8 + map->overlap->view.size() : 0) +   // (table: overlap confidence only)
            (map->color ? map->color->rec.size() * 16 : 0) +   // (gradient records: coloured ICP only)
-           (map->icp_sample ? cloud_bytes(map->icp_sample->cloud.get()) : 0);   // (the source sample: ICP sampling only)
+           (map->icp_sample ? cloud_bytes(map->icp_sample->cloud.get()) : 0) +   // (the source sample: ICP sampling only)
+           (map->boundary ? map->boundary->flags.size() : 0);   // (boundary flags: the boundary rejector only)
   }
 };
 

@@ -505,7 +505,10 @@ void icp_score_batch(Context *c, const IcpMethodBase *method, IcpScoreJob *jobs,
   // (a robust kernel, IcpScoreJob::robust, likewise: point-to-point's and point-to-plane's ICP then run icp_robust.hip's step)
   const mm3d_icp_robust_options *robust = (run_icp && n_jobs) ? jobs[0].robust : nullptr;
   const bool plain = !method || method == icp_plane_method();      // (the setters keep the other methods and a kernel apart)
+  // (step 1b of the rejecting step, IcpScoreJob::geometry, rides on the rejection options: mm3d_set_icp_geometry_rejection)
+  const mm3d_icp_geometry_options *geometry = (reject && plain) ? jobs[0].geometry : nullptr;
   const std::unique_ptr<IcpStep> step = robust && plain ? icp_robust_step(*robust, method != nullptr, max_iterations)
+                                        : geometry      ? icp_reject_step(*reject, method != nullptr, geometry)
                                         : method        ? method->step(reject)
                                         : reject        ? icp_reject_step(*reject, false)
                                                         : std::unique_ptr<IcpStep>(new PointStep());

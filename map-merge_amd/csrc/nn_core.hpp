@@ -210,8 +210,16 @@ void icp_plane_finalize(Context *c, const NnPlaneJob *jobs_dev, int count, doubl
 const IcpMethodBase *icp_plane_method();
 
 // icp_reject.hip (mm3d_set_icp_rejection): the step that puts a correspondence stage between the search and the sums of the
-// point-to-point ICP or, with normals, of point-to-plane
-std::unique_ptr<IcpStep> icp_reject_step(const mm3d_icp_rejection_options &opt, bool normals);
+// point-to-point ICP or, with normals, of point-to-plane; geometry (mm3d_set_icp_geometry_rejection): non-null = with step 1b,
+// whose operands the jobs carry
+std::unique_ptr<IcpStep> icp_reject_step(const mm3d_icp_rejection_options &opt, bool normals, const mm3d_icp_geometry_options *geometry = nullptr);
+// icp_geometry.hip: the boundary flags of `points` with `normals` (device, the points' order) by the rule of include/mm3d.h into
+// flags_dev [points->n]; asynchronous on c's stream
+void boundary_flags(Context *c, const mm3d_cloud *points, const float4 *normals_dev, double radius, double angle_deg, int min_neighbours,
+                    unsigned char *flags_dev);
+// ... and their number, after a wait
+long long boundary_count(Context *c, const unsigned char *flags_dev, size_t n);
+bool icp_geometry_options_valid(const mm3d_icp_geometry_options *o);
 
 // icp_robust.hip (mm3d_set_icp_robust): the step whose fused search weights every match by an M-estimator of its d2 before the
 // sums of the point-to-point ICP or, with normals, of point-to-plane; max_iterations sizes its table of scales

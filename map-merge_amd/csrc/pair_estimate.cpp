@@ -92,9 +92,12 @@ std::unique_ptr<mm3d_map> mm3d::map_features_impl(mm3d_ctx *ctx, const mm3d_clou
   if (wait) ctx->sync();
   std::unique_ptr<mm3d_map> m = make_map(std::move(filt), std::move(kp), std::move(desc));
   // point-to-plane, coloured and generalized ICP read them (mm3d_set_icp_method, mm3d_set_icp_color, mm3d_set_icp_generalized),
-  // the correlative signature, and normal-space sampling (mm3d_set_icp_sampling)
+  // the correlative signature, normal-space sampling (mm3d_set_icp_sampling), and the geometric rejectors: the boundary flags are
+  // made from them, the normal test reads them (mm3d_set_icp_geometry_rejection)
   const bool normal_space = ctx->sel.sampler && ctx->sel.sampling_options.method == MM3D_ICP_SAMPLE_NORMAL_SPACE;
-  if (ctx->sel.icp || ctx->sel.coarse || ctx->sel.color || ctx->sel.generalized || normal_space) m->normals = std::move(nrm);
+  if (ctx->sel.icp || ctx->sel.coarse || ctx->sel.color || ctx->sel.generalized || normal_space || ctx->sel.geometry_options.normals == 1 ||
+      ctx->sel.geometry_options.boundary == 1)
+    m->normals = std::move(nrm);
   return m;
 }
 
@@ -108,6 +111,7 @@ void mm3d::map_prepare_impl(mm3d_ctx *ctx, mm3d_map *m, const mm3d_params *p)
   if (sel.coarse) sel.coarse->prepare(ctx, m, p);                      // the correlative signature (mm3d_set_coarse_alignment)
   if (sel.confidence) sel.confidence->prepare(ctx, m, p);              // the overlap table (mm3d_set_confidence)
   if (sel.sampler && p->refine_transform) (void)sel.sampler->sample(ctx, m, p, nullptr);   // the ICP's source sample (mm3d_set_icp_sampling)
+  if (sel.geometry && p->refine_transform) sel.geometry->prepare(ctx, m, p);   // the normals and the boundary flags (mm3d_set_icp_geometry_rejection)
   prepare_pair_search(ctx, m->points, p->max_correspondence_distance, p->max_correspondence_distance);
   if (p->estimation_method == MM3D_EST_SAC_IA && sel.align) sel.align->prepare(ctx, m->keypoints, p->max_correspondence_distance);
   else if (p->estimation_method == MM3D_EST_SAC_IA) prepare_sacia_target(ctx, m->keypoints, (float)p->max_correspondence_distance);
@@ -282,7 +286,9 @@ void mm3d::pairs_estimate_batch(mm3d_ctx *ctx, PairWork *w, size_t n, const mm3d
     jobs[i].tgt = w[i].t->points;
     jobs[i].guess_dev = fronts[i].on_device ? fronts[i].dT0.get() : nullptr;
     std::memcpy(jobs[i].guess_host, fronts[i].T0, sizeof(fronts[i].T0));
-    if (sel.rejecting()) jobs[i].reject = &sel.reject_options;         // (mm3d_set_icp_rejection; NDT does not read it)
+    // (mm3d_set_icp_rejection; NDT does not read it.  An active mm3d_set_icp_geometry_rejection takes the rejecting step too.)
+    if (sel.rejecting() || sel.geometric()) jobs[i].reject = &sel.reject_options;
+    if (sel.geometry && p->refine_transform && !sel.refine) sel.geometry->bind(ctx, w[i].s, w[i].t, p, &jobs[i]);
     if (sel.robust()) jobs[i].robust = &sel.robust_options;            // (mm3d_set_icp_robust; point-to-point and point-to-plane read it)
     // (mm3d_set_icp_sampling: the ICP searches with the source map's sample, the score stays over the map)
     if (sel.sampler && p->refine_transform) jobs[i].icp_src = sel.sampler->sample(ctx, w[i].s, p, &ctx->last_sampling_stats);
@@ -310,7 +316,8 @@ void mm3d::pairs_estimate_batch(mm3d_ctx *ctx, PairWork *w, size_t n, const mm3d
     out->icp_correspondences = jobs[i].out.n_corr;
     out->confidence = 1.0 / jobs[i].out.score;
   }
-  if (sel.rejecting() && !sel.refine && p->refine_transform && n) ctx->last_reject_stats = jobs[n - 1].reject_stats;
+  if ((sel.rejecting() || sel.geometric()) && !sel.refine && p->refine_transform && n) ctx->last_reject_stats = jobs[n - 1].reject_stats;
+  if (sel.geometric() && !sel.refine && p->refine_transform && n) ctx->last_geometry_stats = jobs[n - 1].geometry_stats;
   if (sel.robust() && p->refine_transform && n) ctx->last_robust_stats = jobs[n - 1].robust_stats;
   if (sel.confidence) {
     // the transforms are on the host: both maps' tables (made on first use), one launch and one wait for the whole batch

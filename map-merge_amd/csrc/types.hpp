@@ -25,6 +25,7 @@ struct OutlierFilterBase;
 struct ClusterFilterBase;
 struct SmootherBase;
 struct PlaneFilterBase;
+struct IcpGeometryBase;
 
 // The opt-in stages of a context's pipeline (mm3d_set_icp_method, mm3d_set_alignment, mm3d_set_keypoints, mm3d_set_refinement,
 // mm3d_set_coarse_alignment, mm3d_set_confidence, mm3d_set_icp_rejection, mm3d_set_icp_robust, mm3d_set_icp_color, mm3d_set_icp_generalized,
@@ -46,6 +47,7 @@ struct StageSelection {
   const ClusterFilterBase *clusters = nullptr;         // what drops the small connected components of the filtered map
   const SmootherBase *smoother = nullptr;              // what smooths a filtered map before its normals, and the composed map
   const PlaneFilterBase *planes = nullptr;             // what takes the dominant planes out of the filtered map, before the cluster filter
+  const IcpGeometryBase *geometry = nullptr;           // what binds a pair's boundary flags and normals for the rejecting step's step 1b
   mm3d_alignment_options align_options;
   mm3d_keypoint_options keypoint_options;
   mm3d_refine_options refine_options;
@@ -61,9 +63,12 @@ struct StageSelection {
   mm3d_cluster_options cluster_options;                // `clusters` is non-null exactly while their method is not OFF
   mm3d_smooth_options smooth_options;                  // `smoother` is non-null exactly while their method is MLS; `where` says which places ask it
   mm3d_plane_options plane_options;                    // `planes` is non-null exactly while their method is not OFF
-  StageSelection();                                    // capi.cpp: the options are the fifteen mm3d_*_options_default's
+  mm3d_icp_geometry_options geometry_options;          // `geometry` is non-null exactly while boundary || normals
+  StageSelection();                                    // capi.cpp: the options are the sixteen mm3d_*_options_default's
   // the ICP of the pair stage rejects correspondences (mm3d_set_icp_rejection)
   bool rejecting() const { return reject_options.one_to_one || reject_options.distance != MM3D_REJECT_NONE; }
+  // the rejecting step drops correspondences by the maps' geometry too (mm3d_set_icp_geometry_rejection)
+  bool geometric() const { return geometry_options.boundary || geometry_options.normals; }
   // the ICP of the pair stage weights its correspondences (mm3d_set_icp_robust)
   bool robust() const { return robust_options.kernel != MM3D_ROBUST_OFF; }
   int icp_method() const;                              // MM3D_ICP_*
@@ -75,7 +80,7 @@ struct StageSelection {
   // rand(), which is MATCHING's case in pair_rand_replay
   int replay_method(const mm3d_params *p) const { return coarse || prerejective(p) ? (int)MM3D_EST_MATCHING : (int)p->estimation_method; }
   // such a pair is estimated by pairs_estimate_batch alone (pair_estimate_impl hands it a batch of one)
-  bool batch_only(const mm3d_params *p) const { return icp || refine || coarse || confidence || color || generalized || rejecting() || robust() || prerejective(p) || consistency(p) || sampler; }
+  bool batch_only(const mm3d_params *p) const { return icp || refine || coarse || confidence || color || generalized || rejecting() || geometric() || robust() || prerejective(p) || consistency(p) || sampler; }
 };
 
 // The feature / pair cache of mm3d_estimate_maps_transforms (mm3d_set_map_cache; the concrete class is map_cache.cpp's).  The
@@ -112,6 +117,7 @@ struct mm3d_ctx : mm3d::Context {
   mm3d_overlap_stats last_confidence_stats{0, 0, 0, 0, 0, 0, 0.0};
   mm3d_icp_rejection_stats last_reject_stats{0, 0, 0, INFINITY, 0, 0};   // (mm3d_last_icp_rejection_stats)
   mm3d_icp_robust_stats last_robust_stats{0, 0, 0.0, 0.0, 0, 0};         // (mm3d_last_icp_robust_stats)
+  mm3d_icp_geometry_stats last_geometry_stats{0, 0, 0, 0, 0};            // (mm3d_last_icp_geometry_stats)
   mm3d_estimator_stats last_estimator_stats{0, 0, 0, 0, -1, -1, 0};      // (mm3d_last_estimator_stats)
   mm3d_icp_sampling_stats last_sampling_stats{0, 0, 0, 0, 0};            // (mm3d_last_icp_sampling_stats)
   mm3d_outlier_stats last_outlier_stats{0, 0, 0, 0, 0.0, 0.0, 0.0};      // (mm3d_last_outlier_stats)
@@ -234,6 +240,16 @@ struct ColorGradients {
   DevBuf<float4> rec;                              // [n] (gx, gy, gz, I)
 };
 
+// What the boundary rejector keeps of a map (icp_geometry.hip, mm3d_set_icp_geometry_rejection): one flag per point, in the points'
+// order.  1 B per point beside the 16 B of the normals they are made from.
+struct BoundaryFlags {
+  double radius = 0.0, angle_deg = 0.0;            // what they were made with, radius resolved (a map's flags are remade when these change)
+  int min_neighbours = 0;
+  size_t n = 0;
+  long long n_boundary = 0;
+  DevBuf<unsigned char> flags;                     // [n]
+};
+
 }  // namespace mm3d
 
 struct mm3d_cloud {
@@ -310,6 +326,7 @@ struct mm3d_map {
   std::unique_ptr<mm3d::OverlapTable> overlap;      // the overlap confidence's table
   std::unique_ptr<mm3d::ColorGradients> color;      // coloured ICP's gradient records
   std::unique_ptr<mm3d::IcpSample> icp_sample;      // the source sample of the ICP
+  std::unique_ptr<mm3d::BoundaryFlags> boundary;    // the boundary rejector's flags
   mm3d_map() = default;
   mm3d_map(const mm3d_map &) = delete;
   mm3d_map &operator=(const mm3d_map &) = delete;
@@ -468,6 +485,15 @@ struct IcpScoreJob {
   // NDT does not read it.  reject_stats: the last iteration's counts.
   const mm3d_icp_rejection_options *reject = nullptr;
   mm3d_icp_rejection_stats reject_stats{0, 0, 0, INFINITY, 0, 0};
+  // geometric rejectors (mm3d_set_icp_geometry_rejection; icp_geometry.hip, icp_reject.hip): non-null (with `reject` non-null) = the
+  // rejecting step runs its step 1b with these options (the same for every job of a batch).  tgt_boundary: the target's flags on
+  // the device, in its order (boundary == 1); the normals test reads src_normals and tgt_normals.  geometry_stats: the last
+  // iteration's counts.
+  const mm3d_icp_geometry_options *geometry = nullptr;
+  const unsigned char *tgt_boundary = nullptr;
+  long long tgt_boundary_points = 0;
+  const mm3d_normals *geo_tgt_normals = nullptr;   // (tgt_normals stays what selects and feeds the point-to-plane rows)
+  mm3d_icp_geometry_stats geometry_stats{0, 0, 0, 0, 0};
   // robust kernel (mm3d_set_icp_robust; icp_robust.hip): non-null = the point-to-point and point-to-plane ICP run the robust step
   // with these options (the same for every job of a batch); the other methods do not read it.  robust_stats: the last
   // iteration's counts.
@@ -614,6 +640,16 @@ struct PlaneFilterBase {
   virtual mm3d_cloud *filter(Context *c, mm3d_cloud *in, const mm3d_plane_options &o, double resolution, const ClusterFilterBase *clusters,
                              const mm3d_cluster_options &cluster_options, mm3d_plane_stats *stats, mm3d_plane *planes,
                              mm3d_cluster_stats *cluster_stats) const = 0;
+};
+// What binds the geometric rejectors' operands to a pair (mm3d_set_icp_geometry_rejection; the one concrete class is
+// icp_geometry.hip's).  Like IcpSamplerBase, the drivers and pair_estimate.cpp only see this interface, so the host code links
+// without the new kernels (tests/host_san); a null pointer on the context means an inactive selection.
+struct IcpGeometryBase {
+  virtual ~IcpGeometryBase() = default;
+  // the map's normals and, under `boundary`, its flags at the context's options, made when missing or stale (map_kept.hpp)
+  virtual void prepare(mm3d_ctx *ctx, const mm3d_map *m, const mm3d_params *p) const = 0;
+  // the same for a pair's two maps, bound to `job`: geometry, tgt_boundary, src_normals, geo_tgt_normals
+  virtual void bind(mm3d_ctx *ctx, const mm3d_map *s, const mm3d_map *t, const mm3d_params *p, IcpScoreJob *job) const = 0;
 };
 struct PairCounts { int n_correspondences = 0, n_inliers = 0, icp_correspondences = 0; };
 // ICP (optional) from a guess on the device (guess_dev != null) or on the host, then transformScore
