@@ -15,14 +15,14 @@
 //   k_icp_color_wave    k_icp_plane_wave with the record and the source's own colour: nn_search_body.hpp once more, then three
 //                       16-byte loads per matched lane, and the 30 terms formed, wave-summed and stored one at a time into
 //                       partials[block][kPlaneAcc].  lambda == 1 is decided per launch (a kernel argument: wave-uniform), and
-//                       its terms are k_icp_plane_wave's expressions: the same bits.
+//                       its terms are then the ones k_icp_plane_wave forms (icp_tail.hpp's row and terms): the same bits.
 #include <atomic>
 #include <cmath>
 
 #include "capi_guard.hpp"
 #include "drivers.hpp"
 #include "map_kept.hpp"
-#include "icp_solve6.hpp"
+#include "icp_tail.hpp"
 #include "nn_core.hpp"
 
 namespace mm3d {
@@ -207,16 +207,11 @@ k_icp_color_wave(const NnColorJob *__restrict__ cjobs, float max_d2, float rmax,
   if (corr) {
     const unsigned w = (unsigned)(bkey & 0xffffffffull);
     const float4 n = nrm[w];
-    if (isfinite(n.x) && isfinite(n.y) && isfinite(n.z)) {
-      const float4 d = tgt_ref[w];
-      const double sx = p.x, sy = p.y, sz = p.z, nx = n.x, ny = n.y, nz = n.z;
-      v[0] = nz * sy - ny * sz;
-      v[1] = nx * sz - nz * sx;
-      v[2] = ny * sx - nx * sy;
-      v[3] = nx; v[4] = ny; v[5] = nz;
-      r = (nx * (double)d.x + ny * (double)d.y + nz * (double)d.z) - (nx * sx + ny * sy + nz * sz);
+    if (icp_plane_row(p, n, tgt_ref[w], v, r)) {
       has_row = 1.0;
       if (colored) {
+        const float4 d = tgt_ref[w];
+        const double sx = p.x, sy = p.y, sz = p.z, nx = n.x, ny = n.y, nz = n.z;
         const float4 G = grad[w];
         const double is = color_intensity(src_ref[__float_as_uint(src[i].w)].w);
         const double gx = G.x, gy = G.y, gz = G.z;
@@ -232,34 +227,14 @@ k_icp_color_wave(const NnColorJob *__restrict__ cjobs, float max_d2, float rmax,
       }
     }
   }
-  // one term at a time (formed, summed over the wave, stored), as k_icp_plane_wave does
+  // point-to-plane's terms (icp_plane_term), the 27 of the system weighted with the colour rows' when there are any
   auto term = [&](int k) -> double {
-    if (k < 21) return colored ? lam * (v[kUi[k]] * v[kUj[k]]) + mu * (vc[kUi[k]] * vc[kUj[k]]) : v[kUi[k]] * v[kUj[k]];
-    if (k < 27) return colored ? lam * (v[k - 21] * r) + mu * (vc[k - 21] * rc) : v[k - 21] * r;
-    if (k == 27) return corr ? (double)best : 0.0;
-    if (k == 28) return corr ? 1.0 : 0.0;
-    return has_row;
+    const double geo = icp_plane_term(k, v, r, corr, best, has_row);
+    return colored && k < 27 ? lam * geo + mu * icp_plane_term(k, vc, rc, corr, best, has_row) : geo;
   };
   // a wave none of whose points found a neighbour in range adds zeros without the reductions (as k_nn_wave does)
   const bool any_corr = ballot(corr) != 0ull;       // wave-uniform
-  if (SPLIT == 4) {
-#pragma unroll
-    for (int k = 0; k < kPlaneAcc; ++k) {
-      const double s = any_corr ? wave_sum(term(k)) : 0.0;
-      if (lane == 0) partials[(size_t)bid * kPlaneAcc + k] = s;
-    }
-    return;
-  }
-#pragma unroll
-  for (int k = 0; k < kPlaneAcc; ++k) {
-    const double s = any_corr ? wave_sum(term(k)) : 0.0;
-    if (lane == 0) red[wave][k] = s;
-  }
-  __syncthreads();
-  if (threadIdx.x < kPlaneAcc) {
-    const int k = threadIdx.x;
-    partials[(size_t)bid * kPlaneAcc + k] = red[0][k] + red[1][k] + red[2][k] + red[3][k];
-  }
+  icp_store_partials<kPlaneAcc, SPLIT>(term, any_corr, red, partials, bid);
 }
 
 static std::atomic<int> g_color_forced_split{0};      // mm3d_debug_icp_color_split: 0 (by size), 1 or 4

@@ -15,12 +15,11 @@
 //                            from W (6), s (3) and W e (3), each wave-summed and stored one at a time into partials[block][kPlaneAcc].
 #include <atomic>
 #include <cmath>
-#include <type_traits>
 
 #include "capi_guard.hpp"
 #include "drivers.hpp"
 #include "map_kept.hpp"
-#include "icp_solve6.hpp"
+#include "icp_tail.hpp"
 #include "nn_core.hpp"
 
 namespace mm3d {
@@ -50,58 +49,44 @@ __device__ __forceinline__ GicpUnit gicp_unit(const float4 n)
 
 // The 27 terms of one correspondence from W (6), s (3) and We (3).  With C = [s]x: J^T W J = | C W C^T   C W |
 //                                                                                         | W C^T     W   |
-// and J^T W e = (s x We, We).  B<i, j> = (C W)(i, j) = (s x W's column j)(i); A<i, j> = (C W C^T)(i, j) = (s x B's row i)(j).
-// The indices are template arguments and the members scalars, so a term is its own few products on registers: nothing is
-// indexed at run time, and nothing but the twelve doubles is held between two terms.
+// and J^T W e = (s x We, We).  B(i, j) = (C W)(i, j) = (s x W's column j)(i); A(i, j) = (C W C^T)(i, j) = (s x B's row i)(j).
+// The members are scalars and every index is a constant once the term loop is unrolled, so a term is its own few products on
+// registers: nothing is indexed at run time, and nothing but the twelve doubles is held between two terms.
 struct GicpLane {
   double w00, w01, w02, w11, w12, w22, sx, sy, sz, u0, u1, u2;
-  template <int I, int J>
-  __device__ __forceinline__ double w() const
+  __device__ __forceinline__ double w(int i, int j) const
   {
-    constexpr int a = I < J ? I : J, b = I < J ? J : I;
-    if constexpr (a == 0) return b == 0 ? w00 : b == 1 ? w01 : w02;
-    else if constexpr (a == 1) return b == 1 ? w11 : w12;
-    else return w22;
+    const int a = i < j ? i : j, b = i < j ? j : i;
+    if (a == 0) return b == 0 ? w00 : b == 1 ? w01 : w02;
+    if (a == 1) return b == 1 ? w11 : w12;
+    return w22;
   }
-  template <int I, int J>
-  __device__ __forceinline__ double B() const
+  __device__ __forceinline__ double B(int i, int j) const
   {
-    if constexpr (I == 0) return sy * w<2, J>() - sz * w<1, J>();
-    else if constexpr (I == 1) return sz * w<0, J>() - sx * w<2, J>();
-    else return sx * w<1, J>() - sy * w<0, J>();
+    if (i == 0) return sy * w(2, j) - sz * w(1, j);
+    if (i == 1) return sz * w(0, j) - sx * w(2, j);
+    return sx * w(1, j) - sy * w(0, j);
   }
-  template <int I, int J>
-  __device__ __forceinline__ double A() const
+  __device__ __forceinline__ double A(int i, int j) const
   {
-    if constexpr (J == 0) return sy * B<I, 2>() - sz * B<I, 1>();
-    else if constexpr (J == 1) return sz * B<I, 0>() - sx * B<I, 2>();
-    else return sx * B<I, 1>() - sy * B<I, 0>();
+    if (j == 0) return sy * B(i, 2) - sz * B(i, 1);
+    if (j == 1) return sz * B(i, 0) - sx * B(i, 2);
+    return sx * B(i, 1) - sy * B(i, 0);
   }
-  template <int I, int J>      // I <= J, both in [0, 6)
-  __device__ __forceinline__ double ata() const
+  __device__ __forceinline__ double ata(int i, int j) const      // i <= j, both in [0, 6)
   {
-    if constexpr (J < 3) return A<I, J>();
-    else if constexpr (I < 3) return B<I, J - 3>();
-    else return w<I - 3, J - 3>();
+    if (j < 3) return A(i, j);
+    if (i < 3) return B(i, j - 3);
+    return w(i - 3, j - 3);
   }
-  template <int I>
-  __device__ __forceinline__ double atr() const
+  __device__ __forceinline__ double atr(int i) const
   {
-    if constexpr (I == 0) return sy * u2 - sz * u1;
-    else if constexpr (I == 1) return sz * u0 - sx * u2;
-    else if constexpr (I == 2) return sx * u1 - sy * u0;
-    else return I == 3 ? u0 : I == 4 ? u1 : u2;
+    if (i == 0) return sy * u2 - sz * u1;
+    if (i == 1) return sz * u0 - sx * u2;
+    if (i == 2) return sx * u1 - sy * u0;
+    return i == 3 ? u0 : i == 4 ? u1 : u2;
   }
 };
-// f(std::integral_constant<int, k>) for k = K .. kPlaneAcc - 1, in order
-template <int K, class F>
-__device__ __forceinline__ void gicp_for_terms(F &&f)
-{
-  if constexpr (K < kPlaneAcc) {
-    f(std::integral_constant<int, K>{});
-    gicp_for_terms<K + 1>(f);
-  }
-}
 
 template <int SPLIT>
 __global__ void __launch_bounds__(256) MM3D_NN_ATTR
@@ -163,33 +148,17 @@ k_icp_generalized_wave(const NnGeneralizedJob *__restrict__ gjobs, float max_d2,
       rows = 3.0;
     }
   }
-  // one term at a time (formed, summed over the wave, stored), as k_icp_plane_wave does
-  auto term = [&](auto kc) -> double {
-    constexpr int k = decltype(kc)::value;
-    if constexpr (k < 21) return L.template ata<kUi[k], kUj[k]>();
-    else if constexpr (k < 27) return L.template atr<k - 21>();
-    else if constexpr (k == 27) return corr ? (double)best : 0.0;
-    else if constexpr (k == 28) return corr ? 1.0 : 0.0;
-    else return rows;
+  // one term at a time (icp_store_partials)
+  auto term = [&](int k) -> double {
+    if (k < 21) return L.ata(kUi[k], kUj[k]);
+    if (k < 27) return L.atr(k - 21);
+    if (k == 27) return corr ? (double)best : 0.0;
+    if (k == 28) return corr ? 1.0 : 0.0;
+    return rows;
   };
   // a wave none of whose points found a neighbour in range adds zeros without the reductions (as k_nn_wave does)
   const bool any_corr = ballot(corr) != 0ull;       // wave-uniform
-  if (SPLIT == 4) {
-    gicp_for_terms<0>([&](auto kc) {
-      const double s = any_corr ? wave_sum(term(kc)) : 0.0;
-      if (lane == 0) partials[(size_t)bid * kPlaneAcc + decltype(kc)::value] = s;
-    });
-    return;
-  }
-  gicp_for_terms<0>([&](auto kc) {
-    const double s = any_corr ? wave_sum(term(kc)) : 0.0;
-    if (lane == 0) red[wave][decltype(kc)::value] = s;
-  });
-  __syncthreads();
-  if (threadIdx.x < kPlaneAcc) {
-    const int k = threadIdx.x;
-    partials[(size_t)bid * kPlaneAcc + k] = red[0][k] + red[1][k] + red[2][k] + red[3][k];
-  }
+  icp_store_partials<kPlaneAcc, SPLIT>(term, any_corr, red, partials, bid);
 }
 
 static std::atomic<int> g_generalized_forced_split{0};      // mm3d_debug_icp_generalized_split: 0 (by size), 1 or 4

@@ -2,7 +2,7 @@
 //
 // PCL's IterativeClosestPoint with TransformationEstimationPointToPlaneLLS and DefaultConvergenceCriteria: the loop of nn.hip's
 // ICP (float transform of the source, exact float nearest neighbour accepted at d2 <= max_d2, T <- Tinc * T in float, the
-// convergence tests of k_icp_finalize on the same IcpState) with a different transform estimate.  For each correspondence
+// convergence tests on the same IcpState: icp_tail.hpp's icp_advance) with a different transform estimate.  For each correspondence
 // (s = source point after the current transform, d = target point, n = its normal, finite):
 //   row  = [a, b, c, nx, ny, nz],  a = nz sy - ny sz,  b = nx sz - nz sx,  c = ny sx - nx sy
 //   r    = n.d - n.s
@@ -10,18 +10,20 @@
 // AtA x = Atr (an unpivoted LDLt in double), and Tinc = [Rz(gamma) Ry(beta) Rx(alpha) | t] (PCL's constructTransformationMatrix).
 // Both sums are invariant under n -> -n, so the normals' orientation does not matter.
 //
-// Two launches per iteration, like icp_corr_reduce / icp_finalize:
+// Two launches per iteration, like icp_corr_reduce / icp_finalize; the row, its terms, the estimate and the convergence step are
+// icp_tail.hpp's, shared with the other variants:
 //   k_icp_plane_wave      nn_search_body.hpp's wave-cooperative search (the same include as k_nn_wave), then the winner's normal
 //                         (one 16-byte load per lane) and the 30 terms (the 27 above, d2, the correspondence, the row) in
 //                         double, reduced one term at a time through wave shuffles -> LDS -> partials[block][kPlaneAcc] in
 //                         k_nn_wave's fixed order (so the result does not depend on the batch or on the split either);
-//   k_icp_plane_finalize  one block per pair: the partials in a fixed order, the 6x6 solve on one lane, Tinc, the convergence tail.
+//   k_icp_plane_finalize  one block per pair: the partials in a fixed order, the 6x6 solve on one lane, Tinc, the convergence step.
+//                         Coloured ICP, generalized ICP and the rejecting step with normals end an iteration with it too.
 #include <cmath>
 
 #include "capi_guard.hpp"
 #include "drivers.hpp"
 #include "map_kept.hpp"
-#include "icp_solve6.hpp"
+#include "icp_tail.hpp"
 #include "nn_core.hpp"
 
 namespace mm3d {
@@ -55,52 +57,17 @@ k_icp_plane_wave(const NnPlaneJob *__restrict__ pjobs, float max_d2, float rmax)
 #include "nn_search_body.hpp"
   if (SPLIT == 4 && wave != 0) return;     // the four waves hold the same result
   const bool corr = valid && best <= max_d2;   // false for INFINITY / NaN
-  // the lane's row (zero where it has none, or where the target normal is not finite: such a correspondence still counts,
-  // and its d2 goes into the MSE of the convergence test)
+  // the lane's row (zero where it has none, or where the target normal is not finite)
   double v[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
   double r = 0.0, has_row = 0.0;
   if (corr) {
     const unsigned w = (unsigned)(bkey & 0xffffffffull);
-    const float4 n = nrm[w];
-    if (isfinite(n.x) && isfinite(n.y) && isfinite(n.z)) {
-      const float4 d = tgt_ref[w];
-      const double sx = p.x, sy = p.y, sz = p.z, nx = n.x, ny = n.y, nz = n.z;
-      v[0] = nz * sy - ny * sz;
-      v[1] = nx * sz - nz * sx;
-      v[2] = ny * sx - nx * sy;
-      v[3] = nx; v[4] = ny; v[5] = nz;
-      r = (nx * (double)d.x + ny * (double)d.y + nz * (double)d.z) - (nx * sx + ny * sy + nz * sz);
-      has_row = 1.0;
-    }
+    if (icp_plane_row(p, nrm[w], tgt_ref[w], v, r)) has_row = 1.0;
   }
-  // one term at a time (formed, summed over the wave, stored): 30 doubles held at once would cost 60 VGPRs on top of the search
-  auto term = [&](int k) -> double {
-    if (k < 21) return v[kUi[k]] * v[kUj[k]];
-    if (k < 27) return v[k - 21] * r;
-    if (k == 27) return corr ? (double)best : 0.0;
-    if (k == 28) return corr ? 1.0 : 0.0;
-    return has_row;
-  };
+  auto term = [&](int k) -> double { return icp_plane_term(k, v, r, corr, best, has_row); };
   // a wave none of whose points found a neighbour in range adds zeros without the reductions (as k_nn_wave does)
   const bool any_corr = ballot(corr) != 0ull;       // wave-uniform
-  if (SPLIT == 4) {
-#pragma unroll
-    for (int k = 0; k < kPlaneAcc; ++k) {
-      const double s = any_corr ? wave_sum(term(k)) : 0.0;
-      if (lane == 0) partials[(size_t)bid * kPlaneAcc + k] = s;
-    }
-    return;
-  }
-#pragma unroll
-  for (int k = 0; k < kPlaneAcc; ++k) {
-    const double s = any_corr ? wave_sum(term(k)) : 0.0;
-    if (lane == 0) red[wave][k] = s;
-  }
-  __syncthreads();
-  if (threadIdx.x < kPlaneAcc) {
-    const int k = threadIdx.x;
-    partials[(size_t)bid * kPlaneAcc + k] = red[0][k] + red[1][k] + red[2][k] + red[3][k];
-  }
+  icp_store_partials<kPlaneAcc, SPLIT>(term, any_corr, red, partials, bid);
 }
 
 __global__ void __launch_bounds__(256) k_icp_plane_finalize(const NnPlaneJob *__restrict__ pjobs)
@@ -108,72 +75,18 @@ __global__ void __launch_bounds__(256) k_icp_plane_finalize(const NnPlaneJob *__
   __shared__ double red[4][kPlaneAcc];
   __shared__ double tot[kPlaneAcc];
   const NnJob &job = pjobs[blockIdx.x].nn;
-  const double *__restrict__ partials = job.partials;
-  const int split = job.split, n_items = job.n_items;
-  const int nblocks = (n_items + 3) >> 2;              // in units of four items, whichever kernel variant wrote them
   IcpState *st = job.st;
   if (st->done) return;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int k = 0; k < kPlaneAcc; ++k) {
-    double acc = 0.0;
-    for (int b = threadIdx.x; b < nblocks; b += blockDim.x) acc += nn_block_partial_n<kPlaneAcc>(partials, b, k, split, n_items);
-    const double s = wave_sum(acc);
-    if (lane == 0) red[wave][k] = s;
-  }
-  __syncthreads();
-  if (threadIdx.x < kPlaneAcc) tot[threadIdx.x] = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
-  __syncthreads();
+  icp_totals<kPlaneAcc>(job, red, tot);
   if (threadIdx.x != 0) return;
 
   const double cnt = tot[28];
   st->n_corr = (int)cnt;
-  if (cnt < 3.0) {   // min_number_correspondences_: "Not enough correspondences" -> not converged, stop
-    st->converged = 0;
-    st->done = 1;
-    return;
-  }
-  double A[36], b[6], x[6];
-  for (int k = 0; k < 21; ++k) A[kUi[k] * 6 + kUj[k]] = A[kUj[k] * 6 + kUi[k]] = tot[k];
-  for (int i = 0; i < 6; ++i) b[i] = tot[21 + i];
-  const double trace = A[0] + A[7] + A[14] + A[21] + A[28] + A[35];
-  if (tot[29] < 6.0 || !solve6_ldlt(A, b, kPlanePivotTau * trace / 6.0, x)) {
-    // degenerate (fewer than six rows, or a plane / line that leaves a direction free): stop, not converged, T unchanged
-    st->converged = 0;
-    st->done = 1;
-    return;
-  }
-  // constructTransformationMatrix(alpha, beta, gamma, tx, ty, tz) = [Rz(gamma) Ry(beta) Rx(alpha) | t]:
-  //   | cg cb   -sg ca + cg sb sa    sg sa + cg sb ca |
-  //   | sg cb    cg ca + sg sb sa   -cg sa + sg sb ca |
-  //   | -sb      cb sa               cb ca            |
-  const double sa = sin(x[0]), ca = cos(x[0]), sb = sin(x[1]), cb = cos(x[1]), sg = sin(x[2]), cg = cos(x[2]);
-  const double R[9] = {cg * cb, -sg * ca + cg * sb * sa, sg * sa + cg * sb * ca,
-                       sg * cb, cg * ca + sg * sb * sa, -cg * sa + sg * sb * ca,
-                       -sb, cb * sa, cb * ca};
+  if (cnt < 3.0) return icp_stop_unconverged(st);   // min_number_correspondences_: "Not enough correspondences"
   float Ti[16];
-  for (int rr = 0; rr < 3; ++rr)
-    for (int c = 0; c < 3; ++c) Ti[c * 4 + rr] = (float)R[rr * 3 + c];
-  Ti[12] = (float)x[3]; Ti[13] = (float)x[4]; Ti[14] = (float)x[5];
-  Ti[3] = Ti[7] = Ti[11] = 0.0f;
-  Ti[15] = 1.0f;
-  // final = Tinc * final, and the rest of k_icp_finalize's tail
-  float Tn[16];
-  for (int c = 0; c < 4; ++c)
-    for (int rr = 0; rr < 4; ++rr) {
-      float a = 0.0f;
-      for (int k = 0; k < 4; ++k) a += Ti[k * 4 + rr] * st->T[c * 4 + k];
-      Tn[c * 4 + rr] = a;
-    }
-  for (int i = 0; i < 16; ++i) { st->T[i] = Tn[i]; st->Tinc[i] = Ti[i]; }
-  const int iters = ++st->iters;
-  // DefaultConvergenceCriteria::hasConverged
-  if (iters >= st->max_iter) { st->converged = 1; st->done = 1; return; }
-  const double cos_angle = 0.5 * ((double)Ti[0] + (double)Ti[5] + (double)Ti[10] - 1.0);
-  const double translation_sqr = (double)Ti[12] * Ti[12] + (double)Ti[13] * Ti[13] + (double)Ti[14] * Ti[14];
-  if (cos_angle >= st->rot_thresh && translation_sqr <= st->trans_thresh) { st->converged = 1; st->done = 1; return; }
-  const double mse = tot[27] / cnt;
-  if (fabs(mse - st->prev_mse) < 1e-12) { st->converged = 1; st->done = 1; return; }
-  st->prev_mse = mse;
+  // degenerate (fewer than six rows, or a plane / line that leaves a direction free): stop, not converged, T unchanged
+  if (tot[29] < 6.0 || !icp_solve6_transform(tot, Ti)) return icp_stop_unconverged(st);
+  icp_advance(st, Ti, true, tot[27] / cnt);
 }
 
 // (alone after the search of icp_color.hip and after the rejecting correspondence stage of icp_reject.hip, which write the

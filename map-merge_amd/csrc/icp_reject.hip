@@ -25,7 +25,7 @@
 
 #include "capi_guard.hpp"
 #include "drivers.hpp"
-#include "icp_solve6.hpp"
+#include "icp_tail.hpp"
 #include "nn_core.hpp"
 
 namespace mm3d {
@@ -349,32 +349,13 @@ __global__ void __launch_bounds__(256) k_rej_reduce(const NnRejectJob *__restric
       }
     }
   } else {
-    // k_icp_plane_wave's row, terms and order
+    // point-to-plane's row, terms and order (icp_tail.hpp's, as k_icp_plane_wave)
     double v[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     double r = 0.0, has_row = 0.0;
-    if (corr) {
-      const float4 n = nrm[cr.x];
-      if (isfinite(n.x) && isfinite(n.y) && isfinite(n.z)) {
-        const float4 d = tgt_ref[cr.x];
-        const double sx = p.x, sy = p.y, sz = p.z, nx = n.x, ny = n.y, nz = n.z;
-        v[0] = nz * sy - ny * sz;
-        v[1] = nx * sz - nz * sx;
-        v[2] = ny * sx - nx * sy;
-        v[3] = nx; v[4] = ny; v[5] = nz;
-        r = (nx * (double)d.x + ny * (double)d.y + nz * (double)d.z) - (nx * sx + ny * sy + nz * sz);
-        has_row = 1.0;
-      }
-    }
-    auto term = [&](int k) -> double {
-      if (k < 21) return v[kUi[k]] * v[kUj[k]];
-      if (k < 27) return v[k - 21] * r;
-      if (k == 27) return corr ? (double)best : 0.0;
-      if (k == 28) return corr ? 1.0 : 0.0;
-      return has_row;
-    };
+    if (corr && icp_plane_row(p, nrm[cr.x], tgt_ref[cr.x], v, r)) has_row = 1.0;
 #pragma unroll
     for (int k = 0; k < kPlaneAcc; ++k) {
-      const double s = any_corr ? wave_sum(term(k)) : 0.0;
+      const double s = any_corr ? wave_sum(icp_plane_term(k, v, r, corr, best, has_row)) : 0.0;
       if (SPLIT == 4) {
         if (lane == 0 && item < n_items) partials[(size_t)item * kPlaneAcc + k] = s;
       } else if (lane == 0) {

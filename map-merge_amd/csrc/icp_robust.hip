@@ -11,9 +11,9 @@
 //                   through wave_sum and the block step into partials of the step's own width: the default layout plus
 //                   `matched` and `weighted` (19 doubles, or 32 with normals), in the default kernels' order.
 //   k_rob_finalize  one block per pair: the partials in k_icp_finalize's fixed order, Umeyama or the 6x6 solve on totals that
-//                   sum w normalises, Tinc, and the convergence tail behind the final_k gate.  The tails are copies of
-//                   k_icp_finalize's and k_icp_plane_finalize's (-ffp-contract=off: the same expressions round the same way), so
-//                   those two kernels are untouched and with L2 (w = 1.0, x * 1.0 = x) the state holds the default ICP's bits.
+//                   sum w normalises, Tinc, and the convergence step behind the final_k gate.  These are the functions of
+//                   icp_tail.hpp that k_icp_finalize and k_icp_plane_finalize call (-ffp-contract=off: inlined twice, they round
+//                   the same way), so with L2 (w = 1.0, x * 1.0 = x) the state holds the default ICP's bits.
 // No correspondence array, no histogram, no select; per batch one table of doubles, per pair one 32-byte record.
 #include <atomic>
 #include <climits>
@@ -21,7 +21,7 @@
 
 #include "capi_guard.hpp"
 #include "drivers.hpp"
-#include "icp_solve6.hpp"
+#include "icp_tail.hpp"
 #include "nn_core.hpp"
 
 namespace mm3d {
@@ -112,8 +112,7 @@ k_rob_wave(const NnRobustJob *__restrict__ rjobs, RobOpts o, float max_d2, float
     rj.out_d2[orig] = corr ? best : INFINITY;
     rj.out_w[orig] = w;
   }
-  // one term at a time (formed, summed over the wave, stored), as k_icp_plane_wave does: the weight's divides share the
-  // registers the search has left
+  // one term at a time (icp_store_partials): the weight's divides share the registers the search has left
   float bqx = 0.f, bqy = 0.f, bqz = 0.f;
   double v[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
   double r = 0.0, has_row = 0.0;
@@ -121,18 +120,8 @@ k_rob_wave(const NnRobustJob *__restrict__ rjobs, RobOpts o, float max_d2, float
     if (!PLANE) {
       const float4 bq = tgt_ref[widx];
       bqx = bq.x; bqy = bq.y; bqz = bq.z;
-    } else {
-      const float4 n = nrm[widx];
-      if (isfinite(n.x) && isfinite(n.y) && isfinite(n.z)) {
-        const float4 d = tgt_ref[widx];
-        const double sx = p.x, sy = p.y, sz = p.z, nx = n.x, ny = n.y, nz = n.z;
-        v[0] = nz * sy - ny * sz;
-        v[1] = nx * sz - nz * sx;
-        v[2] = ny * sx - nx * sy;
-        v[3] = nx; v[4] = ny; v[5] = nz;
-        r = (nx * (double)d.x + ny * (double)d.y + nz * (double)d.z) - (nx * sx + ny * sy + nz * sz);
-        has_row = pos ? 1.0 : 0.0;
-      }
+    } else if (icp_plane_row(p, nrm[widx], tgt_ref[widx], v, r)) {
+      has_row = pos ? 1.0 : 0.0;
     }
   }
   auto term = [&](int k) -> double {
@@ -147,53 +136,15 @@ k_rob_wave(const NnRobustJob *__restrict__ rjobs, RobOpts o, float max_d2, float
       if (k == 15) return corr ? w * (double)best : 0.0;      // (best is +inf without a match)
       return w;
     }
-    // k_icp_plane_wave's terms, times w
-    if (k < 21) return w * (v[kUi[k]] * v[kUj[k]]);
-    if (k < 27) return w * (v[k - 21] * r);
+    // point-to-plane's terms, times w
+    if (k < 27) return w * icp_plane_term(k, v, r, corr, best, has_row);
     if (k == 27) return corr ? w * (double)best : 0.0;
     if (k == 28) return w;
     return has_row;
   };
   // a wave none of whose points found a neighbour in range adds zeros without the reductions (as k_nn_wave does)
   const bool any_corr = ballot(corr) != 0ull;       // wave-uniform
-  if (SPLIT == 4) {
-#pragma unroll
-    for (int k = 0; k < NACC; ++k) {
-      const double s = any_corr ? wave_sum(term(k)) : 0.0;
-      if (lane == 0) partials[(size_t)bid * NACC + k] = s;
-    }
-    return;
-  }
-#pragma unroll
-  for (int k = 0; k < NACC; ++k) {
-    const double s = any_corr ? wave_sum(term(k)) : 0.0;
-    if (lane == 0) red[wave][k] = s;
-  }
-  __syncthreads();
-  if (threadIdx.x < NACC) {
-    const int k = threadIdx.x;
-    partials[(size_t)bid * NACC + k] = red[0][k] + red[1][k] + red[2][k] + red[3][k];
-  }
-}
-
-// the pair's totals in k_icp_finalize's order: a thread's blocks b = t, t + 256, ..., the wave, the four waves.  By all 256
-// threads of a block; tot is valid for every thread afterwards.
-template <int NACC>
-__device__ __forceinline__ void rob_totals(const NnJob &job, double (*red)[NACC], double *tot)
-{
-  const double *__restrict__ partials = job.partials;
-  const int split = job.split, n_items = job.n_items;
-  const int nblocks = (n_items + 3) >> 2;              // in units of four items, whichever kernel variant wrote them
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int k = 0; k < NACC; ++k) {
-    double acc = 0.0;
-    for (int b = threadIdx.x; b < nblocks; b += blockDim.x) acc += nn_block_partial_n<NACC>(partials, b, k, split, n_items);
-    const double s = wave_sum(acc);
-    if (lane == 0) red[wave][k] = s;
-  }
-  __syncthreads();
-  if (threadIdx.x < NACC) tot[threadIdx.x] = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
-  __syncthreads();
+  icp_store_partials<NACC, SPLIT>(term, any_corr, red, partials, bid);
 }
 
 // mm3d_debug_icp_robust: the totals the finalize kernel would read
@@ -202,30 +153,8 @@ __global__ void __launch_bounds__(256) k_rob_totals(const NnRobustJob *__restric
 {
   __shared__ double red[4][NACC];
   __shared__ double tot[NACC];
-  rob_totals<NACC>(rjobs[0].nn, red, tot);
+  icp_totals<NACC>(rjobs[0].nn, red, tot);
   if (threadIdx.x < NACC) out[threadIdx.x] = tot[threadIdx.x];
-}
-
-// final = Tinc * final, the iteration count and DefaultConvergenceCriteria::hasConverged behind the final_k gate: the tail of
-// k_icp_finalize and k_icp_plane_finalize.  One thread.
-__device__ __forceinline__ void rob_tail(IcpState *st, const float *Ti, bool final_k, double mse)
-{
-  float Tn[16];
-  for (int c = 0; c < 4; ++c)
-    for (int r = 0; r < 4; ++r) {
-      float a = 0.0f;
-      for (int k = 0; k < 4; ++k) a += Ti[k * 4 + r] * st->T[c * 4 + k];
-      Tn[c * 4 + r] = a;
-    }
-  for (int i = 0; i < 16; ++i) { st->T[i] = Tn[i]; st->Tinc[i] = Ti[i]; }
-  const int iters = ++st->iters;
-  if (iters >= st->max_iter) { st->converged = 1; st->done = 1; return; }
-  if (!final_k) return;      // (an annealing run does not stop on a scale it is about to leave)
-  const double cos_angle = 0.5 * ((double)Ti[0] + (double)Ti[5] + (double)Ti[10] - 1.0);
-  const double translation_sqr = (double)Ti[12] * Ti[12] + (double)Ti[13] * Ti[13] + (double)Ti[14] * Ti[14];
-  if (cos_angle >= st->rot_thresh && translation_sqr <= st->trans_thresh) { st->converged = 1; st->done = 1; return; }
-  if (fabs(mse - st->prev_mse) < 1e-12) { st->converged = 1; st->done = 1; return; }
-  st->prev_mse = mse;
 }
 
 template <bool PLANE>
@@ -237,71 +166,29 @@ __global__ void __launch_bounds__(256) k_rob_finalize(const NnRobustJob *__restr
   const NnRobustJob &rj = rjobs[blockIdx.x];
   IcpState *st = rj.nn.st;
   if (st->done) return;
-  rob_totals<NACC>(rj.nn, red, tot);
+  icp_totals<NACC>(rj.nn, red, tot);
   if (threadIdx.x != 0) return;
 
   const double sigma = rob_sigma(o, st->iters);
-  const bool final_k = sigma == o.scale;
+  const bool final_k = sigma == o.scale;      // (an annealing run does not stop on a scale it is about to leave)
   const double wsum = tot[PLANE ? 28 : 16], weighted = tot[NACC - 1];
   *rj.rec = RobRecord{wsum, sigma, (long long)tot[NACC - 2], (long long)weighted};
   st->n_corr = (int)weighted;
-  if (weighted < 3.0) {   // min_number_correspondences_: "Not enough correspondences" -> not converged, stop
-    st->converged = 0;
-    st->done = 1;
-    return;
-  }
+  if (weighted < 3.0) return icp_stop_unconverged(st);   // min_number_correspondences_: "Not enough correspondences"
   float Ti[16];
   double mse;
   if (!PLANE) {
-    // k_icp_finalize's Umeyama on the moments that sum w normalises
+    // Umeyama on the moments that sum w normalises
     const double inv = 1.0 / wsum;
-    double mp[3] = {tot[0] * inv, tot[1] * inv, tot[2] * inv}, mq[3] = {tot[3] * inv, tot[4] * inv, tot[5] * inv};
-    double sg[9];
-    for (int r = 0; r < 3; ++r)
-      for (int c = 0; c < 3; ++c) sg[r * 3 + c] = tot[6 + r * 3 + c] * inv - mq[r] * mp[c];
-    double U[9], S[3], V[9];
-    svd3_shared(sg, U, S, V);
-    double Sd[3] = {1.0, 1.0, 1.0};
-    if (det3_shared(sg) < 0) Sd[2] = -1.0;
-    int rank = 0;
-    for (int i = 0; i < 3; ++i)
-      if (!(fabs(S[i]) <= fabs(S[0]) * 1e-5)) ++rank;
-    if (rank == 2) Sd[2] = (det3_shared(U) * det3_shared(V) > 0) ? 1.0 : -1.0;
-    for (int r = 0; r < 3; ++r)
-      for (int c = 0; c < 3; ++c) {
-        double a = 0;
-        for (int k = 0; k < 3; ++k) a += U[r * 3 + k] * Sd[k] * V[c * 3 + k];
-        Ti[c * 4 + r] = (float)a;
-      }
-    for (int r = 0; r < 3; ++r) {
-      const double a = mq[r] - ((double)Ti[0 * 4 + r] * mp[0] + (double)Ti[1 * 4 + r] * mp[1] + (double)Ti[2 * 4 + r] * mp[2]);
-      Ti[12 + r] = (float)a;
-    }
+    icp_umeyama(tot, inv, Ti);
     mse = tot[15] * inv;
   } else {
-    // k_icp_plane_finalize's 6x6 system (a system scaled by sum w has the same solution: nothing is normalised)
-    double A[36], b[6], x[6];
-    for (int k = 0; k < 21; ++k) A[kUi[k] * 6 + kUj[k]] = A[kUj[k] * 6 + kUi[k]] = tot[k];
-    for (int i = 0; i < 6; ++i) b[i] = tot[21 + i];
-    const double trace = A[0] + A[7] + A[14] + A[21] + A[28] + A[35];
-    if (tot[29] < 6.0 || !solve6_ldlt(A, b, kPlanePivotTau * trace / 6.0, x)) {
-      // degenerate (fewer than six weighted rows, or a plane / line that leaves a direction free): stop, not converged, T unchanged
-      st->converged = 0;
-      st->done = 1;
-      return;
-    }
-    const double sa = sin(x[0]), ca = cos(x[0]), sb = sin(x[1]), cb = cos(x[1]), sgm = sin(x[2]), cg = cos(x[2]);
-    const double R[9] = {cg * cb, -sgm * ca + cg * sb * sa, sgm * sa + cg * sb * ca,
-                         sgm * cb, cg * ca + sgm * sb * sa, -cg * sa + sgm * sb * ca,
-                         -sb, cb * sa, cb * ca};
-    for (int rr = 0; rr < 3; ++rr)
-      for (int c = 0; c < 3; ++c) Ti[c * 4 + rr] = (float)R[rr * 3 + c];
-    Ti[12] = (float)x[3]; Ti[13] = (float)x[4]; Ti[14] = (float)x[5];
+    // the 6x6 system (a system scaled by sum w has the same solution: nothing is normalised); degenerate with fewer than six
+    // weighted rows, or a plane / line that leaves a direction free: stop, not converged, T unchanged
+    if (tot[29] < 6.0 || !icp_solve6_transform(tot, Ti)) return icp_stop_unconverged(st);
     mse = tot[27] / wsum;
   }
-  Ti[3] = Ti[7] = Ti[11] = 0.0f;
-  Ti[15] = 1.0f;
-  rob_tail(st, Ti, final_k, mse);
+  icp_advance(st, Ti, final_k, mse);
 }
 
 static double rob_tuning(const mm3d_icp_robust_options &o)

@@ -21,15 +21,16 @@
 //                   voxel, the terms in double; per lane sum_w P (6), sum_w P q (3), sum w and the term count, from which the
 //                   30 sums are formed and reduced one at a time: wave shuffles -> LDS -> partials[block][kNdtAcc], four
 //                   work items per block whatever the batch, so the result depends on neither batch nor stream count.
-//   k_ndt_finalize  one block per pair: the partials in a fixed order, the 6x6 solve on one lane, Tinc, the convergence tail
-//                   of k_icp_finalize on the same IcpState, with the mean weight in the place of the mean d2.
+//   k_ndt_finalize  one block per pair: the partials in a fixed order, the 6x6 solve on one lane, Tinc, the convergence step
+//                   on the same IcpState, with the mean weight in the place of the mean d2 -- icp_tail.hpp's pieces, the ones
+//                   every ICP's finalize is made of.
 #include <cmath>
 #include <cstring>
 
 #include "capi_guard.hpp"
 #include "drivers.hpp"
 #include "map_kept.hpp"
-#include "icp_solve6.hpp"
+#include "icp_tail.hpp"
 #include "lattice.hpp"
 #include "nn_core.hpp"
 #include "scan_fused.hpp"
@@ -205,7 +206,7 @@ k_ndt_wave(const NdtJob *__restrict__ jobs)
       ++terms;
     }
   }
-  // one sum at a time (formed, summed over the wave, stored), as k_icp_plane_wave does: H_ij = J_i . (A J_j), g_i = -J_i . bq
+  // one sum at a time (icp_store_partials): H_ij = J_i . (A J_j), g_i = -J_i . bq
   auto term = [&](int k) -> double {
     if (k < 21) {
       double ci[3], cj[3];
@@ -226,16 +227,7 @@ k_ndt_wave(const NdtJob *__restrict__ jobs)
   };
   // a wave none of whose points has a term adds zeros without the reductions (as k_nn_wave does)
   const bool any_term = ballot(terms > 0) != 0ull;       // wave-uniform
-#pragma unroll
-  for (int k = 0; k < kNdtAcc; ++k) {
-    const double s = any_term ? wave_sum(term(k)) : 0.0;
-    if (lane == 0) red[wave][k] = s;
-  }
-  __syncthreads();
-  if (threadIdx.x < kNdtAcc) {
-    const int k = threadIdx.x;
-    partials[(size_t)blockIdx.x * kNdtAcc + k] = red[0][k] + red[1][k] + red[2][k] + red[3][k];
-  }
+  icp_store_partials<kNdtAcc, 1>(term, any_term, red, partials, blockIdx.x);
 }
 
 __global__ void __launch_bounds__(256) k_ndt_finalize(const NdtJob *__restrict__ jobs)
@@ -243,62 +235,17 @@ __global__ void __launch_bounds__(256) k_ndt_finalize(const NdtJob *__restrict__
   __shared__ double red[4][kNdtAcc];
   __shared__ double tot[kNdtAcc];
   const NdtJob &job = jobs[blockIdx.x];
-  const double *__restrict__ partials = job.nn.partials;
-  const int nblocks = job.nn.nblocks;
   IcpState *st = job.nn.st;
   if (st->done) return;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int k = 0; k < kNdtAcc; ++k) {
-    double acc = 0.0;
-    for (int b = threadIdx.x; b < nblocks; b += blockDim.x) acc += partials[(size_t)b * kNdtAcc + k];
-    const double s = wave_sum(acc);
-    if (lane == 0) red[wave][k] = s;
-  }
-  __syncthreads();
-  if (threadIdx.x < kNdtAcc) tot[threadIdx.x] = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
-  __syncthreads();
+  icp_totals<kNdtAcc>(job.nn.partials, job.nn.nblocks, 0, job.nn.n_items, red, tot);
   if (threadIdx.x != 0) return;
 
   st->n_corr = (int)tot[29];
-  double A[36], b[6], x[6];
-  for (int k = 0; k < 21; ++k) A[kUi[k] * 6 + kUj[k]] = A[kUj[k] * 6 + kUi[k]] = tot[k];
-  for (int i = 0; i < 6; ++i) b[i] = tot[21 + i];
-  const double trace = A[0] + A[7] + A[14] + A[21] + A[28] + A[35];
-  if (tot[28] < 6.0 || !solve6_ldlt(A, b, kPlanePivotTau * trace / 6.0, x)) {
-    // degenerate (fewer than six terms, or a pivot at or below the threshold): stop, not converged, T unchanged
-    st->converged = 0;
-    st->done = 1;
-    return;
-  }
-  // constructTransformationMatrix(alpha, beta, gamma, tx, ty, tz) = [Rz(gamma) Ry(beta) Rx(alpha) | t], as k_icp_plane_finalize
-  const double sa = sin(x[0]), ca = cos(x[0]), sb = sin(x[1]), cb = cos(x[1]), sg = sin(x[2]), cg = cos(x[2]);
-  const double R[9] = {cg * cb, -sg * ca + cg * sb * sa, sg * sa + cg * sb * ca,
-                       sg * cb, cg * ca + sg * sb * sa, -cg * sa + sg * sb * ca,
-                       -sb, cb * sa, cb * ca};
   float Ti[16];
-  for (int rr = 0; rr < 3; ++rr)
-    for (int c = 0; c < 3; ++c) Ti[c * 4 + rr] = (float)R[rr * 3 + c];
-  Ti[12] = (float)x[3]; Ti[13] = (float)x[4]; Ti[14] = (float)x[5];
-  Ti[3] = Ti[7] = Ti[11] = 0.0f;
-  Ti[15] = 1.0f;
-  // final = Tinc * final, and the rest of k_icp_finalize's tail
-  float Tn[16];
-  for (int c = 0; c < 4; ++c)
-    for (int rr = 0; rr < 4; ++rr) {
-      float a = 0.0f;
-      for (int k = 0; k < 4; ++k) a += Ti[k * 4 + rr] * st->T[c * 4 + k];
-      Tn[c * 4 + rr] = a;
-    }
-  for (int i = 0; i < 16; ++i) { st->T[i] = Tn[i]; st->Tinc[i] = Ti[i]; }
-  const int iters = ++st->iters;
+  // degenerate (fewer than six terms, or a pivot at or below the threshold): stop, not converged, T unchanged
+  if (tot[28] < 6.0 || !icp_solve6_transform(tot, Ti)) return icp_stop_unconverged(st);
   // DefaultConvergenceCriteria::hasConverged, the mean weight F in the place of the mean d2
-  if (iters >= st->max_iter) { st->converged = 1; st->done = 1; return; }
-  const double cos_angle = 0.5 * ((double)Ti[0] + (double)Ti[5] + (double)Ti[10] - 1.0);
-  const double translation_sqr = (double)Ti[12] * Ti[12] + (double)Ti[13] * Ti[13] + (double)Ti[14] * Ti[14];
-  if (cos_angle >= st->rot_thresh && translation_sqr <= st->trans_thresh) { st->converged = 1; st->done = 1; return; }
-  const double F = tot[27] / (double)job.n_src;
-  if (fabs(F - st->prev_mse) < 1e-12) { st->converged = 1; st->done = 1; return; }
-  st->prev_mse = F;
+  icp_advance(st, Ti, true, tot[27] / (double)job.n_src);
 }
 
 // everything but the resolution's "0 = default", which only mm3d_set_refinement admits

@@ -22,6 +22,7 @@
 // icp_finalize (Umeyama by 3x3 Jacobi SVD, accumulate, PCL's convergence tests, all on the device).
 // Algorithmic traffic: 12 B per source point per iteration.
 #include "capi_guard.hpp"
+#include "icp_tail.hpp"
 #include "nn_core.hpp"
 
 namespace mm3d {
@@ -140,85 +141,24 @@ k_nn_probe(const NnJob *__restrict__ jobs, float max_d2, float rmax, int *__rest
   }
 }
 
-// one block: reduce partials, Umeyama, accumulate, convergence (DefaultConvergenceCriteria)
+// one block: reduce partials, Umeyama, accumulate, convergence (DefaultConvergenceCriteria) -- icp_tail.hpp's pieces
 __global__ void __launch_bounds__(256) k_icp_finalize(const NnJob *__restrict__ jobs)
 {
   __shared__ double red[4][kAcc];
   __shared__ double tot[kAcc];
-  const double *__restrict__ partials = jobs[blockIdx.x].partials;
-  const int split = jobs[blockIdx.x].split, n_items = jobs[blockIdx.x].n_items;
-  const int nblocks = (n_items + 3) >> 2;              // in units of four items, whichever kernel wrote them
-  IcpState *st = jobs[blockIdx.x].st;
+  const NnJob &job = jobs[blockIdx.x];
+  IcpState *st = job.st;
   if (st->done) return;
-  double acc[kAcc];
-#pragma unroll
-  for (int k = 0; k < kAcc; ++k) acc[k] = 0.0;
-  for (int b = threadIdx.x; b < nblocks; b += blockDim.x)
-#pragma unroll
-    for (int k = 0; k < kAcc; ++k) acc[k] += nn_block_partial_n<kAcc>(partials, b, k, split, n_items);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < kAcc; ++k) {
-    const double v = wave_sum(acc[k]);
-    if (lane == 0) red[wave][k] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < kAcc) tot[threadIdx.x] = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
-  __syncthreads();
+  icp_totals<kAcc>(job, red, tot);
   if (threadIdx.x != 0) return;
 
   const double cnt = tot[16];
   st->n_corr = (int)cnt;
-  if (cnt < 3.0) {   // min_number_correspondences_: "Not enough correspondences" -> not converged, stop
-    st->converged = 0;
-    st->done = 1;
-    return;
-  }
+  if (cnt < 3.0) return icp_stop_unconverged(st);   // min_number_correspondences_: "Not enough correspondences"
   const double inv = 1.0 / cnt;
-  double mp[3] = {tot[0] * inv, tot[1] * inv, tot[2] * inv}, mq[3] = {tot[3] * inv, tot[4] * inv, tot[5] * inv};
-  double sigma[9];
-  for (int r = 0; r < 3; ++r)
-    for (int c = 0; c < 3; ++c) sigma[r * 3 + c] = tot[6 + r * 3 + c] * inv - mq[r] * mp[c];
-  double U[9], S[3], V[9];
-  svd3_shared(sigma, U, S, V);
-  double Sd[3] = {1.0, 1.0, 1.0};
-  if (det3_shared(sigma) < 0) Sd[2] = -1.0;
-  int rank = 0;
-  for (int i = 0; i < 3; ++i)
-    if (!(fabs(S[i]) <= fabs(S[0]) * 1e-5)) ++rank;
-  if (rank == 2) Sd[2] = (det3_shared(U) * det3_shared(V) > 0) ? 1.0 : -1.0;
   float Ti[16];
-  for (int r = 0; r < 3; ++r)
-    for (int c = 0; c < 3; ++c) {
-      double a = 0;
-      for (int k = 0; k < 3; ++k) a += U[r * 3 + k] * Sd[k] * V[c * 3 + k];
-      Ti[c * 4 + r] = (float)a;
-    }
-  for (int r = 0; r < 3; ++r) {
-    // t = dst_mean - R * src_mean (with the float R, like Eigen's float instantiation)
-    const double a = mq[r] - ((double)Ti[0 * 4 + r] * mp[0] + (double)Ti[1 * 4 + r] * mp[1] + (double)Ti[2 * 4 + r] * mp[2]);
-    Ti[12 + r] = (float)a;
-  }
-  Ti[3] = Ti[7] = Ti[11] = 0.0f;
-  Ti[15] = 1.0f;
-  // final = Tinc * final
-  float Tn[16];
-  for (int c = 0; c < 4; ++c)
-    for (int r = 0; r < 4; ++r) {
-      float a = 0.0f;
-      for (int k = 0; k < 4; ++k) a += Ti[k * 4 + r] * st->T[c * 4 + k];
-      Tn[c * 4 + r] = a;
-    }
-  for (int i = 0; i < 16; ++i) { st->T[i] = Tn[i]; st->Tinc[i] = Ti[i]; }
-  const int iters = ++st->iters;
-  // DefaultConvergenceCriteria::hasConverged
-  if (iters >= st->max_iter) { st->converged = 1; st->done = 1; return; }
-  const double cos_angle = 0.5 * ((double)Ti[0] + (double)Ti[5] + (double)Ti[10] - 1.0);
-  const double translation_sqr = (double)Ti[12] * Ti[12] + (double)Ti[13] * Ti[13] + (double)Ti[14] * Ti[14];
-  if (cos_angle >= st->rot_thresh && translation_sqr <= st->trans_thresh) { st->converged = 1; st->done = 1; return; }
-  const double mse = tot[15] * inv;
-  if (fabs(mse - st->prev_mse) < 1e-12) { st->converged = 1; st->done = 1; return; }
-  st->prev_mse = mse;
+  icp_umeyama(tot, inv, Ti);
+  icp_advance(st, Ti, true, tot[15] * inv);
 }
 
 __global__ void __launch_bounds__(256) k_score_finalize(const NnJob *__restrict__ jobs)

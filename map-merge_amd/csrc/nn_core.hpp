@@ -2,7 +2,8 @@
 // ICP and the score) and the files that put another ICP in its place (icp_plane.hip, icp_color.hip, icp_generalized.hip, icp_reject.hip, icp_robust.hip, ndt.hip):
 // the search knobs, the ICP state, the job layout and the wave helpers of the kernels; and, for the host, the set-up of one
 // search (NnSearch) and the interface through which a variant takes part in a batch (IcpStep).  The search itself is
-// nn_search_body.hpp (see there).
+// nn_search_body.hpp (see there); how an iteration ends -- the partials, the totals, the estimate, the convergence step -- is
+// icp_tail.hpp, one text for every variant's kernels.
 #pragma once
 #include <cfloat>
 #include <cstddef>
