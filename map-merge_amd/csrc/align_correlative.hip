@@ -697,11 +697,10 @@ int mm3d_set_coarse_alignment(mm3d_ctx *ctx, const mm3d_coarse_options *options)
   if (!ctx || !corr_options_ok(options)) return MM3D_EINVAL;
   if (options->cell != 0.0 && !lattice_side_ok(options->cell)) return MM3D_EINVAL;     // (also catches NaN)
   std::lock_guard<std::mutex> lock(ctx->mu);        // (no call is running while the method changes)
-  const bool corr = options->method == MM3D_COARSE_CORRELATIVE;
-  if (corr && refused_on_device_list(ctx, "mm3d_set_coarse_alignment: the correlative alignment is not available on a device-list context"))
-    return MM3D_EUNSUPPORTED;
-  select_stages(ctx, false, [&](StageSelection &s) { s.coarse = corr ? &g_correlative : nullptr; s.coarse_options = *options; });
-  return MM3D_OK;
+  return select_stage(ctx, Stage::Coarse, [&](StageSelection &s) {
+    s.coarse_options = *options;
+    s.coarse = stage_active(Stage::Coarse, s) ? &g_correlative : nullptr;
+  });
 }
 
 int mm3d_get_coarse_alignment(const mm3d_ctx *ctx, mm3d_coarse_options *options)

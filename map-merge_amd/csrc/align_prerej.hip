@@ -489,11 +489,10 @@ int mm3d_set_alignment(mm3d_ctx *ctx, const mm3d_alignment_options *options)
 {
   if (!ctx || !options_ok(options)) return MM3D_EINVAL;
   std::lock_guard<std::mutex> lock(ctx->mu);        // (no call is running while the method changes)
-  const bool prerej = options->method == MM3D_ALIGN_PREREJECTIVE;
-  if (prerej && refused_on_device_list(ctx, "mm3d_set_alignment: prerejective alignment is not available on a device-list context"))
-    return MM3D_EUNSUPPORTED;
-  select_stages(ctx, false, [&](StageSelection &s) { s.align = prerej ? &g_prerejective : nullptr; s.align_options = *options; });
-  return MM3D_OK;
+  return select_stage(ctx, Stage::Alignment, [&](StageSelection &s) {
+    s.align_options = *options;
+    s.align = stage_active(Stage::Alignment, s) ? &g_prerejective : nullptr;
+  });
 }
 
 int mm3d_get_alignment(const mm3d_ctx *ctx, mm3d_alignment_options *options)

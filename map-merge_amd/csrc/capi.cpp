@@ -48,24 +48,6 @@ mm3d::StageSelection::StageSelection()
   mm3d_icp_geometry_options_default(&geometry_options);
 }
 
-void mm3d::select_stages(mm3d_ctx *ctx, bool peers_follow, const std::function<void(StageSelection &)> &edit)
-{
-  auto one = [&](mm3d_ctx *root) {
-    edit(root->sel);
-    for (mm3d_ctx *h : root->helpers) h->sel = root->sel;
-  };
-  one(ctx);
-  if (peers_follow)
-    for (mm3d_ctx *p : ctx->peers) one(p);            // (every device of an mm3d_create_devices context)
-}
-
-bool mm3d::refused_on_device_list(mm3d_ctx *ctx, const char *text)
-{
-  if (!ctx->device_set) return false;
-  ctx->err = text;
-  return true;
-}
-
 extern "C" {
 
 // ---------------------------------------------------------------- enums / params

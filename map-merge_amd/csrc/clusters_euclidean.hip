@@ -329,12 +329,10 @@ int mm3d_set_cluster_filter(mm3d_ctx *ctx, const mm3d_cluster_options *options)
 {
   if (!ctx || !options_ok(options)) return MM3D_EINVAL;
   std::lock_guard<std::mutex> lock(ctx->mu);        // (no call is running while the filter changes)
-  // (a map's filtered points travel in the bundles, so device lists carry the option: the peers follow)
-  select_stages(ctx, true, [&](StageSelection &s) {
-    s.clusters = options->method != MM3D_CLUSTERS_OFF ? &g_euclidean : nullptr;
+  return select_stage(ctx, Stage::Clusters, [&](StageSelection &s) {
     s.cluster_options = *options;
+    s.clusters = stage_active(Stage::Clusters, s) ? &g_euclidean : nullptr;
   });
-  return MM3D_OK;
 }
 
 int mm3d_get_cluster_filter(const mm3d_ctx *ctx, mm3d_cluster_options *options)

@@ -364,11 +364,10 @@ int mm3d_set_confidence(mm3d_ctx *ctx, const mm3d_confidence_options *options)
   if (!ctx || !ovl_options_ok(options)) return MM3D_EINVAL;
   if (options->voxel != 0.0 && !lattice_side_ok(options->voxel)) return MM3D_EINVAL;     // (also catches NaN)
   std::lock_guard<std::mutex> lock(ctx->mu);        // (no call is running while the method changes)
-  const bool ovl = options->method == MM3D_CONFIDENCE_OVERLAP;
-  if (ovl && refused_on_device_list(ctx, "mm3d_set_confidence: the overlap confidence is not available on a device-list context"))
-    return MM3D_EUNSUPPORTED;
-  select_stages(ctx, false, [&](StageSelection &s) { s.confidence = ovl ? &g_overlap : nullptr; s.confidence_options = *options; });
-  return MM3D_OK;
+  return select_stage(ctx, Stage::Confidence, [&](StageSelection &s) {
+    s.confidence_options = *options;
+    s.confidence = stage_active(Stage::Confidence, s) ? &g_overlap : nullptr;
+  });
 }
 
 int mm3d_get_confidence(const mm3d_ctx *ctx, mm3d_confidence_options *options)

@@ -56,19 +56,7 @@ int mm3d_shard_begin(mm3d_ctx *ctx, const mm3d_cloud_view *clouds, size_t n, con
   if (!ctx || !params || !out || (n && !clouds) || world < 1 || rank < 0 || rank >= world) return MM3D_EINVAL;
   *out = nullptr;
   return guarded(ctx, [&] {
-    const StageSelection &sel = ctx->sel;
-    if (sel.icp) throw Error(MM3D_EUNSUPPORTED, "mm3d_shard_begin: shard bundles carry no normals for point-to-plane ICP");
-    if (sel.confidence) throw Error(MM3D_EUNSUPPORTED, "mm3d_shard_begin: shard bundles carry no tables for the overlap confidence");
-    if (sel.coarse) throw Error(MM3D_EUNSUPPORTED, "mm3d_shard_begin: shard bundles carry no signatures for the correlative alignment");
-    if (sel.refine) throw Error(MM3D_EUNSUPPORTED, "mm3d_shard_begin: shard bundles carry no voxel tables for NDT");
-    if (sel.align) throw Error(MM3D_EUNSUPPORTED, "mm3d_shard_begin: the ranks' pair loops run SAC-IA, not the prerejective alignment");
-    if (sel.rejecting()) throw Error(MM3D_EUNSUPPORTED, "mm3d_shard_begin: the ranks' pair loops run the ICP without correspondence rejection");
-    if (sel.geometric()) throw Error(MM3D_EUNSUPPORTED, "mm3d_shard_begin: the ranks' pair loops run the ICP without the geometric rejectors");
-    if (sel.robust()) throw Error(MM3D_EUNSUPPORTED, "mm3d_shard_begin: the ranks' pair loops run the ICP without a robust kernel");
-    if (sel.color) throw Error(MM3D_EUNSUPPORTED, "mm3d_shard_begin: shard bundles carry no colour gradients for coloured ICP");
-    if (sel.generalized) throw Error(MM3D_EUNSUPPORTED, "mm3d_shard_begin: shard bundles carry no normals for generalized ICP");
-    if (sel.estimator) throw Error(MM3D_EUNSUPPORTED, "mm3d_shard_begin: the ranks' pair loops run RANSAC, not the consistency estimation");
-    if (sel.sampler) throw Error(MM3D_EUNSUPPORTED, "mm3d_shard_begin: the ranks' pair loops run the ICP on the whole source, not on a sample");
+    if (const StageRule *r = first_stage_left_home(ctx->sel)) throw Error(MM3D_EUNSUPPORTED, std::string("mm3d_shard_begin: ") + r->stays_home);
     *out = shard_begin_impl(ctx, clouds, n, params, rank, world);
   });
 }

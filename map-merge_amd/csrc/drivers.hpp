@@ -1,7 +1,8 @@
 // drivers.hpp -- what the host files behind the extern "C" boundary share: capi.cpp (the boundary itself), pair_estimate.cpp
 // (the map builders and the pair estimator) and the N-map drivers of mm3d_estimate_maps_transforms (driver_streams.cpp: one
 // device; driver_shard.cpp: one process per device; driver_devices.cpp: a device list in one process).  Host code only: a
-// kernel file includes this for its setter's sake (select_stages) and nothing else.  Everything declared between the visibility pragmas stays inside libmm3d.so.
+// kernel file includes this for its setter's sake (select_stage, stage_rules.hpp) and nothing else.  Everything declared between the
+// visibility pragmas stays inside libmm3d.so.
 #pragma once
 
 #include <atomic>
@@ -14,6 +15,7 @@
 #include <utility>
 #include <vector>
 
+#include "stage_rules.hpp"
 #include "types.hpp"
 
 // one rank's (or one device's) share of a job: the maps it owns and its copies of the others' (driver_shard.cpp)
@@ -46,12 +48,7 @@ struct PrivateObjects {
 #pragma GCC visibility push(hidden)
 namespace mm3d {
 
-// ---- capi.cpp: the one way a context's stage selection changes (the six setters, in their kernel files, under the context's
-// lock).  `edit` is applied to the context's record, which then goes to every helper whole; with peers_follow the same
-// happens on every peer of a device list.
-void select_stages(mm3d_ctx *ctx, bool peers_follow, const std::function<void(StageSelection &)> &edit);
-// a setter's refusal of a stage that device lists do not carry: true, and `text` is the context's error, on such a context
-bool refused_on_device_list(mm3d_ctx *ctx, const char *text);
+// (the one way a context's stage selection changes -- the seventeen setters, in their kernel files -- is stage_rules.hpp's select_stage)
 
 // ---- pair_estimate.cpp: the map builders
 std::unique_ptr<mm3d_cloud> cloud_from_view(mm3d_ctx *c, const mm3d_cloud_view &v);

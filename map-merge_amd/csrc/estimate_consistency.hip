@@ -380,11 +380,10 @@ int mm3d_set_estimator(mm3d_ctx *ctx, const mm3d_estimator_options *options)
 {
   if (!ctx || !options_ok(options)) return MM3D_EINVAL;
   std::lock_guard<std::mutex> lock(ctx->mu);        // (no call is running while the method changes)
-  const bool on = options->method == MM3D_ESTIMATOR_CONSISTENCY;
-  if (on && refused_on_device_list(ctx, "mm3d_set_estimator: consistency estimation is not available on a device-list context"))
-    return MM3D_EUNSUPPORTED;
-  select_stages(ctx, false, [&](StageSelection &s) { s.estimator = on ? &g_consistency : nullptr; s.estimator_options = *options; });
-  return MM3D_OK;
+  return select_stage(ctx, Stage::Estimator, [&](StageSelection &s) {
+    s.estimator_options = *options;
+    s.estimator = stage_active(Stage::Estimator, s) ? &g_consistency : nullptr;
+  });
 }
 
 int mm3d_get_estimator(const mm3d_ctx *ctx, mm3d_estimator_options *options)

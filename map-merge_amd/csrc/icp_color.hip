@@ -354,34 +354,10 @@ int mm3d_set_icp_color(mm3d_ctx *ctx, const mm3d_icp_color_options *options)
 {
   if (!ctx || !options || !icp_color_options_valid(options)) return MM3D_EINVAL;
   std::lock_guard<std::mutex> lock(ctx->mu);        // (no call is running while the selection changes)
-  if (options->enabled) {
-    if (refused_on_device_list(ctx, "mm3d_set_icp_color: not available on a device-list context")) return MM3D_EUNSUPPORTED;
-    if (ctx->sel.rejecting()) {
-      ctx->err = "mm3d_set_icp_color: not available while a correspondence rejection is active (mm3d_set_icp_rejection)";
-      return MM3D_EUNSUPPORTED;
-    }
-    if (ctx->sel.geometric()) {      // (step 1b is the rejecting step's)
-      ctx->err = "mm3d_set_icp_color: not available while a geometric rejector is active (mm3d_set_icp_geometry_rejection)";
-      return MM3D_EUNSUPPORTED;
-    }
-    if (ctx->sel.generalized) {
-      ctx->err = "mm3d_set_icp_color: not available while generalized ICP is enabled (mm3d_set_icp_generalized)";
-      return MM3D_EUNSUPPORTED;
-    }
-    if (ctx->sel.robust()) {                          // (the robust step has no colour variant)
-      ctx->err = "mm3d_set_icp_color: not available while a robust kernel is selected (mm3d_set_icp_robust)";
-      return MM3D_EUNSUPPORTED;
-    }
-    if (ctx->sel.sampler) {                           // (the colour term reads the source's own records by index)
-      ctx->err = "mm3d_set_icp_color: not available while an ICP source sampling is set (mm3d_set_icp_sampling)";
-      return MM3D_EUNSUPPORTED;
-    }
-  }
-  select_stages(ctx, false, [&](StageSelection &s) {
+  return select_stage(ctx, Stage::Color, [&](StageSelection &s) {
     s.color_options = *options;
-    s.color = options->enabled ? &g_coloured : nullptr;
+    s.color = stage_active(Stage::Color, s) ? &g_coloured : nullptr;
   });
-  return MM3D_OK;
 }
 
 int mm3d_get_icp_color(const mm3d_ctx *ctx, mm3d_icp_color_options *options)

@@ -234,34 +234,10 @@ int mm3d_set_icp_generalized(mm3d_ctx *ctx, const mm3d_icp_generalized_options *
 {
   if (!ctx || !options || !icp_generalized_options_valid(options)) return MM3D_EINVAL;
   std::lock_guard<std::mutex> lock(ctx->mu);        // (no call is running while the selection changes)
-  if (options->enabled) {
-    if (refused_on_device_list(ctx, "mm3d_set_icp_generalized: not available on a device-list context")) return MM3D_EUNSUPPORTED;
-    if (ctx->sel.rejecting()) {
-      ctx->err = "mm3d_set_icp_generalized: not available while a correspondence rejection is active (mm3d_set_icp_rejection)";
-      return MM3D_EUNSUPPORTED;
-    }
-    if (ctx->sel.geometric()) {      // (step 1b is the rejecting step's)
-      ctx->err = "mm3d_set_icp_generalized: not available while a geometric rejector is active (mm3d_set_icp_geometry_rejection)";
-      return MM3D_EUNSUPPORTED;
-    }
-    if (ctx->sel.color) {
-      ctx->err = "mm3d_set_icp_generalized: not available while coloured ICP is enabled (mm3d_set_icp_color)";
-      return MM3D_EUNSUPPORTED;
-    }
-    if (ctx->sel.robust()) {                          // (the robust step has no plane-to-plane variant)
-      ctx->err = "mm3d_set_icp_generalized: not available while a robust kernel is selected (mm3d_set_icp_robust)";
-      return MM3D_EUNSUPPORTED;
-    }
-    if (ctx->sel.sampler) {                           // (the source's normals are indexed by the source's own order)
-      ctx->err = "mm3d_set_icp_generalized: not available while an ICP source sampling is set (mm3d_set_icp_sampling)";
-      return MM3D_EUNSUPPORTED;
-    }
-  }
-  select_stages(ctx, false, [&](StageSelection &s) {
+  return select_stage(ctx, Stage::Generalized, [&](StageSelection &s) {
     s.generalized_options = *options;
-    s.generalized = options->enabled ? &g_generalized : nullptr;
+    s.generalized = stage_active(Stage::Generalized, s) ? &g_generalized : nullptr;
   });
-  return MM3D_OK;
 }
 
 int mm3d_get_icp_generalized(const mm3d_ctx *ctx, mm3d_icp_generalized_options *options)

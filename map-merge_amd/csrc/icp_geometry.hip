@@ -304,23 +304,10 @@ int mm3d_set_icp_geometry_rejection(mm3d_ctx *ctx, const mm3d_icp_geometry_optio
 {
   if (!ctx || !options || !icp_geometry_options_valid(options)) return MM3D_EINVAL;
   std::lock_guard<std::mutex> lock(ctx->mu);        // (no call is running while the selection changes)
-  const bool active = options->boundary || options->normals;
-  if (active && refused_on_device_list(ctx, "mm3d_set_icp_geometry_rejection: not available on a device-list context")) return MM3D_EUNSUPPORTED;
-  const char *other = !active                 ? nullptr
-                      : ctx->sel.color        ? "coloured ICP is enabled (mm3d_set_icp_color)"
-                      : ctx->sel.generalized  ? "generalized ICP is enabled (mm3d_set_icp_generalized)"
-                      : ctx->sel.robust()     ? "a robust kernel is selected (mm3d_set_icp_robust)"
-                      : options->normals && ctx->sel.sampler ? "an ICP source sampling is set (mm3d_set_icp_sampling): a sample has no normals"
-                                              : nullptr;
-  if (other) {
-    ctx->err = std::string("mm3d_set_icp_geometry_rejection: not available while ") + other;
-    return MM3D_EUNSUPPORTED;
-  }
-  select_stages(ctx, false, [&](StageSelection &s) {
+  return select_stage(ctx, Stage::Geometry, [&](StageSelection &s) {
     s.geometry_options = *options;
-    s.geometry = active ? &g_icp_geometry : nullptr;
+    s.geometry = stage_active(Stage::Geometry, s) ? &g_icp_geometry : nullptr;
   });
-  return MM3D_OK;
 }
 
 int mm3d_get_icp_geometry_rejection(const mm3d_ctx *ctx, mm3d_icp_geometry_options *options)

@@ -145,9 +145,10 @@ int mm3d_set_icp_method(mm3d_ctx *ctx, int method)
 {
   if (!ctx || (method != MM3D_ICP_POINT_TO_POINT && method != MM3D_ICP_POINT_TO_PLANE)) return MM3D_EINVAL;
   std::lock_guard<std::mutex> lock(ctx->mu);        // (no call is running while the method changes)
-  if (refused_on_device_list(ctx, "mm3d_set_icp_method: not available on a device-list context")) return MM3D_EUNSUPPORTED;
-  select_stages(ctx, false, [&](StageSelection &s) { s.icp = method == MM3D_ICP_POINT_TO_PLANE ? &g_point_to_plane : nullptr; });
-  return MM3D_OK;
+  // deliberate compatibility: a device-list context refuses every call of this setter, MM3D_ICP_POINT_TO_POINT included,
+  // where every other setter accepts an inactive selection
+  if (ctx->device_set) return refuse_device_list(ctx, Stage::IcpMethod);
+  return select_stage(ctx, Stage::IcpMethod, [&](StageSelection &s) { s.icp = method == MM3D_ICP_POINT_TO_PLANE ? &g_point_to_plane : nullptr; });
 }
 
 int mm3d_get_icp_method(const mm3d_ctx *ctx)

@@ -720,22 +720,7 @@ int mm3d_set_icp_rejection(mm3d_ctx *ctx, const mm3d_icp_rejection_options *opti
 {
   if (!ctx || !options || !icp_rejection_options_valid(options)) return MM3D_EINVAL;
   std::lock_guard<std::mutex> lock(ctx->mu);        // (no call is running while the selection changes)
-  const bool active = options->one_to_one || options->distance != MM3D_REJECT_NONE;
-  if (active && refused_on_device_list(ctx, "mm3d_set_icp_rejection: not available on a device-list context")) return MM3D_EUNSUPPORTED;
-  if (active && ctx->sel.color) {      // (k_rej_reduce has no colour variant)
-    ctx->err = "mm3d_set_icp_rejection: not available while coloured ICP is enabled (mm3d_set_icp_color)";
-    return MM3D_EUNSUPPORTED;
-  }
-  if (active && ctx->sel.generalized) {      // (nor a generalized one)
-    ctx->err = "mm3d_set_icp_rejection: not available while generalized ICP is enabled (mm3d_set_icp_generalized)";
-    return MM3D_EUNSUPPORTED;
-  }
-  if (active && ctx->sel.robust()) {      // (the robust step weights every match: it has no correspondence stage)
-    ctx->err = "mm3d_set_icp_rejection: not available while a robust kernel is selected (mm3d_set_icp_robust)";
-    return MM3D_EUNSUPPORTED;
-  }
-  select_stages(ctx, false, [&](StageSelection &s) { s.reject_options = *options; });
-  return MM3D_OK;
+  return select_stage(ctx, Stage::Rejection, [&](StageSelection &s) { s.reject_options = *options; });
 }
 
 int mm3d_get_icp_rejection(const mm3d_ctx *ctx, mm3d_icp_rejection_options *options)

@@ -375,21 +375,7 @@ int mm3d_set_icp_robust(mm3d_ctx *ctx, const mm3d_icp_robust_options *options)
 {
   if (!ctx || !options || !icp_robust_options_valid(options)) return MM3D_EINVAL;
   std::lock_guard<std::mutex> lock(ctx->mu);        // (no call is running while the selection changes)
-  const bool active = options->kernel != MM3D_ROBUST_OFF;
-  if (active && refused_on_device_list(ctx, "mm3d_set_icp_robust: not available on a device-list context")) return MM3D_EUNSUPPORTED;
-  const char *other = !active ? nullptr
-                      : ctx->sel.rejecting() ? "a correspondence rejection is active (mm3d_set_icp_rejection)"
-                      : ctx->sel.geometric() ? "a geometric rejector is active (mm3d_set_icp_geometry_rejection)"
-                      : ctx->sel.color       ? "coloured ICP is enabled (mm3d_set_icp_color)"
-                      : ctx->sel.generalized ? "generalized ICP is enabled (mm3d_set_icp_generalized)"
-                      : ctx->sel.refine      ? "NDT is selected (mm3d_set_refinement)"
-                                             : nullptr;
-  if (other) {      // (k_rob_wave has point-to-point's and point-to-plane's terms only)
-    ctx->err = std::string("mm3d_set_icp_robust: not available while ") + other;
-    return MM3D_EUNSUPPORTED;
-  }
-  select_stages(ctx, false, [&](StageSelection &s) { s.robust_options = *options; });
-  return MM3D_OK;
+  return select_stage(ctx, Stage::Robust, [&](StageSelection &s) { s.robust_options = *options; });
 }
 
 int mm3d_get_icp_robust(const mm3d_ctx *ctx, mm3d_icp_robust_options *options)

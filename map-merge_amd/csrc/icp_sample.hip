@@ -321,30 +321,10 @@ int mm3d_set_icp_sampling(mm3d_ctx *ctx, const mm3d_icp_sampling_options *option
 {
   if (!ctx || !options || !sampling_options_valid(options)) return MM3D_EINVAL;
   std::lock_guard<std::mutex> lock(ctx->mu);        // (no call is running while the selection changes)
-  if (options->method != MM3D_ICP_SAMPLE_NONE) {
-    if (refused_on_device_list(ctx, "mm3d_set_icp_sampling: not available on a device-list context")) return MM3D_EUNSUPPORTED;
-    if (ctx->sel.refine) {
-      ctx->err = "mm3d_set_icp_sampling: not available while NDT is selected (mm3d_set_refinement)";
-      return MM3D_EUNSUPPORTED;
-    }
-    if (ctx->sel.geometry_options.normals) {      // (a sample has no normals of its own index; the boundary rejector is target-side)
-      ctx->err = "mm3d_set_icp_sampling: not available while the normal rejector is active (mm3d_set_icp_geometry_rejection)";
-      return MM3D_EUNSUPPORTED;
-    }
-    if (ctx->sel.color) {
-      ctx->err = "mm3d_set_icp_sampling: not available while coloured ICP is enabled (mm3d_set_icp_color)";
-      return MM3D_EUNSUPPORTED;
-    }
-    if (ctx->sel.generalized) {
-      ctx->err = "mm3d_set_icp_sampling: not available while generalized ICP is enabled (mm3d_set_icp_generalized)";
-      return MM3D_EUNSUPPORTED;
-    }
-  }
-  select_stages(ctx, false, [&](StageSelection &s) {
+  return select_stage(ctx, Stage::Sampling, [&](StageSelection &s) {
     s.sampling_options = *options;
-    s.sampler = options->method != MM3D_ICP_SAMPLE_NONE ? &g_sampler : nullptr;
+    s.sampler = stage_active(Stage::Sampling, s) ? &g_sampler : nullptr;
   });
-  return MM3D_OK;
 }
 
 int mm3d_get_icp_sampling(const mm3d_ctx *ctx, mm3d_icp_sampling_options *options)

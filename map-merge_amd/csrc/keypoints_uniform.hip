@@ -147,12 +147,10 @@ int mm3d_set_keypoints(mm3d_ctx *ctx, const mm3d_keypoint_options *options)
 {
   if (!ctx || !options_ok(options)) return MM3D_EINVAL;
   std::lock_guard<std::mutex> lock(ctx->mu);        // (no call is running while the source changes)
-  // (features travel in the bundles, so device lists carry the option: the peers follow)
-  select_stages(ctx, true, [&](StageSelection &s) {
-    s.keypoints = options->source == MM3D_KEYPOINTS_UNIFORM ? &g_uniform : nullptr;
+  return select_stage(ctx, Stage::Keypoints, [&](StageSelection &s) {
     s.keypoint_options = *options;
+    s.keypoints = stage_active(Stage::Keypoints, s) ? &g_uniform : nullptr;
   });
-  return MM3D_OK;
 }
 
 int mm3d_get_keypoints(const mm3d_ctx *ctx, mm3d_keypoint_options *options)

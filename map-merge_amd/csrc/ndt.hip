@@ -362,18 +362,10 @@ int mm3d_set_refinement(mm3d_ctx *ctx, const mm3d_refine_options *options)
   if (!ctx || !ndt_options_ok(options)) return MM3D_EINVAL;
   if (options->resolution != 0.0 && !lattice_side_ok(options->resolution)) return MM3D_EINVAL;     // (also catches NaN)
   std::lock_guard<std::mutex> lock(ctx->mu);        // (no call is running while the method changes)
-  const bool ndt = options->method == MM3D_REFINE_NDT;
-  if (ndt && refused_on_device_list(ctx, "mm3d_set_refinement: NDT is not available on a device-list context")) return MM3D_EUNSUPPORTED;
-  if (ndt && ctx->sel.sampler) {                     // (NDT searches nothing: there is no source sample for it to read)
-    ctx->err = "mm3d_set_refinement: NDT is not available while an ICP source sampling is set (mm3d_set_icp_sampling)";
-    return MM3D_EUNSUPPORTED;
-  }
-  if (ndt && ctx->sel.robust()) {                    // (NDT has no correspondences to weight)
-    ctx->err = "mm3d_set_refinement: NDT is not available while a robust kernel is selected (mm3d_set_icp_robust)";
-    return MM3D_EUNSUPPORTED;
-  }
-  select_stages(ctx, false, [&](StageSelection &s) { s.refine = ndt ? &g_ndt : nullptr; s.refine_options = *options; });
-  return MM3D_OK;
+  return select_stage(ctx, Stage::Refinement, [&](StageSelection &s) {
+    s.refine_options = *options;
+    s.refine = stage_active(Stage::Refinement, s) ? &g_ndt : nullptr;
+  });
 }
 
 int mm3d_get_refinement(const mm3d_ctx *ctx, mm3d_refine_options *options)

@@ -461,12 +461,10 @@ int mm3d_set_outlier_filter(mm3d_ctx *ctx, const mm3d_outlier_options *options)
 {
   if (!ctx || !options_ok(options)) return MM3D_EINVAL;
   std::lock_guard<std::mutex> lock(ctx->mu);        // (no call is running while the filter changes)
-  // (a map's filtered points travel in the bundles, so device lists carry the option: the peers follow)
-  select_stages(ctx, true, [&](StageSelection &s) {
-    s.outliers = options->method == MM3D_OUTLIERS_STATISTICAL ? &g_statistical : nullptr;
+  return select_stage(ctx, Stage::Outliers, [&](StageSelection &s) {
     s.outlier_options = *options;
+    s.outliers = stage_active(Stage::Outliers, s) ? &g_statistical : nullptr;
   });
-  return MM3D_OK;
 }
 
 int mm3d_get_outlier_filter(const mm3d_ctx *ctx, mm3d_outlier_options *options)

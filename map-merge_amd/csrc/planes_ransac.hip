@@ -636,12 +636,10 @@ int mm3d_set_planes(mm3d_ctx *ctx, const mm3d_plane_options *options)
 {
   if (!ctx || !pl_options_ok(options, false)) return MM3D_EINVAL;
   std::lock_guard<std::mutex> lock(ctx->mu);        // (no call is running while the stage changes)
-  // (a map's points travel in the bundles, so device lists carry the option: the peers follow)
-  select_stages(ctx, true, [&](StageSelection &s) {
-    s.planes = options->method != MM3D_PLANES_OFF ? &g_ransac : nullptr;
+  return select_stage(ctx, Stage::Planes, [&](StageSelection &s) {
     s.plane_options = *options;
+    s.planes = stage_active(Stage::Planes, s) ? &g_ransac : nullptr;
   });
-  return MM3D_OK;
 }
 
 int mm3d_get_planes(const mm3d_ctx *ctx, mm3d_plane_options *options)

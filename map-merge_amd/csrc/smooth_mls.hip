@@ -376,12 +376,10 @@ int mm3d_set_smoothing(mm3d_ctx *ctx, const mm3d_smooth_options *options)
 {
   if (!ctx || !options_ok(options)) return MM3D_EINVAL;
   std::lock_guard<std::mutex> lock(ctx->mu);        // (no call is running while the stage changes)
-  // (a map's smoothed points travel in the bundles, so device lists carry the option: the peers follow)
-  select_stages(ctx, true, [&](StageSelection &s) {
-    s.smoother = options->method == MM3D_SMOOTH_MLS ? &g_mls : nullptr;
+  return select_stage(ctx, Stage::Smoothing, [&](StageSelection &s) {
     s.smooth_options = *options;
+    s.smoother = stage_active(Stage::Smoothing, s) ? &g_mls : nullptr;
   });
-  return MM3D_OK;
 }
 
 int mm3d_get_smoothing(const mm3d_ctx *ctx, mm3d_smooth_options *options)

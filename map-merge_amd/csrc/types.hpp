@@ -31,7 +31,7 @@ struct IcpGeometryBase;
 // mm3d_set_coarse_alignment, mm3d_set_confidence, mm3d_set_icp_rejection, mm3d_set_icp_robust, mm3d_set_icp_color, mm3d_set_icp_generalized,
 // mm3d_set_estimator, mm3d_set_icp_sampling, mm3d_set_outlier_filter, mm3d_set_cluster_filter, mm3d_set_smoothing, mm3d_set_planes): a null method = the reference's stage.  The methods are process-wide
 // objects of their kernel files that hold no state and are not owned.  Every context has its own copy of the record; only
-// select_stages (drivers.hpp) changes one, and it and mm3d_set_streams hand the root's copy to the helpers.
+// select_stage (stage_rules.hpp) changes one, and it and mm3d_set_streams hand the root's copy to the helpers.
 struct StageSelection {
   const IcpMethodBase *icp = nullptr;                  // point-to-plane in the place of point-to-point
   const AlignMethodBase *align = nullptr;              // the initial estimate under SAC_IA
@@ -55,22 +55,24 @@ struct StageSelection {
   mm3d_confidence_options confidence_options;
   mm3d_icp_rejection_options reject_options;           // the ICP's correspondence rejection: no method object, the jobs carry them
   mm3d_icp_robust_options robust_options;              // the ICP's robust kernel: no method object, the jobs carry them
-  mm3d_icp_color_options color_options;                // coloured ICP: `color` is non-null exactly while they are enabled
-  mm3d_icp_generalized_options generalized_options;    // generalized ICP: `generalized` is non-null exactly while they are enabled
-  mm3d_estimator_options estimator_options;            // `estimator` is non-null exactly while their method is CONSISTENCY
-  mm3d_icp_sampling_options sampling_options;          // `sampler` is non-null exactly while their method is not NONE
-  mm3d_outlier_options outlier_options;                // `outliers` is non-null exactly while their method is STATISTICAL
-  mm3d_cluster_options cluster_options;                // `clusters` is non-null exactly while their method is not OFF
-  mm3d_smooth_options smooth_options;                  // `smoother` is non-null exactly while their method is MLS; `where` says which places ask it
-  mm3d_plane_options plane_options;                    // `planes` is non-null exactly while their method is not OFF
-  mm3d_icp_geometry_options geometry_options;          // `geometry` is non-null exactly while boundary || normals
+  mm3d_icp_color_options color_options;
+  mm3d_icp_generalized_options generalized_options;
+  mm3d_estimator_options estimator_options;
+  mm3d_icp_sampling_options sampling_options;
+  mm3d_outlier_options outlier_options;
+  mm3d_cluster_options cluster_options;
+  mm3d_smooth_options smooth_options;                  // `where` says which places ask the smoother
+  mm3d_plane_options plane_options;
+  mm3d_icp_geometry_options geometry_options;
+  // A stage's pointer is non-null exactly while its options make it active; what that means is its row's predicate in
+  // stage_rules.cpp, which the setters' edits and the three members below read.
   StageSelection();                                    // capi.cpp: the options are the sixteen mm3d_*_options_default's
   // the ICP of the pair stage rejects correspondences (mm3d_set_icp_rejection)
-  bool rejecting() const { return reject_options.one_to_one || reject_options.distance != MM3D_REJECT_NONE; }
+  bool rejecting() const;
   // the rejecting step drops correspondences by the maps' geometry too (mm3d_set_icp_geometry_rejection)
-  bool geometric() const { return geometry_options.boundary || geometry_options.normals; }
+  bool geometric() const;
   // the ICP of the pair stage weights its correspondences (mm3d_set_icp_robust)
-  bool robust() const { return robust_options.kernel != MM3D_ROBUST_OFF; }
+  bool robust() const;
   int icp_method() const;                              // MM3D_ICP_*
   // the pair's initial estimate is the prerejective alignment's
   bool prerejective(const mm3d_params *p) const { return !coarse && align && p->estimation_method == MM3D_EST_SAC_IA; }

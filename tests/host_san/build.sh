@@ -1,6 +1,6 @@
 #!/bin/bash
 # Builds the library's host code -- the files of map-merge_amd/csrc/host_sources.sh (runtime.cpp, the extern "C" boundary capi.cpp,
-# pair_estimate.cpp, the driver_*.cpp, host_pipeline.cpp, linalg.cpp, devices.cpp), unchanged -- with a sanitizer against
+# stage_rules.cpp, pair_estimate.cpp, the driver_*.cpp, host_pipeline.cpp, linalg.cpp, devices.cpp), unchanged -- with a sanitizer against
 # the fake HIP runtime and the fake device layer of this directory, into tests/host_san/_build/san_<kind> (git-ignored):
 #   tests/host_san/build.sh thread | address
 # clang's host pass of the HIP language (--cuda-host-only): the headers' __device__ helpers are parsed, never emitted.

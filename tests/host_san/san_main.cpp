@@ -3,7 +3,7 @@
 // type's table entry, the shard driver for a world of 3 ranks emulated in one process, the device-list driver (mm3d_create_devices: 1, 2 and 3
 // fake devices and the duplicate-device hook, the pair records through the fake RCCL), composeMaps, the stage-by-stage
 // calls, parameter parsing, the degenerate inputs of the reference's gtests and the error paths (a map that fails while it is
-// built among them: MM3D_FAKE_FAIL_POINTS).  Built with
+// built among them: MM3D_FAKE_FAIL_POINTS), and the stage table of stage_rules.hpp through select_stage.  Built with
 // -fsanitize=thread or -fsanitize=address,undefined by tests/host_san/build.sh; exit code 0 = the checks passed and no
 // sanitizer spoke.
 #include <cmath>
@@ -11,11 +11,15 @@
 #include <cstdlib>
 #include <algorithm>
 #include <cstring>
+#include <iterator>
+#include <memory>
+#include <mutex>
 #include <string>
 #include <thread>
 #include <vector>
 
 #include "../../include/mm3d.h"
+#include "stage_rules.hpp"      // (the one piece driven below the C ABI: select_stage on the library's own contexts)
 
 static int failures = 0;
 #define CHECK(x) do { if (!(x)) { std::printf("CHECK failed at line %d: %s\n", __LINE__, #x); ++failures; } } while (0)
@@ -29,6 +33,147 @@ static std::vector<Pt> make_cloud(int n, unsigned seed)
   for (int i = 0; i < n; ++i) { v[i] = Pt{u() * 20.f + (float)seed, u() * 20.f, u() * 2.f, 0xff000000u | (s >> 8)}; }
   return v;
 }
+
+// ---------------------------------------------------------------- the stage table (stage_rules.hpp), through select_stage itself
+// What may stand together, written out here and not read from the table under test: the fourteen unordered pairs that refuse
+// each other (geometry - sampling only for the normal rejector) and the five stages whose data travels in the bundles.
+namespace {
+using mm3d::Stage;
+using mm3d::StageSelection;
+
+struct StubIcp : mm3d::IcpMethodBase {              // the ICP-method row reads the pointer: any method object will do
+  int method() const override { return MM3D_ICP_POINT_TO_PLANE; }
+  std::unique_ptr<mm3d::IcpStep> step(const mm3d_icp_rejection_options *) const override { std::abort(); }
+  void prepare_target(mm3d_ctx *, const mm3d_map *, const mm3d_params *, mm3d::IcpScoreJob *) const override {}
+};
+const StubIcp g_stub_icp;
+
+// one way to make a stage active and the way back to its default; geometry has two, its rejectors conflict differently
+struct Selecting { Stage st; const char *setter; void (*on)(StageSelection &); void (*off)(StageSelection &); bool normals; };
+const Selecting kSelecting[] = {
+    {Stage::IcpMethod, "mm3d_set_icp_method", [](StageSelection &s) { s.icp = &g_stub_icp; }, [](StageSelection &s) { s.icp = nullptr; }, false},
+    {Stage::Alignment, "mm3d_set_alignment", [](StageSelection &s) { s.align_options.method = MM3D_ALIGN_PREREJECTIVE; },
+     [](StageSelection &s) { mm3d_alignment_options_default(&s.align_options); }, false},
+    {Stage::Keypoints, "mm3d_set_keypoints", [](StageSelection &s) { s.keypoint_options.source = MM3D_KEYPOINTS_UNIFORM; },
+     [](StageSelection &s) { mm3d_keypoint_options_default(&s.keypoint_options); }, false},
+    {Stage::Refinement, "mm3d_set_refinement", [](StageSelection &s) { s.refine_options.method = MM3D_REFINE_NDT; },
+     [](StageSelection &s) { mm3d_refine_options_default(&s.refine_options); }, false},
+    {Stage::Coarse, "mm3d_set_coarse_alignment", [](StageSelection &s) { s.coarse_options.method = MM3D_COARSE_CORRELATIVE; },
+     [](StageSelection &s) { mm3d_coarse_options_default(&s.coarse_options); }, false},
+    {Stage::Confidence, "mm3d_set_confidence", [](StageSelection &s) { s.confidence_options.method = MM3D_CONFIDENCE_OVERLAP; },
+     [](StageSelection &s) { mm3d_confidence_options_default(&s.confidence_options); }, false},
+    {Stage::Rejection, "mm3d_set_icp_rejection", [](StageSelection &s) { s.reject_options.distance = MM3D_REJECT_TRIMMED; },
+     [](StageSelection &s) { mm3d_icp_rejection_options_default(&s.reject_options); }, false},
+    {Stage::Geometry, "mm3d_set_icp_geometry_rejection", [](StageSelection &s) { s.geometry_options.boundary = 0; s.geometry_options.normals = 1; },
+     [](StageSelection &s) { mm3d_icp_geometry_options_default(&s.geometry_options); }, true},
+    {Stage::Geometry, "mm3d_set_icp_geometry_rejection", [](StageSelection &s) { s.geometry_options.boundary = 1; s.geometry_options.normals = 0; },
+     [](StageSelection &s) { mm3d_icp_geometry_options_default(&s.geometry_options); }, false},
+    {Stage::Robust, "mm3d_set_icp_robust", [](StageSelection &s) { s.robust_options.kernel = MM3D_ROBUST_HUBER; },
+     [](StageSelection &s) { mm3d_icp_robust_options_default(&s.robust_options); }, false},
+    {Stage::Color, "mm3d_set_icp_color", [](StageSelection &s) { s.color_options.enabled = 1; },
+     [](StageSelection &s) { mm3d_icp_color_options_default(&s.color_options); }, false},
+    {Stage::Generalized, "mm3d_set_icp_generalized", [](StageSelection &s) { s.generalized_options.enabled = 1; },
+     [](StageSelection &s) { mm3d_icp_generalized_options_default(&s.generalized_options); }, false},
+    {Stage::Estimator, "mm3d_set_estimator", [](StageSelection &s) { s.estimator_options.method = MM3D_ESTIMATOR_CONSISTENCY; },
+     [](StageSelection &s) { mm3d_estimator_options_default(&s.estimator_options); }, false},
+    {Stage::Sampling, "mm3d_set_icp_sampling", [](StageSelection &s) { s.sampling_options.method = MM3D_ICP_SAMPLE_STRIDE; },
+     [](StageSelection &s) { mm3d_icp_sampling_options_default(&s.sampling_options); }, false},
+    {Stage::Outliers, "mm3d_set_outlier_filter", [](StageSelection &s) { s.outlier_options.method = MM3D_OUTLIERS_STATISTICAL; },
+     [](StageSelection &s) { mm3d_outlier_options_default(&s.outlier_options); }, false},
+    {Stage::Clusters, "mm3d_set_cluster_filter", [](StageSelection &s) { s.cluster_options.method = MM3D_CLUSTERS_LARGEST; },
+     [](StageSelection &s) { mm3d_cluster_options_default(&s.cluster_options); }, false},
+    {Stage::Smoothing, "mm3d_set_smoothing", [](StageSelection &s) { s.smooth_options.method = MM3D_SMOOTH_MLS; },
+     [](StageSelection &s) { mm3d_smooth_options_default(&s.smooth_options); }, false},
+    {Stage::Planes, "mm3d_set_planes", [](StageSelection &s) { s.plane_options.method = MM3D_PLANES_REMOVE; },
+     [](StageSelection &s) { mm3d_plane_options_default(&s.plane_options); }, false},
+};
+const Stage kConflicting[14][2] = {
+    {Stage::Rejection, Stage::Color},  {Stage::Rejection, Stage::Generalized}, {Stage::Rejection, Stage::Robust},
+    {Stage::Geometry, Stage::Color},   {Stage::Geometry, Stage::Generalized},  {Stage::Geometry, Stage::Robust},
+    {Stage::Geometry, Stage::Sampling} /* the normal rejector only */,
+    {Stage::Sampling, Stage::Refinement}, {Stage::Sampling, Stage::Color},     {Stage::Sampling, Stage::Generalized},
+    {Stage::Color, Stage::Generalized},   {Stage::Color, Stage::Robust},       {Stage::Generalized, Stage::Robust},
+    {Stage::Robust, Stage::Refinement},
+};
+const Stage kTravelling[5] = {Stage::Keypoints, Stage::Outliers, Stage::Clusters, Stage::Smoothing, Stage::Planes};
+
+bool conflicting(const Selecting &a, const Selecting &b)
+{
+  for (const auto &pr : kConflicting)
+    if ((pr[0] == a.st && pr[1] == b.st) || (pr[0] == b.st && pr[1] == a.st)) {
+      const bool geometry_sampling = pr[0] == Stage::Geometry && pr[1] == Stage::Sampling;
+      return !geometry_sampling || a.normals || b.normals;
+    }
+  return false;
+}
+bool travelling(Stage st) { return std::find(std::begin(kTravelling), std::end(kTravelling), st) != std::end(kTravelling); }
+int select_locked(mm3d_ctx *c, Stage st, void (*edit)(StageSelection &))
+{
+  std::lock_guard<std::mutex> lock(c->mu);
+  return mm3d::select_stage(c, st, edit);
+}
+bool same_record(const StageSelection &a, const StageSelection &b) { return std::memcmp(&a, &b, sizeof(StageSelection)) == 0; }
+bool error_begins_with(mm3d_ctx *c, const char *setter) { return std::string(mm3d_last_error(c)).rfind(std::string(setter) + ":", 0) == 0; }
+
+void check_stage_rules()
+{
+  // every ordered pair on one stream and with helpers: activate A, then B -- refused exactly when {A, B} is a listed pair,
+  // whichever came first; a refusal names the refused call and the blocking one and leaves the record as it was; B's default
+  // is always accepted
+  mm3d_ctx *c = nullptr;
+  CHECK(mm3d_create(0, &c) == MM3D_OK && c);
+  if (!c) return;
+  CHECK(mm3d_set_streams(c, 3) == MM3D_OK);
+  const StageSelection fresh = c->sel;
+  int refusals = 0;
+  for (const Selecting &a : kSelecting)
+    for (const Selecting &b : kSelecting) {
+      if (a.st == b.st) continue;
+      c->sel = fresh;
+      for (mm3d_ctx *h : c->helpers) h->sel = fresh;
+      CHECK(select_locked(c, a.st, a.on) == MM3D_OK && mm3d::stage_active(a.st, c->sel));
+      const StageSelection before = c->sel;
+      const int st = select_locked(c, b.st, b.on);
+      if (conflicting(a, b)) {
+        ++refusals;
+        CHECK(st == MM3D_EUNSUPPORTED && same_record(c->sel, before));
+        CHECK(error_begins_with(c, b.setter) && std::string(mm3d_last_error(c)).find(std::string("(") + a.setter + ")") != std::string::npos);
+      } else {
+        CHECK(st == MM3D_OK && mm3d::stage_active(a.st, c->sel) && mm3d::stage_active(b.st, c->sel));
+      }
+      for (mm3d_ctx *h : c->helpers) CHECK(same_record(h->sel, c->sel));
+      c->sel = before;
+      CHECK(select_locked(c, b.st, b.off) == MM3D_OK && !mm3d::stage_active(b.st, c->sel) && mm3d::stage_active(a.st, c->sel));
+    }
+  CHECK(refusals == 2 * (14 + 4 - 1));               // geometry's four pairs twice (two rejectors), less boundary - sampling
+  mm3d_destroy(c);
+  // a device list: the twelve stages whose data stays home are refused while active, the five others reach every peer; a
+  // default is accepted either way
+  const int list3[3] = {0, 1, 2};
+  mm3d_ctx *dc = nullptr;
+  CHECK(mm3d_create_devices(list3, 3, &dc) == MM3D_OK && dc);
+  if (!dc) return;
+  CHECK(dc->peers.size() == 2);
+  int refused = 0;
+  for (const Selecting &a : kSelecting) {
+    for (mm3d_ctx *p : dc->peers) p->sel = dc->sel;  // (same_record compares bytes: every record gets the root's padding first)
+    const StageSelection before = dc->sel;
+    const int st = select_locked(dc, a.st, a.on);
+    if (travelling(a.st)) {
+      CHECK(st == MM3D_OK && mm3d::stage_active(a.st, dc->sel));
+    } else {
+      ++refused;
+      CHECK(st == MM3D_EUNSUPPORTED && same_record(dc->sel, before) && error_begins_with(dc, a.setter));
+    }
+    for (mm3d_ctx *p : dc->peers) CHECK(same_record(p->sel, dc->sel));
+    CHECK(select_locked(dc, a.st, a.off) == MM3D_OK && !mm3d::stage_active(a.st, dc->sel));
+    // (a stage that stays home never touches a peer: theirs are still `before`, the root's as they were after the refusal)
+    for (mm3d_ctx *p : dc->peers) CHECK(same_record(p->sel, travelling(a.st) ? dc->sel : before));
+  }
+  CHECK(refused == 13);                              // twelve stages, geometry with either rejector
+  mm3d_destroy(dc);
+}
+}  // namespace
 
 int main()
 {
@@ -305,6 +450,7 @@ int main()
     mm3d_destroy(c2);                                          // the objects below outlive their context
     mm3d_cloud_free(ctx, filt); mm3d_cloud_free(ctx, kp); mm3d_desc_free(ctx, desc); mm3d_cloud_free(ctx, merged);   // (through another context)
   }
+  check_stage_rules();
   mm3d_destroy(ctx);
   std::printf(failures ? "FAILED: %d checks\n" : "host sanitizer driver ok (%d failed checks)\n", failures);
   return failures ? 1 : 0;

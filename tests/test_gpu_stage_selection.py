@@ -4,7 +4,8 @@ checks it alone; here a context holds several selections at once, and whatever t
 -- helpers made before, after, or destroyed and remade -- every context must hold the same selection and compute the same
 bits.  Then what every ICP selection shares, the pair batch: pairs of unequal size in one batch against the stage-level entry
 points, and the entry points with nothing to search.  Every comparison is exact: the library promises bit-identical records
-for every stream count."""
+for every stream count.  Last, which of the seventeen selections may stand together at all, on one device, on a device list and
+in a shard: every ordered pair of setters against the policy written out here."""
 import numpy as np
 import pytest
 
@@ -232,4 +233,130 @@ def test_defaults_exist_once(mm):
     _holds(mm, c, {})
     c.setStreams(3)
     _holds(mm, c, {})
+    c.close()
+
+
+# ---------------------------------------------------------------- which selections may stand together (csrc/stage_rules.cpp)
+# The policy written out, not read from the table it checks: the seventeen setters with a value that makes each active (the
+# geometric rejectors twice: they conflict differently), the fourteen unordered pairs that refuse each other, and the five
+# stages whose data travels in the bundles of a device list and a shard.
+EUNSUPPORTED = -4
+STAGES = [      # (Context.set<name> / get<name>, the C setter a message names, the options class, an active value)
+    ("IcpMethod", "mm3d_set_icp_method", None, 1),
+    ("Alignment", "mm3d_set_alignment", "AlignmentOptions", dict(method=1)),
+    ("Keypoints", "mm3d_set_keypoints", "KeypointOptions", dict(source=1)),
+    ("Refinement", "mm3d_set_refinement", "RefineOptions", dict(method=1)),
+    ("CoarseAlignment", "mm3d_set_coarse_alignment", "CoarseOptions", dict(method=1)),
+    ("Confidence", "mm3d_set_confidence", "ConfidenceOptions", dict(method=1)),
+    ("IcpRejection", "mm3d_set_icp_rejection", "IcpRejectionOptions", dict(distance=1)),
+    ("IcpGeometryRejection", "mm3d_set_icp_geometry_rejection", "IcpGeometryOptions", dict(normals=1)),
+    ("IcpGeometryRejection", "mm3d_set_icp_geometry_rejection", "IcpGeometryOptions", dict(boundary=1)),
+    ("IcpRobust", "mm3d_set_icp_robust", "IcpRobustOptions", dict(kernel=2)),
+    ("IcpColor", "mm3d_set_icp_color", "IcpColorOptions", dict(enabled=1)),
+    ("IcpGeneralized", "mm3d_set_icp_generalized", "IcpGeneralizedOptions", dict(enabled=1)),
+    ("Estimator", "mm3d_set_estimator", "EstimatorOptions", dict(method=1)),
+    ("IcpSampling", "mm3d_set_icp_sampling", "IcpSamplingOptions", dict(method=1)),
+    ("OutlierFilter", "mm3d_set_outlier_filter", "OutlierOptions", dict(method=1)),
+    ("ClusterFilter", "mm3d_set_cluster_filter", "ClusterOptions", dict(method=2)),
+    ("Smoothing", "mm3d_set_smoothing", "SmoothOptions", dict(method=1)),
+    ("Planes", "mm3d_set_planes", "PlaneOptions", dict(method=1)),
+]
+CONFLICTS = [
+    ("IcpRejection", "IcpColor"), ("IcpRejection", "IcpGeneralized"), ("IcpRejection", "IcpRobust"),
+    ("IcpGeometryRejection", "IcpColor"), ("IcpGeometryRejection", "IcpGeneralized"), ("IcpGeometryRejection", "IcpRobust"),
+    ("IcpGeometryRejection", "IcpSampling"),          # only while the normal rejector is set: the boundary rejector composes with a sampler
+    ("IcpSampling", "Refinement"), ("IcpSampling", "IcpColor"), ("IcpSampling", "IcpGeneralized"),
+    ("IcpColor", "IcpGeneralized"), ("IcpColor", "IcpRobust"), ("IcpGeneralized", "IcpRobust"),
+    ("IcpRobust", "Refinement"),
+]
+TRAVELLING = ("Keypoints", "OutlierFilter", "ClusterFilter", "Smoothing", "Planes")
+
+
+def _conflicting(a, b):
+    if (a[0], b[0]) not in CONFLICTS and (b[0], a[0]) not in CONFLICTS:
+        return False
+    if {a[0], b[0]} == {"IcpGeometryRejection", "IcpSampling"}:
+        return bool((a if a[0] == "IcpGeometryRejection" else b)[3].get("normals"))
+    return True
+
+
+def _set_stage(mm, c, stage, active):
+    """(status, message) of the stage's setter with its active value, or with its default"""
+    name, _, cls, what = stage
+    try:
+        if cls is None:
+            c.setIcpMethod(what if active else 0)
+        else:
+            getattr(c, "set" + name)(getattr(mm, cls)(**(what if active else {})))
+    except mm.Mm3dError as e:
+        return e.status, str(e)
+    return 0, ""
+
+
+def _record(c):
+    """what every getter answers, field for field"""
+    out = [int(c.getIcpMethod())]
+    for name, _, cls, _ in STAGES:
+        if cls is not None:
+            o = getattr(c, "get" + name)()
+            out.append(tuple(tuple(v) if hasattr(v, "__len__") else v for v in _fields(o)))
+    return out
+
+
+def test_every_ordered_pair_of_stages(mm):
+    """A active, then B: refused exactly when {A, B} is a listed pair, whichever came first; a refusal names both calls and changes
+    nothing; B's default is always accepted."""
+    c = mm.Context(0)
+    fresh = _record(c)
+    refusals = 0
+    for a in STAGES:
+        for b in STAGES:
+            if a[0] == b[0]:
+                continue
+            for s in STAGES:                                   # back to the defaults
+                assert _set_stage(mm, c, s, False) == (0, "")
+            assert _record(c) == fresh
+            assert _set_stage(mm, c, a, True) == (0, ""), (a[0], b[0])
+            before = _record(c)
+            assert before != fresh
+            st, msg = _set_stage(mm, c, b, True)
+            if _conflicting(a, b):
+                refusals += 1
+                assert st == EUNSUPPORTED and b[1] + ":" in msg and "(" + a[1] + ")" in msg, (a[0], b[0], st, msg)
+                assert _record(c) == before, (a[0], b[0])
+            else:
+                assert st == 0 and _record(c) != before, (a[0], b[0], msg)
+                assert _set_stage(mm, c, a, True) == (0, ""), (a[0], b[0])      # and A again beside B
+            assert _set_stage(mm, c, b, False) == (0, ""), (a[0], b[0])
+            assert _record(c) == before
+    assert refusals == 2 * 17      # fourteen pairs, geometry's four twice (two rejectors), less boundary - sampling; both orders
+    c.close()
+
+
+def test_device_list_and_shard_carry_five_stages(mm):
+    """A device-list context and a shard refuse the twelve stages whose data stays on its device while one is active, and
+    accept its default; the five that travel are accepted."""
+    from test_gpu_icp_plane import _records, box_room
+    d = mm.Context(devices=[0])
+    c = mm.Context(0)
+    cloud = _records(box_room(1, 2000)[0])
+    p = mm.MapMergingParams(descriptor_type=FPFH)
+    for s in STAGES:
+        before = _record(d)
+        st, msg = _set_stage(mm, d, s, True)
+        if s[0] in TRAVELLING:
+            assert st == 0 and _record(d) != before, (s[0], msg)
+        else:
+            assert st == EUNSUPPORTED and s[1] + ":" in msg and _record(d) == before, (s[0], st, msg)
+        # the default is accepted -- but for mm3d_set_icp_method, which a device list refuses whatever the method
+        assert _set_stage(mm, d, s, False)[0] == (EUNSUPPORTED if s[0] == "IcpMethod" else 0), s[0]
+        assert _record(d) == before
+        if s[0] in TRAVELLING:
+            continue                                           # (a shard with the stage: the stage's own file)
+        assert _set_stage(mm, c, s, True) == (0, "")
+        with pytest.raises(mm.Mm3dError) as e:
+            c.shardBegin([cloud, cloud], p, 0, 1)
+        assert e.value.status == EUNSUPPORTED and "mm3d_shard_begin:" in str(e.value), s[0]
+        assert _set_stage(mm, c, s, False) == (0, "")
+    d.close()
     c.close()

@@ -82,7 +82,10 @@ def test_sources_carry_the_stage():
     assert "sel.smoother->smooth(" in capi and "MM3D_SMOOTH_COMPOSED" in capi and "mm3d_smooth_options_default(&smooth_options)" in capi
     assert "smooth_options" in _read("map-merge_amd", "csrc", "map_cache.cpp")
     k = _read("map-merge_amd", "csrc", "smooth_mls.hip")
-    assert "select_stages(ctx, true" in k and "wave_sum" in k and "solve6_ldlt(" in k and "sym_eig3(" in k
+    assert "select_stage(ctx, Stage::Smoothing" in k and "wave_sum" in k and "solve6_ldlt(" in k and "sym_eig3(" in k
+    # the stage travels in the bundles (the peers of a device list follow): its row of the stage table gives no reason to stay home
+    rules = _read("map-merge_amd", "csrc", "stage_rules.cpp")
+    assert re.search(r'\{"mm3d_set_smoothing",[^\n]*\n[^\n]*"the MLS smoothing is selected", nullptr\},', rules)
     assert "voxel_leaf =" not in k                                             # the smoothed cloud is no voxel grid's output
     assert '#include "sym_eig3.hpp"' in _read("map-merge_amd", "csrc", "shot.hip")            # one text for both eigen-solves
     assert "rand(" not in k
